@@ -3,6 +3,7 @@
 
     python bench.py --gpus N --steps K --warmup W                (N > 1 without a launcher: starts N ranks itself)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+    python bench.py ... --dump-outputs DIR                       (also writes the last timed step's results: DIR/<field>.npy)
 
 A step = one pass of the hot path over one mesh already resident in HBM: mh_assemble (FilterDegenerate, BuildQuadMesh,
 element bases, K/M assembly) + excitation sampling + mh_eigs (65 eigenpairs requested for 50 kept modes, as the
@@ -363,6 +364,42 @@ def batch_scan_meshes(count=64):
     return out
 
 
+DUMP_BYTES_MAX = 64 << 20
+RESULT_FIELDS = ("eigenvalues", "freqs", "t60s", "shapes", "positions", "summary_shapes", "original_fundamental", "mass", "center_of_mass",
+                 "inertia_diagonal", "inertia_orientation_wxyz", "sample_point_of_excitation")  # api.ModalResult minus profile (timings) and basis
+
+
+def _as_float(a):
+    a = np.asarray(a)
+    return a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+
+
+def _stack_padded(arrays):
+    """One array per mesh -> (meshes, *largest shape), NaN past each mesh's own extent."""
+    arrays = [_as_float(a) for a in arrays]
+    out = np.full((len(arrays),) + tuple(max(s) for s in zip(*(a.shape for a in arrays))), np.nan, np.result_type(*arrays))
+    for i, a in enumerate(arrays):
+        out[(i,) + tuple(slice(0, n) for n in a.shape)] = a
+    return out
+
+
+def dump_outputs(out_dir, last, records):
+    """--dump-outputs: what the last timed step handed its caller, one DIR/<field>.npy each (float32 or float64).  With gathered
+    records (batch64, several ranks) every mesh's record in index order, each field stacked over the meshes and NaN-padded;
+    else the one mesh's api.ModalResult.  The inputs are built from fixed seeds, so equal arguments give equal inputs."""
+    if records is not None:
+        arrays = {k: _stack_padded([r[k] for r in records]) for k in RESULT_FIELDS if k in records[0]}
+    else:
+        arrays = {k: _as_float(getattr(last, k)) for k in RESULT_FIELDS if getattr(last, k) is not None}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BYTES_MAX:
+        raise RuntimeError("--dump-outputs: %d bytes of outputs exceed the %d-byte budget" % (total, DUMP_BYTES_MAX))
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    print("bench: %d arrays, %d bytes -> %s" % (len(arrays), total, out_dir), file=sys.stderr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -372,7 +409,10 @@ def main():
     ap.add_argument("--threads", type=int, default=3, help="batch64: solves in flight per GPU")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-baseline-metric-mesh", action="store_true", help="only time the CPU oracle on the metric's own mesh on this box (~10 min) and print that record")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step returned as DIR/<field>.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.cpu_baseline_metric_mesh:  # no GPU work at all
         print(json.dumps(cpu_baseline_metric_mesh_live(args.workload)), flush=True)
         return
@@ -500,6 +540,8 @@ def main():
         last = step()
     sync(ctxs)
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:  # before the instrumented steps below replace `records`
+        dump_outputs(args.dump_outputs, last, records)
     # the roofline objects: the same steps once more with HIP events around every launch of the named kernel classes (on the
     # solver's own stream, inside the library).  Kept out of the timed region: ~700 event pairs per solve cost ~5 ms per step
     # (measured: 158.6 / 156.9 ms with them, 151.3 / 153.6 ms without, same box), which is the instrument's time, not the path's.

@@ -20,7 +20,8 @@ std::string Slurp(const fs::path &p) {
     ss << in.rdbuf();
     return ss.str();
 }
-fs::path GoldenDir() { return fs::path{GOLDEN_DIR}; }
+// tests/golden, found from this binary's own place (tests/cpp/bin/): the tree may be built in one directory and run in another
+fs::path GoldenDir() { return fs::canonical("/proc/self/exe").parent_path().parent_path().parent_path() / "golden"; }
 
 ModalModes SmallModel() {
     ModalModes m;

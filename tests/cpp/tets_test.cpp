@@ -9,9 +9,13 @@
 #include <algorithm>
 #include <cmath>
 #include <array>
+#include <filesystem>
 #include <fstream>
 #include <map>
 #include <set>
+#include <string>
+
+#include <unistd.h>
 
 namespace {
 template <class R> std::string ErrorOf(const R &r) { return r ? std::string() : r.error(); } // (error() without an error is a precondition violation)
@@ -730,7 +734,8 @@ CASE(the_general_fill_reports_unsuitable_surfaces) {
 }
 
 CASE(an_obj_file_loads_welded_and_fanned) {
-    const char *path = "/tmp/modalhip_tets_test.obj";
+    // a file of this process's own: a fixed name in the shared temp directory may belong to another user
+    const auto path = std::filesystem::temp_directory_path() / ("modalhip_tets_test_" + std::to_string(::getpid()) + ".obj");
     {
         std::ofstream out{path};
         out << "# a unit cube as quads, one corner listed twice\n"
@@ -739,6 +744,7 @@ CASE(an_obj_file_loads_welded_and_fanned) {
                "f 9 4 3 2\nf 5//1 6//1 7//1 8//1\nf 1/1 2/1 6/1 5/1\nf -7 -6 -2 -3\nf 4 1 5 8\nf 2 3 7 6\n";
     }
     const auto obj = LoadObj(path);
+    std::filesystem::remove(path);
     EXPECT(obj.has_value());
     EXPECT(obj->Positions.size() == 8);
     EXPECT(obj->TriangleIndices.size() == 36);
