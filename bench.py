@@ -4,6 +4,11 @@
     python bench.py --gpus N --steps K --warmup W                (N > 1 without a launcher: starts N ranks itself)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
     python bench.py ... --dump-outputs DIR                       (also writes the last timed step's results: DIR/<field>.npy)
+    python bench.py ... --full                                   (also everything beside the headline: roofline, secondary rows, CPU baselines)
+
+A plain run sets up, warms up, times the steps, dumps if asked and prints the line.  `--full` then runs the steps once more with
+per-launch timing for the roofline objects and, on one GPU, the secondary rows, the CPU baselines and the resonator bank
+(`--no-cpu-baseline` keeps it to the roofline steps); none of that changes `value` or `ms_per_step`.
 
 A step = one pass of the hot path over one mesh already resident in HBM: mh_assemble (FilterDegenerate, BuildQuadMesh,
 element bases, K/M assembly) + excitation sampling + mh_eigs (65 eigenpairs requested for 50 kept modes, as the
@@ -407,7 +412,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", default="cube_s100k", help="a meshes.workload name (one mesh per rank per step) or batch64 (BASELINE config 4)")
     ap.add_argument("--threads", type=int, default=3, help="batch64: solves in flight per GPU")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also the roofline steps and (one GPU) the secondary rows, CPU baselines and bank")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: the roofline steps only")
     ap.add_argument("--cpu-baseline-metric-mesh", action="store_true", help="only time the CPU oracle on the metric's own mesh on this box (~10 min) and print that record")
     ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step returned as DIR/<field>.npy (rank 0)")
     args = ap.parse_args()
@@ -540,22 +546,24 @@ def main():
         last = step()
     sync(ctxs)
     dt = time.perf_counter() - t0
-    if args.dump_outputs and rank == 0:  # before the instrumented steps below replace `records`
+    if args.dump_outputs and rank == 0:  # before the instrumented steps of --full replace `records`
         dump_outputs(args.dump_outputs, last, records)
-    # the roofline objects: the same steps once more with HIP events around every launch of the named kernel classes (on the
-    # solver's own stream, inside the library).  Kept out of the timed region: ~700 event pairs per solve cost ~5 ms per step
-    # (measured: 158.6 / 156.9 ms with them, 151.3 / 153.6 ms without, same box), which is the instrument's time, not the path's.
-    for c in ctxs:
-        c.time_kernels(True)
-    sync(ctxs)
-    t1 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
-    sync(ctxs)
-    dt_instrumented = time.perf_counter() - t1
-    stats = [{k: sum(c.kernel_stats(cls)[k] for c in ctxs) for k in ("launches", "total_ms", "total_bytes")} for cls in (0, 1, 3, 4, 5)]
-    for c in ctxs:
-        c.time_kernels(False)
+    stats = None
+    if args.full:
+        # the roofline objects: the same steps once more with HIP events around every launch of the named kernel classes (on the
+        # solver's own stream, inside the library).  Kept out of the timed region: ~700 event pairs per solve cost ~5 ms per step
+        # (measured: 158.6 / 156.9 ms with them, 151.3 / 153.6 ms without, same box), which is the instrument's time, not the path's.
+        for c in ctxs:
+            c.time_kernels(True)
+        sync(ctxs)
+        t1 = time.perf_counter()
+        for _ in range(args.steps):
+            step()
+        sync(ctxs)
+        dt_instrumented = time.perf_counter() - t1
+        stats = [{k: sum(c.kernel_stats(cls)[k] for c in ctxs) for k in ("launches", "total_ms", "total_bytes")} for cls in (0, 1, 3, 4, 5)]
+        for c in ctxs:
+            c.time_kernels(False)
 
     if dist is not None:
         t = torch.tensor([dt], dtype=torch.float64, device=gather_device)
@@ -597,42 +605,43 @@ def main():
         line["gathered_records"] = {"count": len(records), "words_per_record": sharding.record_length(NEV_MAX, POS_MAX),
                                     "fields": "eigenvalues, freqs, t60s, positions, shapes, mass properties, solve profile",
                                     "collective": "ncclAllGather from C++ (modal::SolveBatch)" if comm is not None else "torch.distributed all_gather (%s)" % ("gloo" if share_gpu else "nccl")}
-    spmm, asm, comb, comb_bytes, comb_full = stats
-    if spmm["launches"]:
-        achieved = spmm["total_bytes"] / (spmm["total_ms"] * 1e-3) / 1e9
-        line["roofline"] = {"bound": "hbm",
-                            "kernel": "k_spmm_wide / k_spmm: BSR 3x3 SpMM of the P2 and P1 operators over n-by-w panels "
-                                      "(every launch of the solve: fp32 smoother products, mixed fp64-A x fp32-panel residuals, fp64 operator products)",
-                            "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": pmc_traffic("spmm_family", args.workload), "traffic_source": "committed profile (profiles/r0N_pmc_traffic.json: separate rocprofv3 --pmc passes of this command), not measured in this run",
-                            "launches": spmm["launches"], "avg_launch_us": 1e3 * spmm["total_ms"] / spmm["launches"],
-                            "algorithmic_bytes_per_launch": spmm["total_bytes"] / spmm["launches"],
-                            "measured_in": "%d further steps after the timed region, HIP events around every launch (%.1f ms per step with them)" % (args.steps, 1e3 * dt_instrumented / args.steps)}
-    if asm["launches"]:
-        achieved = asm["total_bytes"] / (asm["total_ms"] * 1e-3) / 1e9
-        line["roofline_assembly"] = {"bound": "hbm", "kernel": "K/M assembly of the quadratic level (SURVEY 8d bytes: 152 B read per tet, 80 B written per node block)",
-                                     "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": pmc_traffic("assembly", args.workload),
-                                     "launches": asm["launches"], "avg_launch_us": 1e3 * asm["total_ms"] / asm["launches"],
-                                     "algorithmic_bytes_per_launch": asm["total_bytes"] / asm["launches"]}
-    if comb["launches"]:
-        tflops = comb["total_bytes"] / (comb["total_ms"] * 1e-3) / 1e12  # (the class's work is flops)
-        line["roofline_combine"] = {"bound": "mfma", "kernel": "k_combine: basis updates out = [X | W | P] C of the eigensolver, fp64 MFMA (v_mfma_f64_16x16x4_f64); every call of a solve",
-                                    "achieved": tflops, "peak": FP64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": tflops / FP64_MFMA_PEAK_TFLOPS, "traffic": None,
-                                    "launches": comb["launches"], "avg_launch_us": 1e3 * comb["total_ms"] / comb["launches"],
-                                    "algorithmic_flops_per_launch": comb["total_bytes"] / comb["launches"],
-                                    "algorithmic_bytes_per_launch": comb_bytes["total_bytes"] / max(1, comb_bytes["launches"]),
-                                    "hbm_GBps_at_that_time": comb_bytes["total_bytes"] / (comb["total_ms"] * 1e-3) / 1e9,
-                                    "ms_per_step": comb["total_ms"] / args.steps / max(1, len(ctxs)),
-                                    # the iteration's full-size update alone (>= 200 basis columns into >= 128 output columns: X and P together,
-                                    # 240 -> 160 on the 65-pair solve); the class average above also holds the HBM-bound projections (80 -> 80,
-                                    # accumulate: 13 flop per byte) and the coarse solve's short products
-                                    "full_size_update": ({"launches": comb_full["launches"], "avg_launch_us": 1e3 * comb_full["total_ms"] / comb_full["launches"],
-                                                          "algorithmic_flops_per_launch": comb_full["total_bytes"] / comb_full["launches"],
-                                                          "achieved": comb_full["total_bytes"] / (comb_full["total_ms"] * 1e-3) / 1e12,
-                                                          "frac": comb_full["total_bytes"] / (comb_full["total_ms"] * 1e-3) / 1e12 / FP64_MFMA_PEAK_TFLOPS} if comb_full["launches"] else None),
-                                    "peak_note": "78.6 TFLOP/s: the MI355X data sheet's fp64 matrix figure (the microarchitecture guide lists none); the device holds 2.0-2.1 GHz under these kernels, 65 TFLOP/s there"}
+    if stats is not None:
+        spmm, asm, comb, comb_bytes, comb_full = stats
+        if spmm["launches"]:
+            achieved = spmm["total_bytes"] / (spmm["total_ms"] * 1e-3) / 1e9
+            line["roofline"] = {"bound": "hbm",
+                                "kernel": "k_spmm_wide / k_spmm: BSR 3x3 SpMM of the P2 and P1 operators over n-by-w panels "
+                                          "(every launch of the solve: fp32 smoother products, mixed fp64-A x fp32-panel residuals, fp64 operator products)",
+                                "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": pmc_traffic("spmm_family", args.workload), "traffic_source": "committed profile (profiles/r0N_pmc_traffic.json: separate rocprofv3 --pmc passes of this command), not measured in this run",
+                                "launches": spmm["launches"], "avg_launch_us": 1e3 * spmm["total_ms"] / spmm["launches"],
+                                "algorithmic_bytes_per_launch": spmm["total_bytes"] / spmm["launches"],
+                                "measured_in": "%d further steps after the timed region, HIP events around every launch (%.1f ms per step with them)" % (args.steps, 1e3 * dt_instrumented / args.steps)}
+        if asm["launches"]:
+            achieved = asm["total_bytes"] / (asm["total_ms"] * 1e-3) / 1e9
+            line["roofline_assembly"] = {"bound": "hbm", "kernel": "K/M assembly of the quadratic level (SURVEY 8d bytes: 152 B read per tet, 80 B written per node block)",
+                                         "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": pmc_traffic("assembly", args.workload),
+                                         "launches": asm["launches"], "avg_launch_us": 1e3 * asm["total_ms"] / asm["launches"],
+                                         "algorithmic_bytes_per_launch": asm["total_bytes"] / asm["launches"]}
+        if comb["launches"]:
+            tflops = comb["total_bytes"] / (comb["total_ms"] * 1e-3) / 1e12  # (the class's work is flops)
+            line["roofline_combine"] = {"bound": "mfma", "kernel": "k_combine: basis updates out = [X | W | P] C of the eigensolver, fp64 MFMA (v_mfma_f64_16x16x4_f64); every call of a solve",
+                                        "achieved": tflops, "peak": FP64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": tflops / FP64_MFMA_PEAK_TFLOPS, "traffic": None,
+                                        "launches": comb["launches"], "avg_launch_us": 1e3 * comb["total_ms"] / comb["launches"],
+                                        "algorithmic_flops_per_launch": comb["total_bytes"] / comb["launches"],
+                                        "algorithmic_bytes_per_launch": comb_bytes["total_bytes"] / max(1, comb_bytes["launches"]),
+                                        "hbm_GBps_at_that_time": comb_bytes["total_bytes"] / (comb["total_ms"] * 1e-3) / 1e9,
+                                        "ms_per_step": comb["total_ms"] / args.steps / max(1, len(ctxs)),
+                                        # the iteration's full-size update alone (>= 200 basis columns into >= 128 output columns: X and P together,
+                                        # 240 -> 160 on the 65-pair solve); the class average above also holds the HBM-bound projections (80 -> 80,
+                                        # accumulate: 13 flop per byte) and the coarse solve's short products
+                                        "full_size_update": ({"launches": comb_full["launches"], "avg_launch_us": 1e3 * comb_full["total_ms"] / comb_full["launches"],
+                                                              "algorithmic_flops_per_launch": comb_full["total_bytes"] / comb_full["launches"],
+                                                              "achieved": comb_full["total_bytes"] / (comb_full["total_ms"] * 1e-3) / 1e12,
+                                                              "frac": comb_full["total_bytes"] / (comb_full["total_ms"] * 1e-3) / 1e12 / FP64_MFMA_PEAK_TFLOPS} if comb_full["launches"] else None),
+                                        "peak_note": "78.6 TFLOP/s: the MI355X data sheet's fp64 matrix figure (the microarchitecture guide lists none); the device holds 2.0-2.1 GHz under these kernels, 65 TFLOP/s there"}
     if not batch:
         line["profile"] = {k: last.profile.get(k) for k in ("assemble", "sample_excite", "factorize", "iterate", "op_solve", "extract", "restarts", "op_applications", "sytrd_redos", "rr_selfcheck")}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         if not batch and "roofline" in line:
             line["roofline"]["single_launch"] = operator_forms(api, ctxs[0], mesh, mat)
             from tools import lab
