@@ -18,6 +18,7 @@
 #include <condition_variable>
 #include <mutex>
 #include <numeric>
+#include <optional>
 #include <type_traits>
 
 __global__ void k_shift_values(const double *kval, const double *mval, size_t nblocks, double sigma, double *aval);
@@ -52,31 +53,29 @@ constexpr int TB = 256;
 // 2.0x the serial throughput on a batch of 30k-tet meshes with three threads, 2.5x on 4k-tet meshes with eight.
 // MH_CONCURRENT_SOLVES=0 restores one-solve-at-a-time (g_solve_mutex).
 std::mutex g_solve_mutex;
-// The solver's run-time switches, read ONCE per process (first use) into one immutable struct.  These are all there are
-// (DESIGN.md section 10 documents them); the alternatives that were measured and lost are gone from the code, the record of
-// each is in DESIGN.md and profiles/.
+// The solver's run-time switches, read ONCE per process (first use) into one immutable struct.  Every switch this file reads is here,
+// except MH_CONCURRENT_SOLVES=0 (g_concurrent below); DESIGN.md section 10 documents them.  The alternatives that were measured and lost
+// are gone from the code, the record of each is in DESIGN.md and profiles/.
 //   MH_VERBOSE=1            per-iteration log on stderr
 //   MH_PRECOND_FP64=1       double-precision smoothers (default: single precision with double residuals between levels)
-//   MH_CYCLE=d2,d1,g,ratio  shape of the preconditioner cycle: Chebyshev degrees of the P2 and P1 smoothers, P1 cycles per
+//   MH_CYCLE=d2,d1,g,ratio[,ratio1]  shape of the preconditioner cycle: Chebyshev degrees of the P2 and P1 smoothers, P1 cycles per
 //                           application, spectrum ratio lmax / lmin the smoothers target; 0 or missing keeps a built-in value
-//   MH_TEST=...             test hooks, comma separated: sytrd_giveup (treat every multi-workgroup tridiagonalisation as timed out: the
-//                           fall-backs to the one-workgroup kernel / the library's syevd run), no_tridiag_wide (orders above 256: the
-//                           fall-back of the partial-spectrum stage -- the library's divide and conquer and ormtr -- runs)
-//   (the A/B hooks of round 4 -- wide tridiagonalisation, small products, pivot look-ahead, power-iteration norms, wide Gram -- are gone
-//   with their measurements recorded in profiles/r04_setup_ab.txt, r04_dense_kernels.txt, r04_gram_cuts.txt and DESIGN.md section 10)
-//   MH_TEST=redzone / farzone (mh_common.h): 64 KB guard zones around every pool array, checked at release / 32 MB of unchecked slack
-// and, read elsewhere: MH_CONCURRENT_SOLVES=0 (one solve at a time), MH_AGG (aggregate size target), MH_PATCH_Q (sliver-patch
-// threshold), MH_POOL_CAP_MB (idle device-pool cap); MH_TEST also understands `poison` (NaN-filled pool allocations).
+//   MH_TEST=...             test hooks, comma separated (what each forces: beside its member): sytrd_giveup, no_tridiag_wide, last_resort,
+//                           coarse_pivot, selfcheck_fail, lmax_low, potrf_chain, no_poly_start
+// Read elsewhere: MH_AGG, MH_PATCH_Q, MH_CLUSTERS, MH_CLUSTER_CAP, MH_POOL_CAP_MB; MH_TEST's poison, redzone and farzone (mh_common.h),
+// sytrd_multi, sytrd_fused and own_gemm (mh_dense.hip).
 struct Switches {
     bool verbose = getenv("MH_VERBOSE") != nullptr;
     bool fp32_prec = !(getenv("MH_PRECOND_FP64") && atoi(getenv("MH_PRECOND_FP64")) != 0);
     int deg2 = 0, deg1 = 0, gamma = 0; // 0: the built-in cycle shape
     double cheb_ratio = 0.0, cheb_ratio1 = 0.0; // (ratio1: the P1 level's own interval, optional fifth value of MH_CYCLE)
-    bool test_sytrd_giveup = getenv("MH_TEST") && strstr(getenv("MH_TEST"), "sytrd_giveup");
-    bool no_tridiag_wide = getenv("MH_TEST") && strstr(getenv("MH_TEST"), "no_tridiag_wide");
+    bool test_sytrd_giveup = getenv("MH_TEST") && strstr(getenv("MH_TEST"), "sytrd_giveup"); // every multi-workgroup tridiagonalisation counts as timed out: the fall-backs to the one-workgroup kernel / the library's syevd run
+    bool no_tridiag_wide = getenv("MH_TEST") && strstr(getenv("MH_TEST"), "no_tridiag_wide"); // orders above 256: the fall-back of the partial-spectrum stage -- the library's divide and conquer and ormtr -- runs
     bool test_last_resort = getenv("MH_TEST") && strstr(getenv("MH_TEST"), "last_resort"); // every solve of more than 12 288 unknowns goes straight to the last resort
     bool test_coarse_pivot = getenv("MH_TEST") && strstr(getenv("MH_TEST"), "coarse_pivot"); // the first coarse elimination of a system reports a non-positive pivot
     bool test_selfcheck_fail = getenv("MH_TEST") && strstr(getenv("MH_TEST"), "selfcheck_fail"); // the first solve's Rayleigh-Ritz self-check reports a failure
+    bool lmax_low = getenv("MH_TEST") && strstr(getenv("MH_TEST"), "lmax_low"); // the smoothers' spectral bounds 12 % low, below the spectrum's end (as an unconverged power iteration leaves them): the iteration stalls
+    bool potrf_chain = getenv("MH_TEST") && strstr(getenv("MH_TEST"), "potrf_chain"); // the Gram blocks' Cholesky factorisations as the chain of launches they were before round 5
     bool no_poly_start = getenv("MH_TEST") && strstr(getenv("MH_TEST"), "no_poly_start"); // (A/B hook of round 5: the cold start block as rounds 1-4 had it)
     Switches() {
         if (const char *c = getenv("MH_CYCLE")) {
@@ -99,6 +98,7 @@ constexpr uint32_t kSkipP = 4;       // no conjugate directions in the first ite
 constexpr uint32_t kGuardPercent = 10; // guard vectors: max(15, 10 % of the wanted pairs)
 constexpr float kFlatShape = 1e-4f; // element shape measure below which a mesh counts as having flat cells: double-precision smoothers from the start
 constexpr size_t kDenseLastResort = 12288; // unknowns up to which a solve that did not converge is redone as one dense eigensolve (2 x 1.2 GB, seconds)
+constexpr int kLastResortCg = 8; // conjugate-gradient steps per search direction of the larger systems' last resort (a second try has five times as many)
 
 // readers-writer lock with writer priority (glibc's shared_mutex prefers readers: iterating solves would starve a factorisation)
 struct PhaseLock {
@@ -652,9 +652,6 @@ void small_dgemm(mh_context *ctx, rocblas_operation ta, rocblas_operation tb, ro
         ROCBLAS_CHECK(rocblas_dgemm(ctx->blas, ta, tb, M, N, K, alpha, a, lda, b, ldb, beta, c, ldc));
 }
 
-// Small generalised symmetric eigenproblem gA c = theta gM c (lower triangles given, order m, ld m):
-// Cholesky reduction + rocSOLVER syevd (rocSOLVER's sygvd reduces with an unblocked sygs2 that launches O(m) tiny
-// kernels; this form measured 2.3x faster at m = 225).  On return gA holds the gM-orthonormal eigenvectors.
 // max |gM - I| over the lower triangle, as an ordered integer so that atomicMax applies (non-negative doubles)
 __global__ void k_identity_defect(const double *__restrict__ g, uint32_t m, unsigned long long *__restrict__ out) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -726,16 +723,123 @@ void rr_selfcheck(mh_context *ctx, const double *saved, uint32_t m, const double
     KERNEL_CHECK();
 }
 
+int host_info(DevArray<int> &info) { int hinfo = 0; info.download(&hinfo, 1); return hinfo; } // a factorisation's or eigensolve's info word, read back
+// The multi-workgroup reductions can give up (a workgroup stalled by co-resident work past the poll bound): their output is then garbage.
+// flag: the reduction's give-up flag, already read back (MH_TEST=sytrd_giveup counts as set).  A give-up is counted as a redo, and gA
+// gets the symmetric matrix saved before the reduction back.
+bool sytrd_gave_up(mh_context *ctx, int flag, double *gA, const double *saved, uint32_t m) {
+    if (!flag && !switches().test_sytrd_giveup) return false;
+    ++ctx->sytrd_redos;
+    HIP_CHECK(hipMemcpyAsync(gA, saved, size_t(m) * m * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+    return true;
+}
+// Only the nwant lowest pairs are needed: the partial spectrum of T (multisection and inverse iteration) instead of the full divide and
+// conquer, accepted when its residual check passes; its eigenvalues lam then go to evals.
+bool accept_partial(mh_context *ctx, double quality, double *evals, const double *lam, uint32_t nwant) {
+    if (!(quality < 1e-10)) return false;
+    HIP_CHECK(hipMemcpyAsync(evals, lam, size_t(nwant) * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+    return true;
+}
+
+// Orders 8 .. 256: syevd by parts -- the tridiagonalisation (70 % of rocSOLVER's syevd at this order) in one workgroup of ours, then
+// rocSOLVER's divide and conquer on T (or our partial spectrum) and the back-transformation Z <- Q Z.  gA is fully symmetric.
+int eig_tridiag_small(mh_context *ctx, double *gA, uint32_t m, double *evals, double *ework, DevArray<int> &info, uint32_t nwant, std::vector<double> *host_evals) {
+    DevArray<double> z(ctx, size_t(m) * m), tau(ctx, m);
+    const bool partial = nwant && nwant < m;
+    DevArray<double> zl(ctx, partial ? size_t(m) * nwant : 0); // the first attempt's vectors: z still holds the saved matrix then
+    double *zres = z.get();
+    uint32_t ncols = m;
+    // z is free until the tridiagonal stage writes it, so it keeps a copy of the symmetric matrix, and a give-up of the multi-workgroup
+    // reduction redoes the step with the one-workgroup kernel; only a failure of that one fails the solve.
+    HIP_CHECK(hipMemcpyAsync(z.get(), gA, size_t(m) * m * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        mh_sytrd_small(ctx, gA, m, evals, ework, tau, attempt == 0 ? -1 : 0);
+        // the give-up flag travels with the next read-back of this step
+        int gave_up = 0;
+        const bool flagged = attempt == 0 && ctx->sytrd_flag;
+        if (flagged) HIP_CHECK(hipMemcpyAsync(&gave_up, ctx->sytrd_flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        if (partial) {
+            DevArray<double> wv(ctx, 2 * m + 8), ufac(ctx, size_t(3) * m * nwant);
+            double *zout = attempt == 0 ? zl.get() : z.get();
+            if (mh_tridiag_lowest(ctx, evals, ework, m, nwant, wv, zout, m, ufac, wv.get() + m, wv.get() + m + 8)) {
+                double qv[5] = {1, 0, 0, 0, 0};
+                std::vector<double> lam_host(host_evals ? nwant : 0);
+                HIP_CHECK(hipMemcpyAsync(qv, wv.get() + m, sizeof(qv), hipMemcpyDeviceToHost, ctx->stream));
+                if (host_evals) HIP_CHECK(hipMemcpyAsync(lam_host.data(), wv.get(), size_t(nwant) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+                HIP_CHECK(hipStreamSynchronize(ctx->stream));
+                if (flagged && sytrd_gave_up(ctx, gave_up, gA, z, m)) continue;
+                if (switches().verbose)
+                    fprintf(stderr, "[rr] tridiagonal m %u lowest %u: residual / ||T|| %.2e; us: multisection %.0f, inverse iteration %.0f, Gram-Schmidt %.0f, output %.0f\n", m,
+                            nwant, qv[0], qv[1] * 0.01, qv[2] * 0.01, qv[3] * 0.01, qv[4] * 0.01);
+                if (accept_partial(ctx, qv[0], evals, wv, nwant)) {
+                    if (host_evals) host_evals->swap(lam_host);
+                    zres = zout, ncols = nwant;
+                    break;
+                }
+            }
+        }
+        if (flagged) {
+            HIP_CHECK(hipStreamSynchronize(ctx->stream)); // the flag is known before garbage could reach the library
+            if (sytrd_gave_up(ctx, gave_up, gA, z, m)) continue;
+        }
+        ROCBLAS_CHECK(rocsolver_dstedc(ctx->blas, rocblas_evect_tridiagonal, m, evals, ework, z, m, info));
+        if (const int hinfo = host_info(info)) return hinfo;
+        break;
+    }
+    mh_apply_q(ctx, gA, tau, m, zres, m, ncols);
+    if (zres == zl.get()) rr_selfcheck(ctx, z.get(), m, zres, m, evals, ncols); // (z still holds the saved matrix on this path)
+    HIP_CHECK(hipMemcpyAsync(gA, zres, size_t(m) * ncols * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+    // no synchronisation: the workspaces return to the context's pool, whose blocks are only ever used on this same stream
+    return 0;
+}
+
+// Orders 257 .. 768 (the 200-mode configuration iterates at 3 x 240): the tridiagonalisation is 55 % of rocSOLVER's syevd there (8.3 of
+// 15 ms at order 720); k_sytrd_wide does it in 4.4 ms across 48 workgroups.  Then the partial spectrum (multisection, inverse iteration and
+// Cholesky-QR: mh_tridiag_lowest_wide) and Z <- Q Z by our one-launch kernel -- the library's divide and conquer and ormtr cost ~5 ms of
+// launches at order 720 -- or, failing that, those two.  Nothing when the reduction gave up: gA holds the saved matrix again.
+std::optional<int> eig_tridiag_wide(mh_context *ctx, double *gA, uint32_t m, double *evals, double *ework, DevArray<int> &info, uint32_t nwant) {
+    DevArray<double> z(ctx, size_t(m) * m), saved(ctx, size_t(m) * m), tau(ctx, m);
+    HIP_CHECK(hipMemcpyAsync(saved.get(), gA, size_t(m) * m * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+    mh_sytrd_wide(ctx, gA, m, evals, ework, tau);
+    int gave_up = 0;
+    HIP_CHECK(hipMemcpyAsync(&gave_up, ctx->sytrd_flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    if (sytrd_gave_up(ctx, gave_up, gA, saved, m)) return std::nullopt;
+    if (nwant && nwant < m && nwant <= 256 && !switches().no_tridiag_wide) {
+        DevArray<double> work(ctx, size_t(5) * nwant * m + size_t(2) * nwant * nwant + 8), lam(ctx, nwant);
+        double quality = 1.0;
+        if (mh_tridiag_lowest_wide(ctx, evals, ework, m, nwant, lam, z, m, work, info, &quality)) {
+            if (switches().verbose) fprintf(stderr, "[rr] tridiagonal m %u lowest %u (wide): residual / ||T|| %.2e\n", m, nwant, quality);
+            if (accept_partial(ctx, quality, evals, lam, nwant)) {
+                mh_apply_q(ctx, gA, tau, m, z, m, nwant);
+                rr_selfcheck(ctx, saved.get(), m, z, m, evals, nwant);
+                HIP_CHECK(hipMemcpyAsync(gA, z.get(), size_t(m) * nwant * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+                HIP_CHECK(hipStreamSynchronize(ctx->stream)); // (work and lam go back to the pool)
+                return 0;
+            }
+        }
+    }
+    ROCBLAS_CHECK(rocsolver_dstedc(ctx->blas, rocblas_evect_tridiagonal, m, evals, ework, z, m, info));
+    if (const int hinfo = host_info(info)) return hinfo;
+    ROCBLAS_CHECK(rocsolver_dormtr(ctx->blas, rocblas_side_left, rocblas_fill_lower, rocblas_operation_none, m, m, gA, m, tau, z, m));
+    HIP_CHECK(hipMemcpyAsync(gA, z.get(), size_t(m) * m * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+    HIP_CHECK(hipStreamSynchronize(ctx->stream)); // the library's internal workspace use is not ours to reason about: z goes back to the pool after it is done
+    return 0;
+}
+
+// Small generalised symmetric eigenproblem gA c = theta gM c (lower triangles given, order m, ld m) in three stages: the pencil brought to
+// standard form, the standard problem solved by order, the back-transformation (rocSOLVER's sygvd reduces with an unblocked sygs2 that
+// launches O(m) tiny kernels; this form measured 2.3x faster at m = 225).  On return gA holds the gM-orthonormal eigenvectors; a non-zero
+// return is the info of the failed factorisation or eigensolve.
 int rr_solve(mh_context *ctx, double *gA, double *gM, uint32_t m, double *evals, double *ework, DevArray<int> &info, uint32_t nwant = 0, bool gm_is_identity = false,
              std::vector<double> *host_evals = nullptr) { // host_evals: receives the nwant lowest eigenvalues when the partial-spectrum path delivered them (they travel with its quality read-back: no second synchronisation for them); left empty otherwise
     // nwant: only the nwant lowest pairs are needed (the active Ritz vectors): lets the tridiagonal stage compute a partial spectrum
     const double one = 1, zero = 0;
-    int hinfo = 0;
-    k_symmetrize_lower<<<grid1(size_t(m) * m), TB, 0, ctx->stream>>>(gA, m, m);
-    KERNEL_CHECK();
-    // The basis is built M-orthonormal (X and P by construction, W by projection + Cholesky-QR), so gM is the identity
+    // 1. Standard form.  The basis is built M-orthonormal (X and P by construction, W by projection + Cholesky-QR), so gM is the identity
     // up to the orthogonalisation error.  When that error is below 1e-11 the pencil is solved as a standard problem:
     // no Cholesky reduction (potrf + three trsm, ~1.2 ms of a ~4 ms solve at order 225).  Otherwise the full reduction.
+    k_symmetrize_lower<<<grid1(size_t(m) * m), TB, 0, ctx->stream>>>(gA, m, m);
+    KERNEL_CHECK();
     bool identity = gm_is_identity, series = false; // (gm_is_identity: every block of gM was SET by the caller, none measured: no defect to look for, no read-back)
     if (!identity) {
         static_assert(sizeof(unsigned long long) == sizeof(double), "defect word");
@@ -749,14 +853,13 @@ int rr_solve(mh_context *ctx, double *gA, double *gM, uint32_t m, double *evals,
         double d;
         memcpy(&d, &bits, sizeof(d));
         identity = d < 1e-11;
-        const bool verbose = switches().verbose;
-        if (verbose) fprintf(stderr, "[rr] m %u identity defect %.2e\n", m, d);
+        if (switches().verbose) fprintf(stderr, "[rr] m %u identity defect %.2e\n", m, d);
         // A small defect (one Cholesky-QR pass of an ill-conditioned W leaves 1e-10 .. 1e-8) is absorbed by the series
         // S = (I + E)^(-1/2) = I - E/2 + 3/8 E^2 + O(E^3): S gA S z = theta z, c = S z.  Four order-m products instead of the
         // Cholesky reduction's factorisation and three triangular solves (~1.2 ms of single-workgroup kernels).
         series = !identity && d < 1e-7;
     }
-    DevArray<double> sroot, stmp;
+    DevArray<double> sroot, stmp; // (the series' S and workspace: alive until the back-transformation)
     if (series) {
         sroot.reset(ctx, size_t(m) * m);
         stmp.reset(ctx, size_t(m) * m * 2);
@@ -774,127 +877,21 @@ int rr_solve(mh_context *ctx, double *gA, double *gM, uint32_t m, double *evals,
     }
     if (!identity) {
         mh_potrf(ctx, gM, m, m, info);
-        info.download(&hinfo, 1);
-        if (hinfo != 0) return hinfo;
+        if (const int hinfo = host_info(info)) return hinfo;
         ROCBLAS_CHECK(rocblas_dtrsm(ctx->blas, rocblas_side_left, rocblas_fill_lower, rocblas_operation_none, rocblas_diagonal_non_unit, m, m, &one, gM, m, gA, m));
         ROCBLAS_CHECK(rocblas_dtrsm(ctx->blas, rocblas_side_right, rocblas_fill_lower, rocblas_operation_transpose, rocblas_diagonal_non_unit, m, m, &one, gM, m, gA, m));
     }
-    if (m >= 8 && m <= 256) {
-        // syevd by parts: the tridiagonalisation (70 % of rocSOLVER's syevd at this order) in one workgroup of ours, then
-        // rocSOLVER's divide and conquer on T and the back-transformation Z <- Q Z
-        DevArray<double> z(ctx, size_t(m) * m), tau(ctx, m);
-        const bool partial = nwant && nwant < m;
-        DevArray<double> zl(ctx, partial ? size_t(m) * nwant : 0); // the first attempt's vectors: z still holds the saved matrix then
-        double *zres = z.get();
-        uint32_t ncols = m;
-        // The multi-workgroup reduction can give up (a workgroup stalled by co-resident work past the poll bound): its output is
-        // then garbage.  z is free until the tridiagonal stage writes it, so it keeps a copy of the symmetric matrix, and a
-        // give-up redoes the step with the one-workgroup kernel; only a failure of that one fails the solve.
-        for (int attempt = 0; attempt < 2; ++attempt) {
-            if (attempt == 0) HIP_CHECK(hipMemcpyAsync(z.get(), gA, size_t(m) * m * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-            else HIP_CHECK(hipMemcpyAsync(gA, z.get(), size_t(m) * m * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-            mh_sytrd_small(ctx, gA, m, evals, ework, tau, attempt == 0 ? -1 : 0); // gA is fully symmetric here (k_symmetrize_lower above / the reduction)
-            // the give-up flag travels with the next read-back of this step (a workgroup stalled past the poll bound by co-resident work)
-            int sytrd_gave_up = 0;
-            const bool flagged = attempt == 0 && ctx->sytrd_flag;
-            if (flagged) HIP_CHECK(hipMemcpyAsync(&sytrd_gave_up, ctx->sytrd_flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-            // only the nwant lowest pairs are needed: our multisection + inverse iteration (mh_tridiag_lowest) instead of
-            // the full divide and conquer, accepted when its residual check passes
-            bool done = false;
-            if (partial) {
-                DevArray<double> wv(ctx, 2 * m + 8), ufac(ctx, size_t(3) * m * nwant);
-                double *zout = attempt == 0 ? zl.get() : z.get();
-                if (mh_tridiag_lowest(ctx, evals, ework, m, nwant, wv, zout, m, ufac, wv.get() + m, wv.get() + m + 8)) {
-                    double qv[5] = {1, 0, 0, 0, 0};
-                    std::vector<double> lam_host(host_evals ? nwant : 0);
-                    HIP_CHECK(hipMemcpyAsync(qv, wv.get() + m, sizeof(qv), hipMemcpyDeviceToHost, ctx->stream));
-                    if (host_evals) HIP_CHECK(hipMemcpyAsync(lam_host.data(), wv.get(), size_t(nwant) * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-                    HIP_CHECK(hipStreamSynchronize(ctx->stream));
-                    if (flagged && switches().test_sytrd_giveup) sytrd_gave_up = 1;
-                    if (sytrd_gave_up) {
-                        ++ctx->sytrd_redos;
-                        continue;
-                    }
-                    const double quality = qv[0];
-                    const bool verbose = switches().verbose;
-                    if (verbose)
-                        fprintf(stderr, "[rr] tridiagonal m %u lowest %u: residual / ||T|| %.2e; us: multisection %.0f, inverse iteration %.0f, Gram-Schmidt %.0f, output %.0f\n", m,
-                                nwant, quality, qv[1] * 0.01, qv[2] * 0.01, qv[3] * 0.01, qv[4] * 0.01);
-                    if (quality < 1e-10) {
-                        if (host_evals) host_evals->swap(lam_host);
-                        HIP_CHECK(hipMemcpyAsync(evals, wv.get(), size_t(nwant) * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-                        zres = zout;
-                        ncols = nwant;
-                        done = true;
-                    }
-                }
-            }
-            if (!done) {
-                if (flagged) HIP_CHECK(hipStreamSynchronize(ctx->stream)); // the flag is known before garbage could reach the library
-                if (flagged && switches().test_sytrd_giveup) sytrd_gave_up = 1;
-                if (sytrd_gave_up) {
-                    ++ctx->sytrd_redos;
-                    continue;
-                }
-                ROCBLAS_CHECK(rocsolver_dstedc(ctx->blas, rocblas_evect_tridiagonal, m, evals, ework, z, m, info));
-                info.download(&hinfo, 1);
-                if (hinfo != 0) return hinfo;
-            }
-            break;
-        }
-        mh_apply_q(ctx, gA, tau, m, zres, m, ncols);
-        if (zres == zl.get()) rr_selfcheck(ctx, z.get(), m, zres, m, evals, ncols); // (z still holds the saved matrix on this path)
-        HIP_CHECK(hipMemcpyAsync(gA, zres, size_t(m) * ncols * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-        // no synchronisation: the workspaces return to the context's pool, whose blocks are only ever used on this same stream
-    } else {
-        // Orders 257 .. 768 (the 200-mode configuration iterates at 3 x 240): the tridiagonalisation is 55 % of rocSOLVER's syevd
-        // there (8.3 of 15 ms at order 720); k_sytrd_wide does it in 4.4 ms across 48 workgroups, then the library's divide and
-        // conquer on T and its back-transformation.  A give-up (see above) falls back to the library's syevd on the saved matrix.
-        bool done = false;
-        if (m > 256 && m <= 768 && !ctx->exchange_disabled) {
-            DevArray<double> z(ctx, size_t(m) * m), saved(ctx, size_t(m) * m), tau(ctx, m);
-            HIP_CHECK(hipMemcpyAsync(saved.get(), gA, size_t(m) * m * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-            mh_sytrd_wide(ctx, gA, m, evals, ework, tau);
-            int gave_up = 0;
-            HIP_CHECK(hipMemcpyAsync(&gave_up, ctx->sytrd_flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-            HIP_CHECK(hipStreamSynchronize(ctx->stream));
-            if (switches().test_sytrd_giveup) gave_up = 1;
-            if (gave_up) ++ctx->sytrd_redos;
-            if (gave_up) {
-                HIP_CHECK(hipMemcpyAsync(gA, saved.get(), size_t(m) * m * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-            } else if (nwant && nwant < m && nwant <= 256 && !switches().no_tridiag_wide && [&] {
-                           // only the nwant lowest pairs are needed: multisection, inverse iteration and Cholesky-QR (mh_tridiag_lowest_wide)
-                           // instead of the full divide and conquer (stedc + ormtr: ~5 ms of library launches at order 720), accepted when
-                           // its residual check passes; Z <- Q Z by our one-launch kernel
-                           DevArray<double> work(ctx, size_t(5) * nwant * m + size_t(2) * nwant * nwant + 8), lam(ctx, nwant);
-                           double quality = 1.0;
-                           if (!mh_tridiag_lowest_wide(ctx, evals, ework, m, nwant, lam, z, m, work, info, &quality)) return false;
-                           if (switches().verbose) fprintf(stderr, "[rr] tridiagonal m %u lowest %u (wide): residual / ||T|| %.2e\n", m, nwant, quality);
-                           if (!(quality < 1e-10)) return false;
-                           HIP_CHECK(hipMemcpyAsync(evals, lam.get(), size_t(nwant) * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-                           mh_apply_q(ctx, gA, tau, m, z, m, nwant);
-                           rr_selfcheck(ctx, saved.get(), m, z, m, evals, nwant);
-                           HIP_CHECK(hipMemcpyAsync(gA, z.get(), size_t(m) * nwant * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-                           HIP_CHECK(hipStreamSynchronize(ctx->stream)); // (work and lam go back to the pool)
-                           return true;
-                       }()) {
-                done = true;
-            } else {
-                ROCBLAS_CHECK(rocsolver_dstedc(ctx->blas, rocblas_evect_tridiagonal, m, evals, ework, z, m, info));
-                info.download(&hinfo, 1);
-                if (hinfo != 0) return hinfo;
-                ROCBLAS_CHECK(rocsolver_dormtr(ctx->blas, rocblas_side_left, rocblas_fill_lower, rocblas_operation_none, m, m, gA, m, tau, z, m));
-                HIP_CHECK(hipMemcpyAsync(gA, z.get(), size_t(m) * m * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-                HIP_CHECK(hipStreamSynchronize(ctx->stream)); // the library's internal workspace use is not ours to reason about: z goes back to the pool after it is done
-                done = true;
-            }
-        }
-        if (!done) {
-            ROCBLAS_CHECK(rocsolver_dsyevd(ctx->blas, rocblas_evect_original, rocblas_fill_lower, m, gA, m, evals, ework, info));
-            info.download(&hinfo, 1);
-            if (hinfo != 0) return hinfo;
-        }
+    // 2. The standard problem, by order; the library's syevd below order 8, above 768, at 257 .. 768 with the exchange kernels disabled
+    // and after a give-up of the wide reduction.
+    std::optional<int> hinfo;
+    if (m >= 8 && m <= 256) hinfo = eig_tridiag_small(ctx, gA, m, evals, ework, info, nwant, host_evals);
+    else if (m > 256 && m <= 768 && !ctx->exchange_disabled) hinfo = eig_tridiag_wide(ctx, gA, m, evals, ework, info, nwant);
+    if (!hinfo) {
+        ROCBLAS_CHECK(rocsolver_dsyevd(ctx->blas, rocblas_evect_original, rocblas_fill_lower, m, gA, m, evals, ework, info));
+        hinfo = host_info(info);
     }
+    if (*hinfo != 0) return *hinfo;
+    // 3. Back to the pencil's eigenvectors
     if (series) { // c = S z
         small_dgemm(ctx, rocblas_operation_none, rocblas_operation_none, m, m, m, &one, sroot, m, gA, m, &zero, stmp, m);
         HIP_CHECK(hipMemcpyAsync(gA, stmp.get(), size_t(m) * m * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
@@ -1131,10 +1128,7 @@ double estimate_lmax(mh_context *ctx, BsrLevel &lvl, const PatchSet &ps) {
     auto h = nrm.to_host();
     double m = 0;
     for (double s : h) m = std::max(m, std::sqrt(s));
-    // MH_TEST=lmax_low: the bound 12 % below its value, i.e. BELOW the spectrum's end -- what a power iteration that has not converged would
-    // deliver; the long Chebyshev sequences then amplify the top of the spectrum and the iteration stalls (the retry in eigs_impl is tested with it)
-    static const bool low = getenv("MH_TEST") && strstr(getenv("MH_TEST"), "lmax_low");
-    return 1.1 * m * (low ? 0.88 : 1.0);
+    return 1.1 * m * (switches().lmax_low ? 0.88 : 1.0);
 }
 } // namespace
 
@@ -1187,7 +1181,7 @@ void mh_build_hierarchy(mh_system *sys, double sigma, bool defer) {
     // (a mesh with flat cells: the Galerkin product cancels entries of 1e17 down to rigid-body terms of 1e10 and below -- its rounding is
     // ~1e-9 of the diagonal, enough to cost the coarse operator its definiteness: "coarse operator not positive definite" on one stretched
     // UV sphere of the round-6 soak.  The diagonal is lifted by that much instead of by 1e-12.)
-    k_fix_coarse_diag<<<grid1(n0), TB, 0, ctx->stream>>>(sys->a0, uint32_t(n0), std::max(std::max(sys->coarse_lift, getenv("MH_COARSE_LIFT") ? atof(getenv("MH_COARSE_LIFT")) : 0.0), sys->worst_quality < kFlatShape ? 1e-8 : 1e-12));
+    k_fix_coarse_diag<<<grid1(n0), TB, 0, ctx->stream>>>(sys->a0, uint32_t(n0), std::max(sys->coarse_lift, sys->worst_quality < kFlatShape ? 1e-8 : 1e-12));
     KERNEL_CHECK();
     DevArray<int> &info = sys->coarse_info;
     info.reset(ctx, 1);
@@ -1587,8 +1581,7 @@ struct BlockLobpcg {
             if (w <= 128) {
                 // one workgroup of ours: factor, unscale and invert in one launch (round 5; before: potrf, unscale, memset and the library's
                 // trtri -- six to eight launches, ~130 us with their gaps, twice per iteration); MH_TEST=potrf_chain: the old chain
-                static const bool chain = getenv("MH_TEST") && strstr(getenv("MH_TEST"), "potrf_chain");
-                fused_inverse = !chain;
+                fused_inverse = !switches().potrf_chain;
                 if (fused_inverse) mh_potrf_small_inverse(ctx, Gs, w, info, dscale, Linv);
                 else mh_potrf_small(ctx, Gs, w, info);
                 int both[2] = {0, 0};
@@ -2078,8 +2071,7 @@ struct BlockLobpcg {
             // Up to 128 columns: factor, unscale and invert in one launch, then Cp <- Cp L^-T as one small product (round 5; before: potrf,
             // unscale and the library's trsm, which is a trtri and several GEMM launches of its own -- a dozen launches on the serial path of
             // every iteration).  MH_TEST=potrf_chain: the old chain.
-            static const bool chain = getenv("MH_TEST") && strstr(getenv("MH_TEST"), "potrf_chain");
-            const bool fused = w <= 128 && !chain;
+            const bool fused = w <= 128 && !switches().potrf_chain;
             {
                 if (fused) mh_potrf_small_inverse(ctx, Gs, w, info, dscale, Linv_p);
                 else mh_potrf(ctx, Gs, w, w, info); // ours at every order (one workgroup up to 128 columns, 128-column blocks above)
@@ -2230,169 +2222,174 @@ struct BlockLobpcg {
         finish(eigenvalues);
     }
 };
+// One solve's attempts of the block iteration (eigs_impl): what each hands to BlockLobpcg, the seed (cleared when a seeded basis has
+// not served) and the solve's profile, which the attempts write.
+struct Attempt {
+    mh_system *sys;
+    uint32_t nev, b;
+    double sigma, residual_tol;
+    const float *seed;
+    uint32_t srows, scols;
+    const volatile unsigned char *cancel;
+    volatile float *progress;
+    double *eigenvalues;
+    mh_profile &prof;
+    mh_profile *profile;
+    // The only place a BlockLobpcg is built (inner_cg: conjugate-gradient steps per search direction, 0: the cycle alone).  Returns the
+    // MhError the run ended with, nothing when it converged; any other exception propagates.
+    std::optional<MhError> run(uint32_t max_iters, int inner_cg = 0) {
+        try {
+            BlockLobpcg solver(sys, nev, b, sigma, residual_tol, max_iters, seed, srows, scols, cancel, progress, prof, profile, inner_cg);
+            solver.run(eigenvalues);
+            return std::nullopt;
+        } catch (const MhError &e) {
+            return e;
+        }
+    }
+    // the profile the system last stored (this solve's stiffness_nonzeros and factorize are not carried over)
+    void reset_profile() {
+        prof = sys->profile;
+        prof.dofs = uint32_t(size_t(3) * sys->n_nodes);
+    }
+    // both smoothers' spectral bounds a quarter wider, once per system
+    void widen_lmax() {
+        if (sys->lmax_widened) return;
+        sys->L1.lmax *= 1.25;
+        sys->L2.lmax *= 1.25;
+        sys->lmax_widened = true;
+    }
+};
 } // namespace
 
 static void eigs_impl(mh_system *sys, uint32_t nev, double sigma, double residual_tol, uint32_t max_iters, const float *seed_basis, uint32_t seed_rows,
                       uint32_t seed_cols, const volatile unsigned char *cancel, volatile float *progress, double *eigenvalues, mh_profile *profile) {
-    {
-        mh_context *ctx = sys->ctx;
-        HIP_CHECK(hipSetDevice(ctx->device));
-        const size_t n = size_t(3) * sys->n_nodes;
-        if (nev >= n) mh_throw(MH_EINVAL, "nev %u must be below the %zu unknowns", nev, n);
-        if (!(sigma < 0)) mh_throw(MH_EFACTOR, "shift must be negative for a positive-definite shifted operator");
-        // A mesh point that no kept tetrahedron uses has empty rows in K and M: K - sigma M is singular there and the reference's
-        // Cholesky factorisation fails ("Modal shift-invert factorization failed.", CholeskyShiftInvert.cpp:44) -- so does this solve.
-        if (sys->unreferenced_points) mh_throw(MH_EFACTOR, "%u mesh point(s) belong to no tetrahedron: the shifted operator is singular", sys->unreferenced_points);
-        mh_profile prof = sys->profile;
-        prof.dofs = uint32_t(n);
-        // the reference counts the lower triangle of K (Eigen nonZeros of the lower-stored matrix, mesh2modes.cpp:615)
-        prof.stiffness_nonzeros = uint32_t((sys->L2.n_blocks - sys->n_nodes) / 2 * 9 + uint64_t(6) * sys->n_nodes);
-        if (cancel && *cancel) mh_throw(MH_ECANCELLED, "cancelled");
-        // guard vectors: at least 15 (measured at S100k, nev = 65: 10 -> 23 iterations / 338 ms, 15 -> 19 / 317 ms,
-        // 31 -> 15 / 338 ms), block rounded up to whole 16-column MFMA tiles
-        // (every further disconnected body brings six more zero modes: the block grows by as many columns)
-        // (215 pairs: 240 columns -> 23 / 24 / 21 iterations on the three 215-pair workloads, 256 columns -> 21 / 21 / 19 but +2 ... +4 % time)
-        uint32_t guards = std::max(15u, nev * kGuardPercent / 100);
-        if (const char *g = getenv("MH_GUARDS")) guards = uint32_t(std::max(1, atoi(g))); // (A/B hook: tools/probe/guard_sweep.sh)
-        uint32_t b = (nev + guards + 6u * (sys->n_components - 1u) + 15u) / 16u * 16u;
-        if (n <= 768 || n < size_t(5) * b) {
-            Timer t(ctx);
-            dense_eigs(sys, nev, sigma, eigenvalues);
-            prof.iterate = t.stop();
-            prof.restarts = 1;
-            sys->profile = prof;
-            if (profile) *profile = prof;
-        } else {
-            // Solves of any block width share the device with other contexts' work.  (Rounds 2-4 ran blocks wider than 128 columns alone, under
-            // an exclusive process-wide lock: other contexts' solves broke beside them.  Round 5 found the cause -- not the wide path
-            // itself but what ran beside it: rocBLAS's LDS-bound dsymm kernel, which only wide blocks call, on the same CU as a workgroup
-            // of k_sytrd_multi, whose barrier at the top of the column loop hipcc had left without its LDS wait; mh_common.h:
-            // mh_lds_writes_landed, DESIGN.md section 6.  With the wait in place the lock is gone.)
-            const float *seed = seed_basis; // (a warm start that fails is retried cold: build_and_solve)
-            uint32_t srows = seed_rows, scols = seed_cols;
-            const auto build_and_solve = [&] {
+    mh_context *ctx = sys->ctx;
+    HIP_CHECK(hipSetDevice(ctx->device));
+    const size_t n = size_t(3) * sys->n_nodes;
+    if (nev >= n) mh_throw(MH_EINVAL, "nev %u must be below the %zu unknowns", nev, n);
+    if (!(sigma < 0)) mh_throw(MH_EFACTOR, "shift must be negative for a positive-definite shifted operator");
+    // A mesh point that no kept tetrahedron uses has empty rows in K and M: K - sigma M is singular there and the reference's
+    // Cholesky factorisation fails ("Modal shift-invert factorization failed.", CholeskyShiftInvert.cpp:44) -- so does this solve.
+    if (sys->unreferenced_points) mh_throw(MH_EFACTOR, "%u mesh point(s) belong to no tetrahedron: the shifted operator is singular", sys->unreferenced_points);
+    mh_profile prof = sys->profile;
+    prof.dofs = uint32_t(n);
+    // the reference counts the lower triangle of K (Eigen nonZeros of the lower-stored matrix, mesh2modes.cpp:615)
+    prof.stiffness_nonzeros = uint32_t((sys->L2.n_blocks - sys->n_nodes) / 2 * 9 + uint64_t(6) * sys->n_nodes);
+    if (cancel && *cancel) mh_throw(MH_ECANCELLED, "cancelled");
+    // guard vectors: at least 15 (measured at S100k, nev = 65: 10 -> 23 iterations / 338 ms, 15 -> 19 / 317 ms,
+    // 31 -> 15 / 338 ms), block rounded up to whole 16-column MFMA tiles
+    // (every further disconnected body brings six more zero modes: the block grows by as many columns)
+    // (215 pairs: 240 columns -> 23 / 24 / 21 iterations on the three 215-pair workloads, 256 columns -> 21 / 21 / 19 but +2 ... +4 % time)
+    const uint32_t guards = std::max(15u, nev * kGuardPercent / 100);
+    const uint32_t b = (nev + guards + 6u * (sys->n_components - 1u) + 15u) / 16u * 16u;
+    if (n <= 768 || n < size_t(5) * b) {
+        Timer t(ctx);
+        dense_eigs(sys, nev, sigma, eigenvalues);
+        prof.iterate = t.stop();
+        prof.restarts = 1;
+        sys->profile = prof;
+        if (profile) *profile = prof;
+        return;
+    }
+    // Solves of any block width share the device with other contexts' work.  (Rounds 2-4 ran blocks wider than 128 columns alone, under
+    // an exclusive process-wide lock: other contexts' solves broke beside them.  Round 5 found the cause -- not the wide path
+    // itself but what ran beside it: rocBLAS's LDS-bound dsymm kernel, which only wide blocks call, on the same CU as a workgroup
+    // of k_sytrd_multi, whose barrier at the top of the column loop hipcc had left without its LDS wait; mh_common.h:
+    // mh_lds_writes_landed, DESIGN.md section 6.  With the wait in place the lock is gone.)
+    const Switches &sw = switches();
+    Attempt attempt{sys, nev, b, sigma, residual_tol, seed_basis, seed_rows, seed_cols, cancel, progress, eigenvalues, prof, profile};
+    // The shift is negative (checked above), so K - sigma M IS positive definite and so is every Galerkin coarse operator of it in exact
+    // arithmetic: a coarse elimination that meets a non-positive pivot has lost it to rounding (flat cells: entries of 1e17 cancelling).
+    // That is not the caller's "factorization failed": the diagonal lift of the coarse operator goes up a thousandfold and the hierarchy
+    // and every attempt below are redone, twice at most.
+    for (int lifted = 0;; ++lifted) {
+        try {
             {
                 Timer t(ctx);
                 mh_build_hierarchy(sys, sigma, true); // (the coarse elimination may still run: the first preconditioner application waits for it)
                 prof.factorize = t.stop();
             }
             if (progress) *progress = 0.3f;
-            try {
-                try {
-                    try {
-                        if (switches().test_last_resort) mh_throw(MH_ENOTCONVERGED, "MH_TEST=last_resort");
-                        try {
-                            BlockLobpcg solver(sys, nev, b, sigma, residual_tol, max_iters, seed, srows, scols, cancel, progress, prof, profile);
-                            solver.run(eigenvalues);
-                        } catch (const MhError &e) {
-                            // A seeded basis that does not serve -- its columns in another order than the solve left them (the exact rigid-body vectors
-                            // then stand beside their seeded copies: a rank-deficient block), zeros, a NaN, one column forty-five times -- is no
-                            // reason to go through the fall-backs below with it, or to return nothing: the reference's SubspaceIterate takes what
-                            // it is given.  Once more from a cold start, and the fall-backs after that are cold as well.
-                            if (!seed || e.code != MH_ENOTCONVERGED || max_iters < 50) throw;
-                            if (switches().verbose) fprintf(stderr, "[lobpcg] %s -- the seeded basis did not serve: once more from a cold start\n", e.what());
-                            seed = nullptr, srows = 0, scols = 0;
-                            prof = sys->profile;
-                            prof.dofs = uint32_t(n);
-                            BlockLobpcg solver(sys, nev, b, sigma, residual_tol, max_iters, seed, srows, scols, cancel, progress, prof, profile);
-                            solver.run(eigenvalues);
-                        }
-                    } catch (const MhError &e) {
-                        // A Rayleigh-Ritz step whose eigenpairs do not fit the step's own matrix (k_rr_selfcheck: sampled per step, read once at
-                        // the end) means a dense kernel delivered wrong numbers -- in rounds 2-4 the tagged exchange beside an LDS-bound
-                        // neighbour.  Rather than hand the caller MH_EHIP after a whole solve's time: once more with the
-                        // exchange kernel out of the path (orders 257-768 go to the library's syevd); the context remembers.
-                        if (e.code != MH_EHIP || !strstr(e.what(), "self-check") || ctx->exchange_disabled) throw;
-                        if (switches().verbose) fprintf(stderr, "[lobpcg] %s -- once more without the exchange kernels\n", e.what());
-                        ctx->exchange_disabled = true;
-                        prof = sys->profile;
-                        prof.dofs = uint32_t(n);
-                        BlockLobpcg solver(sys, nev, b, sigma, residual_tol, max_iters, seed, srows, scols, cancel, progress, prof, profile);
-                        solver.run(eigenvalues);
-                    }
-                } catch (const MhError &e) {
-                    // A Chebyshev smoother whose interval ends below lmax(D^-1 A) amplifies the top of the spectrum instead of damping it -- by
-                    // T_deg(1 + 2 x overshoot): twelve-fold per smoothing at degree 16 for 2 %.  The bound is a power-iteration estimate times 1.1
-                    // (measured margin on the workloads: 6-9 %); should it fall short on some mesh, the iteration stalls or loses rank.  One retry
-                    // with both levels' bounds widened by a quarter (costs the smoothers a few per cent of their efficiency, nothing else).
-                    // (not for a mesh with flat cells: what fails there is not the bound -- the last resort below is next)
-                    if (e.code != MH_ENOTCONVERGED || max_iters < 50 || sys->lmax_widened || switches().test_last_resort || sys->worst_quality < kFlatShape) throw;
-                    if (switches().verbose) fprintf(stderr, "[lobpcg] %s -- once more with the smoothers' spectral bounds widened by 25 %%\n", e.what());
-                    sys->L1.lmax *= 1.25;
-                    sys->L2.lmax *= 1.25;
-                    sys->lmax_widened = true;
-                    BlockLobpcg solver(sys, nev, b, sigma, residual_tol, max_iters, seed, srows, scols, cancel, progress, prof, profile);
-                    solver.run(eigenvalues);
+            // The first attempt, then the rescues in order.  Each rescue runs only when the error the latest attempt left matches its guard;
+            // otherwise that error passes on to the next one, and what is left after the last is thrown.
+            std::optional<MhError> err;
+            if (sw.test_last_resort) err = MhError(MH_ENOTCONVERGED, "MH_TEST=last_resort"); // (test hook: no first attempt and no seeded-basis retry)
+            else err = attempt.run(max_iters);
+            // A seeded basis that does not serve -- its columns in another order than the solve left them (the exact rigid-body vectors
+            // then stand beside their seeded copies: a rank-deficient block), zeros, a NaN, one column forty-five times -- is no
+            // reason to go through the rescues below with it, or to return nothing: the reference's SubspaceIterate takes what
+            // it is given.  Once more from a cold start, and the rescues after that are cold as well.
+            if (err && !sw.test_last_resort && attempt.seed && err->code == MH_ENOTCONVERGED && max_iters >= 50) {
+                if (sw.verbose) fprintf(stderr, "[lobpcg] %s -- the seeded basis did not serve: once more from a cold start\n", err->what());
+                attempt.seed = nullptr, attempt.srows = 0, attempt.scols = 0;
+                attempt.reset_profile();
+                err = attempt.run(max_iters);
+            }
+            // A Rayleigh-Ritz step whose eigenpairs do not fit the step's own matrix (k_rr_selfcheck: sampled per step, read once at
+            // the end) means a dense kernel delivered wrong numbers -- in rounds 2-4 the tagged exchange beside an LDS-bound
+            // neighbour.  Rather than hand the caller MH_EHIP after a whole solve's time: once more with the
+            // exchange kernel out of the path (orders 257-768 go to the library's syevd); the context remembers.
+            if (err && err->code == MH_EHIP && strstr(err->what(), "self-check") && !ctx->exchange_disabled) {
+                if (sw.verbose) fprintf(stderr, "[lobpcg] %s -- once more without the exchange kernels\n", err->what());
+                ctx->exchange_disabled = true;
+                attempt.reset_profile();
+                err = attempt.run(max_iters);
+            }
+            // A Chebyshev smoother whose interval ends below lmax(D^-1 A) amplifies the top of the spectrum instead of damping it -- by
+            // T_deg(1 + 2 x overshoot): twelve-fold per smoothing at degree 16 for 2 %.  The bound is a power-iteration estimate times 1.1
+            // (measured margin on the workloads: 6-9 %); should it fall short on some mesh, the iteration stalls or loses rank.  One retry
+            // with both levels' bounds widened by a quarter (costs the smoothers a few per cent of their efficiency, nothing else).
+            // (not for a mesh with flat cells: what fails there is not the bound -- the last resort below is next)
+            if (err && err->code == MH_ENOTCONVERGED && max_iters >= 50 && !sys->lmax_widened && !sw.test_last_resort && !(sys->worst_quality < kFlatShape)) {
+                if (sw.verbose) fprintf(stderr, "[lobpcg] %s -- once more with the smoothers' spectral bounds widened by 25 %%\n", err->what());
+                attempt.widen_lmax();
+                err = attempt.run(max_iters);
+            }
+            // Last resort of a LARGER system (round 6): the block iteration once more with (nearly) the reference's own search directions --
+            // A^-1 r by eight conjugate-gradient steps around the double-precision cycle instead of the cycle alone (PanelCg).  Ten times
+            // the cost per iteration, a handful of iterations; reached only by meshes the attempts above gave up on (cells flat to
+            // 1e-9 in a caller's own mesh: the front end's fills have none since round 6).  MH_ENOTCONVERGED is what is left when this
+            // fails too.  MH_TEST=last_resort sends every solve here (tests).
+            if (err && err->code == MH_ENOTCONVERGED && n > kDenseLastResort && max_iters >= 50) {
+                if (sw.verbose) fprintf(stderr, "[lobpcg] %s -- last resort: conjugate-gradient search directions\n", err->what());
+                const MhError stopped = *err; // (what the caller reads first should this fail too: why the solve itself stopped)
+                attempt.reset_profile();
+                // (with the smoothers' bounds a quarter wider, if they are not already: the conjugate gradients around the cycle need it to be
+                // positive definite, i.e. no end of the spectrum above the bound -- on the 128 x 64 sphere's flat fill 19 iterations with the
+                // wider bounds against 59 without)
+                attempt.widen_lmax();
+                // (eight steps first; a mesh they do not do -- ||A|| / theta ~ 1e11: the cycle is a poor preconditioner of the flat cells' rows -- gets
+                // forty: each outer iteration is then nearly an exact inverse iteration, at fifty cycles' cost)
+                err = attempt.run(max_iters, kLastResortCg);
+                if (err && err->code == MH_ENOTCONVERGED) {
+                    if (sw.verbose) fprintf(stderr, "[lobpcg] the last resort with %d conjugate-gradient steps: %s -- once more with %d\n", kLastResortCg, err->what(), 5 * kLastResortCg);
+                    attempt.reset_profile();
+                    err = attempt.run(std::min<uint32_t>(max_iters, 120), 5 * kLastResortCg);
+                    if (err && err->code == MH_ENOTCONVERGED) mh_throw(MH_ENOTCONVERGED, "%s (the last resort too: %s)", stopped.what(), err->what());
                 }
-            } catch (const MhError &e) {
-                // Last resort of a LARGER system (round 6): the block iteration once more with (nearly) the reference's own search directions --
-                // A^-1 r by eight conjugate-gradient steps around the double-precision cycle instead of the cycle alone (PanelCg).  Ten times
-                // the cost per iteration, a handful of iterations; reached only by meshes the two attempts above gave up on (cells flat to
-                // 1e-9 in a caller's own mesh: the front end's fills have none since round 6).  MH_ENOTCONVERGED is what is left when this
-                // fails too.  MH_TEST=last_resort sends every solve here (tests).
-                if (e.code == MH_ENOTCONVERGED && n > kDenseLastResort && max_iters >= 50) {
-                    if (switches().verbose) fprintf(stderr, "[lobpcg] %s -- last resort: conjugate-gradient search directions\n", e.what());
-                    prof = sys->profile;
-                    prof.dofs = uint32_t(n);
-                    // (with the smoothers' bounds a quarter wider, if they are not already: the conjugate gradients around the cycle need it to be
-                    // positive definite, i.e. no end of the spectrum above the bound -- on the 128 x 64 sphere's flat fill 19 iterations with the
-                    // wider bounds against 59 without)
-                    if (!sys->lmax_widened) {
-                        sys->L1.lmax *= 1.25;
-                        sys->L2.lmax *= 1.25;
-                        sys->lmax_widened = true;
-                    }
-                    // (eight steps first; a mesh they do not do -- ||A|| / theta ~ 1e11: the cycle is a poor preconditioner of the flat cells' rows -- gets
-                    // forty: each outer iteration is then nearly an exact inverse iteration, at fifty cycles' cost)
-                    static const int first_steps = getenv("MH_LAST_RESORT_CG") ? std::max(1, atoi(getenv("MH_LAST_RESORT_CG"))) : 8;
-                    for (const int steps : {first_steps, 5 * first_steps}) {
-                        try {
-                            BlockLobpcg solver(sys, nev, b, sigma, residual_tol, steps == first_steps ? max_iters : std::min<uint32_t>(max_iters, 120), seed, srows, scols, cancel, progress, prof, profile, steps);
-                            solver.run(eigenvalues);
-                            return;
-                        } catch (const MhError &again) {
-                            if (again.code != MH_ENOTCONVERGED) throw;
-                            if (steps == first_steps) {
-                                if (switches().verbose) fprintf(stderr, "[lobpcg] the last resort with %d conjugate-gradient steps: %s -- once more with %d\n", steps, again.what(), 5 * steps);
-                                prof = sys->profile;
-                                prof.dofs = uint32_t(n);
-                                continue;
-                            }
-                            mh_throw(MH_ENOTCONVERGED, "%s (the last resort too: %s)", e.what(), again.what()); // what the caller reads first is why the solve itself stopped
-                        }
-                    }
-                    return;
-                }
-                // Last resort of a SMALL system whose iteration stalled (measured: a UV sphere's surface filled without interior
-                // points -- a quarter of the tetrahedra flat to 1e-8, ||A|| / theta ~ 1e13): one dense eigensolve in the inverse
-                // form.  O(n^3), seconds at the size limit: better than no modes for an editor primitive.
-                // (not when the caller's own iteration limit is what stopped it: MaxRestarts exceeded stays the reference's empty result)
-                if (e.code != MH_ENOTCONVERGED || n > kDenseLastResort || max_iters < 50) throw;
-                if (switches().verbose) fprintf(stderr, "[lobpcg] %s -- dense eigensolve of order %zu instead\n", e.what(), n);
+            }
+            // Last resort of a SMALL system whose iteration stalled (measured: a UV sphere's surface filled without interior
+            // points -- a quarter of the tetrahedra flat to 1e-8, ||A|| / theta ~ 1e13): one dense eigensolve in the inverse
+            // form.  O(n^3), seconds at the size limit: better than no modes for an editor primitive.
+            // (not when the caller's own iteration limit is what stopped it: MaxRestarts exceeded stays the reference's empty result)
+            if (err && err->code == MH_ENOTCONVERGED && n <= kDenseLastResort && max_iters >= 50) {
+                if (sw.verbose) fprintf(stderr, "[lobpcg] %s -- dense eigensolve of order %zu instead\n", err->what(), n);
                 Timer t(ctx);
                 dense_eigs(sys, nev, sigma, eigenvalues, true);
-                prof = sys->profile;
-                prof.dofs = uint32_t(n);
+                attempt.reset_profile();
                 prof.iterate += t.stop();
                 prof.restarts = max_iters + 1;
                 sys->profile = prof;
                 if (profile) *profile = prof;
+                err.reset();
             }
-            };
-            // The shift is negative (checked above), so K - sigma M IS positive definite and so is every Galerkin coarse operator of it in exact
-            // arithmetic: a coarse elimination that meets a non-positive pivot has lost it to rounding (flat cells: entries of 1e17 cancelling).
-            // That is not the caller's "factorization failed": the diagonal lift of the coarse operator goes up a thousandfold, twice at most.
-            for (int lifted = 0;; ++lifted) {
-                try {
-                    build_and_solve();
-                    break;
-                } catch (const MhError &e) {
-                    if (e.code != MH_EFACTOR || !strstr(e.what(), "coarse operator") || lifted >= 2) throw;
-                    sys->coarse_lift = (sys->coarse_lift > 0 ? sys->coarse_lift : 1e-9) * 1e3;
-                    sys->hierarchy_ready = false;
-                    if (switches().verbose) fprintf(stderr, "[lobpcg] %s -- the coarse operator's diagonal lifted by %.0e, once more\n", e.what(), sys->coarse_lift);
-                }
-            }
+            if (err) throw *err;
+            return;
+        } catch (const MhError &e) {
+            if (e.code != MH_EFACTOR || !strstr(e.what(), "coarse operator") || lifted >= 2) throw;
+            sys->coarse_lift = (sys->coarse_lift > 0 ? sys->coarse_lift : 1e-9) * 1e3;
+            sys->hierarchy_ready = false;
+            if (sw.verbose) fprintf(stderr, "[lobpcg] %s -- the coarse operator's diagonal lifted by %.0e, once more\n", e.what(), sys->coarse_lift);
         }
     }
 }
