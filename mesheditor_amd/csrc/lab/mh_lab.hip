@@ -283,6 +283,87 @@ int mhl_context_tridiagonalize_full(mh_context *ctx, int variant, uint32_t m, co
     } catch (const std::exception &e) { return mh_guard(ctx, e); }
 }
 
+// The k lowest eigenpairs of the symmetric tridiagonal (d[m], e[m - 1]) by the Rayleigh-Ritz step's partial-spectrum kernels:
+// mh_tridiag_lowest for m <= 256, mh_tridiag_lowest_wide for 257 .. 768.  w[k], z (m x k, column-major), *quality the kernels' own
+// residual measure (NaN when a factorisation failed); *taken = 0 when the call declined the problem (w, z, quality then untouched).
+int mhl_context_tridiag_lowest(mh_context *ctx, uint32_t m, uint32_t k, const double *d, const double *e, double *w, double *z, double *quality, int *taken) {
+    if (!ctx || !d || !e || !w || !z || !quality || !taken || m < 2 || m > 768 || k < 1) return MH_EINVAL;
+    try {
+        HIP_CHECK(hipSetDevice(ctx->device));
+        MhSharedPhase not_during_a_factorisation(ctx->device);
+        DevArray<double> dd(ctx, m), de(ctx, m), dw(ctx, k), dz(ctx, size_t(m) * k);
+        dd.upload(d, m);
+        de.zero();
+        de.upload(e, m - 1);
+        bool ok;
+        double q = std::numeric_limits<double>::quiet_NaN();
+        if (m <= 256) {
+            DevArray<double> ufac(ctx, size_t(3) * m * k), qv(ctx, 8), lam(ctx, k);
+            ok = mh_tridiag_lowest(ctx, dd, de, m, k, dw, dz, m, ufac, qv, lam);
+            if (ok) qv.download(&q, 1);
+        } else {
+            DevArray<double> work(ctx, size_t(5) * k * m + size_t(2) * k * k + 8);
+            DevArray<int> info(ctx, 2);
+            ok = mh_tridiag_lowest_wide(ctx, dd, de, m, k, dw, dz, m, work, info, &q);
+        }
+        *taken = ok ? 1 : 0;
+        if (ok) {
+            dw.download(w, k);
+            dz.download(z, size_t(m) * k);
+            *quality = q;
+        }
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        return MH_OK;
+    } catch (const std::exception &ex) { return mh_guard(ctx, ex); }
+}
+
+// One Rayleigh-Ritz step, mh_rr_solve itself, on host matrices (order m, column-major, lower triangles used; mmat may be null when
+// gm_is_identity).  evals receives the *ncols eigenvalues, vectors (m x *ncols, column-major) the gM-orthonormal eigenvectors: nwant
+// columns when a partial path delivered them, m otherwise.  host_evals (nwant) receives the eigenvalues the partial path read back
+// itself.  trace[6]: reduction, measured defect (-1: none), standard solver (MhRrTrace's codes), partial quality (NaN: none ran),
+// the self-check word (zeroed before the step, read after it), the count of host eigenvalues.  MH_EFACTOR when the step failed.
+int mhl_context_rr_solve(mh_context *ctx, uint32_t m, const double *a, const double *mmat, uint32_t nwant, int gm_is_identity, double *evals, double *vectors, uint32_t *ncols,
+                         double *host_evals, double *trace) {
+    if (!ctx || !a || (!mmat && !gm_is_identity) || !evals || !vectors || !ncols || !trace || m < 1 || m > 1024 || nwant > m) return MH_EINVAL;
+    struct TraceOn {
+        mh_context *ctx;
+        ~TraceOn() { ctx->rr_trace = nullptr; }
+    };
+    try {
+        HIP_CHECK(hipSetDevice(ctx->device));
+        MhSharedPhase not_during_a_factorisation(ctx->device);
+        const size_t mm = size_t(m) * m;
+        DevArray<double> gA(ctx, mm), gM(ctx, mm), ev(ctx, m), ework(ctx, m);
+        DevArray<int> info(ctx, 2);
+        info.zero();
+        gA.upload(a, mm);
+        if (mmat) gM.upload(mmat, mm);
+        else gM.zero();
+        if (ctx->rr_check) HIP_CHECK(hipMemsetAsync(ctx->rr_check, 0, sizeof(unsigned long long), ctx->stream));
+        MhRrTrace tr;
+        std::vector<double> hv;
+        int hinfo;
+        {
+            ctx->rr_trace = &tr;
+            TraceOn off{ctx};
+            hinfo = mh_rr_solve(ctx, gA, gM, m, ev, ework, info, nwant, gm_is_identity != 0, host_evals ? &hv : nullptr);
+        }
+        unsigned long long check = 0;
+        if (ctx->rr_check) HIP_CHECK(hipMemcpyAsync(&check, ctx->rr_check, sizeof(check), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        double checkd;
+        memcpy(&checkd, &check, sizeof(checkd));
+        const bool partial = tr.solver == MhRrTrace::SMALL_PARTIAL || tr.solver == MhRrTrace::WIDE_PARTIAL;
+        *ncols = hinfo ? 0 : (partial ? nwant : m);
+        trace[0] = tr.reduction, trace[1] = tr.defect, trace[2] = tr.solver, trace[3] = tr.quality, trace[4] = checkd, trace[5] = double(hv.size());
+        if (hinfo) return MH_EFACTOR;
+        ev.download(evals, *ncols);
+        gA.download(vectors, size_t(m) * *ncols);
+        if (host_evals && !hv.empty()) std::copy(hv.begin(), hv.end(), host_evals);
+        return MH_OK;
+    } catch (const std::exception &ex) { return mh_guard(ctx, ex); }
+}
+
 // The Cholesky-QR step's one-launch kernel: l <- diag(1 / dscale) chol(a) (lower, zeros above), linv <- l^-1; info[0] = 0 or the failing column,
 // info[1] = the diagonal spread report.  Column-major host arrays of order w <= 128.
 int mhl_context_potrf_inverse(mh_context *ctx, uint32_t w, const double *a, const double *dscale, double *l, double *linv, int *info2) {

@@ -20,6 +20,14 @@ int mhl_context_bench_dense(mh_context *, int kind, uint64_t n, uint32_t wa, uin
 int mhl_context_tridiagonalize(mh_context *, int variant, uint32_t m, const double *a, double *d, double *e, uint32_t reps, double *avg_ms);
 /* the same with the reflectors (m x m, LAPACK's lower storage) and tau returned; variant 2 = the wide kernel, orders up to 768 */
 int mhl_context_tridiagonalize_full(mh_context *, int variant, uint32_t m, const double *a, double *d, double *e, double *reflectors, double *tau, uint32_t reps, double *avg_ms);
+/* The k lowest eigenpairs of a symmetric tridiagonal matrix (d[m], e[m - 1]) by the Rayleigh-Ritz step's partial-spectrum kernels (m <= 256:
+ * one workgroup; 257 .. 768: the wide form): w[k], z (m x k, column-major), the kernels' own quality (NaN: a factorisation failed), taken = 0
+ * when the call declined. */
+int mhl_context_tridiag_lowest(mh_context *, uint32_t m, uint32_t k, const double *d, const double *e, double *w, double *z, double *quality, int *taken);
+/* One Rayleigh-Ritz step (the solver's rr_solve) on host matrices, lower triangles, column-major: evals[ncols], vectors (m x ncols),
+ * host_evals (nwant), trace[6] = reduction, defect, standard solver, partial quality, self-check word, host eigenvalue count */
+int mhl_context_rr_solve(mh_context *, uint32_t m, const double *a, const double *mmat, uint32_t nwant, int gm_is_identity, double *evals, double *vectors, uint32_t *ncols,
+                         double *host_evals, double *trace);
 /* C (M x N, ldc) = alpha op(A) op(B) + beta C through the Rayleigh-Ritz step's small-product kernel; column-major host arrays, c in and out */
 int mhl_context_potrf_inverse(mh_context *, uint32_t w, const double *a, const double *dscale, double *l, double *linv, int *info2);
 int mhl_context_spd_inverse(mh_context *, uint32_t w, const double *a, double *out, uint32_t reps, double *avg_ms);

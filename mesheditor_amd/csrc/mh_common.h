@@ -13,6 +13,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <iterator>
+#include <limits>
 #include <map>
 #include <mutex>
 #include <stdexcept>
@@ -294,6 +295,7 @@ struct mh_context {
     bool exchange_disabled{false};          // set after a failed Rayleigh-Ritz self-check: orders 257-768 then go to the library's syevd instead of the tagged-exchange kernel (k_sytrd_wide), and the solve is redone once
     uint32_t sytrd_redos{0};                // Rayleigh-Ritz steps redone by a fall-back because a workgroup of the exchange gave up (co-resident work stalled it past the poll bound); mh_profile reports the count per solve
     unsigned long long *rr_check{nullptr};  // device word: worst sampled residual of the Rayleigh-Ritz steps' self-check (k_rr_selfcheck), double bits folded by atomicMax
+    struct MhRrTrace *rr_trace{nullptr};    // when set (lab entry points only, never the product): mh_rr_solve records there what it ran
     // Optional per-launch timing of the path's named kernels (measurement aid for bench.py's roofline objects): HIP
     // events on this stream around every launch of a kernel class, resolved lazily.  `work` is the class's algorithmic
     // unit: bytes for the HBM-bound classes, flops for the resonator bank.
@@ -546,6 +548,19 @@ bool mh_tridiag_lowest_wide(mh_context *ctx, const double *d, const double *e, u
 void mh_apply_q(mh_context *ctx, const double *a, const double *tau, uint32_t m, double *z, uint32_t ldz, uint32_t ncols); // mh_dense.hip: Z <- Q Z after mh_sytrd_small / mh_sytrd_wide (order <= 768)
 bool mh_tridiag_lowest(mh_context *ctx, const double *d, const double *e, uint32_t m, uint32_t k, double *w, double *z, uint32_t ldz, double *ufac,
                        double *quality, double *lam_scratch); // mh_dense.hip: k lowest eigenpairs of a tridiagonal matrix (quality: 8 doubles, lam_scratch: k)
+// What one Rayleigh-Ritz step ran, from values mh_rr_solve already holds on the host (no launch, read-back or synchronisation of its own)
+struct MhRrTrace {
+    enum Reduction { GIVEN_IDENTITY = 0, MEASURED_IDENTITY = 1, SERIES = 2, CHOLESKY = 3 };
+    enum Solver { SYEVD = 0, SMALL_PARTIAL = 1, SMALL_STEDC = 2, WIDE_PARTIAL = 3, WIDE_STEDC_ORMTR = 4 };
+    int reduction{-1};
+    double defect{-1};   // max |gM - I| over the lower triangle; -1 when not measured
+    int solver{-1};
+    double quality{std::numeric_limits<double>::quiet_NaN()}; // the last partial-spectrum quality accept_partial judged; NaN when none ran
+};
+// mh_eigs.hip: the small generalised eigenproblem gA c = theta gM c of a Rayleigh-Ritz step (lower triangles, column-major, ld m); on return
+// gA holds the gM-orthonormal eigenvectors (nwant columns when a partial path delivered them, else m).  Non-zero: the failed factorisation's info.
+int mh_rr_solve(mh_context *ctx, double *gA, double *gM, uint32_t m, double *evals, double *ework, DevArray<int> &info, uint32_t nwant = 0, bool gm_is_identity = false,
+                std::vector<double> *host_evals = nullptr);
 void mh_spd_inverse_small(mh_context *ctx, const double *a, uint32_t lda, uint32_t w, double *out, uint32_t ldo, int *info); // mh_dense.hip
 void mh_potrf(mh_context *ctx, double *a, uint32_t ld, uint32_t w, int *info); // mh_dense.hip: lower Cholesky of any order without rocSOLVER (info: two ints)
 void mh_potrf_small(mh_context *ctx, double *a, uint32_t w, int *info); // mh_dense.hip: lower Cholesky, order <= 128, one workgroup

@@ -771,6 +771,7 @@ int eig_tridiag_small(mh_context *ctx, double *gA, uint32_t m, double *evals, do
                 if (switches().verbose)
                     fprintf(stderr, "[rr] tridiagonal m %u lowest %u: residual / ||T|| %.2e; us: multisection %.0f, inverse iteration %.0f, Gram-Schmidt %.0f, output %.0f\n", m,
                             nwant, qv[0], qv[1] * 0.01, qv[2] * 0.01, qv[3] * 0.01, qv[4] * 0.01);
+                if (ctx->rr_trace) ctx->rr_trace->quality = qv[0];
                 if (accept_partial(ctx, qv[0], evals, wv, nwant)) {
                     if (host_evals) host_evals->swap(lam_host);
                     zres = zout, ncols = nwant;
@@ -786,6 +787,7 @@ int eig_tridiag_small(mh_context *ctx, double *gA, uint32_t m, double *evals, do
         if (const int hinfo = host_info(info)) return hinfo;
         break;
     }
+    if (ctx->rr_trace) ctx->rr_trace->solver = ncols < m ? MhRrTrace::SMALL_PARTIAL : MhRrTrace::SMALL_STEDC;
     mh_apply_q(ctx, gA, tau, m, zres, m, ncols);
     if (zres == zl.get()) rr_selfcheck(ctx, z.get(), m, zres, m, evals, ncols); // (z still holds the saved matrix on this path)
     HIP_CHECK(hipMemcpyAsync(gA, zres, size_t(m) * ncols * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
@@ -810,7 +812,9 @@ std::optional<int> eig_tridiag_wide(mh_context *ctx, double *gA, uint32_t m, dou
         double quality = 1.0;
         if (mh_tridiag_lowest_wide(ctx, evals, ework, m, nwant, lam, z, m, work, info, &quality)) {
             if (switches().verbose) fprintf(stderr, "[rr] tridiagonal m %u lowest %u (wide): residual / ||T|| %.2e\n", m, nwant, quality);
+            if (ctx->rr_trace) ctx->rr_trace->quality = quality;
             if (accept_partial(ctx, quality, evals, lam, nwant)) {
+                if (ctx->rr_trace) ctx->rr_trace->solver = MhRrTrace::WIDE_PARTIAL;
                 mh_apply_q(ctx, gA, tau, m, z, m, nwant);
                 rr_selfcheck(ctx, saved.get(), m, z, m, evals, nwant);
                 HIP_CHECK(hipMemcpyAsync(gA, z.get(), size_t(m) * nwant * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
@@ -822,17 +826,20 @@ std::optional<int> eig_tridiag_wide(mh_context *ctx, double *gA, uint32_t m, dou
     ROCBLAS_CHECK(rocsolver_dstedc(ctx->blas, rocblas_evect_tridiagonal, m, evals, ework, z, m, info));
     if (const int hinfo = host_info(info)) return hinfo;
     ROCBLAS_CHECK(rocsolver_dormtr(ctx->blas, rocblas_side_left, rocblas_fill_lower, rocblas_operation_none, m, m, gA, m, tau, z, m));
+    if (ctx->rr_trace) ctx->rr_trace->solver = MhRrTrace::WIDE_STEDC_ORMTR;
     HIP_CHECK(hipMemcpyAsync(gA, z.get(), size_t(m) * m * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
     HIP_CHECK(hipStreamSynchronize(ctx->stream)); // the library's internal workspace use is not ours to reason about: z goes back to the pool after it is done
     return 0;
 }
 
+} // namespace
+
 // Small generalised symmetric eigenproblem gA c = theta gM c (lower triangles given, order m, ld m) in three stages: the pencil brought to
 // standard form, the standard problem solved by order, the back-transformation (rocSOLVER's sygvd reduces with an unblocked sygs2 that
 // launches O(m) tiny kernels; this form measured 2.3x faster at m = 225).  On return gA holds the gM-orthonormal eigenvectors; a non-zero
-// return is the info of the failed factorisation or eigensolve.
-int rr_solve(mh_context *ctx, double *gA, double *gM, uint32_t m, double *evals, double *ework, DevArray<int> &info, uint32_t nwant = 0, bool gm_is_identity = false,
-             std::vector<double> *host_evals = nullptr) { // host_evals: receives the nwant lowest eigenvalues when the partial-spectrum path delivered them (they travel with its quality read-back: no second synchronisation for them); left empty otherwise
+// return is the info of the failed factorisation or eigensolve.  ctx->rr_trace, when set, receives what ran.
+int mh_rr_solve(mh_context *ctx, double *gA, double *gM, uint32_t m, double *evals, double *ework, DevArray<int> &info, uint32_t nwant, bool gm_is_identity,
+                std::vector<double> *host_evals) { // host_evals: receives the nwant lowest eigenvalues when the partial-spectrum path delivered them (they travel with its quality read-back: no second synchronisation for them); left empty otherwise
     // nwant: only the nwant lowest pairs are needed (the active Ritz vectors): lets the tridiagonal stage compute a partial spectrum
     const double one = 1, zero = 0;
     // 1. Standard form.  The basis is built M-orthonormal (X and P by construction, W by projection + Cholesky-QR), so gM is the identity
@@ -858,7 +865,9 @@ int rr_solve(mh_context *ctx, double *gA, double *gM, uint32_t m, double *evals,
         // S = (I + E)^(-1/2) = I - E/2 + 3/8 E^2 + O(E^3): S gA S z = theta z, c = S z.  Four order-m products instead of the
         // Cholesky reduction's factorisation and three triangular solves (~1.2 ms of single-workgroup kernels).
         series = !identity && d < 1e-7;
+        if (ctx->rr_trace) ctx->rr_trace->defect = d;
     }
+    if (ctx->rr_trace) ctx->rr_trace->reduction = gm_is_identity ? MhRrTrace::GIVEN_IDENTITY : identity ? MhRrTrace::MEASURED_IDENTITY : series ? MhRrTrace::SERIES : MhRrTrace::CHOLESKY;
     DevArray<double> sroot, stmp; // (the series' S and workspace: alive until the back-transformation)
     if (series) {
         sroot.reset(ctx, size_t(m) * m);
@@ -889,6 +898,7 @@ int rr_solve(mh_context *ctx, double *gA, double *gM, uint32_t m, double *evals,
     if (!hinfo) {
         ROCBLAS_CHECK(rocsolver_dsyevd(ctx->blas, rocblas_evect_original, rocblas_fill_lower, m, gA, m, evals, ework, info));
         hinfo = host_info(info);
+        if (ctx->rr_trace) ctx->rr_trace->solver = MhRrTrace::SYEVD;
     }
     if (*hinfo != 0) return *hinfo;
     // 3. Back to the pencil's eigenvectors
@@ -900,6 +910,8 @@ int rr_solve(mh_context *ctx, double *gA, double *gM, uint32_t m, double *evals,
         ROCBLAS_CHECK(rocblas_dtrsm(ctx->blas, rocblas_side_left, rocblas_fill_lower, rocblas_operation_transpose, rocblas_diagonal_non_unit, m, m, &one, gM, m, gA, m));
     return 0;
 }
+
+namespace {
 
 void colsumsq(mh_context *ctx, const double *x, size_t rows, uint32_t w, double *out, DevArray<double> &scratch) {
     const uint32_t rpb = 256;
@@ -1474,7 +1486,7 @@ struct BlockLobpcg {
     // The residuals of the active columns as the image product's epilogue leaves them (mh_spmm_mapped): compact panel of pitch
     // res_pitch for the columns res_act, per-node norm partials, the reduced norms [2][res_pitch]
     DevArray<double> Rr, res_partial, res_blocks, res_norms_d;
-    std::vector<double> rr_evals; // the Rayleigh-Ritz step's eigenvalues when rr_solve read them back itself
+    std::vector<double> rr_evals; // the Rayleigh-Ritz step's eigenvalues when mh_rr_solve read them back itself
     std::vector<uint32_t> res_act, res_pos; // (res_pos: a member so that its asynchronous upload never outlives it)
     std::vector<double> res_norms;
     uint32_t res_pitch = 0;
@@ -1744,7 +1756,7 @@ struct BlockLobpcg {
             gram(ctx, n, X, b, MX, b, gM, b);
             // (the library's divide and conquer here: every pair of a start block's matrix, whose spectrum spans |sigma| .. ||A|| -- our partial-spectrum
             // kernels, accepted at a residual of 1e-10 ||T||, left the small pairs at 1e-8 .. 1e-7 in the step's self-check: measured in round 5)
-            const int hinfo = rr_solve(ctx, gA, gM, b, evals, ework, info);
+            const int hinfo = mh_rr_solve(ctx, gA, gM, b, evals, ework, info);
             if (hinfo != 0) mh_throw(MH_ENOTCONVERGED, "initial Rayleigh-Ritz failed (info %d)", hinfo);
             panel_mul(ctx, n, X, b, gA, b, Xn, b, 1.0, 0.0);
             panel_mul(ctx, n, AX, b, gA, b, AXn, b, 1.0, 0.0);
@@ -2037,7 +2049,7 @@ struct BlockLobpcg {
             HIP_CHECK(hipMemcpyAsync(gA0, gA, size_t(m) * m * sizeof(double), hipMemcpyDeviceToDevice, st));
             HIP_CHECK(hipMemcpyAsync(gM0, gM, size_t(m) * m * sizeof(double), hipMemcpyDeviceToDevice, st));
             rr_evals.clear();
-            const int hinfo = rr_solve(ctx, gA, gM, m, evals, ework, info, wa, gm_identity, &rr_evals);
+            const int hinfo = mh_rr_solve(ctx, gA, gM, m, evals, ework, info, wa, gm_identity, &rr_evals);
             if (hinfo == 0) break;
             if (attempt == 1 || wp == 0) mh_throw(MH_ENOTCONVERGED, "Rayleigh-Ritz failed at iteration %u (info %d)", it, hinfo);
             wp = 0; // drop the previous directions and retry on [X W]

@@ -42,16 +42,40 @@ def test_the_bindings_struct_images_match_the_library(core):
     assert list(sizes) == [C.sizeof(core.Profile), C.sizeof(core.SolverConfig), C.sizeof(core.Material), C.sizeof(core.MassProps)], list(sizes)
 
 
-def test_lab_library_is_separate_from_the_product(core):
-    """libmodalhip_lab.so (timing loops, kernel variants called directly, the matrix-free operator) exports what its own header
-    declares; the product library exports none of it."""
+def _exported_functions(path, prefix):
+    """Names of the functions an ELF64 shared library defines in its dynamic symbol table (.dynsym), those starting with `prefix`."""
+    import struct
+    data = open(path, "rb").read()
+    assert data[:4] == b"\x7fELF" and data[4] == 2 and data[5] == 1, path  # 64-bit little-endian
+    shoff, = struct.unpack_from("<Q", data, 0x28)
+    shentsize, shnum = struct.unpack_from("<HH", data, 0x3A)
+    sections = [struct.unpack_from("<IIQQQQIIQQ", data, shoff + i * shentsize) for i in range(shnum)]
+    names = set()
+    for _, sh_type, _, _, off, size, link, _, _, entsize in sections:
+        if sh_type != 11:  # SHT_DYNSYM
+            continue
+        stroff = sections[link][4]
+        for q in range(off, off + size, entsize):
+            st_name, st_info, _, st_shndx = struct.unpack_from("<IBBH", data, q)
+            if st_shndx != 0 and (st_info & 0xF) == 2:  # defined here, STT_FUNC
+                name = data[stroff + st_name:data.index(b"\0", stroff + st_name)].decode()
+                if name.startswith(prefix):
+                    names.add(name)
+    return names
+
+
+def test_lab_library_exports_exactly_its_header(core):
+    """libmodalhip_lab.so (timing loops, kernel variants called directly, the matrix-free operator, the Rayleigh-Ritz step's pieces)
+    exports what its own header declares and nothing more under that prefix; the product library exports none of it."""
     from tools import lab
     L = lab.lib()
     header = open(os.path.join(ROOT, "mesheditor_amd", "csrc", "lab", "modalhip_lab.h")).read()
     declared = sorted(set(re.findall(r"\b(mhl_[a-z0-9_]+)\s*\(", header)))
-    assert len(declared) == 17 and all(hasattr(L, n) for n in declared)
+    assert len(declared) == 19 and all(hasattr(L, n) for n in declared)
+    assert _exported_functions(lab.SO_PATH, "mhl_") == set(declared)
     P = core.lib()
     assert not [n for n in declared if hasattr(P, n)] and not hasattr(P, "mh_system_bench_spmm")
+    assert not _exported_functions(P._name, "mhl_")
 
 
 def test_no_gpu_fails_loudly(core):

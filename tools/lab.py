@@ -33,6 +33,8 @@ def lib():
         L.mhl_context_small_gemm.restype, L.mhl_context_small_gemm.argtypes = i32, [vp, i32, i32, u32, u32, u32, C.c_double, vp, u32, vp, u32, C.c_double, vp, u32, u32, f64p]
         L.mhl_context_tridiagonalize_full.restype, L.mhl_context_tridiagonalize_full.argtypes = i32, [vp, i32, u32, vp, vp, vp, vp, vp, u32, f64p]
         L.mhl_graph_aggregates.restype, L.mhl_graph_aggregates.argtypes = u32, [vp, vp, u32, u32, u32, vp]
+        L.mhl_context_tridiag_lowest.restype, L.mhl_context_tridiag_lowest.argtypes = i32, [vp, u32, u32, vp, vp, vp, vp, f64p, C.POINTER(i32)]
+        L.mhl_context_rr_solve.restype, L.mhl_context_rr_solve.argtypes = i32, [vp, u32, vp, vp, u32, i32, vp, vp, C.POINTER(u32), vp, vp]
         _LIB = L
     return _LIB
 
@@ -86,6 +88,40 @@ def tridiagonalize_full(ctx, a, variant=2, reps=1):
     d, e, refl, tau, ms = np.zeros(m), np.zeros(m - 1), np.zeros((m, m)), np.zeros(m), C.c_double(0)
     ctx.check(lib().mhl_context_tridiagonalize_full(ctx.h, variant, m, _p(a), _p(d), _p(e), _p(refl), _p(tau), reps, C.byref(ms)))
     return d, e, refl.T.copy(), tau, ms.value  # (the device's column-major image read as rows: transposed back)
+
+
+def tridiag_lowest(ctx, d, e, k):
+    """(w [k], z [m x k], quality, taken) of the k lowest eigenpairs of the symmetric tridiagonal (d, e) by the Rayleigh-Ritz step's
+    partial-spectrum kernels (orders <= 256: one workgroup; 257 .. 768: the wide form).  quality is the kernels' own residual measure
+    (NaN when a factorisation failed); taken is False when the call declined the problem (w, z zero, quality NaN)."""
+    d = np.ascontiguousarray(d, dtype=np.float64)
+    e = np.ascontiguousarray(e, dtype=np.float64)
+    m = len(d)
+    assert len(e) == m - 1
+    w, z, q, taken = np.zeros(k), np.zeros((m, k), order="F"), C.c_double(np.nan), C.c_int(0)
+    ctx.check(lib().mhl_context_tridiag_lowest(ctx.h, m, k, _p(d), _p(e), _p(w), _p(z), C.byref(q), C.byref(taken)))
+    return w, z, q.value, bool(taken.value)
+
+
+RR_REDUCTIONS = ("given identity", "measured identity", "series", "cholesky")
+RR_SOLVERS = ("syevd", "small partial", "small stedc", "wide partial", "wide stedc+ormtr")
+
+
+def rr_solve(ctx, a, mmat=None, nwant=0, gm_is_identity=False):
+    """One Rayleigh-Ritz step (the solver's rr_solve) on the pencil (a, mmat), lower triangles used.  Returns (theta, C, host_evals,
+    trace): the ncols eigenvalues and gM-orthonormal vectors (m x ncols; ncols = nwant on a partial path, else m), the eigenvalues the
+    partial path read back on the host (None when it did not), and a dict of what ran: reduction, defect (None when not measured),
+    solver, quality (NaN when no partial spectrum ran) and selfcheck (the sampled self-check word; 0 when none ran)."""
+    af = np.asfortranarray(a, dtype=np.float64)
+    m = af.shape[0]
+    mf = None if mmat is None else np.asfortranarray(mmat, dtype=np.float64)
+    ev, vec, hv, tr, ncols = np.zeros(m), np.zeros((m, m), order="F"), np.zeros(max(nwant, 1)), np.zeros(6), C.c_uint32(0)
+    ctx.check(lib().mhl_context_rr_solve(ctx.h, m, _p(af), None if mf is None else _p(mf), nwant, int(gm_is_identity), _p(ev), _p(vec), C.byref(ncols), _p(hv), _p(tr)))
+    n = ncols.value
+    trace = {"reduction": RR_REDUCTIONS[int(tr[0])], "defect": None if tr[1] < 0 else float(tr[1]), "solver": RR_SOLVERS[int(tr[2])], "quality": float(tr[3]),
+             "selfcheck": float(tr[4])}
+    vectors = vec.reshape(-1, order="F")[: m * n].reshape((m, n), order="F").copy()
+    return ev[:n].copy(), vectors, (hv[: int(tr[5])].copy() if tr[5] > 0 else None), trace
 
 
 def gram(ctx, x, y):
