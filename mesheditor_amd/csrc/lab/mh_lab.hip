@@ -79,6 +79,22 @@ __global__ void __launch_bounds__(256) k_stream_read(const f4_stream *__restrict
 }
 } // namespace
 
+namespace {
+// reference node id of every P1 (internal) point: perm[p1_corner[p]], checked to be a permutation of the mesh points
+std::vector<uint32_t> lab_point_ref(const mh_system *s) {
+    const std::vector<uint32_t> perm = s->perm.to_host(), corner = s->p1_corner.to_host();
+    std::vector<uint32_t> ref(s->n_points);
+    std::vector<uint8_t> seen(s->n_points, 0);
+    for (uint32_t p = 0; p < s->n_points; ++p) {
+        ref[p] = perm[corner[p]];
+        if (ref[p] >= s->n_points || seen[ref[p]]) mh_throw(MH_EINVAL, "hierarchy export: P1 point %u has reference id %u", p, ref[p]);
+        seen[ref[p]] = 1;
+    }
+    return ref;
+}
+const PatchSet &lab_patches(const mh_system *s, int level) { return level == 2 ? s->patches2 : s->patches1; }
+} // namespace
+
 extern "C" {
 // The rigid-body level's graph aggregation (host code, no device): CSR graph of a level's node blocks in, aggregate of every node
 // out; returns the aggregate count.
@@ -362,6 +378,118 @@ int mhl_context_rr_solve(mh_context *ctx, uint32_t m, const double *a, const dou
         if (host_evals && !hv.empty()) std::copy(hv.begin(), hv.end(), host_evals);
         return MH_OK;
     } catch (const std::exception &ex) { return mh_guard(ctx, ex); }
+}
+
+// y = B x: the eigensolver's preconditioner cycle at the shift sigma with single- (precision 0) or double-precision (1) smoothers, through
+// mh_precondition_panel (the eigensolver's own slab loop above 256 columns).  x, y: column-major n x width (width <= 1 024), the reference's DOF order.
+int mhl_system_precondition(mh_system *s, double sigma, int precision, const double *x, double *y, uint32_t width) {
+    if (!s || !x || !y || width == 0 || width > 1024 || (precision != 0 && precision != 1)) return MH_EINVAL;
+    mh_context *ctx = s->ctx;
+    try {
+        HIP_CHECK(hipSetDevice(ctx->device));
+        const size_t n = size_t(3) * s->n_nodes;
+        DevArray<double> xr(ctx, n * width), xp(ctx, n * width), yp(ctx, n * width);
+        xr.upload(x, n * width);
+        k_lab_ref_to_panel<<<div_up(n * width, TB), TB, 0, ctx->stream>>>(xr, s->perm, s->n_nodes, width, xp);
+        KERNEL_CHECK();
+        mh_precondition_panel(s, sigma, precision, xp, yp, width);
+        k_lab_panel_to_ref<<<div_up(n * width, TB), TB, 0, ctx->stream>>>(yp, s->perm, s->n_nodes, width, xr.get());
+        KERNEL_CHECK();
+        xr.download(y, n * width);
+        return MH_OK;
+    } catch (const std::exception &e) { return mh_guard(ctx, e); }
+}
+
+// The preconditioner's hierarchy built at sigma (rebuild != 0: built anew even when one at sigma stands) and finished, and its sizes:
+// sizes[0..3] = n_points, n_agg, n0 = 6 n_agg, node blocks of the P1 operator; then per level (P2 at 4, P1 at 12): patches, nodes per
+// patch, clusters, cluster rows, cluster inverse values, bad elements, nodes of the largest cluster, patches and clusters dropped.
+int mhl_system_hierarchy_sizes(mh_system *s, double sigma, int rebuild, uint64_t *sizes) {
+    if (!s || !sizes) return MH_EINVAL;
+    mh_context *ctx = s->ctx;
+    try {
+        HIP_CHECK(hipSetDevice(ctx->device));
+        std::lock_guard<std::mutex> lock(mh_solve_mutex());
+        if (rebuild) s->hierarchy_ready = false;
+        mh_build_hierarchy(s, sigma);
+        sizes[0] = s->n_points, sizes[1] = s->n_agg, sizes[2] = uint64_t(6) * s->n_agg, sizes[3] = s->L1.n_blocks;
+        for (int level : {2, 1}) {
+            const PatchSet &ps = lab_patches(s, level);
+            uint64_t *o = sizes + (level == 2 ? 4 : 12);
+            o[0] = ps.n_patches, o[1] = ps.npe, o[2] = ps.n_clusters, o[3] = ps.cluster_rows, o[4] = ps.cinv64.count, o[5] = ps.n_bad_elements,
+            o[6] = ps.largest_cluster, o[7] = s->dropped_patches[level == 2 ? 0 : 1];
+        }
+        return MH_OK;
+    } catch (const std::exception &e) { return mh_guard(ctx, e); }
+}
+
+// The standing hierarchy (mhl_system_hierarchy_sizes first).  scalars[10] = lmax of L2 and of L1, the coarse diagonal lift applied, the cycle
+// shape for `width` columns (deg2, ratio, deg1, gamma, ratio1), the shift, the worst element shape.  Per mesh point in the reference numbering:
+// agg_of (its aggregate), agg_t (its 3 x 6 block, row-major).  The P1 operator's node blocks: l1_row, l1_col (reference point ids), l1_val (3 x 3
+// row-major).  a0: the coarse operator's explicit inverse (n0 x n0, column-major).  Any output may be null.
+int mhl_system_hierarchy_export(mh_system *s, uint32_t width, double *scalars, uint32_t *agg_of, double *agg_t, uint32_t *l1_row, uint32_t *l1_col, double *l1_val,
+                                double *a0) {
+    if (!s || !scalars || width == 0) return MH_EINVAL;
+    mh_context *ctx = s->ctx;
+    try {
+        HIP_CHECK(hipSetDevice(ctx->device));
+        std::lock_guard<std::mutex> lock(mh_solve_mutex());
+        if (!s->hierarchy_ready) mh_throw(MH_EINVAL, "hierarchy export: no hierarchy built");
+        MhCycleShape sh;
+        mh_cycle_shape(s, width, &sh);
+        const double sc[10] = {s->L2.lmax, s->L1.lmax, mh_coarse_lift(s), double(sh.deg2), sh.ratio, double(sh.deg1), double(sh.gamma), sh.ratio1, s->sigma_built,
+                               double(s->worst_quality)};
+        std::copy(sc, sc + 10, scalars);
+        const std::vector<uint32_t> ref = lab_point_ref(s);
+        if (agg_of) {
+            const std::vector<uint32_t> h = s->agg_of.to_host();
+            for (uint32_t p = 0; p < s->n_points; ++p) agg_of[ref[p]] = h[p];
+        }
+        if (agg_t) {
+            const std::vector<double> h = s->agg_t.to_host();
+            for (uint32_t p = 0; p < s->n_points; ++p) std::copy(h.begin() + 18 * size_t(p), h.begin() + 18 * size_t(p + 1), agg_t + 18 * size_t(ref[p]));
+        }
+        if (l1_row || l1_col) {
+            const std::vector<uint32_t> rp = s->L1.row_ptr.to_host(), cl = s->L1.col.to_host();
+            for (uint32_t r = 0; r < s->L1.n_nodes; ++r)
+                for (uint32_t b = rp[r]; b < rp[r + 1]; ++b) {
+                    if (l1_row) l1_row[b] = ref[r];
+                    if (l1_col) l1_col[b] = ref[cl[b]];
+                }
+        }
+        if (l1_val) s->L1.aval.download(l1_val, s->L1.n_blocks * 9);
+        if (a0) s->a0.download(a0, s->a0.count);
+        return MH_OK;
+    } catch (const std::exception &e) { return mh_guard(ctx, e); }
+}
+
+// The sliver patches of level 2 (P2) or 1 (P1) of the standing hierarchy: nodes (patches x nodes per patch, the reference's node ids of that level:
+// P2 nodes, or mesh points), weight, inv64 (per patch its weighted inverse, row-major); per cluster: cluster_row (its DOF rows, 3 node + k in the
+// reference numbering), cluster_ptr (clusters + 1 row offsets), cinv64 (its inverse, order^2 values each, row-major).  Any output may be null.
+int mhl_system_patch_export(mh_system *s, int level, uint32_t *nodes, double *weight, double *inv64, uint32_t *cluster_row, uint32_t *cluster_ptr, double *cinv64) {
+    if (!s || (level != 1 && level != 2)) return MH_EINVAL;
+    mh_context *ctx = s->ctx;
+    try {
+        HIP_CHECK(hipSetDevice(ctx->device));
+        std::lock_guard<std::mutex> lock(mh_solve_mutex());
+        if (!s->hierarchy_ready) mh_throw(MH_EINVAL, "patch export: no hierarchy built");
+        const PatchSet &ps = lab_patches(s, level);
+        std::vector<uint32_t> node_ref;
+        if (level == 2) node_ref = s->perm.to_host();
+        else node_ref = lab_point_ref(s);
+        if (nodes && ps.n_patches) {
+            const std::vector<uint32_t> h = ps.nodes.to_host();
+            for (size_t i = 0; i < h.size(); ++i) nodes[i] = node_ref[h[i]];
+        }
+        if (weight && ps.n_patches) ps.weight.download(weight, ps.n_patches);
+        if (inv64 && ps.n_patches) ps.inv64.download(inv64, ps.inv64.count);
+        if (cluster_row && ps.n_clusters) {
+            const std::vector<uint32_t> h = ps.cluster_row.to_host();
+            for (size_t i = 0; i < h.size(); ++i) cluster_row[i] = 3 * node_ref[h[i] / 3] + h[i] % 3;
+        }
+        if (cluster_ptr && ps.n_clusters) std::copy(ps.h_cluster_ptr.begin(), ps.h_cluster_ptr.end(), cluster_ptr);
+        if (cinv64 && ps.n_clusters) ps.cinv64.download(cinv64, ps.cinv64.count);
+        return MH_OK;
+    } catch (const std::exception &e) { return mh_guard(ctx, e); }
 }
 
 // The Cholesky-QR step's one-launch kernel: l <- diag(1 / dscale) chol(a) (lower, zeros above), linv <- l^-1; info[0] = 0 or the failing column,

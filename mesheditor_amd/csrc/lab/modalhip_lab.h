@@ -39,6 +39,14 @@ int mhl_context_gram(mh_context *, uint64_t n, const double *x, uint32_t wa, con
 int mhl_context_bench_stream(mh_context *, uint64_t bytes, uint32_t reps, double *copy_gbs, double *read_gbs);
 /* the context's device pool: bytes held from the device, bytes of them idle in the cache, the cap on the idle part */
 int mhl_context_pool_stats(mh_context *, uint64_t *reserved, uint64_t *idle, uint64_t *cap);
+/* y = B x, the eigensolver's preconditioner cycle at the shift sigma, single- (precision 0) or double-precision (1) smoothers; x, y column-major
+ * n x width (width <= 1 024), the reference's DOF order */
+int mhl_system_precondition(mh_system *, double sigma, int precision, const double *x, double *y, uint32_t width);
+/* The preconditioner's hierarchy: built at sigma (anew when rebuild != 0) with its sizes[20]; then the standing hierarchy's coarse level, P1
+ * operator and cycle shape, and each smoothed level's sliver patches and clusters, in the reference's numbering (lab/mh_lab.hip lists the fields) */
+int mhl_system_hierarchy_sizes(mh_system *, double sigma, int rebuild, uint64_t *sizes);
+int mhl_system_hierarchy_export(mh_system *, uint32_t width, double *scalars, uint32_t *agg_of, double *agg_t, uint32_t *l1_row, uint32_t *l1_col, double *l1_val, double *a0);
+int mhl_system_patch_export(mh_system *, int level, uint32_t *nodes, double *weight, double *inv64, uint32_t *cluster_row, uint32_t *cluster_ptr, double *cinv64);
 /* The rigid-body level's graph aggregation (host code): CSR node graph in (diagonal entries included), aggregate per node out. */
 uint32_t mhl_graph_aggregates(const uint32_t *row_ptr, const uint32_t *col, uint32_t n, uint32_t target, uint32_t max_order, uint32_t *agg_of);
 /* Soak of the multi-workgroup tridiagonalisation's tagged exchange with its transport as a parameter (lab/mh_soak.hip): `launches` runs of

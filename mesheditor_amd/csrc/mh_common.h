@@ -527,6 +527,17 @@ void mh_build_system(mh_context *ctx, const mh_mesh *mesh, const mh_material &ma
 void mh_build_hierarchy(mh_system *sys, double sigma, bool defer = false);
 void mh_finish_hierarchy(mh_system *sys);
 uint32_t mh_shift_invert_panel(mh_system *sys, double sigma, const double *b, double *x, uint32_t w, double rel_tol, uint32_t max_iters, double *worst_rel); // mh_eigs.hip: x = (K - sigma M)^-1 b by preconditioned CG
+// The preconditioner cycle's shape for panels of w columns: Chebyshev degrees of the P2 and P1 smoothers, P1 cycles per application, and the
+// spectrum ratios lmax / lmin of their intervals (ratio1 > 0: the P1 level's own).  mh_eigs.hip: what Precond's constructor picks, MH_CYCLE included.
+struct MhCycleShape {
+    int deg2{2}, deg1{5}, gamma{3};
+    double ratio{8.0}, ratio1{0.0};
+};
+void mh_cycle_shape(const mh_system *sys, uint32_t w, MhCycleShape *shape);
+double mh_coarse_lift(const mh_system *sys); // mh_eigs.hip: relative lift of the coarse operator's diagonal that mh_build_hierarchy applies
+// z = B r for an internal-order n x w panel (w <= 1 024): the hierarchy built at sigma, then the cycle with single- (precision 0) or
+// double-precision (1) smoothers, in the eigensolver's column slabs above 256 columns.  mh_eigs.hip
+void mh_precondition_panel(mh_system *sys, double sigma, int precision, const double *r, double *z, uint32_t w);
  // no-op unless a deferred elimination is pending // mh_pipeline.hip: A = K - sigma M on both levels, dense coarse factor
 uint32_t mh_graph_aggregates(const std::vector<uint32_t> &row_ptr, const std::vector<uint32_t> &col, uint32_t n, uint32_t target, uint32_t max_order, std::vector<uint32_t> &agg_of); // mh_pipeline.hip
 void mh_select_patches(mh_system *sys, float threshold);                                  // mh_patch.hip: elements whose shape measure is below the threshold

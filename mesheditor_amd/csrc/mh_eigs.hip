@@ -924,6 +924,28 @@ void colsumsq(mh_context *ctx, const double *x, size_t rows, uint32_t w, double 
     KERNEL_CHECK();
 }
 
+// z = B r for w columns (n x w panels) by `one`, an application of the preconditioner to at most kPrecondColumns columns.  The smoothers'
+// wide-load products take panels of at most 256 columns (64 lanes x 4 floats): a wider block (more than ~230 wanted pairs: beyond the reference
+// editor's 128 + margin and BASELINE's 200) goes through in column slabs, gathered into a compact panel and scattered back (two extra passes
+// over the slab, a few per cent of the cycle's own traffic).
+template<typename F> void precondition_in_slabs(mh_context *ctx, size_t n, const double *r, double *z, uint32_t w, F &&one) {
+    if (w <= kPrecondColumns) return one(r, z, w);
+    const hipStream_t st = ctx->stream;
+    const uint32_t slabs = div_up(w, kPrecondColumns), step = (div_up(w, slabs) + 3u) & ~3u;
+    if (w > 1024) mh_throw(MH_EINVAL, "a block of %u columns exceeds the 1 024 the column maps cover", w);
+    DevArray<double> rs(ctx, n * step), zs(ctx, n * step);
+    const uint32_t *iota = mh_identity_map(ctx);
+    for (uint32_t c0 = 0; c0 < w; c0 += step) {
+        const uint32_t wc = std::min(step, w - c0);
+        k_gather_cols<<<grid1(n * wc), TB, 0, st>>>(r, iota + c0, rs.get(), n, w, wc);
+        KERNEL_CHECK();
+        one(rs, zs, wc);
+        k_scatter_cols<<<grid1(n * wc), TB, 0, st>>>(zs.get(), iota + c0, z, n, w, wc);
+        KERNEL_CHECK();
+    }
+    HIP_CHECK(hipStreamSynchronize(st)); // the slabs return to the pool
+}
+
 // ---- multilevel preconditioner ---------------------------------------------------------------------------------
 // T = precision of the two smoothed levels (float by default: the smoothers are gather-bound, so halving the bytes
 // nearly halves their time, and the outer iteration -- residuals, Rayleigh-Ritz, convergence test -- stays double).
@@ -932,8 +954,8 @@ template<typename T> struct Precond {
     mh_system *sys;
     mh_context *ctx;
     uint32_t wmax;
-    int deg2{2}, deg1{5}, gamma{3}; // (the constructor picks the cycle shape by the kind of mesh)
-    double ratio{8.0}, ratio1{0.0}; // ratio1 > 0: the P1 level's own interval [lmax / ratio1, lmax]
+    int deg2, deg1, gamma; // (the constructor picks the cycle shape by the kind of mesh: mh_cycle_shape)
+    double ratio, ratio1; // ratio1 > 0: the P1 level's own interval [lmax / ratio1, lmax]
     DevArray<T> rin, z2, d2, t2, r2, r1, x1, d1, t1, rr1;
     DevArray<double> r0, x0, x0_partial;
     static constexpr uint32_t COARSE_SLICES = 8;
@@ -955,45 +977,9 @@ template<typename T> struct Precond {
         x0.reset(ctx, n0 * w);
         x0_partial.reset(ctx, n0 * w * COARSE_SLICES);
         patch_y.reset(ctx, std::max(s->patches2.scratch_rows(), s->patches1.scratch_rows()) * w);
-        const Switches &sw = switches();
-        // Three cycle shapes, each the measured best of its class (round 5; MH_CYCLE = deg2, deg1, gamma, ratio[, ratio1] overrides; profiles/r05_cycle_by_body.txt):
-        //  * a mesh with SLIVER PATCHES: P2 Chebyshev degree 5 over [lmax / 60, lmax]; P1: see below (three cycles of degree 5 over the same ratio until the end of round 5).  The P1 space
-        //    represents the smooth error of such a mesh poorly (measured two-grid bound, exact coarse solve, 30k-tet skillet scan: condition 34 with two
-        //    steps over [lmax/8, lmax], 12 with four over [lmax/30, lmax]); with the patches scaled by their overlap (mh_patch.hip) five steps over
-        //    [lmax/60, lmax] are the measured best on the four scan workloads: 24 / 26 / 40 / 40 iterations (4 over lmax/30: 26 / 33 / 44 / 48).
-        //  * a SURFACE-DOMINATED body without patches -- fewer than 4.5 tetrahedra per mesh point (a bulk fill has 5-6.7; a plate two cells thick 3.9,
-        //    a UV sphere's fill 4.2, the reference's test bars 2.4-3.7): the same long P2 smoother (the 215-pair Kuhn plate 860 -> 674 ms, 22 -> 17
-        //    iterations; the 48 x 24 UV sphere 64 -> 53 ms, 28 -> 21; the thin bar 24 -> 19 ms), and ONE P1 cycle of degree 16 over [lmax / 250, lmax]
-        //    instead of three of degree 5 (plate 674 -> 643 ms, sphere 54 -> 50.5).
-        //  * a BULK body (Kuhn cubes, jittered boxes): the short P2 smoother (degree 2 over [lmax / 8, lmax]: the long one costs 8-18 % there) and one
-        //    P1 cycle of degree 12 over [lmax / 100, lmax] instead of three of degree 5 over [lmax / 8, lmax]: the P1 level's launches are latency-bound
-        //    (~25 us each whatever the size) and one long sequence over a wide interval smooths better than three short ones around the coarse solve --
-        //    26^3 / 17^3 / 12^3 cubes 133.0 -> 122.3 / 54.7 -> 49.8 / 32.8 -> 31.4 ms, the batch of 64 boxes 1.65 -> 1.54 s (with [lmax / 8, lmax] the
-        //    same single cycle LOSES 10 %: the interval is what makes it work).
-        const bool surface_dominated = s->kept_tets < 4.5 * s->n_points;
-        if (s->patches2.any()) {
-            deg2 = 5;
-            ratio = 60.0;
-            // one P1 cycle of degree 28 over [lmax / 800, lmax]: the single cycle of degree 16 over lmax / 250 that suits the patch-free bodies lost 6-8 % on
-            // the 65-pair solves of the 100k-tet scans (and won 4-5 % on the 215-pair ones); longer and wider it is level with the three short cycles or
-            // ahead on all nine patch workloads -- scan_s100k_repaired 336 -> 317 ms, config3_s100k_repaired 1 093 -> 1 007, config3_s30k 464 -> 438, the
-            // unrepaired scan_s100k 570 -> 579, ball and 30k-tet scans within 1 %
-            // -- except the fills DENSE in patches at blocks up to 128 columns (unrepaired scans with and without interior points, 9-28 patches per
-            // thousand tetrahedra: 65-pair solves +2 ... +8 % with it; the repaired fills have 0.3-0.5 per thousand), which keep three cycles of degree 5
-            const bool few_patches = uint64_t(s->patches2.n_bad_elements) * 500 < s->kept_tets;
-            if (w_in > 128 || few_patches) deg1 = 28, gamma = 1, ratio1 = 800.0;
-        } else if (surface_dominated) {
-            deg2 = 5;
-            ratio = 60.0;
-            deg1 = 16, gamma = 1, ratio1 = 250.0;
-        } else {
-            deg1 = 12, gamma = 1, ratio1 = 100.0;
-        }
-        if (sw.deg2 > 0) deg2 = sw.deg2;
-        if (sw.deg1 > 0) deg1 = sw.deg1;
-        if (sw.gamma > 0) gamma = sw.gamma;
-        if (sw.cheb_ratio > 0) ratio = std::max(1.5, sw.cheb_ratio), ratio1 = 0.0; // (a given ratio holds for both levels unless a fifth value follows)
-        if (sw.cheb_ratio1 > 0) ratio1 = std::max(1.5, sw.cheb_ratio1);
+        MhCycleShape shape;
+        mh_cycle_shape(s, w_in, &shape);
+        deg2 = shape.deg2, deg1 = shape.deg1, gamma = shape.gamma, ratio = shape.ratio, ratio1 = shape.ratio1;
     }
     void spmm(const BsrLevel &lvl, const T *x, T *y, uint32_t w) {
         if constexpr (kDouble) mh_spmm(ctx, lvl, lvl.aval, x, y, nullptr, nullptr, w);
@@ -1144,6 +1130,52 @@ double estimate_lmax(mh_context *ctx, BsrLevel &lvl, const PatchSet &ps) {
 }
 } // namespace
 
+void mh_cycle_shape(const mh_system *s, uint32_t w_in, MhCycleShape *shape) {
+    MhCycleShape sh;
+    const Switches &sw = switches();
+    // Three cycle shapes, each the measured best of its class (round 5; MH_CYCLE = deg2, deg1, gamma, ratio[, ratio1] overrides; profiles/r05_cycle_by_body.txt):
+    //  * a mesh with SLIVER PATCHES: P2 Chebyshev degree 5 over [lmax / 60, lmax]; P1: see below (three cycles of degree 5 over the same ratio until the end of round 5).  The P1 space
+    //    represents the smooth error of such a mesh poorly (measured two-grid bound, exact coarse solve, 30k-tet skillet scan: condition 34 with two
+    //    steps over [lmax/8, lmax], 12 with four over [lmax/30, lmax]); with the patches scaled by their overlap (mh_patch.hip) five steps over
+    //    [lmax/60, lmax] are the measured best on the four scan workloads: 24 / 26 / 40 / 40 iterations (4 over lmax/30: 26 / 33 / 44 / 48).
+    //  * a SURFACE-DOMINATED body without patches -- fewer than 4.5 tetrahedra per mesh point (a bulk fill has 5-6.7; a plate two cells thick 3.9,
+    //    a UV sphere's fill 4.2, the reference's test bars 2.4-3.7): the same long P2 smoother (the 215-pair Kuhn plate 860 -> 674 ms, 22 -> 17
+    //    iterations; the 48 x 24 UV sphere 64 -> 53 ms, 28 -> 21; the thin bar 24 -> 19 ms), and ONE P1 cycle of degree 16 over [lmax / 250, lmax]
+    //    instead of three of degree 5 (plate 674 -> 643 ms, sphere 54 -> 50.5).
+    //  * a BULK body (Kuhn cubes, jittered boxes): the short P2 smoother (degree 2 over [lmax / 8, lmax]: the long one costs 8-18 % there) and one
+    //    P1 cycle of degree 12 over [lmax / 100, lmax] instead of three of degree 5 over [lmax / 8, lmax]: the P1 level's launches are latency-bound
+    //    (~25 us each whatever the size) and one long sequence over a wide interval smooths better than three short ones around the coarse solve --
+    //    26^3 / 17^3 / 12^3 cubes 133.0 -> 122.3 / 54.7 -> 49.8 / 32.8 -> 31.4 ms, the batch of 64 boxes 1.65 -> 1.54 s (with [lmax / 8, lmax] the
+    //    same single cycle LOSES 10 %: the interval is what makes it work).
+    const bool surface_dominated = s->kept_tets < 4.5 * s->n_points;
+    if (s->patches2.any()) {
+        sh.deg2 = 5;
+        sh.ratio = 60.0;
+        // one P1 cycle of degree 28 over [lmax / 800, lmax]: the single cycle of degree 16 over lmax / 250 that suits the patch-free bodies lost 6-8 % on
+        // the 65-pair solves of the 100k-tet scans (and won 4-5 % on the 215-pair ones); longer and wider it is level with the three short cycles or
+        // ahead on all nine patch workloads -- scan_s100k_repaired 336 -> 317 ms, config3_s100k_repaired 1 093 -> 1 007, config3_s30k 464 -> 438, the
+        // unrepaired scan_s100k 570 -> 579, ball and 30k-tet scans within 1 %
+        // -- except the fills DENSE in patches at blocks up to 128 columns (unrepaired scans with and without interior points, 9-28 patches per
+        // thousand tetrahedra: 65-pair solves +2 ... +8 % with it; the repaired fills have 0.3-0.5 per thousand), which keep three cycles of degree 5
+        const bool few_patches = uint64_t(s->patches2.n_bad_elements) * 500 < s->kept_tets;
+        if (w_in > 128 || few_patches) sh.deg1 = 28, sh.gamma = 1, sh.ratio1 = 800.0;
+    } else if (surface_dominated) {
+        sh.deg2 = 5;
+        sh.ratio = 60.0;
+        sh.deg1 = 16, sh.gamma = 1, sh.ratio1 = 250.0;
+    } else {
+        sh.deg1 = 12, sh.gamma = 1, sh.ratio1 = 100.0;
+    }
+    if (sw.deg2 > 0) sh.deg2 = sw.deg2;
+    if (sw.deg1 > 0) sh.deg1 = sw.deg1;
+    if (sw.gamma > 0) sh.gamma = sw.gamma;
+    if (sw.cheb_ratio > 0) sh.ratio = std::max(1.5, sw.cheb_ratio), sh.ratio1 = 0.0; // (a given ratio holds for both levels unless a fifth value follows)
+    if (sw.cheb_ratio1 > 0) sh.ratio1 = std::max(1.5, sw.cheb_ratio1);
+    *shape = sh;
+}
+
+double mh_coarse_lift(const mh_system *sys) { return std::max(sys->coarse_lift, sys->worst_quality < kFlatShape ? 1e-8 : 1e-12); }
+
 void mh_finish_hierarchy(mh_system *sys) {
     if (!sys->coarse_pending) return;
     mh_context *ctx = sys->ctx;
@@ -1193,7 +1225,7 @@ void mh_build_hierarchy(mh_system *sys, double sigma, bool defer) {
     // (a mesh with flat cells: the Galerkin product cancels entries of 1e17 down to rigid-body terms of 1e10 and below -- its rounding is
     // ~1e-9 of the diagonal, enough to cost the coarse operator its definiteness: "coarse operator not positive definite" on one stretched
     // UV sphere of the round-6 soak.  The diagonal is lifted by that much instead of by 1e-12.)
-    k_fix_coarse_diag<<<grid1(n0), TB, 0, ctx->stream>>>(sys->a0, uint32_t(n0), std::max(sys->coarse_lift, sys->worst_quality < kFlatShape ? 1e-8 : 1e-12));
+    k_fix_coarse_diag<<<grid1(n0), TB, 0, ctx->stream>>>(sys->a0, uint32_t(n0), mh_coarse_lift(sys));
     KERNEL_CHECK();
     DevArray<int> &info = sys->coarse_info;
     info.reset(ctx, 1);
@@ -1634,29 +1666,13 @@ struct BlockLobpcg {
         return true;
     }
 
-    // z = B r for w columns.  The smoothers' wide-load products take panels of at most 256 columns (64 lanes x 4 floats): a wider block
-    // (more than ~230 wanted pairs: beyond the reference editor's 128 + margin and BASELINE's 200) goes through in column slabs,
-    // gathered into a compact panel and scattered back (two extra passes over the slab, a few per cent of the cycle's own traffic).
+    // z = B r for w columns (in column slabs above kPrecondColumns: precondition_in_slabs)
     void precondition(const double *r, double *z, uint32_t w) {
-        auto one = [&](const double *rp, double *zp, uint32_t wc) {
+        precondition_in_slabs(ctx, n, r, z, w, [&](const double *rp, double *zp, uint32_t wc) {
             if (panel_cg) panel_cg->solve(*prec64, rp, zp, wc, inner_cg);
             else if (prec32) prec32->apply(rp, zp, wc);
             else prec64->apply(rp, zp, wc);
-        };
-        if (w <= kPrecondColumns) return one(r, z, w);
-        const uint32_t slabs = div_up(w, kPrecondColumns), step = (div_up(w, slabs) + 3u) & ~3u;
-        if (w > 1024) mh_throw(MH_EINVAL, "a block of %u columns exceeds the 1 024 the column maps cover", w);
-        DevArray<double> rs(ctx, n * step), zs(ctx, n * step);
-        const uint32_t *iota = mh_identity_map(ctx);
-        for (uint32_t c0 = 0; c0 < w; c0 += step) {
-            const uint32_t wc = std::min(step, w - c0);
-            k_gather_cols<<<grid1(n * wc), TB, 0, st>>>(r, iota + c0, rs.get(), n, w, wc);
-            KERNEL_CHECK();
-            one(rs, zs, wc);
-            k_scatter_cols<<<grid1(n * wc), TB, 0, st>>>(zs.get(), iota + c0, z, n, w, wc);
-            KERNEL_CHECK();
-        }
-        HIP_CHECK(hipStreamSynchronize(st)); // the slabs return to the pool
+        });
     }
 
     // The initial block: seed columns (warm start), then Gaussian noise, the exact rigid-body modes, one smoothing pass;
@@ -2495,6 +2511,26 @@ uint32_t mh_shift_invert_panel(mh_system *sys, double sigma, const double *b, do
     if (!(worst <= std::max(rel_tol, 1e-8))) mh_throw(MH_ENOTCONVERGED, "shift-invert: relative residual %.2e after %u iterations (asked %.1e)", worst, it, rel_tol);
     HIP_CHECK(hipStreamSynchronize(st));
     return it;
+}
+
+// The cycle B as an operation (lab and tests: tests/test_preconditioner_gpu.py): the hierarchy at sigma, finished, then one application through
+// the eigensolver's own slab loop.  r, z: internal-order n x w panels.
+void mh_precondition_panel(mh_system *sys, double sigma, int precision, const double *r, double *z, uint32_t w) {
+    mh_context *ctx = sys->ctx;
+    if ((precision != 0 && precision != 1) || w == 0) mh_throw(MH_EINVAL, "precondition panel: precision %d, %u columns", precision, w);
+    std::lock_guard<std::mutex> lock(g_solve_mutex);
+    mh_build_hierarchy(sys, sigma);
+    const size_t n = size_t(3) * sys->n_nodes;
+    const uint32_t wp = std::min(w, kPrecondColumns);
+    if (precision == 0) {
+        Precond<float> prec(sys, wp);
+        precondition_in_slabs(ctx, n, r, z, w, [&](const double *rp, double *zp, uint32_t wc) { prec.apply(rp, zp, wc); });
+        HIP_CHECK(hipStreamSynchronize(ctx->stream)); // (the cycle's panels return to the pool)
+    } else {
+        Precond<double> prec(sys, wp);
+        precondition_in_slabs(ctx, n, r, z, w, [&](const double *rp, double *zp, uint32_t wc) { prec.apply(rp, zp, wc); });
+        HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    }
 }
 
 std::mutex &mh_solve_mutex() { return g_solve_mutex; }

@@ -35,6 +35,10 @@ def lib():
         L.mhl_graph_aggregates.restype, L.mhl_graph_aggregates.argtypes = u32, [vp, vp, u32, u32, u32, vp]
         L.mhl_context_tridiag_lowest.restype, L.mhl_context_tridiag_lowest.argtypes = i32, [vp, u32, u32, vp, vp, vp, vp, f64p, C.POINTER(i32)]
         L.mhl_context_rr_solve.restype, L.mhl_context_rr_solve.argtypes = i32, [vp, u32, vp, vp, u32, i32, vp, vp, C.POINTER(u32), vp, vp]
+        L.mhl_system_precondition.restype, L.mhl_system_precondition.argtypes = i32, [vp, C.c_double, i32, vp, vp, u32]
+        L.mhl_system_hierarchy_sizes.restype, L.mhl_system_hierarchy_sizes.argtypes = i32, [vp, C.c_double, i32, vp]
+        L.mhl_system_hierarchy_export.restype, L.mhl_system_hierarchy_export.argtypes = i32, [vp, u32, vp, vp, vp, vp, vp, vp, vp]
+        L.mhl_system_patch_export.restype, L.mhl_system_patch_export.argtypes = i32, [vp, i32, vp, vp, vp, vp, vp, vp]
         _LIB = L
     return _LIB
 
@@ -185,3 +189,48 @@ def graph_aggregates(row_ptr, col, target=16, max_order=6144):
     out = np.zeros(n, np.uint32)
     na = lib().mhl_graph_aggregates(_p(rp), _p(cl), n, target, max_order, _p(out))
     return out, int(na)
+
+
+SIGMA = -(2 * np.pi * 20.0) ** 2  # the reference's shift (mesh2modes.cpp:460)
+
+
+def precondition(system, x, precision=1, sigma=SIGMA):
+    """B x: the eigensolver's preconditioner cycle at `sigma` with single- (precision 0) or double-precision (1) smoothers, columns in the
+    reference's DOF order (at most 1 024; above 256 the eigensolver's column slabs)."""
+    x = np.asfortranarray(x, dtype=np.float64)
+    if x.ndim == 1:
+        x = x[:, None]
+    y = np.zeros_like(x, order="F")
+    system.ctx.check(lib().mhl_system_precondition(system.h, sigma, precision, _p(x), _p(y), x.shape[1]))
+    return y
+
+
+def _level_patches(system, level, o):
+    """The sliver patches and clusters of level 2 (P2) or 1 (P1), node ids and DOF rows in the reference numbering of that level."""
+    npatch, npe, ncl, crows, cvals = (int(v) for v in o[:5])
+    nodes, weight, inv = np.zeros((npatch, npe), np.uint32), np.zeros(npatch), np.zeros((npatch, 3 * npe, 3 * npe))
+    crow, cptr, cinv = np.zeros(crows, np.uint32), np.zeros(ncl + 1, np.uint32), np.zeros(cvals)
+    system.ctx.check(lib().mhl_system_patch_export(system.h, level, _p(nodes), _p(weight), _p(inv), _p(crow), _p(cptr), _p(cinv)))
+    clusters, off = [], 0
+    for c in range(ncl):
+        rows = crow[cptr[c]:cptr[c + 1]].astype(np.int64)
+        clusters.append((rows, cinv[off:off + len(rows) ** 2].reshape(len(rows), len(rows))))
+        off += len(rows) ** 2
+    return {"nodes": nodes.astype(np.int64), "weight": weight, "inv64": inv, "clusters": clusters, "n_bad_elements": int(o[5]), "largest_cluster": int(o[6]),
+            "dropped": int(o[7])}
+
+
+def hierarchy(system, sigma=SIGMA, width=64, rebuild=False):
+    """The preconditioner's hierarchy built at `sigma` (anew when `rebuild`), exported in the reference's numbering: sizes, both levels'
+    spectral bounds, the coarse lift, the cycle shape for `width` columns, per mesh point its aggregate and 3 x 6 rigid-body block, the P1
+    operator's node blocks, the coarse inverse a0, and the sliver patches and clusters of both smoothed levels."""
+    sizes = np.zeros(20, np.uint64)
+    system.ctx.check(lib().mhl_system_hierarchy_sizes(system.h, sigma, int(rebuild), _p(sizes)))
+    npts, nagg, n0, nb1 = (int(v) for v in sizes[:4])
+    sc, agg, tm = np.zeros(10), np.zeros(npts, np.uint32), np.zeros((npts, 3, 6))
+    r1, c1, v1, a0 = np.zeros(nb1, np.uint32), np.zeros(nb1, np.uint32), np.zeros((nb1, 3, 3)), np.zeros((n0, n0), order="F")
+    system.ctx.check(lib().mhl_system_hierarchy_export(system.h, width, _p(sc), _p(agg), _p(tm), _p(r1), _p(c1), _p(v1), _p(a0)))
+    return {"n_points": npts, "n_agg": nagg, "n0": n0, "lmax2": sc[0], "lmax1": sc[1], "lift": sc[2],
+            "shape": {"deg2": int(sc[3]), "ratio": sc[4], "deg1": int(sc[5]), "gamma": int(sc[6]), "ratio1": sc[7]}, "sigma": sc[8], "worst_quality": sc[9],
+            "agg_of": agg.astype(np.int64), "agg_t": tm, "l1_row": r1.astype(np.int64), "l1_col": c1.astype(np.int64), "l1_val": v1, "a0": a0,
+            "patches2": _level_patches(system, 2, sizes[4:12]), "patches1": _level_patches(system, 1, sizes[12:20])}
