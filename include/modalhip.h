@@ -219,6 +219,28 @@ int mh_bank_render(mh_bank *, uint32_t frames, float click_gain, uint32_t n_impa
                    uint32_t n_renderers, const uint32_t *deal_offset, const uint32_t *deal_objects, const uint32_t *render_count,
                    const uint32_t *tuned_count, const float *out_gain, const float *listener_gain, void *out, double *object_energy,
                    uint32_t *object_live, uint8_t *object_silenced, double *object_modal_energy);
+/* A sustained force drive (no reference counterpart in ModalAudio; the bank-side primitive under the drive rows of the reference's
+ * surface renderer, src/audio/surface/): a caller-supplied force signal applied to `object` at excitation position `ex_pos` along
+ * (jx, jy, jz), for the block it is passed with.  Stateless between blocks, no force curve, no click filter.  Fields are float, as
+ * ModalEvent's are (ModalAudio.h:28-37). */
+typedef struct {
+    uint32_t object, ex_pos;
+    float jx, jy, jz;
+} mh_drive;
+/* sizeof(mh_drive) as this library was built (extends mh_abi_struct_sizes, whose four entries stay as they are) */
+uint32_t mh_drive_struct_size(void);
+/* mh_bank_render (one block of RenderModal, ModalAudio.cpp:486-555) with drives: signals is [n_drives][frames] float.  Per mode k of
+ * its object a drive has the impact's gain, expression for expression (ImpactGainRow, ModalAudio.h:182-188):
+ * rad_gain[k] * (shape_x[p,k]*jx + shape_y[p,k]*jy + shape_z[p,k]*jz); per sample the mode's excitation is the running sum of
+ * f_row[t] * gain_row[k] from +0 over the object's impacts in impact order (:104-113), then over its drives in the order given here.
+ * A sample that is not finite is rendered as 0.  A dealt object with a drive counts as excited like one with an impact: it is not
+ * silenced, and the caller passes its tuned mode count as render_count.  A drive is left out when it names no object of the bank, an
+ * object that is not dealt or has no modes, or an ex_pos beyond the object's shape columns.  With n_drives = 0 this is mh_bank_render. */
+int mh_bank_render_driven(mh_bank *, uint32_t frames, float click_gain, uint32_t n_impacts, mh_impact *impacts,
+                          uint32_t n_renderers, const uint32_t *deal_offset, const uint32_t *deal_objects, const uint32_t *render_count,
+                          const uint32_t *tuned_count, const float *out_gain, const float *listener_gain, void *out, double *object_energy,
+                          uint32_t *object_live, uint8_t *object_silenced, double *object_modal_energy, uint32_t n_drives,
+                          const mh_drive *drives, const float *signals);
 /* Read back state columns (for parity tests and the modal-energy diagnostic, ModalAudio.cpp:564-577). */
 int mh_bank_read_state(const mh_bank *, uint32_t first, uint32_t count, double *state_re, double *state_im);
 

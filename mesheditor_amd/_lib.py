@@ -38,6 +38,10 @@ class Impact(C.Structure):
                                           "click_b0", "click_a1", "click_a2", "click_z1", "click_z2")]
 
 
+class Drive(C.Structure):  # mh_drive
+    _fields_ = [("object", C.c_uint32), ("ex_pos", C.c_uint32), ("jx", C.c_float), ("jy", C.c_float), ("jz", C.c_float)]
+
+
 def build(force=False):
     """Compile libmodalhip.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     src = os.path.join(_HERE, "csrc")
@@ -80,6 +84,8 @@ def lib():
         "mh_bank_set_coefficients": (i32, [vp, u32, u32, vp, vp, vp, vp, vp]), "mh_bank_set_shapes": (i32, [vp, u32, u32, vp, vp, vp]),
         "mh_bank_zero_state": (i32, [vp, u32, u32]),
         "mh_bank_render": (i32, [vp, u32, C.c_float, u32, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "mh_bank_render_driven": (i32, [vp, u32, C.c_float, u32, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp, vp]),
+        "mh_drive_struct_size": (u32, []),
         "mh_bank_read_state": (i32, [vp, u32, u32, vp, vp]),
     }
     for name, (res, args) in sig.items():

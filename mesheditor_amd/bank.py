@@ -20,6 +20,10 @@ class Event(C.Structure):  # ModalEvent, src/audio/ModalAudio.h:28-37
                 ("click_a2", C.c_float)]
 
 
+class Drive(C.Structure):  # ModalDrive, modal/bank.hpp (mh_drive of modalhip.h field for field)
+    _fields_ = [("object", C.c_uint32), ("ex_pos", C.c_uint32), ("jx", C.c_float), ("jy", C.c_float), ("jz", C.c_float)]
+
+
 def lib():
     global _LIB
     if _LIB is not None:
@@ -35,7 +39,7 @@ def lib():
         "mhx_add_object": (u32, [vp, u32, u32, u32, vp, vp, u32, vp]), "mhx_tune_object": (None, [vp, i32, u32, u32, vp, vp, f32]),
         "mhx_set_shapes": (i32, [vp, i32, u32, u32, u32, vp]), "mhx_set_gains": (None, [vp, i32, u32, f32, f32]), "mhx_install": (i32, [vp]),
         "mhx_set_renderers": (None, [vp, u32]), "mhx_set_click_gain": (None, [vp, f32]), "mhx_set_max_impacts": (None, [vp, u32]),
-        "mhx_enqueue": (i32, [vp, C.POINTER(Event)]), "mhx_render": (i32, [vp, vp, u32]), "mhx_num_objects": (u32, [vp]),
+        "mhx_enqueue": (i32, [vp, C.POINTER(Event)]), "mhx_render": (i32, [vp, vp, u32]), "mhx_render_driven": (i32, [vp, vp, u32, u32, vp, vp]), "mhx_num_objects": (u32, [vp]),
         "mhx_active_impacts": (u32, [vp]), "mhx_modal_energy": (f64, [vp]), "mhx_render_share": (f32, [vp]), "mhx_find_object": (i32, [vp, u32]),
         "mhx_time_kernels": (i32, [vp, i32]), "mhx_kernel_class_stats": (i32, [vp, i32, C.POINTER(C.c_uint64), C.POINTER(f64), C.POINTER(f64)]),
         "mhx_column": (u32, [vp, i32, i32, vp]), "mhx_object_state": (None, [vp, vp, vp, vp]),
@@ -107,6 +111,16 @@ class Scene:
     def render(self, out):
         assert out.dtype == self.dtype and out.flags["C_CONTIGUOUS"]
         if self.L.mhx_render(self.h, _p(out), len(out)):
+            raise RuntimeError(self.L.mhx_last_error().decode())
+
+    def render_driven(self, out, drives, signals):
+        """RenderModalDriven: one block with sustained force drives.  drives: a ctypes array of Drive (passed on as it is), or a
+        sequence of Drive records or (object, ex_pos, jx, jy, jz) tuples; signals: float32 [len(drives)][len(out)], one force sample per
+        drive and frame."""
+        assert out.dtype == self.dtype and out.flags["C_CONTIGUOUS"]
+        rows = drives if isinstance(drives, C.Array) else (Drive * max(len(drives), 1))(*[v if isinstance(v, Drive) else Drive(*v) for v in drives])
+        sig = np.ascontiguousarray(signals, np.float32).reshape(len(drives), len(out))
+        if self.L.mhx_render_driven(self.h, _p(out), len(out), len(drives), C.cast(rows, C.c_void_p), _p(sig)):
             raise RuntimeError(self.L.mhx_last_error().decode())
 
     def time_kernels(self, enable=True):

@@ -35,6 +35,15 @@ struct ModalEvent {
     float ClickB0{0}, ClickA1{0}, ClickA2{0};
 };
 
+// Not in the reference's ModalAudio.h: a sustained force drive, the bank-side primitive under the drive rows of the reference's
+// surface renderer (src/audio/surface/).  The caller supplies the force signal itself, `frame_count` samples per drive and block
+// (RenderModalDriven); the bank applies it at ExPos along (Jx, Jy, Jz) with the gain an impact has there.  No pulse, no click, no
+// state between blocks: a drive lasts as long as the caller keeps passing it.  Fields are float like ModalEvent's.
+struct ModalDrive {
+    uint32_t Object{0}, ExPos{0};
+    float Jx{0}, Jy{0}, Jz{0};
+};
+
 constexpr float AirDensity{1.204f}, SpeedOfSound{343.f}, ListenerDistance{1.f};
 constexpr float Ln1000 = 3 * std::numbers::ln10_v<float>;
 
@@ -173,6 +182,14 @@ void EnqueueModalEvent(ModalAudio64 &, const ModalEvent &);
 // Adds frame_count mono samples into `out`.  Events take effect at the start of the block.
 void RenderModal(ModalAudio &, float *out, uint32_t frame_count);
 void RenderModal(ModalAudio64 &, double *out, uint32_t frame_count);
+// Not in the reference: RenderModal with sustained drives.  `signals` holds drives.size() rows of frame_count force samples, in the
+// drives' order.  Per sample a mode's excitation is the running sum over its object's impacts (impact-list order, as RenderModal),
+// then over its drives in the order given here.  A sample that is not finite counts as 0.  An object with a drive is excited for the
+// block like one with an impact in flight: it rings, is dealt at and renders its tuned mode count, is not silenced, and leaves the
+// block with LiveModeCount = TunedModeCount.  A drive addressed to an object the bank does not have, to one without modes, or to an
+// excitation position its shape columns do not cover is dropped, as such an impact is.  Without drives this is RenderModal.
+void RenderModalDriven(ModalAudio &, std::span<const ModalDrive> drives, const float *signals, float *out, uint32_t frame_count);
+void RenderModalDriven(ModalAudio64 &, std::span<const ModalDrive> drives, const float *signals, double *out, uint32_t frame_count);
 // Not in the reference: the libmodalhip context the bank's device mirror lives on (created on demand), for callers that
 // time its kernels (mh_context_time_kernels / mh_context_kernel_class_stats).
 mh_context *ModalDeviceContext(ModalAudio &);

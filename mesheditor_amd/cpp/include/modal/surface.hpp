@@ -3,6 +3,12 @@
 // build always links the "absent" implementation (cpp/src/surface_absent.cpp, reference SurfaceContactAbsent.cpp:6-25):
 // every hook does nothing and reports nothing, so objects sound by collision alone.  The declarations are the
 // reference's, so code that includes <audio/SurfaceContact.h> and calls them compiles and links unchanged.
+//
+// What the bank does have of it: sustained excitation.  The reference's surface renderer drives an object's modes with per-sample force
+// signals through per-mode gain rows; that primitive exists here as ModalDrive / RenderModalDriven (modal/bank.hpp) -- a caller-supplied
+// force signal at an excitation position along a direction, for as long as the caller keeps supplying it.  What is still absent is the
+// model on top of it: contact tracking and voices, contact points blended between excitation positions, the feedback reads of the
+// object's displacement at the contact point inside the sample loop, and the roughness / friction signal generators.
 #pragma once
 #include "bank.hpp"
 

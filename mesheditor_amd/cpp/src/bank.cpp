@@ -2,7 +2,7 @@
 //
 // What lives here is bookkeeping: building and tuning the struct-of-arrays bank, the single-producer event ring, the
 // impact list, the deterministic deal of objects to renderers and the publish protocol.  Every per-sample operation
-// (force curves, click filters, mode recurrences, ordered mix) runs on the device in mh_bank_render.
+// (force curves, click filters, mode recurrences, ordered mix) runs on the device in mh_bank_render_driven.
 //
 // Written from the behaviour described in SURVEY.md section 8a rows R0-R8, not from the reference's text.  Where a
 // value must be BIT-identical to the reference's (coefficient columns are compared bit for bit with the CPU oracle),
@@ -34,6 +34,8 @@ struct ModalDeviceMirror {
     std::vector<double> Energy, ModalEnergy;
     std::vector<uint8_t> Silenced;
     std::vector<mh_impact> Impacts;
+    std::vector<mh_drive> Drives; // the block's drives that passed the checks, with their signal rows
+    std::vector<float> DriveSignals;
     std::vector<std::vector<uint32_t>> Renderers;
     ~ModalDeviceMirror() {
         mh_bank_destroy(Bank);
@@ -477,7 +479,16 @@ struct ReaderScope {
 // ------------------------------------------------------------------------------------------------------------------
 // One block (ModalAudio.cpp:486-590).  Host: events, deal, bookkeeping.  Device: everything per sample.
 // ------------------------------------------------------------------------------------------------------------------
-template<typename Audio, typename Real> void RenderBlock(Audio &m, Real *out, uint32_t frames) {
+// Whether excitation position `ex_pos` of `object` lies inside the object's shape columns.  (A position the object does not have: the reference
+// reads past the object's shapes there -- undefined, NaN in the oracle's run of tools/probe/r06_odd_bank_probe.py; on the device that read may
+// leave the shape buffer altogether.  Such an impact, or drive, is dropped.)
+template<typename Real> bool HasExcitationPosition(const ModalBankColumns<Real> &b, uint32_t object, uint32_t ex_pos) {
+    const uint32_t first = b.ShapeOffset[object];
+    const uint32_t last = size_t(object) + 1 < b.ShapeOffset.size() ? b.ShapeOffset[object + 1] : uint32_t(b.ShapeX.size());
+    return uint64_t(ex_pos) * b.ModeCount[object] + b.ModeCount[object] <= uint64_t(last - first);
+}
+
+template<typename Audio, typename Real> void RenderBlock(Audio &m, std::span<const ModalDrive> drives, const float *signals, Real *out, uint32_t frames) {
     if (frames == 0) return;
     const auto started = std::chrono::steady_clock::now();
     const ReaderScope reading(m.ReaderSeq);
@@ -489,13 +500,7 @@ template<typename Audio, typename Real> void RenderBlock(Audio &m, Real *out, ui
     const uint32_t impact_cap = m.MaxImpacts.load(std::memory_order_relaxed);
     RingConsume(m, [&](const ModalEvent &e) {
         if (e.Object >= b.Entities.size()) return; // addressed to a slot this bank does not have
-        // (an excitation position the object does not have: the reference reads past the object's shapes there -- undefined, NaN in the oracle's run
-        // of tools/probe/r06_odd_bank_probe.py; on the device that read may leave the shape buffer altogether.  Such an impact is dropped.)
-        if (e.Kind == ModalEventKind::Impact && b.ModeCount[e.Object] > 0) {
-            const uint32_t first = b.ShapeOffset[e.Object];
-            const uint32_t last = size_t(e.Object) + 1 < b.ShapeOffset.size() ? b.ShapeOffset[e.Object + 1] : uint32_t(b.ShapeX.size());
-            if (uint64_t(e.ExPos) * b.ModeCount[e.Object] + b.ModeCount[e.Object] > uint64_t(last - first)) return;
-        }
+        if (e.Kind == ModalEventKind::Impact && b.ModeCount[e.Object] > 0 && !HasExcitationPosition(b, e.Object, e.ExPos)) return;
         if (e.Kind == ModalEventKind::Silence) Quiet(m, b, e.Object, false);
         else if (e.Kind == ModalEventKind::Impact && e.PulseStep > 0) StartImpact(b, e, impact_cap);
     });
@@ -505,6 +510,23 @@ template<typename Audio, typename Real> void RenderBlock(Audio &m, Real *out, ui
     const uint32_t n_objects = uint32_t(b.Entities.size()), renderers = m.RenderPool.Size();
     d.ImpactsOn.assign(n_objects, 0);
     for (const auto &im : b.Impacts) ++d.ImpactsOn[im.Object];
+    // drives: the ones the bank can follow, in the caller's order.  A driven object is excited like a struck one -- ImpactsOn counts both
+    // kinds from here on, so every decision below that asks "is it excited" covers drives -- and it rings, so it is dealt.
+    d.Drives.clear();
+    d.DriveSignals.clear();
+    for (size_t j = 0; j < drives.size(); ++j) {
+        const ModalDrive &v = drives[j];
+        const bool keep = v.Object < n_objects && b.ModeCount[v.Object] > 0 && HasExcitationPosition(b, v.Object, v.ExPos);
+        if (!keep) {
+            if (d.Drives.size() == j) d.DriveSignals.assign(signals, signals + j * frames); // the first drop: from here on the kept rows are packed
+            continue;
+        }
+        if (d.Drives.size() != j) d.DriveSignals.insert(d.DriveSignals.end(), signals + j * frames, signals + (j + 1) * frames);
+        d.Drives.push_back({v.Object, v.ExPos, v.Jx, v.Jy, v.Jz});
+        ++d.ImpactsOn[v.Object];
+        b.Ringing[v.Object] = 1;
+    }
+    const float *drive_signals = d.Drives.size() == drives.size() ? signals : d.DriveSignals.data(); // nothing dropped: the caller's rows as they are
     Deal(d, b, renderers);
     d.DealOffset.assign(1, 0);
     d.DealObjects.clear();
@@ -544,8 +566,9 @@ template<typename Audio, typename Real> void RenderBlock(Audio &m, Real *out, ui
         narrow_listener.assign(b.ListenerGain.begin(), b.ListenerGain.end());
         out_gain = narrow_out.data(), listener_gain = narrow_listener.data();
     }
-    if (mh_bank_render(d.Bank, frames, m.ClickGain.load(std::memory_order_relaxed), n_impacts, d.Impacts.data(), renderers, d.DealOffset.data(), d.DealObjects.data(),
-                       d.RenderCount.data(), d.Tuned.data(), out_gain, listener_gain, out, d.Energy.data(), d.Live.data(), d.Silenced.data(), d.ModalEnergy.data()) != MH_OK)
+    if (mh_bank_render_driven(d.Bank, frames, m.ClickGain.load(std::memory_order_relaxed), n_impacts, d.Impacts.data(), renderers, d.DealOffset.data(), d.DealObjects.data(),
+                              d.RenderCount.data(), d.Tuned.data(), out_gain, listener_gain, out, d.Energy.data(), d.Live.data(), d.Silenced.data(), d.ModalEnergy.data(),
+                              uint32_t(d.Drives.size()), d.Drives.data(), drive_signals) != MH_OK)
         Fail(d);
 
     // impacts: carry the recurrences' state over to the next block
@@ -615,8 +638,14 @@ std::optional<uint32_t> FindModalObject(const ModalBank &b, entt::entity e) { re
 std::optional<uint32_t> FindModalObject(const ModalBank64 &b, entt::entity e) { return SlotOf<double>(b, e); }
 void EnqueueModalEvent(ModalAudio &m, const ModalEvent &e) { RingPush(m, e); }
 void EnqueueModalEvent(ModalAudio64 &m, const ModalEvent &e) { RingPush(m, e); }
-void RenderModal(ModalAudio &m, float *out, uint32_t frame_count) { RenderBlock<ModalAudio, float>(m, out, frame_count); }
-void RenderModal(ModalAudio64 &m, double *out, uint32_t frame_count) { RenderBlock<ModalAudio64, double>(m, out, frame_count); }
+void RenderModal(ModalAudio &m, float *out, uint32_t frame_count) { RenderBlock<ModalAudio, float>(m, {}, nullptr, out, frame_count); }
+void RenderModal(ModalAudio64 &m, double *out, uint32_t frame_count) { RenderBlock<ModalAudio64, double>(m, {}, nullptr, out, frame_count); }
+void RenderModalDriven(ModalAudio &m, std::span<const ModalDrive> drives, const float *signals, float *out, uint32_t frame_count) {
+    RenderBlock<ModalAudio, float>(m, drives, signals, out, frame_count);
+}
+void RenderModalDriven(ModalAudio64 &m, std::span<const ModalDrive> drives, const float *signals, double *out, uint32_t frame_count) {
+    RenderBlock<ModalAudio64, double>(m, drives, signals, out, frame_count);
+}
 mh_context *ModalDeviceContext(ModalAudio &m) { return NeedContext(m), m.Dev->Context; }
 mh_context *ModalDeviceContext(ModalAudio64 &m) { return NeedContext(m), m.Dev->Context; }
 void SyncModalState(ModalAudio &m) { PullState(m); }

@@ -108,6 +108,15 @@ int mhx_render(mhx_scene *s, void *out, uint32_t frames) {
         return 0;
     } catch (const std::exception &e) { g_error = e.what(); return 1; }
 }
+// RenderModalDriven: `drives` is n_drives ModalDrive records, `signals` [n_drives][frames] float in either precision
+int mhx_render_driven(mhx_scene *s, void *out, uint32_t frames, uint32_t n_drives, const ModalDrive *drives, const float *signals) {
+    try {
+        const std::span<const ModalDrive> list(drives, n_drives);
+        if (s->dbl) RenderModalDriven(s->audio64, list, signals, static_cast<double *>(out), frames);
+        else RenderModalDriven(s->audio, list, signals, static_cast<float *>(out), frames);
+        return 0;
+    } catch (const std::exception &e) { g_error = e.what(); return 1; }
+}
 // Kernel timing of the scene's device context: enable / read one class (modalhip.h MH_KERNEL_*)
 int mhx_time_kernels(mhx_scene *s, int enable) {
     try {

@@ -83,6 +83,17 @@ __global__ void k_bank_forces(ImpactDev<Real> *__restrict__ impacts, uint32_t n_
     back[i] = {left, phase_re, phase_im, z1, z2}; // what the host takes back, written where it reads it (pinned memory)
 }
 
+// Force rows of the caller's drives (mh_bank_render_driven): the float signals become `Real` rows that follow the impacts' rows in
+// `force`, so the resonator kernel addresses both kinds alike.  A sample that is not finite is rendered as 0 -- one NaN would ring in
+// the state for ever.  No curve, no click filter, no state: a drive lasts for the block it was passed with.
+template<typename Real>
+__global__ void __launch_bounds__(256) k_bank_drive_rows(const float *__restrict__ signals, size_t n, Real *__restrict__ rows) {
+    const size_t i = size_t(blockIdx.x) * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float v = signals[i];
+    rows[i] = (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u ? Real(v) : Real(0); // exponent all ones: Inf or NaN
+}
+
 template<typename Real> struct BankCols {
     Real *coeff_re, *coeff_im, *state_re, *state_im, *rad_gain, *phase_im, *phase_re, *shape_x, *shape_y, *shape_z;
     const uint32_t *mode_offset, *mode_count, *shape_offset;
@@ -125,14 +136,22 @@ template<typename Real> __device__ __forceinline__ Real chunk_sum_in_order(Real 
 // into an LDS tile [sample][mode]; after the tile the wave turns around -- lane = (chunk group, sample) -- and adds each chunk's 8
 // terms in mode order 0..7, which is the reference's summation order at two LDS reads per mode-sample instead of a cross-lane
 // chain per sample, and makes the partial-signal stores contiguous in the sample.
+//
+// Force rows.  An object's rows are its impacts in impact-list order, then its drives in the caller's order (imp_idx lists both: a drive
+// is an ImpactDev entry behind the impacts, with a force row at the same index).  Per sample the excitation is the running sum over
+// them, from +0.  Up to IMP_REG rows: gain and force tile in registers (run).  IMP_REG < rows <= ROWS_MAX, in a launch that carries
+// drives (MANY): run_rows -- the force tiles of all rows go to LDS once per 32-sample tile, [sample][row], so that a sample's forces
+// arrive with one or two wave-uniform LDS reads instead of a lane broadcast per row; the gains of the first ROWS_REG rows stay in
+// registers, those of the rows behind them in LDS.  More rows than that (or a drive-free launch): the scratch-row path (EXTRA).
 constexpr int MODES_PER_WAVE = 2 * WAVE;
-template<typename Real>
-__global__ void __launch_bounds__(WAVE) k_bank_modes(BankCols<Real> b, const WaveDesc *__restrict__ waves, const uint32_t *__restrict__ deal_objects,
-                                                    const uint32_t *__restrict__ render_count, const uint32_t *__restrict__ chunk_base,
-                                                    const uint32_t *__restrict__ imp_ptr, const uint32_t *__restrict__ imp_idx,
-                                                    const ImpactDev<Real> *__restrict__ impacts, const Real *__restrict__ force,
-                                                    const Real *__restrict__ out_gain, const Real *__restrict__ listener_gain, uint32_t frames,
-                                                    Real *__restrict__ partial, Real *__restrict__ chunk_energy, Real *__restrict__ gain_scratch, uint32_t max_imp) {
+constexpr uint32_t IMP_REG = 2, ROWS_REG = 8, ROWS_MAX = 12;
+template<typename Real, bool MANY>
+__device__ __forceinline__ void bank_modes(const BankCols<Real> &b, const WaveDesc *__restrict__ waves, const uint32_t *__restrict__ deal_objects,
+                                           const uint32_t *__restrict__ render_count, const uint32_t *__restrict__ chunk_base,
+                                           const uint32_t *__restrict__ imp_ptr, const uint32_t *__restrict__ imp_idx,
+                                           const ImpactDev<Real> *__restrict__ impacts, const Real *__restrict__ force,
+                                           const Real *__restrict__ out_gain, const Real *__restrict__ listener_gain, uint32_t frames,
+                                           Real *__restrict__ partial, Real *__restrict__ chunk_energy, Real *__restrict__ gain_scratch, uint32_t max_imp) {
     typedef Real Pair __attribute__((ext_vector_type(2)));
     constexpr uint32_t TS = 32, PITCH = MODES_PER_WAVE + 2, CHUNKS = MODES_PER_WAVE / LANES;
     __shared__ __attribute__((aligned(16))) Real s_term[TS * PITCH];
@@ -156,26 +175,56 @@ __global__ void __launch_bounds__(WAVE) k_bank_modes(BankCols<Real> b, const Wav
     const uint32_t i0 = imp_ptr[wd.dealt], n_imp = imp_ptr[wd.dealt + 1] - i0;
     // Hoisted impact gains (ImpactGainRow, ModalAudio.h:182-188); zero on padded modes.  The first IMP_REG impacts of
     // the object live in registers, further ones (rare) in a scratch row.
-    constexpr uint32_t IMP_REG = 2;
     Pair g_reg[IMP_REG] = {};
     uint32_t f_row[IMP_REG] = {};
     Real *g_mem = gain_scratch + size_t(blockIdx.x) * max_imp * MODES_PER_WAVE;
-    for (uint32_t t = 0; t < n_imp; ++t) {
+    const bool many_rows = MANY && n_imp > IMP_REG && n_imp <= ROWS_MAX; // run_rows computes its own gains
+    auto gain_of = [&](uint32_t t) {
         Pair g = {0, 0};
-        const uint32_t ii = imp_idx[i0 + t];
-        const ImpactDev<Real> &im = impacts[ii];
+        const ImpactDev<Real> &im = impacts[imp_idx[i0 + t]];
 #pragma unroll
         for (int h = 0; h < 2; ++h)
             if (live[h]) {
                 const uint32_t base = shape0 + im.ex_pos * stride + k + h;
                 g[h] = b.rad_gain[k0 + k + h] * (b.shape_x[base] * im.jx + b.shape_y[base] * im.jy + b.shape_z[base] * im.jz);
             }
-        if (t < IMP_REG) { g_reg[t] = g; f_row[t] = ii; }
+        return g;
+    };
+    for (uint32_t t = 0; t < (many_rows ? 0u : n_imp); ++t) {
+        const Pair g = gain_of(t);
+        if (t < IMP_REG) { g_reg[t] = g; f_row[t] = imp_idx[i0 + t]; }
         else *reinterpret_cast<Pair *>(g_mem + size_t(t) * MODES_PER_WAVE + 2 * lane) = g;
     }
     const Real mix_gain = out_gain[o] * listener_gain[o];
     const uint32_t half = lane / TS, ts = lane % TS; // turn-around mapping: chunks 8*half .. 8*half+7 of sample ts
 
+    // one sample of this lane's two resonators; their output terms go to the turn-around tile
+    auto step = [&](const Pair &excite, uint32_t ds) {
+        const Pair re = z_re * c_re - z_im * c_im + excite;
+        z_im = z_re * c_im + z_im * c_re;
+        z_re = re;
+        *reinterpret_cast<Pair *>(s_term + ds * PITCH + 2 * lane) = p_im * z_im + p_re * re;
+    };
+    // after a tile's samples: every chunk's 8 terms added in mode order, sample ts of chunks 8*half .. 8*half+7 per lane
+    auto turn_around = [&](uint32_t s0, uint32_t sn) {
+        __syncthreads();
+        if (ts < sn) {
+            const Real *row = s_term + ts * PITCH + half * (CHUNKS / 2 * LANES);
+#pragma unroll
+            for (uint32_t c = 0; c < CHUNKS / 2; ++c) {
+                Real acc = 0;
+#pragma unroll
+                for (uint32_t l = 0; l < LANES; l += 2) {
+                    const Pair v = *reinterpret_cast<const Pair *>(row + c * LANES + l);
+                    acc += v.x;
+                    acc += v.y;
+                }
+                const uint32_t chunk = CHUNKS / 2 * half + c;
+                if (chunk < chunks_here) partial[size_t(chunk0 + chunk) * frames + s0 + ts] = acc * mix_gain;
+            }
+        }
+        __syncthreads();
+    };
     // NR = impacts held in registers (0, 1 or 2); EXTRA = the object has more than IMP_REG impacts.
     auto run = [&](auto nr_tag, auto extra_tag) {
         constexpr uint32_t NR = decltype(nr_tag)::value;
@@ -203,10 +252,7 @@ __global__ void __launch_bounds__(WAVE) k_bank_modes(BankCols<Real> b, const Wav
                         excite += f * *reinterpret_cast<const Pair *>(g_mem + size_t(t) * MODES_PER_WAVE + 2 * lane);
                     }
                 }
-                const Pair re = z_re * c_re - z_im * c_im + excite;
-                z_im = z_re * c_im + z_im * c_re;
-                z_re = re;
-                *reinterpret_cast<Pair *>(s_term + ds * PITCH + 2 * lane) = p_im * z_im + p_re * re;
+                step(excite, ds);
             };
             if (sn == TS && !EXTRA) {
 #pragma unroll
@@ -214,32 +260,72 @@ __global__ void __launch_bounds__(WAVE) k_bank_modes(BankCols<Real> b, const Wav
             } else {
                 for (uint32_t ds = 0; ds < sn; ++ds) sample(ds);
             }
-            __syncthreads();
-            if (ts < sn) {
-                const Real *row = s_term + ts * PITCH + half * (CHUNKS / 2 * LANES);
-#pragma unroll
-                for (uint32_t c = 0; c < CHUNKS / 2; ++c) {
-                    Real acc = 0;
-#pragma unroll
-                    for (uint32_t l = 0; l < LANES; l += 2) {
-                        const Pair v = *reinterpret_cast<const Pair *>(row + c * LANES + l);
-                        acc += v.x;
-                        acc += v.y;
-                    }
-                    const uint32_t chunk = CHUNKS / 2 * half + c;
-                    if (chunk < chunks_here) partial[size_t(chunk0 + chunk) * frames + s0 + ts] = acc * mix_gain;
-                }
-            }
-            __syncthreads();
+            turn_around(s0, sn);
         }
     };
     using T0 = std::integral_constant<uint32_t, 0>;
     using T1 = std::integral_constant<uint32_t, 1>;
     using T2 = std::integral_constant<uint32_t, 2>;
-    if (n_imp == 0) run(T0{}, std::false_type{});
-    else if (n_imp == 1) run(T1{}, std::false_type{});
-    else if (n_imp == 2) run(T2{}, std::false_type{});
-    else run(T2{}, std::true_type{});
+    if constexpr (MANY) {
+        // R = rows whose gains are in registers (3 .. ROWS_REG); MORE = rows R .. n_imp-1 follow, their gains in LDS.
+        __shared__ __attribute__((aligned(16))) Real s_force[TS * ROWS_MAX]; // [sample][row]: this tile's forces of every row
+        __shared__ __attribute__((aligned(16))) Real s_gain[(ROWS_MAX - ROWS_REG) * MODES_PER_WAVE]; // [row - ROWS_REG][mode]
+        auto run_rows = [&](auto r_tag, auto more_tag) {
+            constexpr uint32_t R = decltype(r_tag)::value;
+            constexpr bool MORE = decltype(more_tag)::value;
+            Pair g[R];
+#pragma unroll
+            for (uint32_t t = 0; t < R; ++t) g[t] = gain_of(t);
+            if (MORE) // a lane reads back only what it wrote itself: no barrier between these stores and the sample loop's reads
+                for (uint32_t t = R; t < n_imp; ++t) *reinterpret_cast<Pair *>(s_gain + (t - R) * MODES_PER_WAVE + 2 * lane) = gain_of(t);
+            // staging: lane = (row parity, sample); rows half, half + 2, ... of the object
+            const Real *mine[ROWS_MAX / 2] = {};
+#pragma unroll
+            for (uint32_t j = 0; j < ROWS_MAX / 2; ++j)
+                if (half + 2 * j < n_imp) mine[j] = force + size_t(imp_idx[i0 + half + 2 * j]) * frames + ts;
+            for (uint32_t s0 = 0; s0 < frames; s0 += TS) {
+                const uint32_t sn = min(TS, frames - s0);
+#pragma unroll
+                for (uint32_t j = 0; j < ROWS_MAX / 2; ++j)
+                    if (half + 2 * j < n_imp) s_force[ts * ROWS_MAX + half + 2 * j] = ts < sn ? mine[j][s0] : Real(0);
+                __syncthreads();
+                auto sample = [&](uint32_t ds) {
+                    const Real *f = s_force + ds * ROWS_MAX;
+                    Pair excite = {0, 0};
+                    // (zero samples are added, not skipped: the same bits, see run)
+#pragma unroll
+                    for (uint32_t t = 0; t < R; ++t) excite += f[t] * g[t];
+                    if (MORE)
+                        for (uint32_t t = R; t < n_imp; ++t) excite += f[t] * *reinterpret_cast<const Pair *>(s_gain + (t - R) * MODES_PER_WAVE + 2 * lane);
+                    step(excite, ds);
+                };
+                if (sn == TS) {
+#pragma unroll
+                    for (uint32_t ds = 0; ds < TS; ++ds) sample(ds);
+                } else {
+                    for (uint32_t ds = 0; ds < sn; ++ds) sample(ds);
+                }
+                turn_around(s0, sn); // its last barrier also separates this tile's force reads from the next tile's staging
+            }
+        };
+        if (many_rows) {
+            switch (n_imp) {
+            case 3: run_rows(std::integral_constant<uint32_t, 3>{}, std::false_type{}); break;
+            case 4: run_rows(std::integral_constant<uint32_t, 4>{}, std::false_type{}); break;
+            case 5: run_rows(std::integral_constant<uint32_t, 5>{}, std::false_type{}); break;
+            case 6: run_rows(std::integral_constant<uint32_t, 6>{}, std::false_type{}); break;
+            case 7: run_rows(std::integral_constant<uint32_t, 7>{}, std::false_type{}); break;
+            case 8: run_rows(std::integral_constant<uint32_t, ROWS_REG>{}, std::false_type{}); break;
+            default: run_rows(std::integral_constant<uint32_t, ROWS_REG>{}, std::true_type{}); break;
+            }
+        }
+    }
+    if (!many_rows) {
+        if (n_imp == 0) run(T0{}, std::false_type{});
+        else if (n_imp == 1) run(T1{}, std::false_type{});
+        else if (n_imp == 2) run(T2{}, std::false_type{});
+        else run(T2{}, std::true_type{});
+    }
 #pragma unroll
     for (int h = 0; h < 2; ++h)
         if (live[h]) {
@@ -259,6 +345,19 @@ __global__ void __launch_bounds__(WAVE) k_bank_modes(BankCols<Real> b, const Wav
     chunk += row_shl<3>(e1);
     if ((lane & (LANES / 2 - 1)) == 0 && lane / (LANES / 2) < chunks_here) chunk_energy[chunk0 + lane / (LANES / 2)] = chunk;
 }
+#define BANK_MODES_PARAMS                                                                                                                                  \
+    BankCols<Real> b, const WaveDesc *__restrict__ waves, const uint32_t *__restrict__ deal_objects, const uint32_t *__restrict__ render_count,          \
+        const uint32_t *__restrict__ chunk_base, const uint32_t *__restrict__ imp_ptr, const uint32_t *__restrict__ imp_idx,                             \
+        const ImpactDev<Real> *__restrict__ impacts, const Real *__restrict__ force, const Real *__restrict__ out_gain,                                   \
+        const Real *__restrict__ listener_gain, uint32_t frames, Real *__restrict__ partial, Real *__restrict__ chunk_energy,                             \
+        Real *__restrict__ gain_scratch, uint32_t max_imp
+#define BANK_MODES_ARGS b, waves, deal_objects, render_count, chunk_base, imp_ptr, imp_idx, impacts, force, out_gain, listener_gain, frames, partial, chunk_energy, gain_scratch, max_imp
+// The launch of a block without drives, or whose objects have at most IMP_REG rows each: the turn-around tile is all its LDS.
+template<typename Real> __global__ void __launch_bounds__(WAVE) k_bank_modes(BANK_MODES_PARAMS) { bank_modes<Real, false>(BANK_MODES_ARGS); }
+// The launch of a block with drives in which some object has more than IMP_REG rows: the same code plus run_rows and its LDS.
+template<typename Real> __global__ void __launch_bounds__(WAVE) k_bank_modes_rows(BANK_MODES_PARAMS) { bank_modes<Real, true>(BANK_MODES_ARGS); }
+#undef BANK_MODES_PARAMS
+#undef BANK_MODES_ARGS
 
 // Per dealt object (one wave each): energy, audible prefix, whole-object silence (ModalAudio.cpp:132-146).  Loads are
 // lane-parallel; every sum runs in the reference's order through wave-uniform lane broadcasts.
@@ -516,8 +615,8 @@ template<typename Real> struct BankImpl {
     // per-block scratch
     Arena arena;
     DevArray<Real> force, click, partial, chunk_energy, gain_scratch, rout;
-    std::vector<int32_t> dealt_of_object;
-    std::vector<uint32_t> imp_fill;
+    std::vector<int32_t> dealt_of_object, drive_dealt;
+    std::vector<uint32_t> imp_fill, h_shape_offset;
     BankCols<Real> cols() {
         return {coeff_re, coeff_im, state_re, state_im, rad_gain, phase_im, phase_re, shape_x, shape_y, shape_z, mode_offset, mode_count, shape_offset};
     }
@@ -538,7 +637,8 @@ void upload_converted(mh_context *ctx, DevArray<Real> &dst, size_t offset, const
 template<typename Real>
 void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t n_impacts, mh_impact *impacts, uint32_t n_renderers, const uint32_t *deal_offset,
                  const uint32_t *deal_objects, const uint32_t *render_count, const uint32_t *tuned_count, const float *out_gain, const float *listener_gain,
-                 void *out_v, double *object_energy, uint32_t *object_live, uint8_t *object_silenced, double *object_modal_energy) {
+                 void *out_v, double *object_energy, uint32_t *object_live, uint8_t *object_silenced, double *object_modal_energy, uint32_t n_drives,
+                 const mh_drive *drives, const float *signals) {
     mh_context *ctx = B.ctx;
     hipStream_t st = ctx->stream;
     Real *out = static_cast<Real *>(out_v);
@@ -551,8 +651,11 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
     const size_t o_out_gain = A.take(B.n_objects * sizeof(Real)), o_listener = A.take(B.n_objects * sizeof(Real));
     const size_t o_waves = A.take((n_waves + 1) * sizeof(WaveDesc)), o_deal = A.take((n_dealt + 1) * 4), o_count = A.take((n_dealt + 1) * 4);
     const size_t o_tuned = A.take((n_dealt + 1) * 4), o_chunk_base = A.take((n_dealt + 1) * 4), o_imp_ptr = A.take((n_dealt + 1) * 4);
-    const size_t o_imp_idx = A.take((n_impacts + 1) * 4), o_rcp = A.take((n_renderers + 1) * 4);
-    const size_t o_out = A.take(frames * sizeof(Real)), o_impacts = A.take((n_impacts + 1) * sizeof(ImpactDev<Real>));
+    // (a drive is a row like an impact's: entry n_impacts + j of the impact array and of the index list, force row n_impacts + j)
+    const uint32_t n_rows = n_impacts + n_drives;
+    const size_t o_imp_idx = A.take((n_rows + 1) * 4), o_rcp = A.take((n_renderers + 1) * 4);
+    const size_t o_out = A.take(frames * sizeof(Real)), o_impacts = A.take((n_rows + 1) * sizeof(ImpactDev<Real>));
+    const size_t o_signals = A.take(size_t(n_drives) * frames * sizeof(float));
     const size_t both_end = A.used;
     // (written by the kernels straight into the pinned arena -- no copy back: the host sees them once the block's last kernel has
     // raised the sequence number)
@@ -579,11 +682,23 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
         }
         imp_ptr[0] = 0;
     }
-    uint32_t max_imp = 1;
+    uint32_t max_imp = 1, driven_rows = 0;
     if (n_dealt) {
         for (uint32_t i = 0; i < n_impacts; ++i) {
             const int32_t d = impacts[i].object < B.n_objects ? B.dealt_of_object[impacts[i].object] : -1;
             if (d >= 0) ++imp_ptr[d + 1];
+        }
+        // a drive the kernel must not follow is left out here: no such object, an object that was not dealt or has no modes, or an
+        // excitation position beyond the object's shape columns (the read would leave the shape buffer)
+        B.drive_dealt.assign(n_drives, -1);
+        for (uint32_t j = 0; j < n_drives; ++j) {
+            const uint32_t o = drives[j].object;
+            if (o >= B.n_objects || B.dealt_of_object[o] < 0 || B.h_mode_count[o] == 0) continue;
+            const uint64_t shapes_end = o + 1 < B.n_objects ? B.h_shape_offset[o + 1] : B.n_shapes;
+            if ((uint64_t(drives[j].ex_pos) + 1) * B.h_mode_count[o] > shapes_end - B.h_shape_offset[o]) continue;
+            B.drive_dealt[j] = B.dealt_of_object[o];
+            ++imp_ptr[B.drive_dealt[j] + 1];
+            ++driven_rows;
         }
         for (uint32_t d = 0; d < n_dealt; ++d) {
             max_imp = std::max(max_imp, imp_ptr[d + 1]);
@@ -594,6 +709,8 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
             const int32_t d = impacts[i].object < B.n_objects ? B.dealt_of_object[impacts[i].object] : -1;
             if (d >= 0) imp_idx[B.imp_fill[d]++] = i;
         }
+        for (uint32_t j = 0; j < n_drives; ++j) // behind the object's impacts, in the caller's order
+            if (B.drive_dealt[j] >= 0) imp_idx[B.imp_fill[B.drive_dealt[j]]++] = n_impacts + j;
     }
     for (uint32_t q = 0; q <= n_renderers; ++q) {
         const uint32_t d0 = q < n_renderers ? deal_offset[q] : n_dealt;
@@ -612,14 +729,24 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
         himp[i] = {m.object, m.ex_pos, m.samples_left, 0, Real(m.jx), Real(m.jy), Real(m.jz), Real(m.phase_re), Real(m.phase_im), Real(m.rot_re), Real(m.rot_im),
                    Real(m.gamma), Real(m.accel_amp), Real(m.click_b0), Real(m.click_a1), Real(m.click_a2), Real(m.click_z1), Real(m.click_z2)};
     }
+    for (uint32_t j = 0; j < n_drives; ++j) { // only object, ex_pos and the direction are read of a drive's entry
+        const mh_drive &m = drives[j];
+        himp[n_impacts + j] = {m.object, m.ex_pos, 0, 0, Real(m.jx), Real(m.jy), Real(m.jz), 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    }
+    if (n_drives) std::copy(signals, signals + size_t(n_drives) * frames, A.h<float>(o_signals));
     HIP_CHECK(hipMemcpyAsync(A.dev, A.host, both_end, hipMemcpyHostToDevice, st));
     // ---- device passes ----
     Real *d_out_gain = A.d<Real>(o_out_gain), *d_listener = A.d<Real>(o_listener), *d_out = A.d<Real>(o_out);
     ImpactDev<Real> *d_impacts = A.d<ImpactDev<Real>>(o_impacts);
-    ensure(ctx, B.force, size_t(std::max<uint32_t>(n_impacts, 1)) * frames);
+    ensure(ctx, B.force, size_t(std::max<uint32_t>(n_rows, 1)) * frames);
     ensure(ctx, B.click, size_t(std::max<uint32_t>(n_impacts, 1)) * frames);
     if (n_impacts) {
         k_bank_forces<Real><<<div_up(n_impacts, 64), 64, 0, st>>>(d_impacts, n_impacts, d_listener, Real(click_gain), frames, B.force, B.click, A.hd<ImpactBack<Real>>(o_back));
+        KERNEL_CHECK();
+    }
+    if (n_drives) {
+        const size_t n = size_t(n_drives) * frames;
+        k_bank_drive_rows<Real><<<uint32_t(div_up(n, size_t(256))), 256, 0, st>>>(A.d<float>(o_signals), n, B.force.get() + size_t(n_impacts) * frames);
         KERNEL_CHECK();
     }
     ensure(ctx, B.rout, size_t(std::max<uint32_t>(n_renderers, 1)) * frames);
@@ -631,9 +758,15 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
         if (n_waves) {
             uint64_t rendered_modes = 0;
             for (uint32_t d = 0; d < n_dealt; ++d) rendered_modes += render_count[d];
-            TimedLaunch timed(ctx, MH_KERNEL_BANK, 11.0 * double(rendered_modes) * double(frames)); // ~11 flop per mode-sample
-            k_bank_modes<Real><<<n_waves, WAVE, 0, st>>>(B.cols(), A.d<WaveDesc>(o_waves), d_deal, d_count, d_chunk_base, d_imp_ptr, A.d<uint32_t>(o_imp_idx), d_impacts,
-                                                         B.force, d_out_gain, d_listener, frames, B.partial, B.chunk_energy, B.gain_scratch, max_imp);
+            uint64_t driven_modes = 0; // a drive row adds a multiply and an add per mode-sample of its object
+            for (uint32_t j = 0; j < n_drives; ++j)
+                if (B.drive_dealt[j] >= 0) driven_modes += render_count[B.drive_dealt[j]];
+            TimedLaunch timed(ctx, MH_KERNEL_BANK, (11.0 * double(rendered_modes) + 2.0 * double(driven_modes)) * double(frames)); // ~11 flop per mode-sample
+            // a block without drives launches what it always did; one with drives takes the launch with the many-row loop (and its
+            // LDS) only when some object has more rows than the register path holds
+            auto *modes_kernel = driven_rows && max_imp > IMP_REG ? &k_bank_modes_rows<Real> : &k_bank_modes<Real>;
+            modes_kernel<<<n_waves, WAVE, 0, st>>>(B.cols(), A.d<WaveDesc>(o_waves), d_deal, d_count, d_chunk_base, d_imp_ptr, A.d<uint32_t>(o_imp_idx), d_impacts,
+                                                  B.force, d_out_gain, d_listener, frames, B.partial, B.chunk_energy, B.gain_scratch, max_imp);
             KERNEL_CHECK();
         }
     } else if (n_renderers) {
@@ -713,6 +846,7 @@ static std::unique_ptr<BankImpl<Real>> make_bank(mh_context *ctx, uint32_t n_obj
         HIP_CHECK(hipStreamSynchronize(ctx->stream));
     }
     B->h_mode_count.assign(mode_count, mode_count + n_objects);
+    B->h_shape_offset.assign(shape_offset, shape_offset + n_objects);
     return B;
 }
 
@@ -782,20 +916,31 @@ int mh_bank_zero_state(mh_bank *bank, uint32_t first, uint32_t count) {
         return MH_OK;
     } catch (const std::exception &e) { return mh_guard(bank->ctx, e); }
 }
-int mh_bank_render(mh_bank *bank, uint32_t frames, float click_gain, uint32_t n_impacts, mh_impact *impacts, uint32_t n_renderers, const uint32_t *deal_offset,
-                   const uint32_t *deal_objects, const uint32_t *render_count, const uint32_t *tuned_count, const float *out_gain, const float *listener_gain,
-                   void *out, double *object_energy, uint32_t *object_live, uint8_t *object_silenced, double *object_modal_energy) {
-    if (!bank || !out || (n_impacts && !impacts) || (n_renderers && !deal_offset) || !out_gain || !listener_gain) return MH_EINVAL;
+int mh_bank_render_driven(mh_bank *bank, uint32_t frames, float click_gain, uint32_t n_impacts, mh_impact *impacts, uint32_t n_renderers, const uint32_t *deal_offset,
+                          const uint32_t *deal_objects, const uint32_t *render_count, const uint32_t *tuned_count, const float *out_gain, const float *listener_gain,
+                          void *out, double *object_energy, uint32_t *object_live, uint8_t *object_silenced, double *object_modal_energy, uint32_t n_drives,
+                          const mh_drive *drives, const float *signals) {
+    if (!bank || !out || (n_impacts && !impacts) || (n_renderers && !deal_offset) || !out_gain || !listener_gain || (n_drives && (!drives || !signals))) return MH_EINVAL;
     if (n_renderers && deal_offset[n_renderers] && (!deal_objects || !render_count || !tuned_count || !object_energy || !object_live || !object_silenced)) return MH_EINVAL;
     if (frames == 0) return MH_OK;
     try {
         MhSharedPhase not_during_a_factorisation(bank->ctx->device); // a solve's dense coarse factorisation runs alone on the device (mh_eigs.hip)
         HIP_CHECK(hipSetDevice(bank->ctx->device));
-        if (bank->dbl) render_impl(*bank->d, frames, click_gain, n_impacts, impacts, n_renderers, deal_offset, deal_objects, render_count, tuned_count, out_gain, listener_gain, out, object_energy, object_live, object_silenced, object_modal_energy);
-        else render_impl(*bank->f, frames, click_gain, n_impacts, impacts, n_renderers, deal_offset, deal_objects, render_count, tuned_count, out_gain, listener_gain, out, object_energy, object_live, object_silenced, object_modal_energy);
+        auto go = [&](auto &B) {
+            render_impl(B, frames, click_gain, n_impacts, impacts, n_renderers, deal_offset, deal_objects, render_count, tuned_count, out_gain, listener_gain, out, object_energy,
+                        object_live, object_silenced, object_modal_energy, n_drives, drives, signals);
+        };
+        if (bank->dbl) go(*bank->d); else go(*bank->f);
         return MH_OK;
     } catch (const std::exception &e) { return mh_guard(bank->ctx, e); }
 }
+int mh_bank_render(mh_bank *bank, uint32_t frames, float click_gain, uint32_t n_impacts, mh_impact *impacts, uint32_t n_renderers, const uint32_t *deal_offset,
+                   const uint32_t *deal_objects, const uint32_t *render_count, const uint32_t *tuned_count, const float *out_gain, const float *listener_gain,
+                   void *out, double *object_energy, uint32_t *object_live, uint8_t *object_silenced, double *object_modal_energy) {
+    return mh_bank_render_driven(bank, frames, click_gain, n_impacts, impacts, n_renderers, deal_offset, deal_objects, render_count, tuned_count, out_gain, listener_gain, out,
+                                 object_energy, object_live, object_silenced, object_modal_energy, 0, nullptr, nullptr);
+}
+uint32_t mh_drive_struct_size(void) { return uint32_t(sizeof(mh_drive)); }
 int mh_bank_read_state(const mh_bank *bank, uint32_t first, uint32_t count, double *state_re, double *state_im) {
     if (!bank || (count && (!state_re || !state_im))) return MH_EINVAL;
     try {
