@@ -241,6 +241,45 @@ int mh_bank_render_driven(mh_bank *, uint32_t frames, float click_gain, uint32_t
                           const uint32_t *tuned_count, const float *out_gain, const float *listener_gain, void *out, double *object_energy,
                           uint32_t *object_live, uint8_t *object_silenced, double *object_modal_energy, uint32_t n_drives,
                           const mh_drive *drives, const float *signals);
+/* TuneModalObject's DeflectionGain column (ModalAudio.cpp:380), [first, first+count): float for an fp32 bank, double for an fp64 bank.
+ * Only pickups read it; a bank that never received it holds zeros there. */
+int mh_bank_set_deflection_gain(mh_bank *, uint32_t first, uint32_t count, const void *deflection_gain);
+/* A deflection pickup (no reference counterpart in ModalAudio; the bank-side primitive under the feedback reads of the reference's surface
+ * renderer: ReadDeflection / ReadRow with ModeReadGains, src/audio/surface/): a read-only probe of `object`.  Per frame it returns the
+ * object's modal displacement along (nx, ny, nz) at the blend weights[0..2] of the excitation positions points[0..2]
+ * ({1,0,0} = points[0] alone), from the resonator state AFTER that frame's step.  Per mode k, in the bank's precision:
+ *   shape = weights[0]*shape[points[0],k] + weights[1]*shape[points[1],k] + weights[2]*shape[points[2],k]   (x, y, z each)
+ *   read  = scale * (shape_x*nx + shape_y*ny + shape_z*nz) * DeflectionGain[k]
+ *   advance 0: g_im = read,                        g_re = 0
+ *   advance 1: g_im = read * c_re,                 g_re = read * c_im
+ *   advance 2: g_im = read * (c_re^2 - c_im^2),    g_re = read * (2 c_re c_im)
+ * and frame s is the sum over the object's rendered modes of g_im[k]*Im z[k] + g_re[k]*Re z[k].  scale: the caller's coupling already
+ * multiplied by the object's DeflectionScale. */
+typedef struct {
+    uint32_t object;
+    uint32_t points[3];
+    float weights[3];
+    float nx, ny, nz;
+    float scale;
+    uint32_t advance;
+} mh_pickup;
+/* the most pickups one object can carry in a call; further ones (in the caller's order) are left out */
+#define MH_PICKUPS_PER_OBJECT 8
+/* sizeof(mh_pickup) as this library was built */
+uint32_t mh_pickup_struct_size(void);
+/* mh_bank_render_driven with pickups.  pickup_out is [n_pickups][frames] in the bank's precision, WRITTEN (not added to); pickup_read[q]
+ * is 1 when pickup q was read, 0 when it was left out (its row is zeros then): an object the bank does not have or without modes, a
+ * point beyond the object's shape columns, a weight, direction component or scale that is not finite, advance > 2, or more than
+ * MH_PICKUPS_PER_OBJECT pickups on the object before it.  A pickup on an object that is not dealt (at rest) reads zeros and counts as
+ * read.  Pickups observe: `out`, the state, the per-object results and the impacts are bit for bit those of the call without them.
+ * A pickup's row depends on its object's state and its own record only (summation order: DESIGN.md section 3b).  With n_pickups = 0
+ * this is mh_bank_render_driven. */
+int mh_bank_render_read(mh_bank *, uint32_t frames, float click_gain, uint32_t n_impacts, mh_impact *impacts,
+                        uint32_t n_renderers, const uint32_t *deal_offset, const uint32_t *deal_objects, const uint32_t *render_count,
+                        const uint32_t *tuned_count, const float *out_gain, const float *listener_gain, void *out, double *object_energy,
+                        uint32_t *object_live, uint8_t *object_silenced, double *object_modal_energy, uint32_t n_drives,
+                        const mh_drive *drives, const float *signals, uint32_t n_pickups, const mh_pickup *pickups, void *pickup_out,
+                        uint8_t *pickup_read);
 /* Read back state columns (for parity tests and the modal-energy diagnostic, ModalAudio.cpp:564-577). */
 int mh_bank_read_state(const mh_bank *, uint32_t first, uint32_t count, double *state_re, double *state_im);
 

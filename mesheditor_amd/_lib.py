@@ -42,6 +42,11 @@ class Drive(C.Structure):  # mh_drive
     _fields_ = [("object", C.c_uint32), ("ex_pos", C.c_uint32), ("jx", C.c_float), ("jy", C.c_float), ("jz", C.c_float)]
 
 
+class Pickup(C.Structure):  # mh_pickup
+    _fields_ = [("object", C.c_uint32), ("points", C.c_uint32 * 3), ("weights", C.c_float * 3), ("nx", C.c_float), ("ny", C.c_float), ("nz", C.c_float),
+                ("scale", C.c_float), ("advance", C.c_uint32)]
+
+
 def build(force=False):
     """Compile libmodalhip.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     src = os.path.join(_HERE, "csrc")
@@ -86,6 +91,9 @@ def lib():
         "mh_bank_render": (i32, [vp, u32, C.c_float, u32, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "mh_bank_render_driven": (i32, [vp, u32, C.c_float, u32, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp, vp]),
         "mh_drive_struct_size": (u32, []),
+        "mh_bank_set_deflection_gain": (i32, [vp, u32, u32, vp]),
+        "mh_bank_render_read": (i32, [vp, u32, C.c_float, u32, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp]),
+        "mh_pickup_struct_size": (u32, []),
         "mh_bank_read_state": (i32, [vp, u32, u32, vp, vp]),
     }
     for name, (res, args) in sig.items():

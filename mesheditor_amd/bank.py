@@ -24,6 +24,17 @@ class Drive(C.Structure):  # ModalDrive, modal/bank.hpp (mh_drive of modalhip.h 
     _fields_ = [("object", C.c_uint32), ("ex_pos", C.c_uint32), ("jx", C.c_float), ("jy", C.c_float), ("jz", C.c_float)]
 
 
+class Pickup(C.Structure):  # ModalPickup, modal/bank.hpp (mh_pickup of modalhip.h field for field; `scale` is the caller's coupling here)
+    _fields_ = [("object", C.c_uint32), ("points", C.c_uint32 * 3), ("weights", C.c_float * 3), ("nx", C.c_float), ("ny", C.c_float), ("nz", C.c_float),
+                ("scale", C.c_float), ("advance", C.c_uint32)]
+
+    @classmethod
+    def of(cls, obj, points, weights, direction, coupling=1.0, advance=0):
+        """points: one excitation position or three; weights: the blend of the three ((1, 0, 0) for one point)."""
+        pts = (points,) * 3 if np.isscalar(points) else tuple(points)
+        return cls(obj, (C.c_uint32 * 3)(*pts), (C.c_float * 3)(*weights), direction[0], direction[1], direction[2], coupling, advance)
+
+
 def lib():
     global _LIB
     if _LIB is not None:
@@ -39,7 +50,8 @@ def lib():
         "mhx_add_object": (u32, [vp, u32, u32, u32, vp, vp, u32, vp]), "mhx_tune_object": (None, [vp, i32, u32, u32, vp, vp, f32]),
         "mhx_set_shapes": (i32, [vp, i32, u32, u32, u32, vp]), "mhx_set_gains": (None, [vp, i32, u32, f32, f32]), "mhx_install": (i32, [vp]),
         "mhx_set_renderers": (None, [vp, u32]), "mhx_set_click_gain": (None, [vp, f32]), "mhx_set_max_impacts": (None, [vp, u32]),
-        "mhx_enqueue": (i32, [vp, C.POINTER(Event)]), "mhx_render": (i32, [vp, vp, u32]), "mhx_render_driven": (i32, [vp, vp, u32, u32, vp, vp]), "mhx_num_objects": (u32, [vp]),
+        "mhx_enqueue": (i32, [vp, C.POINTER(Event)]), "mhx_render": (i32, [vp, vp, u32]), "mhx_render_driven": (i32, [vp, vp, u32, u32, vp, vp]),
+        "mhx_render_read": (i32, [vp, vp, u32, u32, vp, vp, u32, vp, vp, vp]), "mhx_num_objects": (u32, [vp]),
         "mhx_active_impacts": (u32, [vp]), "mhx_modal_energy": (f64, [vp]), "mhx_render_share": (f32, [vp]), "mhx_find_object": (i32, [vp, u32]),
         "mhx_time_kernels": (i32, [vp, i32]), "mhx_kernel_class_stats": (i32, [vp, i32, C.POINTER(C.c_uint64), C.POINTER(f64), C.POINTER(f64)]),
         "mhx_column": (u32, [vp, i32, i32, vp]), "mhx_object_state": (None, [vp, vp, vp, vp]),
@@ -122,6 +134,19 @@ class Scene:
         sig = np.ascontiguousarray(signals, np.float32).reshape(len(drives), len(out))
         if self.L.mhx_render_driven(self.h, _p(out), len(out), len(drives), C.cast(rows, C.c_void_p), _p(sig)):
             raise RuntimeError(self.L.mhx_last_error().decode())
+
+    def render_read(self, out, drives, signals, pickups):
+        """RenderModalRead: render_driven plus deflection pickups (a ctypes array or a sequence of Pickup records).  Returns (reads,
+        read_flags): reads[q] is pickup q's row of len(out) values in the scene's precision, read_flags[q] is 1 when it was read and 0
+        when it was left out (its row is zeros then)."""
+        assert out.dtype == self.dtype and out.flags["C_CONTIGUOUS"]
+        rows = drives if isinstance(drives, C.Array) else (Drive * max(len(drives), 1))(*[v if isinstance(v, Drive) else Drive(*v) for v in drives])
+        sig = np.ascontiguousarray(signals, np.float32).reshape(len(drives), len(out))
+        probes = pickups if isinstance(pickups, C.Array) else (Pickup * max(len(pickups), 1))(*pickups)
+        reads, flags = np.zeros((len(pickups), len(out)), self.dtype), np.zeros(len(pickups), np.uint8)
+        if self.L.mhx_render_read(self.h, _p(out), len(out), len(drives), C.cast(rows, C.c_void_p), _p(sig), len(pickups), C.cast(probes, C.c_void_p), _p(reads), _p(flags)):
+            raise RuntimeError(self.L.mhx_last_error().decode())
+        return reads, flags
 
     def time_kernels(self, enable=True):
         """HIP-event timing of the bank's kernels on its device context (measurement aid)."""

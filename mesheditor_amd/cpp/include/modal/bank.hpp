@@ -44,6 +44,20 @@ struct ModalDrive {
     float Jx{0}, Jy{0}, Jz{0};
 };
 
+// Not in the reference's ModalAudio.h: a deflection pickup, the bank-side primitive under the feedback reads of the reference's surface
+// renderer (ReadDeflection / ReadRow over ModeReadGains, src/audio/surface/).  A read-only probe: per frame, the object's modal
+// displacement along (Nx, Ny, Nz) at the blend Weights of the excitation positions Points ({1, 0, 0} = Points[0] alone), taken from the
+// resonator state after that frame's step and advanced freely by Advance samples (0, 1 or 2).  Coupling is the caller's factor; the
+// render multiplies it by the object's DeflectionScale.  Passed with a render call (RenderModalRead); it excites and changes nothing.
+struct ModalPickup {
+    uint32_t Object{0};
+    uint32_t Points[3]{0, 0, 0};
+    float Weights[3]{1, 0, 0};
+    float Nx{0}, Ny{0}, Nz{0};
+    float Coupling{1};
+    uint32_t Advance{0};
+};
+
 constexpr float AirDensity{1.204f}, SpeedOfSound{343.f}, ListenerDistance{1.f};
 constexpr float Ln1000 = 3 * std::numbers::ln10_v<float>;
 
@@ -190,6 +204,15 @@ void RenderModal(ModalAudio64 &, double *out, uint32_t frame_count);
 // excitation position its shape columns do not cover is dropped, as such an impact is.  Without drives this is RenderModal.
 void RenderModalDriven(ModalAudio &, std::span<const ModalDrive> drives, const float *signals, float *out, uint32_t frame_count);
 void RenderModalDriven(ModalAudio64 &, std::span<const ModalDrive> drives, const float *signals, double *out, uint32_t frame_count);
+// Not in the reference: RenderModalDriven with pickups.  `reads` receives pickups.size() rows of frame_count values (written, not added
+// to), `read_flags` (nullable) one byte per pickup: 1 = read, 0 = left out (row of zeros) -- an object the bank does not have or without
+// modes, a point its shape columns do not cover, a weight, direction component or coupling that is not finite, Advance > 2, or more than
+// MH_PICKUPS_PER_OBJECT (modalhip.h) pickups on the object before it.  A pickup on an object at rest reads zeros and counts as read.
+// Pickups observe: `out`, the bank and every decision of the block are those of RenderModalDriven.  Without pickups this is it.
+void RenderModalRead(ModalAudio &, std::span<const ModalDrive> drives, const float *signals, std::span<const ModalPickup> pickups, float *reads, float *out,
+                     uint32_t frame_count, uint8_t *read_flags = nullptr);
+void RenderModalRead(ModalAudio64 &, std::span<const ModalDrive> drives, const float *signals, std::span<const ModalPickup> pickups, double *reads, double *out,
+                     uint32_t frame_count, uint8_t *read_flags = nullptr);
 // Not in the reference: the libmodalhip context the bank's device mirror lives on (created on demand), for callers that
 // time its kernels (mh_context_time_kernels / mh_context_kernel_class_stats).
 mh_context *ModalDeviceContext(ModalAudio &);

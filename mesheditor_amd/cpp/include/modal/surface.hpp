@@ -6,9 +6,11 @@
 //
 // What the bank does have of it: sustained excitation.  The reference's surface renderer drives an object's modes with per-sample force
 // signals through per-mode gain rows; that primitive exists here as ModalDrive / RenderModalDriven (modal/bank.hpp) -- a caller-supplied
-// force signal at an excitation position along a direction, for as long as the caller keeps supplying it.  What is still absent is the
-// model on top of it: contact tracking and voices, contact points blended between excitation positions, the feedback reads of the
-// object's displacement at the contact point inside the sample loop, and the roughness / friction signal generators.
+// force signal at an excitation position along a direction, for as long as the caller keeps supplying it -- and the read side: the
+// renderer's feedback reads (ReadDeflection / ReadRow over ModeReadGains: the object's modal displacement at the contact point along the
+// contact normal, the point blended between three excitation positions) exist as ModalPickup / RenderModalRead, one row of reads per
+// pickup and block.  What is still absent is the model on top of them: contact tracking and voices, the per-sample contact solve (a
+// sample's force depending on the displacement read in the same sample), and the roughness / friction signal generators.
 #pragma once
 #include "bank.hpp"
 

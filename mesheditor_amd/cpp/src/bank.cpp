@@ -2,7 +2,7 @@
 //
 // What lives here is bookkeeping: building and tuning the struct-of-arrays bank, the single-producer event ring, the
 // impact list, the deterministic deal of objects to renderers and the publish protocol.  Every per-sample operation
-// (force curves, click filters, mode recurrences, ordered mix) runs on the device in mh_bank_render_driven.
+// (force curves, click filters, mode recurrences, ordered mix, pickup reads) runs on the device in mh_bank_render_read.
 //
 // Written from the behaviour described in SURVEY.md section 8a rows R0-R8, not from the reference's text.  Where a
 // value must be BIT-identical to the reference's (coefficient columns are compared bit for bit with the CPU oracle),
@@ -36,6 +36,8 @@ struct ModalDeviceMirror {
     std::vector<mh_impact> Impacts;
     std::vector<mh_drive> Drives; // the block's drives that passed the checks, with their signal rows
     std::vector<float> DriveSignals;
+    std::vector<mh_pickup> Pickups; // the block's pickups, one per caller's record
+    std::vector<uint8_t> PickupRead;
     std::vector<std::vector<uint32_t>> Renderers;
     ~ModalDeviceMirror() {
         mh_bank_destroy(Bank);
@@ -416,6 +418,7 @@ template<typename Real> void PushCoefficients(ModalDeviceMirror &d, const ModalB
     if (mh_bank_set_coefficients(d.Bank, first, n, b.CoeffRe.data() + first, b.CoeffIm.data() + first, b.RadiationGain.data() + first, b.OutPhaseIm.data() + first,
                                  b.OutPhaseRe.data() + first) != MH_OK)
         Fail(d);
+    if (mh_bank_set_deflection_gain(d.Bank, first, n, b.DeflectionGain.data() + first) != MH_OK) Fail(d); // the column pickups read
 }
 
 // Layout + shapes + coefficients into HBM; the device state starts from zero like a freshly built host bank.
@@ -488,7 +491,9 @@ template<typename Real> bool HasExcitationPosition(const ModalBankColumns<Real> 
     return uint64_t(ex_pos) * b.ModeCount[object] + b.ModeCount[object] <= uint64_t(last - first);
 }
 
-template<typename Audio, typename Real> void RenderBlock(Audio &m, std::span<const ModalDrive> drives, const float *signals, Real *out, uint32_t frames) {
+template<typename Audio, typename Real>
+void RenderBlock(Audio &m, std::span<const ModalDrive> drives, const float *signals, Real *out, uint32_t frames, std::span<const ModalPickup> pickups = {}, Real *reads = nullptr,
+                 uint8_t *read_flags = nullptr) {
     if (frames == 0) return;
     const auto started = std::chrono::steady_clock::now();
     const ReaderScope reading(m.ReaderSeq);
@@ -527,6 +532,16 @@ template<typename Audio, typename Real> void RenderBlock(Audio &m, std::span<con
         b.Ringing[v.Object] = 1;
     }
     const float *drive_signals = d.Drives.size() == drives.size() ? signals : d.DriveSignals.data(); // nothing dropped: the caller's rows as they are
+    // pickups: record for record (a row per caller's pickup), the coupling scaled as the reference scales it (Coupling * DeflectionScale[o], in
+    // Real, narrowed to the record's float).  They take no part in any decision below.  A pickup the bank cannot follow is left out by the
+    // device entry, which checks every field again; one without an object here is handed on as it is and left out there.
+    d.Pickups.resize(pickups.size());
+    d.PickupRead.assign(pickups.size(), 0);
+    for (size_t q = 0; q < pickups.size(); ++q) {
+        const ModalPickup &v = pickups[q];
+        const float scale = v.Object < n_objects ? float(Real(v.Coupling) * b.DeflectionScale[v.Object]) : v.Coupling;
+        d.Pickups[q] = {v.Object, {v.Points[0], v.Points[1], v.Points[2]}, {v.Weights[0], v.Weights[1], v.Weights[2]}, v.Nx, v.Ny, v.Nz, scale, v.Advance};
+    }
     Deal(d, b, renderers);
     d.DealOffset.assign(1, 0);
     d.DealObjects.clear();
@@ -566,10 +581,11 @@ template<typename Audio, typename Real> void RenderBlock(Audio &m, std::span<con
         narrow_listener.assign(b.ListenerGain.begin(), b.ListenerGain.end());
         out_gain = narrow_out.data(), listener_gain = narrow_listener.data();
     }
-    if (mh_bank_render_driven(d.Bank, frames, m.ClickGain.load(std::memory_order_relaxed), n_impacts, d.Impacts.data(), renderers, d.DealOffset.data(), d.DealObjects.data(),
+    if (mh_bank_render_read(d.Bank, frames, m.ClickGain.load(std::memory_order_relaxed), n_impacts, d.Impacts.data(), renderers, d.DealOffset.data(), d.DealObjects.data(),
                               d.RenderCount.data(), d.Tuned.data(), out_gain, listener_gain, out, d.Energy.data(), d.Live.data(), d.Silenced.data(), d.ModalEnergy.data(),
-                              uint32_t(d.Drives.size()), d.Drives.data(), drive_signals) != MH_OK)
+                              uint32_t(d.Drives.size()), d.Drives.data(), drive_signals, uint32_t(d.Pickups.size()), d.Pickups.data(), reads, d.PickupRead.data()) != MH_OK)
         Fail(d);
+    if (read_flags) std::copy(d.PickupRead.begin(), d.PickupRead.end(), read_flags);
 
     // impacts: carry the recurrences' state over to the next block
     for (uint32_t i = 0; i < n_impacts; ++i) {
@@ -645,6 +661,14 @@ void RenderModalDriven(ModalAudio &m, std::span<const ModalDrive> drives, const 
 }
 void RenderModalDriven(ModalAudio64 &m, std::span<const ModalDrive> drives, const float *signals, double *out, uint32_t frame_count) {
     RenderBlock<ModalAudio64, double>(m, drives, signals, out, frame_count);
+}
+void RenderModalRead(ModalAudio &m, std::span<const ModalDrive> drives, const float *signals, std::span<const ModalPickup> pickups, float *reads, float *out,
+                     uint32_t frame_count, uint8_t *read_flags) {
+    RenderBlock<ModalAudio, float>(m, drives, signals, out, frame_count, pickups, reads, read_flags);
+}
+void RenderModalRead(ModalAudio64 &m, std::span<const ModalDrive> drives, const float *signals, std::span<const ModalPickup> pickups, double *reads, double *out,
+                     uint32_t frame_count, uint8_t *read_flags) {
+    RenderBlock<ModalAudio64, double>(m, drives, signals, out, frame_count, pickups, reads, read_flags);
 }
 mh_context *ModalDeviceContext(ModalAudio &m) { return NeedContext(m), m.Dev->Context; }
 mh_context *ModalDeviceContext(ModalAudio64 &m) { return NeedContext(m), m.Dev->Context; }

@@ -117,6 +117,18 @@ int mhx_render_driven(mhx_scene *s, void *out, uint32_t frames, uint32_t n_drive
         return 0;
     } catch (const std::exception &e) { g_error = e.what(); return 1; }
 }
+// RenderModalRead: mhx_render_driven plus `pickups` (n_pickups ModalPickup records); `reads` [n_pickups][frames] in the scene's precision,
+// `read_flags` one byte per pickup
+int mhx_render_read(mhx_scene *s, void *out, uint32_t frames, uint32_t n_drives, const ModalDrive *drives, const float *signals, uint32_t n_pickups,
+                    const ModalPickup *pickups, void *reads, uint8_t *read_flags) {
+    try {
+        const std::span<const ModalDrive> list(drives, n_drives);
+        const std::span<const ModalPickup> probes(pickups, n_pickups);
+        if (s->dbl) RenderModalRead(s->audio64, list, signals, probes, static_cast<double *>(reads), static_cast<double *>(out), frames, read_flags);
+        else RenderModalRead(s->audio, list, signals, probes, static_cast<float *>(reads), static_cast<float *>(out), frames, read_flags);
+        return 0;
+    } catch (const std::exception &e) { g_error = e.what(); return 1; }
+}
 // Kernel timing of the scene's device context: enable / read one class (modalhip.h MH_KERNEL_*)
 int mhx_time_kernels(mhx_scene *s, int enable) {
     try {

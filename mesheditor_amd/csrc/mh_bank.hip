@@ -143,15 +143,36 @@ template<typename Real> __device__ __forceinline__ Real chunk_sum_in_order(Real 
 // drives (MANY): run_rows -- the force tiles of all rows go to LDS once per 32-sample tile, [sample][row], so that a sample's forces
 // arrive with one or two wave-uniform LDS reads instead of a lane broadcast per row; the gains of the first ROWS_REG rows stay in
 // registers, those of the rows behind them in LDS.  More rows than that (or a drive-free launch): the scratch-row path (EXTRA).
+//
+// Pickups (READ, mh_bank_render_read).  A wave of an object that carries pickups also keeps the tile's states -- Im z and Re z after each
+// sample's step, [sample][mode] like the output terms -- and at the turn-around every lane (half, sample) adds, per pickup, the 64 modes of
+// its half: acc = fma(g_im[k], Im z[k], acc), then acc = fma(g_re[k], Re z[k], acc), even modes into one accumulator and odd modes into a
+// second one (a packed pair), k ascending, from +0; the lane's value is even + odd.  The gains of the object's pickups are staged once per
+// block in LDS, [pickup][im | re][mode], and read wave-uniformly per half.  Each (wave, half) writes its own partial row; k_bank_read_rows
+// adds an object's rows in ascending (wave, half) order, so a pickup's row does not depend on the deal or on anything else in the call.
+// Waves of objects without a pickup take no part in any of it.
 constexpr int MODES_PER_WAVE = 2 * WAVE;
 constexpr uint32_t IMP_REG = 2, ROWS_REG = 8, ROWS_MAX = 12;
-template<typename Real, bool MANY>
+template<typename Real> struct PickupDev { // a pickup the block reads: its record, and where its partial rows begin
+    uint32_t p0, p1, p2, advance;
+    Real w0, w1, w2, nx, ny, nz, scale;
+    uint32_t first_row;
+};
+template<typename Real> struct ReadArgs {
+    const Real *defl_gain; // DeflectionGain column
+    const uint32_t *pick_ptr; // [dealt + 1] into pickups
+    const PickupDev<Real> *pickups; // grouped by dealt object, the caller's order within one
+    Real *rows; // [partial row][frames]
+    uint32_t rows_loop; // what selects k_bank_modes_rows over k_bank_modes in a call without pickups
+};
+template<typename Real, bool MANY, bool READ = false>
 __device__ __forceinline__ void bank_modes(const BankCols<Real> &b, const WaveDesc *__restrict__ waves, const uint32_t *__restrict__ deal_objects,
                                            const uint32_t *__restrict__ render_count, const uint32_t *__restrict__ chunk_base,
                                            const uint32_t *__restrict__ imp_ptr, const uint32_t *__restrict__ imp_idx,
                                            const ImpactDev<Real> *__restrict__ impacts, const Real *__restrict__ force,
                                            const Real *__restrict__ out_gain, const Real *__restrict__ listener_gain, uint32_t frames,
-                                           Real *__restrict__ partial, Real *__restrict__ chunk_energy, Real *__restrict__ gain_scratch, uint32_t max_imp) {
+                                           Real *__restrict__ partial, Real *__restrict__ chunk_energy, Real *__restrict__ gain_scratch, uint32_t max_imp,
+                                           const ReadArgs<Real> &rd = {}) {
     typedef Real Pair __attribute__((ext_vector_type(2)));
     constexpr uint32_t TS = 32, PITCH = MODES_PER_WAVE + 2, CHUNKS = MODES_PER_WAVE / LANES;
     __shared__ __attribute__((aligned(16))) Real s_term[TS * PITCH];
@@ -178,7 +199,7 @@ __device__ __forceinline__ void bank_modes(const BankCols<Real> &b, const WaveDe
     Pair g_reg[IMP_REG] = {};
     uint32_t f_row[IMP_REG] = {};
     Real *g_mem = gain_scratch + size_t(blockIdx.x) * max_imp * MODES_PER_WAVE;
-    const bool many_rows = MANY && n_imp > IMP_REG && n_imp <= ROWS_MAX; // run_rows computes its own gains
+    const bool many_rows = MANY && (!READ || rd.rows_loop) && n_imp > IMP_REG && n_imp <= ROWS_MAX; // run_rows computes its own gains
     auto gain_of = [&](uint32_t t) {
         Pair g = {0, 0};
         const ImpactDev<Real> &im = impacts[imp_idx[i0 + t]];
@@ -197,6 +218,51 @@ __device__ __forceinline__ void bank_modes(const BankCols<Real> &b, const WaveDe
     }
     const Real mix_gain = out_gain[o] * listener_gain[o];
     const uint32_t half = lane / TS, ts = lane % TS; // turn-around mapping: chunks 8*half .. 8*half+7 of sample ts
+    // pickups of this wave's object: the state tiles and the staged gains (see above); none of it exists in the other entries
+    __shared__ __attribute__((aligned(16))) Real s_zim[READ ? TS * PITCH : 1], s_zre[READ ? TS * PITCH : 1];
+    __shared__ __attribute__((aligned(16))) Real s_pick[READ ? MH_PICKUPS_PER_OBJECT * 2 * MODES_PER_WAVE : 1]; // [pickup][im | re][mode]
+    uint32_t pk0 = 0, n_pick = 0;
+    if constexpr (READ) {
+        pk0 = rd.pick_ptr[wd.dealt];
+        n_pick = min(rd.pick_ptr[wd.dealt + 1] - pk0, uint32_t(MH_PICKUPS_PER_OBJECT));
+        for (uint32_t q = 0; q < n_pick; ++q) {
+            const PickupDev<Real> pk = rd.pickups[pk0 + q];
+            Pair g_im = {0, 0}, g_re = {0, 0};
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+                if (live[h]) {
+                    const uint32_t a = shape0 + pk.p0 * stride + k + h, bb = shape0 + pk.p1 * stride + k + h, c = shape0 + pk.p2 * stride + k + h;
+                    const Real sx = pk.w0 * b.shape_x[a] + pk.w1 * b.shape_x[bb] + pk.w2 * b.shape_x[c];
+                    const Real sy = pk.w0 * b.shape_y[a] + pk.w1 * b.shape_y[bb] + pk.w2 * b.shape_y[c];
+                    const Real sz = pk.w0 * b.shape_z[a] + pk.w1 * b.shape_z[bb] + pk.w2 * b.shape_z[c];
+                    const Real read = pk.scale * (sx * pk.nx + sy * pk.ny + sz * pk.nz) * rd.defl_gain[k0 + k + h];
+                    const Real cr = c_re[h], ci = c_im[h];
+                    g_im[h] = pk.advance == 0 ? read : pk.advance == 1 ? read * cr : read * (cr * cr - ci * ci);
+                    g_re[h] = pk.advance == 0 ? Real(0) : pk.advance == 1 ? read * ci : read * (Real(2) * cr * ci);
+                }
+            *reinterpret_cast<Pair *>(s_pick + (2 * q) * MODES_PER_WAVE + 2 * lane) = g_im;
+            *reinterpret_cast<Pair *>(s_pick + (2 * q + 1) * MODES_PER_WAVE + 2 * lane) = g_re;
+        }
+    }
+    // G pickups from q0 on: sample ts of this lane's half of the wave's modes
+    auto read_group = [&](auto g_tag, uint32_t q0, uint32_t s0) {
+        constexpr uint32_t G = decltype(g_tag)::value;
+        Pair acc[G] = {};
+        const Real *zi = s_zim + ts * PITCH + half * WAVE, *zr = s_zre + ts * PITCH + half * WAVE;
+        const Real *g = s_pick + size_t(q0) * 2 * MODES_PER_WAVE + half * WAVE;
+#pragma unroll 4
+        for (uint32_t m = 0; m < WAVE; m += 2) {
+            const Pair vi = *reinterpret_cast<const Pair *>(zi + m), vr = *reinterpret_cast<const Pair *>(zr + m);
+#pragma unroll
+            for (uint32_t j = 0; j < G; ++j) {
+                acc[j] = __builtin_elementwise_fma(*reinterpret_cast<const Pair *>(g + (2 * j) * MODES_PER_WAVE + m), vi, acc[j]);
+                acc[j] = __builtin_elementwise_fma(*reinterpret_cast<const Pair *>(g + (2 * j + 1) * MODES_PER_WAVE + m), vr, acc[j]);
+            }
+        }
+#pragma unroll
+        for (uint32_t j = 0; j < G; ++j)
+            rd.rows[(size_t(rd.pickups[pk0 + q0 + j].first_row) + 2 * (wd.first_mode / MODES_PER_WAVE) + half) * frames + s0 + ts] = acc[j].x + acc[j].y;
+    };
 
     // one sample of this lane's two resonators; their output terms go to the turn-around tile
     auto step = [&](const Pair &excite, uint32_t ds) {
@@ -204,6 +270,11 @@ __device__ __forceinline__ void bank_modes(const BankCols<Real> &b, const WaveDe
         z_im = z_re * c_im + z_im * c_re;
         z_re = re;
         *reinterpret_cast<Pair *>(s_term + ds * PITCH + 2 * lane) = p_im * z_im + p_re * re;
+        if constexpr (READ)
+            if (n_pick) {
+                *reinterpret_cast<Pair *>(s_zim + ds * PITCH + 2 * lane) = z_im;
+                *reinterpret_cast<Pair *>(s_zre + ds * PITCH + 2 * lane) = re;
+            }
     };
     // after a tile's samples: every chunk's 8 terms added in mode order, sample ts of chunks 8*half .. 8*half+7 per lane
     auto turn_around = [&](uint32_t s0, uint32_t sn) {
@@ -221,6 +292,13 @@ __device__ __forceinline__ void bank_modes(const BankCols<Real> &b, const WaveDe
                 }
                 const uint32_t chunk = CHUNKS / 2 * half + c;
                 if (chunk < chunks_here) partial[size_t(chunk0 + chunk) * frames + s0 + ts] = acc * mix_gain;
+            }
+            if constexpr (READ) {
+                uint32_t q = 0;
+                for (; q + 4 <= n_pick; q += 4) read_group(std::integral_constant<uint32_t, 4>{}, q, s0);
+                if (n_pick - q == 3) read_group(std::integral_constant<uint32_t, 3>{}, q, s0);
+                else if (n_pick - q == 2) read_group(std::integral_constant<uint32_t, 2>{}, q, s0);
+                else if (n_pick - q == 1) read_group(std::integral_constant<uint32_t, 1>{}, q, s0);
             }
         }
         __syncthreads();
@@ -356,6 +434,24 @@ __device__ __forceinline__ void bank_modes(const BankCols<Real> &b, const WaveDe
 template<typename Real> __global__ void __launch_bounds__(WAVE) k_bank_modes(BANK_MODES_PARAMS) { bank_modes<Real, false>(BANK_MODES_ARGS); }
 // The launch of a block with drives in which some object has more than IMP_REG rows: the same code plus run_rows and its LDS.
 template<typename Real> __global__ void __launch_bounds__(WAVE) k_bank_modes_rows(BANK_MODES_PARAMS) { bank_modes<Real, true>(BANK_MODES_ARGS); }
+// The launch of a block with pickups: the same code again (both row loops) plus the state tiles, the staged pickup gains and the reads.
+template<typename Real> __global__ void __launch_bounds__(WAVE) k_bank_modes_read(BANK_MODES_PARAMS, ReadArgs<Real> rd) {
+    bank_modes<Real, true, true>(BANK_MODES_ARGS, rd);
+}
+// A pickup's row: its object's partial rows added in ascending (wave, half) order from +0, written (not added) where the host reads it.
+// A pickup without rows (left out, or its object at rest) gets zeros.
+struct PickupRows {
+    uint32_t first_row, n_rows;
+};
+template<typename Real>
+__global__ void __launch_bounds__(256) k_bank_read_rows(const Real *__restrict__ rows, const PickupRows *__restrict__ desc, uint32_t frames, Real *__restrict__ out_host) {
+    const uint32_t s = blockIdx.x * 256 + threadIdx.x;
+    if (s >= frames) return;
+    const PickupRows d = desc[blockIdx.y];
+    Real acc = 0;
+    for (uint32_t r = 0; r < d.n_rows; ++r) acc += rows[size_t(d.first_row + r) * frames + s];
+    out_host[size_t(blockIdx.y) * frames + s] = acc;
+}
 #undef BANK_MODES_PARAMS
 #undef BANK_MODES_ARGS
 
@@ -610,8 +706,10 @@ template<typename Real> struct BankImpl {
     mh_context *ctx;
     uint32_t n_objects, n_modes, n_shapes;
     DevArray<Real> coeff_re, coeff_im, state_re, state_im, rad_gain, phase_im, phase_re, shape_x, shape_y, shape_z;
+    DevArray<Real> defl_gain, read_rows; // the column only pickups read; their partial rows
     DevArray<uint32_t> mode_offset, mode_count, shape_offset;
-    std::vector<uint32_t> h_mode_count;
+    std::vector<uint32_t> h_mode_count, picks_on, pick_fill;
+    std::vector<int32_t> pick_dealt;
     // per-block scratch
     Arena arena;
     DevArray<Real> force, click, partial, chunk_energy, gain_scratch, rout;
@@ -638,7 +736,7 @@ template<typename Real>
 void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t n_impacts, mh_impact *impacts, uint32_t n_renderers, const uint32_t *deal_offset,
                  const uint32_t *deal_objects, const uint32_t *render_count, const uint32_t *tuned_count, const float *out_gain, const float *listener_gain,
                  void *out_v, double *object_energy, uint32_t *object_live, uint8_t *object_silenced, double *object_modal_energy, uint32_t n_drives,
-                 const mh_drive *drives, const float *signals) {
+                 const mh_drive *drives, const float *signals, uint32_t n_pickups, const mh_pickup *pickups, void *pickup_out_v, uint8_t *pickup_read) {
     mh_context *ctx = B.ctx;
     hipStream_t st = ctx->stream;
     Real *out = static_cast<Real *>(out_v);
@@ -656,11 +754,13 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
     const size_t o_imp_idx = A.take((n_rows + 1) * 4), o_rcp = A.take((n_renderers + 1) * 4);
     const size_t o_out = A.take(frames * sizeof(Real)), o_impacts = A.take((n_rows + 1) * sizeof(ImpactDev<Real>));
     const size_t o_signals = A.take(size_t(n_drives) * frames * sizeof(float));
+    const size_t o_pick_ptr = A.take((n_dealt + 2) * 4), o_pick_dev = A.take((n_pickups + 1) * sizeof(PickupDev<Real>)), o_pick_rows = A.take((n_pickups + 1) * sizeof(PickupRows));
     const size_t both_end = A.used;
     // (written by the kernels straight into the pinned arena -- no copy back: the host sees them once the block's last kernel has
     // raised the sequence number)
     const size_t o_energy = A.take((n_dealt + 1) * 8), o_modal = A.take((n_dealt + 1) * 8), o_live = A.take((n_dealt + 1) * 4), o_silenced = A.take(n_dealt + 1);
     const size_t o_back = A.take((n_impacts + 1) * sizeof(ImpactBack<Real>));
+    const size_t o_pick_out = A.take(size_t(n_pickups) * frames * sizeof(Real));
     const size_t total = A.used;
     if (total > A.cap) {
         HIP_CHECK(hipStreamSynchronize(st));
@@ -712,6 +812,46 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
         for (uint32_t j = 0; j < n_drives; ++j) // behind the object's impacts, in the caller's order
             if (B.drive_dealt[j] >= 0) imp_idx[B.imp_fill[B.drive_dealt[j]]++] = n_impacts + j;
     }
+    // ---- pickups: the ones the kernel may follow, grouped by dealt object in the caller's order; everything else gets a zero row ----
+    uint32_t read_row_count = 0, picks_dealt = 0;
+    uint64_t picked_modes = 0; // a pickup adds two multiply-adds per mode-sample of its object
+    if (n_pickups) {
+        uint32_t *pick_ptr = A.h<uint32_t>(o_pick_ptr);
+        PickupDev<Real> *pick_dev = A.h<PickupDev<Real>>(o_pick_dev);
+        PickupRows *pick_rows = A.h<PickupRows>(o_pick_rows);
+        std::fill(pick_ptr, pick_ptr + n_dealt + 2, 0u);
+        B.picks_on.assign(B.n_objects, 0);
+        B.pick_dealt.assign(n_pickups, -1);
+        for (uint32_t q = 0; q < n_pickups; ++q) {
+            const mh_pickup &m = pickups[q];
+            pickup_read[q] = 0;
+            pick_rows[q] = {0, 0};
+            if (m.object >= B.n_objects || B.h_mode_count[m.object] == 0 || m.advance > 2) continue;
+            const uint64_t shapes_end = m.object + 1 < B.n_objects ? B.h_shape_offset[m.object + 1] : B.n_shapes, held = shapes_end - B.h_shape_offset[m.object];
+            bool ok = std::isfinite(m.nx) && std::isfinite(m.ny) && std::isfinite(m.nz) && std::isfinite(m.scale);
+            for (int c = 0; c < 3; ++c) ok = ok && std::isfinite(m.weights[c]) && (uint64_t(m.points[c]) + 1) * B.h_mode_count[m.object] <= held;
+            if (!ok || B.picks_on[m.object] >= MH_PICKUPS_PER_OBJECT) continue;
+            ++B.picks_on[m.object];
+            pickup_read[q] = 1;
+            const int32_t d = B.dealt_of_object[m.object];
+            if (d < 0 || render_count[d] == 0) continue; // at rest: read, and all zeros
+            B.pick_dealt[q] = d;
+            ++pick_ptr[d + 1];
+            ++picks_dealt;
+        }
+        for (uint32_t d = 0; d < n_dealt; ++d) pick_ptr[d + 1] += pick_ptr[d];
+        B.pick_fill.assign(pick_ptr, pick_ptr + n_dealt + 1);
+        for (uint32_t q = 0; q < n_pickups; ++q) {
+            const int32_t d = B.pick_dealt[q];
+            if (d < 0) continue;
+            const mh_pickup &m = pickups[q];
+            pick_rows[q] = {read_row_count, 2 * ((render_count[d] + MODES_PER_WAVE - 1) / MODES_PER_WAVE)}; // a row per (wave, half) of the object
+            pick_dev[B.pick_fill[d]++] = {m.points[0], m.points[1], m.points[2], m.advance, Real(m.weights[0]), Real(m.weights[1]), Real(m.weights[2]),
+                                          Real(m.nx), Real(m.ny), Real(m.nz), Real(m.scale), read_row_count};
+            read_row_count += pick_rows[q].n_rows;
+            picked_modes += render_count[d];
+        }
+    }
     for (uint32_t q = 0; q <= n_renderers; ++q) {
         const uint32_t d0 = q < n_renderers ? deal_offset[q] : n_dealt;
         rcp[q] = chunk_base[std::min(d0, n_dealt)];
@@ -761,16 +901,28 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
             uint64_t driven_modes = 0; // a drive row adds a multiply and an add per mode-sample of its object
             for (uint32_t j = 0; j < n_drives; ++j)
                 if (B.drive_dealt[j] >= 0) driven_modes += render_count[B.drive_dealt[j]];
-            TimedLaunch timed(ctx, MH_KERNEL_BANK, (11.0 * double(rendered_modes) + 2.0 * double(driven_modes)) * double(frames)); // ~11 flop per mode-sample
+            TimedLaunch timed(ctx, MH_KERNEL_BANK, (11.0 * double(rendered_modes) + 2.0 * double(driven_modes) + 4.0 * double(picked_modes)) * double(frames)); // ~11 flop per mode-sample
             // a block without drives launches what it always did; one with drives takes the launch with the many-row loop (and its
             // LDS) only when some object has more rows than the register path holds
-            auto *modes_kernel = driven_rows && max_imp > IMP_REG ? &k_bank_modes_rows<Real> : &k_bank_modes<Real>;
-            modes_kernel<<<n_waves, WAVE, 0, st>>>(B.cols(), A.d<WaveDesc>(o_waves), d_deal, d_count, d_chunk_base, d_imp_ptr, A.d<uint32_t>(o_imp_idx), d_impacts,
-                                                  B.force, d_out_gain, d_listener, frames, B.partial, B.chunk_energy, B.gain_scratch, max_imp);
+            const bool rows_loop = driven_rows && max_imp > IMP_REG;
+            if (picks_dealt) { // a block with pickups some dealt object carries: the entry that also reads
+                ensure(ctx, B.read_rows, size_t(read_row_count + 1) * frames);
+                const ReadArgs<Real> rd{B.defl_gain, A.d<uint32_t>(o_pick_ptr), A.d<PickupDev<Real>>(o_pick_dev), B.read_rows, rows_loop ? 1u : 0u};
+                k_bank_modes_read<Real><<<n_waves, WAVE, 0, st>>>(B.cols(), A.d<WaveDesc>(o_waves), d_deal, d_count, d_chunk_base, d_imp_ptr, A.d<uint32_t>(o_imp_idx), d_impacts,
+                                                                 B.force, d_out_gain, d_listener, frames, B.partial, B.chunk_energy, B.gain_scratch, max_imp, rd);
+            } else {
+                auto *modes_kernel = rows_loop ? &k_bank_modes_rows<Real> : &k_bank_modes<Real>;
+                modes_kernel<<<n_waves, WAVE, 0, st>>>(B.cols(), A.d<WaveDesc>(o_waves), d_deal, d_count, d_chunk_base, d_imp_ptr, A.d<uint32_t>(o_imp_idx), d_impacts,
+                                                      B.force, d_out_gain, d_listener, frames, B.partial, B.chunk_energy, B.gain_scratch, max_imp);
+            }
             KERNEL_CHECK();
         }
     } else if (n_renderers) {
         HIP_CHECK(hipMemsetAsync(B.rout.get(), 0, size_t(n_renderers) * frames * sizeof(Real), st));
+    }
+    if (picks_dealt) { // the pickups' rows, written straight into the pinned arena like everything else the host reads
+        k_bank_read_rows<Real><<<dim3(div_up(frames, 256u), n_pickups), 256, 0, st>>>(B.read_rows, A.d<PickupRows>(o_pick_rows), frames, A.hd<Real>(o_pick_out));
+        KERNEL_CHECK();
     }
     // out[s] += clicks in impact order, then the renderers in order.  With many impacts in flight the click chain is the
     // same latency problem as a renderer's chunks (1 024 impacts: 100 us as a per-sample loop): it goes through the streaming
@@ -799,6 +951,11 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
         std::copy(A.h<uint8_t>(o_silenced), A.h<uint8_t>(o_silenced) + n_dealt, object_silenced);
         if (object_modal_energy) std::copy(A.h<double>(o_modal), A.h<double>(o_modal) + n_dealt, object_modal_energy);
     }
+    if (n_pickups) {
+        Real *pickup_out = static_cast<Real *>(pickup_out_v);
+        if (picks_dealt) std::copy(A.h<Real>(o_pick_out), A.h<Real>(o_pick_out) + size_t(n_pickups) * frames, pickup_out);
+        else std::fill(pickup_out, pickup_out + size_t(n_pickups) * frames, Real(0));
+    }
     const ImpactBack<Real> *back = A.h<ImpactBack<Real>>(o_back);
     for (uint32_t i = 0; i < n_impacts; ++i) {
         mh_impact &m = impacts[i];
@@ -826,7 +983,7 @@ static std::unique_ptr<BankImpl<Real>> make_bank(mh_context *ctx, uint32_t n_obj
     B->n_objects = n_objects;
     B->n_modes = n_modes;
     B->n_shapes = n_shapes;
-    for (auto *col : {&B->coeff_re, &B->coeff_im, &B->state_re, &B->state_im, &B->rad_gain, &B->phase_im, &B->phase_re}) {
+    for (auto *col : {&B->coeff_re, &B->coeff_im, &B->state_re, &B->state_im, &B->rad_gain, &B->phase_im, &B->phase_re, &B->defl_gain}) {
         col->reset(ctx, std::max<uint32_t>(n_modes, 1));
         col->zero();
     }
@@ -916,11 +1073,25 @@ int mh_bank_zero_state(mh_bank *bank, uint32_t first, uint32_t count) {
         return MH_OK;
     } catch (const std::exception &e) { return mh_guard(bank->ctx, e); }
 }
-int mh_bank_render_driven(mh_bank *bank, uint32_t frames, float click_gain, uint32_t n_impacts, mh_impact *impacts, uint32_t n_renderers, const uint32_t *deal_offset,
-                          const uint32_t *deal_objects, const uint32_t *render_count, const uint32_t *tuned_count, const float *out_gain, const float *listener_gain,
-                          void *out, double *object_energy, uint32_t *object_live, uint8_t *object_silenced, double *object_modal_energy, uint32_t n_drives,
-                          const mh_drive *drives, const float *signals) {
+int mh_bank_set_deflection_gain(mh_bank *bank, uint32_t first, uint32_t count, const void *deflection_gain) {
+    if (!bank || (count && !deflection_gain)) return MH_EINVAL;
+    try {
+        HIP_CHECK(hipSetDevice(bank->ctx->device));
+        auto go = [&](auto &B, auto tag) {
+            using Real = decltype(tag);
+            if (size_t(first) + count > B.n_modes) mh_throw(MH_EINVAL, "mode range [%u, %u) outside the bank's %u modes", first, first + count, B.n_modes);
+            upload_converted(bank->ctx, B.defl_gain, first, static_cast<const Real *>(deflection_gain), count);
+        };
+        if (bank->dbl) go(*bank->d, double{}); else go(*bank->f, float{});
+        return MH_OK;
+    } catch (const std::exception &e) { return mh_guard(bank->ctx, e); }
+}
+int mh_bank_render_read(mh_bank *bank, uint32_t frames, float click_gain, uint32_t n_impacts, mh_impact *impacts, uint32_t n_renderers, const uint32_t *deal_offset,
+                        const uint32_t *deal_objects, const uint32_t *render_count, const uint32_t *tuned_count, const float *out_gain, const float *listener_gain,
+                        void *out, double *object_energy, uint32_t *object_live, uint8_t *object_silenced, double *object_modal_energy, uint32_t n_drives,
+                        const mh_drive *drives, const float *signals, uint32_t n_pickups, const mh_pickup *pickups, void *pickup_out, uint8_t *pickup_read) {
     if (!bank || !out || (n_impacts && !impacts) || (n_renderers && !deal_offset) || !out_gain || !listener_gain || (n_drives && (!drives || !signals))) return MH_EINVAL;
+    if (n_pickups && (!pickups || !pickup_out || !pickup_read)) return MH_EINVAL;
     if (n_renderers && deal_offset[n_renderers] && (!deal_objects || !render_count || !tuned_count || !object_energy || !object_live || !object_silenced)) return MH_EINVAL;
     if (frames == 0) return MH_OK;
     try {
@@ -928,11 +1099,18 @@ int mh_bank_render_driven(mh_bank *bank, uint32_t frames, float click_gain, uint
         HIP_CHECK(hipSetDevice(bank->ctx->device));
         auto go = [&](auto &B) {
             render_impl(B, frames, click_gain, n_impacts, impacts, n_renderers, deal_offset, deal_objects, render_count, tuned_count, out_gain, listener_gain, out, object_energy,
-                        object_live, object_silenced, object_modal_energy, n_drives, drives, signals);
+                        object_live, object_silenced, object_modal_energy, n_drives, drives, signals, n_pickups, pickups, pickup_out, pickup_read);
         };
         if (bank->dbl) go(*bank->d); else go(*bank->f);
         return MH_OK;
     } catch (const std::exception &e) { return mh_guard(bank->ctx, e); }
+}
+int mh_bank_render_driven(mh_bank *bank, uint32_t frames, float click_gain, uint32_t n_impacts, mh_impact *impacts, uint32_t n_renderers, const uint32_t *deal_offset,
+                          const uint32_t *deal_objects, const uint32_t *render_count, const uint32_t *tuned_count, const float *out_gain, const float *listener_gain,
+                          void *out, double *object_energy, uint32_t *object_live, uint8_t *object_silenced, double *object_modal_energy, uint32_t n_drives,
+                          const mh_drive *drives, const float *signals) {
+    return mh_bank_render_read(bank, frames, click_gain, n_impacts, impacts, n_renderers, deal_offset, deal_objects, render_count, tuned_count, out_gain, listener_gain, out,
+                               object_energy, object_live, object_silenced, object_modal_energy, n_drives, drives, signals, 0, nullptr, nullptr, nullptr);
 }
 int mh_bank_render(mh_bank *bank, uint32_t frames, float click_gain, uint32_t n_impacts, mh_impact *impacts, uint32_t n_renderers, const uint32_t *deal_offset,
                    const uint32_t *deal_objects, const uint32_t *render_count, const uint32_t *tuned_count, const float *out_gain, const float *listener_gain,
@@ -941,6 +1119,7 @@ int mh_bank_render(mh_bank *bank, uint32_t frames, float click_gain, uint32_t n_
                                  object_energy, object_live, object_silenced, object_modal_energy, 0, nullptr, nullptr);
 }
 uint32_t mh_drive_struct_size(void) { return uint32_t(sizeof(mh_drive)); }
+uint32_t mh_pickup_struct_size(void) { return uint32_t(sizeof(mh_pickup)); }
 int mh_bank_read_state(const mh_bank *bank, uint32_t first, uint32_t count, double *state_re, double *state_im) {
     if (!bank || (count && (!state_re || !state_im))) return MH_EINVAL;
     try {
