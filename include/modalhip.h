@@ -98,8 +98,10 @@ void mh_default_config(mh_solver_config *);
  *                      the same launches' algorithmic bytes (8 n (basis + output columns)) as its work, no time of its own.
  *                      MH_KERNEL_COMBINE_FULL: the subset of those launches with >= 200 basis and >= 128 output columns (an iteration's
  *                      full-size update of X and P together: 240 -> 160 columns on the 65-pair solve), same work unit.
+ *   MH_KERNEL_JUNCTION the coupled resonator kernel of a block with contact junctions (k_bank_modes_coupled); work: frames x junctions,
+ *                      the number of per-frame contact solves (its time is a serial chain per frame, not arithmetic)
  * Stats are the totals since the last enable: launches, summed device milliseconds, summed work. */
-enum { MH_KERNEL_SPMM = 0, MH_KERNEL_ASSEMBLY = 1, MH_KERNEL_BANK = 2, MH_KERNEL_COMBINE = 3, MH_KERNEL_COMBINE_BYTES = 4, MH_KERNEL_COMBINE_FULL = 5, MH_KERNEL_CLASSES = 6 };
+enum { MH_KERNEL_SPMM = 0, MH_KERNEL_ASSEMBLY = 1, MH_KERNEL_BANK = 2, MH_KERNEL_COMBINE = 3, MH_KERNEL_COMBINE_BYTES = 4, MH_KERNEL_COMBINE_FULL = 5, MH_KERNEL_JUNCTION = 6, MH_KERNEL_CLASSES = 7 };
 int mh_context_time_kernels(mh_context *, int enable);
 int mh_context_kernel_stats(mh_context *, uint64_t *launches, double *total_ms, double *total_bytes); /* MH_KERNEL_SPMM */
 int mh_context_kernel_class_stats(mh_context *, int kernel_class, uint64_t *launches, double *total_ms, double *total_work);
@@ -280,6 +282,67 @@ int mh_bank_render_read(mh_bank *, uint32_t frames, float click_gain, uint32_t n
                         uint32_t *object_live, uint8_t *object_silenced, double *object_modal_energy, uint32_t n_drives,
                         const mh_drive *drives, const float *signals, uint32_t n_pickups, const mh_pickup *pickups, void *pickup_out,
                         uint8_t *pickup_read);
+/* A contact junction (no reference counterpart in ModalAudio; the bank-side primitive under the per-sample contact solve of the reference's
+ * surface renderer, SolveChannelStep in src/audio/surface/, with a linear law): a unilateral -- or, MH_JUNCTION_BILATERAL, bilateral --
+ * linear spring of stiffness K between a contact point on one bank object (side a) and either a second bank object (side b) or an
+ * exciter the caller moves (b.object = MH_NO_OBJECT), solved implicitly once per frame inside the render call.  Passed with the block it
+ * acts in; no state between blocks.
+ * A side is a pickup's contact point and a drive's direction in one record; (nx, ny, nz) is the direction in which the junction pushes
+ * that side.  Per mode k of the side's object, in the bank's precision, with `shape` the pickup's blend (above):
+ *   a[k]    = RadiationGain[k] * (shape_x*nx + shape_y*ny + shape_z*nz)            the drive gain (weights {1,0,0}: a drive's gain, bit for bit)
+ *   read[k] = scale * (shape_x*nx + shape_y*ny + shape_z*nz) * DeflectionGain[k]   the pickup's `read`
+ *   g_im[k] = read[k] * c_re[k],   g_re[k] = read[k] * c_im[k]                     the pickup's advance-1 row
+ * With the junctions comes one approach signal u per junction, [n_junctions][frames] float: the rigid indentation the caller's physics
+ * imposes (converted to the bank's precision like a drive's signal; a sample that is not finite counts as 0).
+ * Per frame s, over the modes the block advances for each side's object (render_count: the caller passes the tuned count, an object on a
+ * junction's side is excited for the block exactly as one with a drive is):
+ *   1. the free step, as without the junction: z~ = z*c + e[s], e[s] the running sum over the object's impacts and drives;
+ *   2. the free prediction of the next frame's deflection: d = sum_sides sum_k g_im[k]*Im z~[k] + g_re[k]*Re z~[k];
+ *   3. the compliance, constant over the block: C = sum_sides sum_k g_re[k]*a[k]  (a force f at frame s enters Re z[s] and reaches
+ *      Im z[s+1] through c_im: it moves the prediction by C f);
+ *   4. x = u[s] - d;  f[s] = (K * max(x, 0)) / (1 + K*C);  bilateral: f[s] = (K * x) / (1 + K*C);
+ *   5. Re z[k] = Re z~[k] + a[k]*f[s] on every side; the frame's output term is formed from that state.
+ * So the force of frame s meets the spring law at the displacement of frame s + 1: f[s] = K*max(u[s] - sum read[k]*Im z[s+1][k], 0).
+ * The sums of d and C have a fixed order that depends on the sides' mode counts only.
+ * Returned per junction: the force row (force_out, [n_junctions][frames] in the bank's precision, WRITTEN, not added to), C as a double
+ * (compliance_out) and a status byte (status_out): MH_JUNCTION_LEFT_OUT, MH_JUNCTION_SOLVED, or MH_JUNCTION_REFUSED -- 1 + K*C is not a
+ * finite number above 0: f = 0 for the block and the objects render as with K = 0.
+ * Left out (status 0, a zero row, C = 0; it excites nothing, like a dropped drive): a side naming no object of the bank, an object that is
+ * not dealt, has no modes or renders none, a point beyond the object's shape columns, a weight, direction component, scale or K that is
+ * not finite, K < 0, both sides the same object, an object already on a side of an earlier junction of the call that was not left out
+ * (one junction per object in this version), and a junction whose sides together take more than MH_JUNCTION_MODES / 128 waves of 128
+ * rendered modes (each side's count rounded up to whole waves).  MH_JUNCTION_MODES = 1024 is what one workgroup holds: eight waves' output
+ * tiles (16 640 B each) fill the 160 KiB of LDS; the registers (78 / 103 VGPRs in fp32 / fp64, nothing spilled, of the 256 a wave of an
+ * eight-wave workgroup may take) would allow more.
+ * In this version a pickup on an object that is on a junction's side is left out (pickup_read = 0, a zero row). */
+typedef struct {
+    uint32_t object;
+    uint32_t points[3];
+    float weights[3];
+    float nx, ny, nz;
+    float scale; /* the caller's coupling already multiplied by the object's DeflectionScale */
+} mh_junction_side;
+typedef struct {
+    mh_junction_side a, b;
+    float stiffness; /* K */
+    uint32_t flags;
+} mh_junction;
+#define MH_NO_OBJECT 0xffffffffu
+#define MH_JUNCTION_BILATERAL 1u
+#define MH_JUNCTION_MODES 1024
+enum { MH_JUNCTION_LEFT_OUT = 0, MH_JUNCTION_SOLVED = 1, MH_JUNCTION_REFUSED = 2 };
+/* sizeof(mh_junction) as this library was built */
+uint32_t mh_junction_struct_size(void);
+/* mh_bank_render_read with junctions.  Every object that is not on a solved or refused junction's side goes through the kernels it would
+ * have gone through without junctions; `out`, the per-object results and the impacts come back as from mh_bank_render_read.  With
+ * n_junctions = 0 this is mh_bank_render_read. */
+int mh_bank_render_coupled(mh_bank *, uint32_t frames, float click_gain, uint32_t n_impacts, mh_impact *impacts,
+                           uint32_t n_renderers, const uint32_t *deal_offset, const uint32_t *deal_objects, const uint32_t *render_count,
+                           const uint32_t *tuned_count, const float *out_gain, const float *listener_gain, void *out, double *object_energy,
+                           uint32_t *object_live, uint8_t *object_silenced, double *object_modal_energy, uint32_t n_drives,
+                           const mh_drive *drives, const float *signals, uint32_t n_pickups, const mh_pickup *pickups, void *pickup_out,
+                           uint8_t *pickup_read, uint32_t n_junctions, const mh_junction *junctions, const float *approach, void *force_out,
+                           double *compliance_out, uint8_t *status_out);
 /* Read back state columns (for parity tests and the modal-energy diagnostic, ModalAudio.cpp:564-577). */
 int mh_bank_read_state(const mh_bank *, uint32_t first, uint32_t count, double *state_re, double *state_im);
 

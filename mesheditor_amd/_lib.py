@@ -47,6 +47,18 @@ class Pickup(C.Structure):  # mh_pickup
                 ("scale", C.c_float), ("advance", C.c_uint32)]
 
 
+class JunctionSide(C.Structure):  # mh_junction_side
+    _fields_ = [("object", C.c_uint32), ("points", C.c_uint32 * 3), ("weights", C.c_float * 3), ("nx", C.c_float), ("ny", C.c_float), ("nz", C.c_float),
+                ("scale", C.c_float)]
+
+
+class Junction(C.Structure):  # mh_junction
+    _fields_ = [("a", JunctionSide), ("b", JunctionSide), ("stiffness", C.c_float), ("flags", C.c_uint32)]
+
+
+NO_OBJECT, JUNCTION_BILATERAL, JUNCTION_MODES = 0xffffffff, 1, 1024  # MH_NO_OBJECT, MH_JUNCTION_BILATERAL, MH_JUNCTION_MODES
+
+
 def build(force=False):
     """Compile libmodalhip.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     src = os.path.join(_HERE, "csrc")
@@ -94,6 +106,8 @@ def lib():
         "mh_bank_set_deflection_gain": (i32, [vp, u32, u32, vp]),
         "mh_bank_render_read": (i32, [vp, u32, C.c_float, u32, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp]),
         "mh_pickup_struct_size": (u32, []),
+        "mh_bank_render_coupled": (i32, [vp, u32, C.c_float, u32, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp, u32, vp, vp, vp, vp, vp]),
+        "mh_junction_struct_size": (u32, []),
         "mh_bank_read_state": (i32, [vp, u32, u32, vp, vp]),
     }
     for name, (res, args) in sig.items():

@@ -35,6 +35,31 @@ class Pickup(C.Structure):  # ModalPickup, modal/bank.hpp (mh_pickup of modalhip
         return cls(obj, (C.c_uint32 * 3)(*pts), (C.c_float * 3)(*weights), direction[0], direction[1], direction[2], coupling, advance)
 
 
+class JunctionSide(C.Structure):  # ModalJunctionSide, modal/bank.hpp (mh_junction_side of modalhip.h field for field; `scale` is the caller's coupling here)
+    _fields_ = [("object", C.c_uint32), ("points", C.c_uint32 * 3), ("weights", C.c_float * 3), ("nx", C.c_float), ("ny", C.c_float), ("nz", C.c_float),
+                ("scale", C.c_float)]
+
+    @classmethod
+    def of(cls, obj, points, weights, direction, coupling=1.0):
+        """points: one excitation position or three; weights: the blend of the three ((1, 0, 0) for one point)."""
+        pts = (points,) * 3 if np.isscalar(points) else tuple(points)
+        return cls(obj, (C.c_uint32 * 3)(*pts), (C.c_float * 3)(*weights), direction[0], direction[1], direction[2], coupling)
+
+
+NO_OBJECT, JUNCTION_BILATERAL = 0xffffffff, 1  # NoModalObject, ModalJunctionBilateral
+
+
+class Junction(C.Structure):  # ModalJunction, modal/bank.hpp (mh_junction of modalhip.h field for field)
+    _fields_ = [("a", JunctionSide), ("b", JunctionSide), ("stiffness", C.c_float), ("flags", C.c_uint32)]
+
+    @classmethod
+    def of(cls, a, b=None, stiffness=0.0, bilateral=False):
+        """a, b: JunctionSide records or the arguments of JunctionSide.of as tuples; b = None: one-sided (an exciter the caller moves)."""
+        side = lambda v: v if isinstance(v, JunctionSide) else JunctionSide.of(*v)
+        none = JunctionSide(NO_OBJECT, (C.c_uint32 * 3)(0, 0, 0), (C.c_float * 3)(1, 0, 0), 0.0, 0.0, 0.0, 1.0)
+        return cls(side(a), side(b) if b is not None else none, stiffness, JUNCTION_BILATERAL if bilateral else 0)
+
+
 def lib():
     global _LIB
     if _LIB is not None:
@@ -52,6 +77,7 @@ def lib():
         "mhx_set_renderers": (None, [vp, u32]), "mhx_set_click_gain": (None, [vp, f32]), "mhx_set_max_impacts": (None, [vp, u32]),
         "mhx_enqueue": (i32, [vp, C.POINTER(Event)]), "mhx_render": (i32, [vp, vp, u32]), "mhx_render_driven": (i32, [vp, vp, u32, u32, vp, vp]),
         "mhx_render_read": (i32, [vp, vp, u32, u32, vp, vp, u32, vp, vp, vp]), "mhx_num_objects": (u32, [vp]),
+        "mhx_render_coupled": (i32, [vp, vp, u32, u32, vp, vp, u32, vp, vp, vp, u32, vp, vp, vp, vp, vp]),
         "mhx_active_impacts": (u32, [vp]), "mhx_modal_energy": (f64, [vp]), "mhx_render_share": (f32, [vp]), "mhx_find_object": (i32, [vp, u32]),
         "mhx_time_kernels": (i32, [vp, i32]), "mhx_kernel_class_stats": (i32, [vp, i32, C.POINTER(C.c_uint64), C.POINTER(f64), C.POINTER(f64)]),
         "mhx_column": (u32, [vp, i32, i32, vp]), "mhx_object_state": (None, [vp, vp, vp, vp]),
@@ -147,6 +173,24 @@ class Scene:
         if self.L.mhx_render_read(self.h, _p(out), len(out), len(drives), C.cast(rows, C.c_void_p), _p(sig), len(pickups), C.cast(probes, C.c_void_p), _p(reads), _p(flags)):
             raise RuntimeError(self.L.mhx_last_error().decode())
         return reads, flags
+
+    def render_coupled(self, out, drives, signals, pickups, junctions, approach):
+        """RenderModalCoupled: render_read plus contact junctions (a ctypes array or a sequence of Junction records) and their approach
+        signals, float32 [len(junctions)][len(out)].  Returns (reads, read_flags, forces, compliances, statuses): forces[j] is junction
+        j's contact force row in the scene's precision, compliances[j] its compliance C, statuses[j] 0 = left out (a zero row), 1 =
+        solved, 2 = refused (1 + K C not a finite number above 0: a zero row)."""
+        assert out.dtype == self.dtype and out.flags["C_CONTIGUOUS"]
+        rows = drives if isinstance(drives, C.Array) else (Drive * max(len(drives), 1))(*[v if isinstance(v, Drive) else Drive(*v) for v in drives])
+        sig = np.ascontiguousarray(signals, np.float32).reshape(len(drives), len(out))
+        probes = pickups if isinstance(pickups, C.Array) else (Pickup * max(len(pickups), 1))(*pickups)
+        contacts = junctions if isinstance(junctions, C.Array) else (Junction * max(len(junctions), 1))(*junctions)
+        u = np.ascontiguousarray(approach, np.float32).reshape(len(junctions), len(out))
+        reads, flags = np.zeros((len(pickups), len(out)), self.dtype), np.zeros(len(pickups), np.uint8)
+        forces, compliances, statuses = np.zeros((len(junctions), len(out)), self.dtype), np.zeros(len(junctions)), np.zeros(len(junctions), np.uint8)
+        if self.L.mhx_render_coupled(self.h, _p(out), len(out), len(drives), C.cast(rows, C.c_void_p), _p(sig), len(pickups), C.cast(probes, C.c_void_p), _p(reads), _p(flags),
+                                     len(junctions), C.cast(contacts, C.c_void_p), _p(u), _p(forces), _p(compliances), _p(statuses)):
+            raise RuntimeError(self.L.mhx_last_error().decode())
+        return reads, flags, forces, compliances, statuses
 
     def time_kernels(self, enable=True):
         """HIP-event timing of the bank's kernels on its device context (measurement aid)."""

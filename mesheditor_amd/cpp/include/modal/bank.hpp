@@ -58,6 +58,28 @@ struct ModalPickup {
     uint32_t Advance{0};
 };
 
+// Not in the reference's ModalAudio.h: a contact junction, the bank-side primitive under the per-sample contact solve of the reference's
+// surface renderer (SolveChannelStep, src/audio/surface/) with a linear law.  A unilateral -- Flags bit 0: bilateral -- linear spring of
+// stiffness Stiffness between a contact point on object A.Object and either a second object (B) or an exciter the caller moves
+// (B.Object = NoModalObject), solved implicitly once per frame inside the render call (RenderModalCoupled; the contract, its five steps
+// and the returned force rows: include/modalhip.h, mh_junction).  A side is a pickup's contact point and a drive's direction in one record:
+// (Nx, Ny, Nz) is the direction in which the junction pushes that side; Coupling is the caller's factor, which the render multiplies by
+// the object's DeflectionScale.  Passed with the block it acts in; no state between blocks.
+constexpr uint32_t NoModalObject{0xffffffffu};
+constexpr uint32_t ModalJunctionBilateral{1};
+struct ModalJunctionSide {
+    uint32_t Object{NoModalObject};
+    uint32_t Points[3]{0, 0, 0};
+    float Weights[3]{1, 0, 0};
+    float Nx{0}, Ny{0}, Nz{0};
+    float Coupling{1};
+};
+struct ModalJunction {
+    ModalJunctionSide A, B;
+    float Stiffness{0};
+    uint32_t Flags{0};
+};
+
 constexpr float AirDensity{1.204f}, SpeedOfSound{343.f}, ListenerDistance{1.f};
 constexpr float Ln1000 = 3 * std::numbers::ln10_v<float>;
 
@@ -213,6 +235,24 @@ void RenderModalRead(ModalAudio &, std::span<const ModalDrive> drives, const flo
                      uint32_t frame_count, uint8_t *read_flags = nullptr);
 void RenderModalRead(ModalAudio64 &, std::span<const ModalDrive> drives, const float *signals, std::span<const ModalPickup> pickups, double *reads, double *out,
                      uint32_t frame_count, uint8_t *read_flags = nullptr);
+// Not in the reference: RenderModalRead with contact junctions.  `approach` holds junctions.size() rows of frame_count samples (the rigid
+// indentation the caller's physics imposes; a sample that is not finite counts as 0), `forces` receives as many rows of the contact force
+// (written, not added to), `compliances` (nullable) the compliance C of each junction and `statuses` (nullable) one byte each: 0 = left
+// out (row of zeros), 1 = solved, 2 = refused (1 + K C is not a finite number above 0: no force, the objects render as with K = 0).  An
+// object on a side of a junction that is not left out is excited for the block like one with a drive: it rings, is dealt at and renders
+// its tuned mode count, is not silenced, and leaves the block with LiveModeCount = TunedModeCount.  Left out, and exciting nothing: a
+// side naming no object of the bank (B.Object = NoModalObject is the one-sided junction, not that), an object without modes or without
+// tuned modes, a point its shape columns do not cover, a weight, direction component, coupling or stiffness that is not finite, a
+// negative stiffness, both sides the same object, an object already on a side of an earlier junction of the call that was kept (one
+// junction per object in this version), and sides that together take more than MH_JUNCTION_MODES / 128 waves of 128 tuned modes
+// (modalhip.h).  A pickup on an object that is on a kept junction's side is left out in this version.  Without junctions this is
+// RenderModalRead.
+void RenderModalCoupled(ModalAudio &, std::span<const ModalDrive> drives, const float *signals, std::span<const ModalPickup> pickups, float *reads,
+                        std::span<const ModalJunction> junctions, const float *approach, float *forces, float *out, uint32_t frame_count, uint8_t *read_flags = nullptr,
+                        double *compliances = nullptr, uint8_t *statuses = nullptr);
+void RenderModalCoupled(ModalAudio64 &, std::span<const ModalDrive> drives, const float *signals, std::span<const ModalPickup> pickups, double *reads,
+                        std::span<const ModalJunction> junctions, const float *approach, double *forces, double *out, uint32_t frame_count, uint8_t *read_flags = nullptr,
+                        double *compliances = nullptr, uint8_t *statuses = nullptr);
 // Not in the reference: the libmodalhip context the bank's device mirror lives on (created on demand), for callers that
 // time its kernels (mh_context_time_kernels / mh_context_kernel_class_stats).
 mh_context *ModalDeviceContext(ModalAudio &);

@@ -38,6 +38,11 @@ struct ModalDeviceMirror {
     std::vector<float> DriveSignals;
     std::vector<mh_pickup> Pickups; // the block's pickups, one per caller's record
     std::vector<uint8_t> PickupRead;
+    std::vector<mh_junction> Junctions; // the block's junctions that passed the checks, with their approach rows, and where each came from
+    std::vector<uint32_t> JunctionFrom;
+    std::vector<float> Approach;
+    std::vector<double> JunctionCompliance;
+    std::vector<uint8_t> JunctionStatus, OnJunction;
     std::vector<std::vector<uint32_t>> Renderers;
     ~ModalDeviceMirror() {
         mh_bank_destroy(Bank);
@@ -491,9 +496,18 @@ template<typename Real> bool HasExcitationPosition(const ModalBankColumns<Real> 
     return uint64_t(ex_pos) * b.ModeCount[object] + b.ModeCount[object] <= uint64_t(last - first);
 }
 
+// What a junction hands back to the caller of RenderModalCoupled.
+template<typename Real> struct JunctionResults {
+    std::span<const ModalJunction> Junctions;
+    const float *Approach{nullptr};
+    Real *Forces{nullptr};
+    double *Compliances{nullptr};
+    uint8_t *Statuses{nullptr};
+};
+
 template<typename Audio, typename Real>
 void RenderBlock(Audio &m, std::span<const ModalDrive> drives, const float *signals, Real *out, uint32_t frames, std::span<const ModalPickup> pickups = {}, Real *reads = nullptr,
-                 uint8_t *read_flags = nullptr) {
+                 uint8_t *read_flags = nullptr, const JunctionResults<Real> &coupled = {}) {
     if (frames == 0) return;
     const auto started = std::chrono::steady_clock::now();
     const ReaderScope reading(m.ReaderSeq);
@@ -542,6 +556,45 @@ void RenderBlock(Audio &m, std::span<const ModalDrive> drives, const float *sign
         const float scale = v.Object < n_objects ? float(Real(v.Coupling) * b.DeflectionScale[v.Object]) : v.Coupling;
         d.Pickups[q] = {v.Object, {v.Points[0], v.Points[1], v.Points[2]}, {v.Weights[0], v.Weights[1], v.Weights[2]}, v.Nx, v.Ny, v.Nz, scale, v.Advance};
     }
+    // junctions: the ones the bank can follow, packed in the caller's order with their approach rows (the device entry checks every field
+    // again).  Both sides of a kept junction are excited for the block, as a driven object is.  A side's coupling is scaled like a pickup's.
+    const auto junctions = coupled.Junctions;
+    d.Junctions.clear();
+    d.JunctionFrom.clear();
+    d.Approach.clear();
+    d.OnJunction.assign(n_objects, 0);
+    auto side_ok = [&](const ModalJunctionSide &v) {
+        if (v.Object >= n_objects || b.ModeCount[v.Object] == 0 || b.TunedModeCount[v.Object] == 0 || d.OnJunction[v.Object]) return false;
+        bool ok = std::isfinite(v.Nx) && std::isfinite(v.Ny) && std::isfinite(v.Nz) && std::isfinite(v.Coupling);
+        for (int c = 0; c < 3; ++c) ok = ok && std::isfinite(v.Weights[c]) && HasExcitationPosition(b, v.Object, v.Points[c]);
+        return ok;
+    };
+    auto side_waves = [&](const ModalJunctionSide &v) { return (b.TunedModeCount[v.Object] + 127) / 128; };
+    auto side_record = [&](const ModalJunctionSide &v) {
+        return mh_junction_side{v.Object, {v.Points[0], v.Points[1], v.Points[2]}, {v.Weights[0], v.Weights[1], v.Weights[2]}, v.Nx, v.Ny, v.Nz, float(Real(v.Coupling) * b.DeflectionScale[v.Object])};
+    };
+    for (size_t j = 0; j < junctions.size(); ++j) {
+        const ModalJunction &v = junctions[j];
+        const bool two_sided = v.B.Object != NoModalObject;
+        if (!std::isfinite(v.Stiffness) || v.Stiffness < 0 || !side_ok(v.A) || (two_sided && (v.A.Object == v.B.Object || !side_ok(v.B)))) continue;
+        if (side_waves(v.A) + (two_sided ? side_waves(v.B) : 0u) > MH_JUNCTION_MODES / 128) continue;
+        mh_junction_side none{};
+        none.object = MH_NO_OBJECT;
+        d.Junctions.push_back({side_record(v.A), two_sided ? side_record(v.B) : none, v.Stiffness, v.Flags});
+        d.JunctionFrom.push_back(uint32_t(j));
+        d.Approach.insert(d.Approach.end(), coupled.Approach + j * frames, coupled.Approach + (j + 1) * frames);
+        auto excite = [&](uint32_t o) {
+            d.OnJunction[o] = 1;
+            ++d.ImpactsOn[o];
+            b.Ringing[o] = 1;
+        };
+        excite(v.A.Object);
+        if (two_sided) excite(v.B.Object);
+    }
+    const uint32_t kept_junctions = uint32_t(d.Junctions.size());
+    std::vector<Real> junction_forces(size_t(kept_junctions) * frames);
+    d.JunctionCompliance.assign(kept_junctions, 0.0);
+    d.JunctionStatus.assign(kept_junctions, 0);
     Deal(d, b, renderers);
     d.DealOffset.assign(1, 0);
     d.DealObjects.clear();
@@ -581,11 +634,23 @@ void RenderBlock(Audio &m, std::span<const ModalDrive> drives, const float *sign
         narrow_listener.assign(b.ListenerGain.begin(), b.ListenerGain.end());
         out_gain = narrow_out.data(), listener_gain = narrow_listener.data();
     }
-    if (mh_bank_render_read(d.Bank, frames, m.ClickGain.load(std::memory_order_relaxed), n_impacts, d.Impacts.data(), renderers, d.DealOffset.data(), d.DealObjects.data(),
+    if (mh_bank_render_coupled(d.Bank, frames, m.ClickGain.load(std::memory_order_relaxed), n_impacts, d.Impacts.data(), renderers, d.DealOffset.data(), d.DealObjects.data(),
                               d.RenderCount.data(), d.Tuned.data(), out_gain, listener_gain, out, d.Energy.data(), d.Live.data(), d.Silenced.data(), d.ModalEnergy.data(),
-                              uint32_t(d.Drives.size()), d.Drives.data(), drive_signals, uint32_t(d.Pickups.size()), d.Pickups.data(), reads, d.PickupRead.data()) != MH_OK)
+                              uint32_t(d.Drives.size()), d.Drives.data(), drive_signals, uint32_t(d.Pickups.size()), d.Pickups.data(), reads, d.PickupRead.data(), kept_junctions, d.Junctions.data(), d.Approach.data(),
+                               junction_forces.data(), d.JunctionCompliance.data(), d.JunctionStatus.data()) != MH_OK)
         Fail(d);
     if (read_flags) std::copy(d.PickupRead.begin(), d.PickupRead.end(), read_flags);
+    if (!junctions.empty()) { // every caller's junction gets its row: zeros and status 0 for the ones left out
+        std::fill(coupled.Forces, coupled.Forces + junctions.size() * frames, Real(0));
+        if (coupled.Compliances) std::fill(coupled.Compliances, coupled.Compliances + junctions.size(), 0.0);
+        if (coupled.Statuses) std::fill(coupled.Statuses, coupled.Statuses + junctions.size(), uint8_t(0));
+        for (uint32_t c = 0; c < kept_junctions; ++c) {
+            const size_t j = d.JunctionFrom[c];
+            std::copy(junction_forces.begin() + size_t(c) * frames, junction_forces.begin() + size_t(c + 1) * frames, coupled.Forces + j * frames);
+            if (coupled.Compliances) coupled.Compliances[j] = d.JunctionCompliance[c];
+            if (coupled.Statuses) coupled.Statuses[j] = d.JunctionStatus[c];
+        }
+    }
 
     // impacts: carry the recurrences' state over to the next block
     for (uint32_t i = 0; i < n_impacts; ++i) {
@@ -669,6 +734,16 @@ void RenderModalRead(ModalAudio &m, std::span<const ModalDrive> drives, const fl
 void RenderModalRead(ModalAudio64 &m, std::span<const ModalDrive> drives, const float *signals, std::span<const ModalPickup> pickups, double *reads, double *out,
                      uint32_t frame_count, uint8_t *read_flags) {
     RenderBlock<ModalAudio64, double>(m, drives, signals, out, frame_count, pickups, reads, read_flags);
+}
+void RenderModalCoupled(ModalAudio &m, std::span<const ModalDrive> drives, const float *signals, std::span<const ModalPickup> pickups, float *reads,
+                        std::span<const ModalJunction> junctions, const float *approach, float *forces, float *out, uint32_t frame_count, uint8_t *read_flags, double *compliances,
+                        uint8_t *statuses) {
+    RenderBlock<ModalAudio, float>(m, drives, signals, out, frame_count, pickups, reads, read_flags, {junctions, approach, forces, compliances, statuses});
+}
+void RenderModalCoupled(ModalAudio64 &m, std::span<const ModalDrive> drives, const float *signals, std::span<const ModalPickup> pickups, double *reads,
+                        std::span<const ModalJunction> junctions, const float *approach, double *forces, double *out, uint32_t frame_count, uint8_t *read_flags, double *compliances,
+                        uint8_t *statuses) {
+    RenderBlock<ModalAudio64, double>(m, drives, signals, out, frame_count, pickups, reads, read_flags, {junctions, approach, forces, compliances, statuses});
 }
 mh_context *ModalDeviceContext(ModalAudio &m) { return NeedContext(m), m.Dev->Context; }
 mh_context *ModalDeviceContext(ModalAudio64 &m) { return NeedContext(m), m.Dev->Context; }

@@ -129,6 +129,24 @@ int mhx_render_read(mhx_scene *s, void *out, uint32_t frames, uint32_t n_drives,
         return 0;
     } catch (const std::exception &e) { g_error = e.what(); return 1; }
 }
+// RenderModalCoupled: mhx_render_read plus `junctions` (n_junctions ModalJunction records) and their `approach` rows [n_junctions][frames]
+// float; `forces` [n_junctions][frames] in the scene's precision, `compliances` one double and `statuses` one byte per junction
+int mhx_render_coupled(mhx_scene *s, void *out, uint32_t frames, uint32_t n_drives, const ModalDrive *drives, const float *signals, uint32_t n_pickups,
+                       const ModalPickup *pickups, void *reads, uint8_t *read_flags, uint32_t n_junctions, const ModalJunction *junctions, const float *approach,
+                       void *forces, double *compliances, uint8_t *statuses) {
+    try {
+        const std::span<const ModalDrive> list(drives, n_drives);
+        const std::span<const ModalPickup> probes(pickups, n_pickups);
+        const std::span<const ModalJunction> contacts(junctions, n_junctions);
+        if (s->dbl)
+            RenderModalCoupled(s->audio64, list, signals, probes, static_cast<double *>(reads), contacts, approach, static_cast<double *>(forces), static_cast<double *>(out), frames,
+                               read_flags, compliances, statuses);
+        else
+            RenderModalCoupled(s->audio, list, signals, probes, static_cast<float *>(reads), contacts, approach, static_cast<float *>(forces), static_cast<float *>(out), frames,
+                               read_flags, compliances, statuses);
+        return 0;
+    } catch (const std::exception &e) { g_error = e.what(); return 1; }
+}
 // Kernel timing of the scene's device context: enable / read one class (modalhip.h MH_KERNEL_*)
 int mhx_time_kernels(mhx_scene *s, int enable) {
     try {

@@ -10,6 +10,7 @@
 #include "mh_common.h"
 
 #include <algorithm>
+#include <limits>
 #include <memory>
 
 namespace {
@@ -455,6 +456,204 @@ __global__ void __launch_bounds__(256) k_bank_read_rows(const Real *__restrict__
 #undef BANK_MODES_PARAMS
 #undef BANK_MODES_ARGS
 
+// Contact junctions (mh_bank_render_coupled; contract in modalhip.h).  ONE WORKGROUP PER JUNCTION, one wave per 128
+// modes of each side (side a's waves first, then side b's), modes in registers two per lane as in bank_modes; the waves of a junction's
+// objects are taken out of the main launch's wave list and write the same partial chunk rows and chunk energies here.  The workgroup has
+// as many waves as the largest junction of the call; a wave beyond a junction's own holds no modes (zero gains, zero state), stores
+// nothing to global memory and takes part in every barrier.
+// Per frame: the free step -> the lane's part of d (four multiply-adds from +0: g_im*Im z~, g_re*Re z~ of its even mode, then of its odd
+// mode) -> mh_wave_sum (DPP moves, never the LDS crossbar) -> one LDS slot per wave -> barrier -> every wave adds the junction's slots
+// from +0 in ascending wave order and computes the same f -> Re z += a*f -> output term into the wave's turn-around tile.  C is one such
+// reduction ahead of the loop.  The slots are double-buffered by frame parity (C uses the odd buffer, frame 0 the even one): a wave
+// overwrites a buffer only after the barrier of the frame in between, which every wave reaches after it has read that buffer.
+// Barriers: 1 + frames + 2 per tile, executed by every wave of the workgroup whatever it holds -- a function of `frames` alone.
+// Force rows: the tile's excitation sums (the running sum over the object's rows from +0, uncontracted, as in bank_modes) are formed
+// ahead of the tile's serial loop and parked in the turn-around tile, where each lane's output term replaces them frame by frame: the
+// loads of forces and gains stay off the serial chain.
+constexpr uint32_t JUNCTION_WAVES = MH_JUNCTION_MODES / MODES_PER_WAVE;
+template<typename Real> struct JunctionSideDev {
+    uint32_t dealt, waves, p0, p1, p2, pad;
+    Real w0, w1, w2, nx, ny, nz, scale;
+};
+template<typename Real> struct JunctionDev {
+    JunctionSideDev<Real> side[2]; // side[1].waves = 0: one-sided
+    Real k;
+    uint32_t flags, row, first_wave; // row: the caller's index (approach, force, compliance, status); first_wave: into the gain scratch
+};
+template<typename Real> struct CoupledArgs {
+    const Real *defl_gain;
+    const JunctionDev<Real> *junctions;
+    const float *approach; // [caller's junction][frames]
+    Real *force_out; // [caller's junction][frames], where the host reads it
+    double *compliance_out;
+    uint32_t *status_out;
+};
+template<typename Real> constexpr uint32_t coupled_tile() { return sizeof(Real) == 4 ? 32 : 16; } // samples per turn-around tile: 16 640 B per wave either way
+template<typename Real> size_t coupled_lds(uint32_t waves) {
+    return 2 * JUNCTION_WAVES * sizeof(Real) + size_t(waves) * coupled_tile<Real>() * (MODES_PER_WAVE + 2) * sizeof(Real);
+}
+__device__ __forceinline__ float fma_real(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+__device__ __forceinline__ double fma_real(double a, double b, double c) { return __builtin_fma(a, b, c); }
+template<typename Real>
+__global__ void __launch_bounds__(JUNCTION_WAVES *WAVE)
+    k_bank_modes_coupled(BankCols<Real> b, const uint32_t *__restrict__ deal_objects, const uint32_t *__restrict__ render_count, const uint32_t *__restrict__ chunk_base,
+                         const uint32_t *__restrict__ imp_ptr, const uint32_t *__restrict__ imp_idx, const ImpactDev<Real> *__restrict__ impacts,
+                         const Real *__restrict__ force, const Real *__restrict__ out_gain, const Real *__restrict__ listener_gain, uint32_t frames,
+                         Real *__restrict__ partial, Real *__restrict__ chunk_energy, Real *__restrict__ gain_scratch, uint32_t max_imp, CoupledArgs<Real> ca) {
+    typedef Real Pair __attribute__((ext_vector_type(2)));
+    constexpr uint32_t TS = coupled_tile<Real>(), PITCH = MODES_PER_WAVE + 2, CHUNKS = MODES_PER_WAVE / LANES, GROUPS = WAVE / TS, PER_GROUP = CHUNKS / GROUPS;
+    extern __shared__ __attribute__((aligned(16))) unsigned char coupled_mem[];
+    Real *s_slot = reinterpret_cast<Real *>(coupled_mem); // [2][JUNCTION_WAVES]
+    const uint32_t wave = threadIdx.x / WAVE, lane = threadIdx.x % WAVE;
+    Real *s_term = s_slot + 2 * JUNCTION_WAVES + size_t(wave) * TS * PITCH; // this wave's tile, [sample][mode]
+    const JunctionDev<Real> J = ca.junctions[blockIdx.x];
+    const uint32_t waves_a = J.side[0].waves, n_w = waves_a + J.side[1].waves;
+    const bool active = wave < n_w;
+    const JunctionSideDev<Real> S = J.side[active && wave >= waves_a ? 1 : 0];
+    const uint32_t first_mode = active ? (wave - (wave >= waves_a ? waves_a : 0u)) * MODES_PER_WAVE : 0u;
+    const uint32_t o = deal_objects[S.dealt];
+    const uint32_t count = active ? render_count[S.dealt] : 0u; // an idle wave has no live mode: nothing below loads or stores for it
+    const uint32_t k0 = b.mode_offset[o], stride = b.mode_count[o], shape0 = b.shape_offset[o];
+    const uint32_t k = first_mode + 2 * lane;
+    const bool live[2] = {k < count, k + 1 < count};
+    const uint32_t chunk0 = chunk_base[S.dealt] + first_mode / LANES;
+    const uint32_t chunks_here = active ? min(CHUNKS, (count - first_mode + LANES - 1) / LANES) : 0u;
+    Pair z_re = {0, 0}, z_im = {0, 0}, c_re = {0, 0}, c_im = {0, 0}, p_re = {0, 0}, p_im = {0, 0};
+    Pair a = {0, 0}, g_im = {0, 0}, g_re = {0, 0}; // the junction's drive gain and its advance-1 read row
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+        if (live[h]) {
+            z_re[h] = b.state_re[k0 + k + h]; z_im[h] = b.state_im[k0 + k + h];
+            c_re[h] = b.coeff_re[k0 + k + h]; c_im[h] = b.coeff_im[k0 + k + h];
+            p_im[h] = b.phase_im[k0 + k + h]; p_re[h] = b.phase_re[k0 + k + h];
+            const uint32_t i0s = shape0 + S.p0 * stride + k + h, i1s = shape0 + S.p1 * stride + k + h, i2s = shape0 + S.p2 * stride + k + h;
+            const Real sx = S.w0 * b.shape_x[i0s] + S.w1 * b.shape_x[i1s] + S.w2 * b.shape_x[i2s];
+            const Real sy = S.w0 * b.shape_y[i0s] + S.w1 * b.shape_y[i1s] + S.w2 * b.shape_y[i2s];
+            const Real sz = S.w0 * b.shape_z[i0s] + S.w1 * b.shape_z[i1s] + S.w2 * b.shape_z[i2s];
+            const Real along = sx * S.nx + sy * S.ny + sz * S.nz;
+            a[h] = b.rad_gain[k0 + k + h] * along;
+            const Real read = S.scale * along * ca.defl_gain[k0 + k + h];
+            g_im[h] = read * c_re[h];
+            g_re[h] = read * c_im[h];
+        }
+    // the object's force rows: gains of the first IMP_REG in registers, of further ones in this wave's scratch rows (a lane reads back
+    // what it wrote)
+    const uint32_t i0 = imp_ptr[S.dealt], n_imp = active ? imp_ptr[S.dealt + 1] - i0 : 0u;
+    Pair g_reg[IMP_REG] = {};
+    Real *g_mem = gain_scratch + size_t(J.first_wave + wave) * max_imp * MODES_PER_WAVE;
+    for (uint32_t t = 0; t < n_imp; ++t) {
+        Pair g = {0, 0};
+        const ImpactDev<Real> &im = impacts[imp_idx[i0 + t]];
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+            if (live[h]) {
+                const uint32_t base = shape0 + im.ex_pos * stride + k + h;
+                g[h] = b.rad_gain[k0 + k + h] * (b.shape_x[base] * im.jx + b.shape_y[base] * im.jy + b.shape_z[base] * im.jz);
+            }
+        if (t < IMP_REG) g_reg[t] = g;
+        else *reinterpret_cast<Pair *>(g_mem + size_t(t) * MODES_PER_WAVE + 2 * lane) = g;
+    }
+    const Real mix_gain = out_gain[o] * listener_gain[o];
+    // a sum over the junction's modes: the lane's part -> the wave (DPP tree) -> the waves in ascending order from +0; the same bits in
+    // every lane of every wave.  One barrier.
+    auto junction_sum = [&](Real mine, uint32_t buffer) {
+        const Real w = mh_wave_sum(mine);
+        if (lane == 0) s_slot[buffer * JUNCTION_WAVES + wave] = w;
+        mh_lds_writes_landed();
+        __syncthreads();
+        Real v[JUNCTION_WAVES];
+#pragma unroll
+        for (uint32_t i = 0; i < JUNCTION_WAVES; ++i) v[i] = s_slot[buffer * JUNCTION_WAVES + i];
+        Real acc = 0;
+#pragma unroll
+        for (uint32_t i = 0; i < JUNCTION_WAVES; ++i) acc = i < n_w ? acc + v[i] : acc; // a slot beyond the junction's waves is not added
+        return acc;
+    };
+    const Real zero = 0;
+    const Real compliance = junction_sum(fma_real(g_re.y, a.y, fma_real(g_re.x, a.x, zero)), 1);
+    const Real denom_k = Real(1) + J.k * compliance;
+    const bool solved = denom_k > Real(0) && denom_k <= std::numeric_limits<Real>::max(); // a finite number above 0 (a NaN fails both)
+    const Real stiffness = solved ? J.k : Real(0), denom = solved ? denom_k : Real(1);
+    const bool bilateral = (J.flags & MH_JUNCTION_BILATERAL) != 0;
+    if (threadIdx.x == 0) {
+        ca.compliance_out[J.row] = double(compliance);
+        ca.status_out[J.row] = solved ? MH_JUNCTION_SOLVED : MH_JUNCTION_REFUSED;
+    }
+    const uint32_t group = lane / TS, ts = lane % TS; // turn-around mapping: chunks PER_GROUP*group .. of sample ts
+    const float *u_row = ca.approach + size_t(J.row) * frames;
+    Real *f_row = ca.force_out + size_t(J.row) * frames;
+    for (uint32_t s0 = 0; s0 < frames; s0 += TS) {
+        const uint32_t sn = min(TS, frames - s0);
+        // this tile's approach samples, lane = sample (not finite: 0, as a drive's)
+        Real u_tile = 0;
+        if (lane < sn) {
+            const float v = u_row[s0 + lane];
+            u_tile = (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u ? Real(v) : Real(0);
+        }
+        // the tile's excitation, parked where the output terms will go
+        for (uint32_t ds = 0; ds < sn; ++ds) {
+            Pair excite = {0, 0};
+            for (uint32_t t = 0; t < n_imp; ++t) {
+                const Real f = force[size_t(imp_idx[i0 + t]) * frames + s0 + ds];
+                excite += f * (t < IMP_REG ? g_reg[t] : *reinterpret_cast<const Pair *>(g_mem + size_t(t) * MODES_PER_WAVE + 2 * lane));
+            }
+            *reinterpret_cast<Pair *>(s_term + ds * PITCH + 2 * lane) = excite;
+        }
+        Real f_tile = 0;
+        for (uint32_t ds = 0; ds < sn; ++ds) {
+            const Pair excite = *reinterpret_cast<const Pair *>(s_term + ds * PITCH + 2 * lane); // what this lane parked
+            const Pair re = z_re * c_re - z_im * c_im + excite;
+            z_im = z_re * c_im + z_im * c_re;
+            const Real mine = fma_real(g_re.y, re.y, fma_real(g_im.y, z_im.y, fma_real(g_re.x, re.x, fma_real(g_im.x, z_im.x, zero))));
+            const Real d = junction_sum(mine, (s0 + ds) & 1u);
+            const Real x = lane_bcast(u_tile, ds) - d;
+            const Real reach = bilateral ? x : (x > Real(0) ? x : Real(0));
+            const Real f = solved ? (stiffness * reach) / denom : Real(0);
+            z_re = re + a * f;
+            *reinterpret_cast<Pair *>(s_term + ds * PITCH + 2 * lane) = p_im * z_im + p_re * z_re;
+            if (lane == ds) f_tile = f;
+        }
+        if (wave == 0 && lane < sn) f_row[s0 + lane] = f_tile;
+        // the turn-around of bank_modes: every chunk's 8 terms added in mode order
+        mh_lds_writes_landed();
+        __syncthreads();
+        if (ts < sn) {
+            const Real *row = s_term + ts * PITCH + group * (PER_GROUP * LANES);
+#pragma unroll
+            for (uint32_t c = 0; c < PER_GROUP; ++c) {
+                Real acc = 0;
+#pragma unroll
+                for (uint32_t l = 0; l < LANES; l += 2) {
+                    const Pair v = *reinterpret_cast<const Pair *>(row + c * LANES + l);
+                    acc += v.x;
+                    acc += v.y;
+                }
+                const uint32_t chunk = PER_GROUP * group + c;
+                if (chunk < chunks_here) partial[size_t(chunk0 + chunk) * frames + s0 + ts] = acc * mix_gain;
+            }
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+        if (live[h]) {
+            b.state_re[k0 + k + h] = z_re[h];
+            b.state_im[k0 + k + h] = z_im[h];
+        }
+    // chunk energy, as in bank_modes
+    const Pair e = z_re * z_re + z_im * z_im;
+    const Real e0 = live[0] ? e.x : Real(0), e1 = live[1] ? e.y : Real(0);
+    Real chunk = Real(0) + e0;
+    chunk += e1;
+    chunk += row_shl<1>(e0);
+    chunk += row_shl<1>(e1);
+    chunk += row_shl<2>(e0);
+    chunk += row_shl<2>(e1);
+    chunk += row_shl<3>(e0);
+    chunk += row_shl<3>(e1);
+    if ((lane & (LANES / 2 - 1)) == 0 && lane / (LANES / 2) < chunks_here) chunk_energy[chunk0 + lane / (LANES / 2)] = chunk;
+}
+
 // Per dealt object (one wave each): energy, audible prefix, whole-object silence (ModalAudio.cpp:132-146).  Loads are
 // lane-parallel; every sum runs in the reference's order through wave-uniform lane broadcasts.
 struct PerDeviceOnceBank { // hipFuncSetAttribute once per (kernel, device)
@@ -710,6 +909,8 @@ template<typename Real> struct BankImpl {
     DevArray<uint32_t> mode_offset, mode_count, shape_offset;
     std::vector<uint32_t> h_mode_count, picks_on, pick_fill;
     std::vector<int32_t> pick_dealt;
+    DevArray<Real> junction_gain; // the coupled kernel's scratch gain rows
+    std::vector<uint8_t> on_junction; // per object: on a side of a junction of this call that was not left out
     // per-block scratch
     Arena arena;
     DevArray<Real> force, click, partial, chunk_energy, gain_scratch, rout;
@@ -736,7 +937,8 @@ template<typename Real>
 void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t n_impacts, mh_impact *impacts, uint32_t n_renderers, const uint32_t *deal_offset,
                  const uint32_t *deal_objects, const uint32_t *render_count, const uint32_t *tuned_count, const float *out_gain, const float *listener_gain,
                  void *out_v, double *object_energy, uint32_t *object_live, uint8_t *object_silenced, double *object_modal_energy, uint32_t n_drives,
-                 const mh_drive *drives, const float *signals, uint32_t n_pickups, const mh_pickup *pickups, void *pickup_out_v, uint8_t *pickup_read) {
+                 const mh_drive *drives, const float *signals, uint32_t n_pickups, const mh_pickup *pickups, void *pickup_out_v, uint8_t *pickup_read,
+                 uint32_t n_junctions, const mh_junction *junctions, const float *approach, void *force_out_v, double *compliance_out, uint8_t *status_out) {
     mh_context *ctx = B.ctx;
     hipStream_t st = ctx->stream;
     Real *out = static_cast<Real *>(out_v);
@@ -755,12 +957,14 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
     const size_t o_out = A.take(frames * sizeof(Real)), o_impacts = A.take((n_rows + 1) * sizeof(ImpactDev<Real>));
     const size_t o_signals = A.take(size_t(n_drives) * frames * sizeof(float));
     const size_t o_pick_ptr = A.take((n_dealt + 2) * 4), o_pick_dev = A.take((n_pickups + 1) * sizeof(PickupDev<Real>)), o_pick_rows = A.take((n_pickups + 1) * sizeof(PickupRows));
+    const size_t o_excited = A.take((n_dealt + 1) * 4), o_junctions = A.take((n_junctions + 1) * sizeof(JunctionDev<Real>)), o_approach = A.take(size_t(n_junctions) * frames * sizeof(float));
     const size_t both_end = A.used;
     // (written by the kernels straight into the pinned arena -- no copy back: the host sees them once the block's last kernel has
     // raised the sequence number)
     const size_t o_energy = A.take((n_dealt + 1) * 8), o_modal = A.take((n_dealt + 1) * 8), o_live = A.take((n_dealt + 1) * 4), o_silenced = A.take(n_dealt + 1);
     const size_t o_back = A.take((n_impacts + 1) * sizeof(ImpactBack<Real>));
     const size_t o_pick_out = A.take(size_t(n_pickups) * frames * sizeof(Real));
+    const size_t o_junction_force = A.take(size_t(n_junctions) * frames * sizeof(Real)), o_compliance = A.take((n_junctions + 1) * 8), o_status = A.take((n_junctions + 1) * 4);
     const size_t total = A.used;
     if (total > A.cap) {
         HIP_CHECK(hipStreamSynchronize(st));
@@ -770,18 +974,52 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
     WaveDesc *waves = A.h<WaveDesc>(o_waves);
     uint32_t *chunk_base = A.h<uint32_t>(o_chunk_base), *imp_ptr = A.h<uint32_t>(o_imp_ptr), *imp_idx = A.h<uint32_t>(o_imp_idx), *rcp = A.h<uint32_t>(o_rcp);
     B.dealt_of_object.assign(B.n_objects, -1);
-    chunk_base[0] = 0;
-    {
-        uint32_t wv = 0;
-        for (uint32_t d = 0; d < n_dealt; ++d) {
-            const uint32_t count = render_count[d];
-            chunk_base[d + 1] = chunk_base[d] + (count + LANES - 1) / LANES;
-            for (uint32_t k = 0; k < count; k += MODES_PER_WAVE) waves[wv++] = {d, k};
-            if (deal_objects[d] < B.n_objects) B.dealt_of_object[deal_objects[d]] = int32_t(d);
-            imp_ptr[d + 1] = 0;
+    for (uint32_t d = 0; d < n_dealt; ++d)
+        if (deal_objects[d] < B.n_objects) B.dealt_of_object[deal_objects[d]] = int32_t(d);
+    // ---- junctions: the ones the coupled kernel may follow, one workgroup each; everything else is left out with a zero row ----
+    uint32_t n_coupled = 0, coupled_waves = 0, widest_junction = 0;
+    if (n_junctions) {
+        JunctionDev<Real> *jd = A.h<JunctionDev<Real>>(o_junctions);
+        B.on_junction.assign(B.n_objects, 0);
+        auto side_ok = [&](const mh_junction_side &sd) {
+            if (sd.object >= B.n_objects || B.h_mode_count[sd.object] == 0 || B.dealt_of_object[sd.object] < 0 || render_count[B.dealt_of_object[sd.object]] == 0) return false;
+            if (B.on_junction[sd.object]) return false; // one junction per object
+            const uint64_t shapes_end = sd.object + 1 < B.n_objects ? B.h_shape_offset[sd.object + 1] : B.n_shapes, held = shapes_end - B.h_shape_offset[sd.object];
+            bool ok = std::isfinite(sd.nx) && std::isfinite(sd.ny) && std::isfinite(sd.nz) && std::isfinite(sd.scale);
+            for (int c = 0; c < 3; ++c) ok = ok && std::isfinite(sd.weights[c]) && (uint64_t(sd.points[c]) + 1) * B.h_mode_count[sd.object] <= held;
+            return ok;
+        };
+        auto side_dev = [&](const mh_junction_side &sd) {
+            const uint32_t d = uint32_t(B.dealt_of_object[sd.object]);
+            return JunctionSideDev<Real>{d, (render_count[d] + MODES_PER_WAVE - 1) / MODES_PER_WAVE, sd.points[0], sd.points[1], sd.points[2], 0, Real(sd.weights[0]), Real(sd.weights[1]),
+                                         Real(sd.weights[2]), Real(sd.nx), Real(sd.ny), Real(sd.nz), Real(sd.scale)};
+        };
+        for (uint32_t j = 0; j < n_junctions; ++j) {
+            const mh_junction &m = junctions[j];
+            status_out[j] = MH_JUNCTION_LEFT_OUT;
+            compliance_out[j] = 0;
+            const bool two_sided = m.b.object != MH_NO_OBJECT;
+            if (!std::isfinite(m.stiffness) || m.stiffness < 0 || !side_ok(m.a) || (two_sided && (m.a.object == m.b.object || !side_ok(m.b)))) continue;
+            JunctionDev<Real> dev{{side_dev(m.a), two_sided ? side_dev(m.b) : JunctionSideDev<Real>{}}, Real(m.stiffness), m.flags, j, coupled_waves};
+            const uint32_t w = dev.side[0].waves + dev.side[1].waves;
+            if (w > JUNCTION_WAVES) continue; // more modes than one workgroup holds
+            B.on_junction[m.a.object] = 1;
+            if (two_sided) B.on_junction[m.b.object] = 1;
+            jd[n_coupled++] = dev;
+            coupled_waves += w;
+            widest_junction = std::max(widest_junction, w);
         }
-        imp_ptr[0] = 0;
     }
+    chunk_base[0] = 0;
+    uint32_t main_waves = 0; // the main launch's waves: every dealt object that is not on a junction's side
+    for (uint32_t d = 0; d < n_dealt; ++d) {
+        const uint32_t count = render_count[d];
+        chunk_base[d + 1] = chunk_base[d] + (count + LANES - 1) / LANES;
+        if (!(n_coupled && deal_objects[d] < B.n_objects && B.on_junction[deal_objects[d]]))
+            for (uint32_t k = 0; k < count; k += MODES_PER_WAVE) waves[main_waves++] = {d, k};
+        imp_ptr[d + 1] = 0;
+    }
+    imp_ptr[0] = 0;
     uint32_t max_imp = 1, driven_rows = 0;
     if (n_dealt) {
         for (uint32_t i = 0; i < n_impacts; ++i) {
@@ -812,6 +1050,14 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
         for (uint32_t j = 0; j < n_drives; ++j) // behind the object's impacts, in the caller's order
             if (B.drive_dealt[j] >= 0) imp_idx[B.imp_fill[B.drive_dealt[j]]++] = n_impacts + j;
     }
+    // an object on a junction's side is excited for the block as one with a drive is: where the per-object pass asks "has it rows", it
+    // sees one more for such an object (a list of its own: the kernels' row lists stay what they are)
+    if (n_coupled) {
+        uint32_t *excited = A.h<uint32_t>(o_excited);
+        excited[0] = 0;
+        for (uint32_t d = 0; d < n_dealt; ++d)
+            excited[d + 1] = excited[d] + (imp_ptr[d + 1] - imp_ptr[d]) + (deal_objects[d] < B.n_objects && B.on_junction[deal_objects[d]] ? 1u : 0u);
+    }
     // ---- pickups: the ones the kernel may follow, grouped by dealt object in the caller's order; everything else gets a zero row ----
     uint32_t read_row_count = 0, picks_dealt = 0;
     uint64_t picked_modes = 0; // a pickup adds two multiply-adds per mode-sample of its object
@@ -827,6 +1073,7 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
             pickup_read[q] = 0;
             pick_rows[q] = {0, 0};
             if (m.object >= B.n_objects || B.h_mode_count[m.object] == 0 || m.advance > 2) continue;
+            if (n_coupled && B.on_junction[m.object]) continue; // its waves are the coupled kernel's, which reads for no pickup (in this version)
             const uint64_t shapes_end = m.object + 1 < B.n_objects ? B.h_shape_offset[m.object + 1] : B.n_shapes, held = shapes_end - B.h_shape_offset[m.object];
             bool ok = std::isfinite(m.nx) && std::isfinite(m.ny) && std::isfinite(m.nz) && std::isfinite(m.scale);
             for (int c = 0; c < 3; ++c) ok = ok && std::isfinite(m.weights[c]) && (uint64_t(m.points[c]) + 1) * B.h_mode_count[m.object] <= held;
@@ -874,6 +1121,7 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
         himp[n_impacts + j] = {m.object, m.ex_pos, 0, 0, Real(m.jx), Real(m.jy), Real(m.jz), 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     }
     if (n_drives) std::copy(signals, signals + size_t(n_drives) * frames, A.h<float>(o_signals));
+    if (n_coupled) std::copy(approach, approach + size_t(n_junctions) * frames, A.h<float>(o_approach));
     HIP_CHECK(hipMemcpyAsync(A.dev, A.host, both_end, hipMemcpyHostToDevice, st));
     // ---- device passes ----
     Real *d_out_gain = A.d<Real>(o_out_gain), *d_listener = A.d<Real>(o_listener), *d_out = A.d<Real>(o_out);
@@ -895,7 +1143,17 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
         ensure(ctx, B.chunk_energy, n_chunks + 1);
         ensure(ctx, B.gain_scratch, size_t(n_waves + 1) * max_imp * MODES_PER_WAVE);
         const uint32_t *d_deal = A.d<uint32_t>(o_deal), *d_count = A.d<uint32_t>(o_count), *d_chunk_base = A.d<uint32_t>(o_chunk_base), *d_imp_ptr = A.d<uint32_t>(o_imp_ptr);
-        if (n_waves) {
+        if (n_coupled) { // the junctions' objects: a launch of their own, one workgroup per junction
+            ensure(ctx, B.junction_gain, size_t(coupled_waves + JUNCTION_WAVES) * max_imp * MODES_PER_WAVE);
+            static PerDeviceOnceBank attr;
+            attr.run(ctx->device, [] { HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_bank_modes_coupled<Real>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); });
+            const CoupledArgs<Real> ca{B.defl_gain, A.d<JunctionDev<Real>>(o_junctions), A.d<float>(o_approach), A.hd<Real>(o_junction_force), A.hd<double>(o_compliance), A.hd<uint32_t>(o_status)};
+            TimedLaunch timed(ctx, MH_KERNEL_JUNCTION, double(n_coupled) * double(frames));
+            k_bank_modes_coupled<Real><<<n_coupled, widest_junction * WAVE, coupled_lds<Real>(widest_junction), st>>>(B.cols(), d_deal, d_count, d_chunk_base, d_imp_ptr, A.d<uint32_t>(o_imp_idx), d_impacts, B.force, d_out_gain,
+                                                                                                                    d_listener, frames, B.partial, B.chunk_energy, B.junction_gain, max_imp, ca);
+            KERNEL_CHECK();
+        }
+        if (main_waves) {
             uint64_t rendered_modes = 0;
             for (uint32_t d = 0; d < n_dealt; ++d) rendered_modes += render_count[d];
             uint64_t driven_modes = 0; // a drive row adds a multiply and an add per mode-sample of its object
@@ -908,11 +1166,11 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
             if (picks_dealt) { // a block with pickups some dealt object carries: the entry that also reads
                 ensure(ctx, B.read_rows, size_t(read_row_count + 1) * frames);
                 const ReadArgs<Real> rd{B.defl_gain, A.d<uint32_t>(o_pick_ptr), A.d<PickupDev<Real>>(o_pick_dev), B.read_rows, rows_loop ? 1u : 0u};
-                k_bank_modes_read<Real><<<n_waves, WAVE, 0, st>>>(B.cols(), A.d<WaveDesc>(o_waves), d_deal, d_count, d_chunk_base, d_imp_ptr, A.d<uint32_t>(o_imp_idx), d_impacts,
+                k_bank_modes_read<Real><<<main_waves, WAVE, 0, st>>>(B.cols(), A.d<WaveDesc>(o_waves), d_deal, d_count, d_chunk_base, d_imp_ptr, A.d<uint32_t>(o_imp_idx), d_impacts,
                                                                  B.force, d_out_gain, d_listener, frames, B.partial, B.chunk_energy, B.gain_scratch, max_imp, rd);
             } else {
                 auto *modes_kernel = rows_loop ? &k_bank_modes_rows<Real> : &k_bank_modes<Real>;
-                modes_kernel<<<n_waves, WAVE, 0, st>>>(B.cols(), A.d<WaveDesc>(o_waves), d_deal, d_count, d_chunk_base, d_imp_ptr, A.d<uint32_t>(o_imp_idx), d_impacts,
+                modes_kernel<<<main_waves, WAVE, 0, st>>>(B.cols(), A.d<WaveDesc>(o_waves), d_deal, d_count, d_chunk_base, d_imp_ptr, A.d<uint32_t>(o_imp_idx), d_impacts,
                                                       B.force, d_out_gain, d_listener, frames, B.partial, B.chunk_energy, B.gain_scratch, max_imp);
             }
             KERNEL_CHECK();
@@ -933,7 +1191,7 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
         constexpr int SW = 16;
         const uint32_t strips = div_up(frames, SW), sum_slices = (n_dealt ? n_renderers : 0) + (streamed_clicks ? 1 : 0);
         const uint32_t object_slices = n_dealt ? div_up(n_dealt, strips * (1024 / WAVE)) : 0;
-        ObjectPassArgs<Real> objects{B.cols(), A.d<uint32_t>(o_deal), A.d<uint32_t>(o_count), A.d<uint32_t>(o_chunk_base), A.d<uint32_t>(o_imp_ptr), d_out_gain, B.chunk_energy, n_dealt,
+        ObjectPassArgs<Real> objects{B.cols(), A.d<uint32_t>(o_deal), A.d<uint32_t>(o_count), A.d<uint32_t>(o_chunk_base), A.d<uint32_t>(n_coupled ? o_excited : o_imp_ptr), d_out_gain, B.chunk_energy, n_dealt,
                                      A.hd<double>(o_energy), A.hd<uint32_t>(o_live), A.hd<uint8_t>(o_silenced), A.d<uint32_t>(o_tuned), A.hd<double>(o_modal)};
         static PerDeviceOnceBank attr;
         attr.run(ctx->device, [] { HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_bank_post<Real, SW>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); });
@@ -955,6 +1213,17 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
         Real *pickup_out = static_cast<Real *>(pickup_out_v);
         if (picks_dealt) std::copy(A.h<Real>(o_pick_out), A.h<Real>(o_pick_out) + size_t(n_pickups) * frames, pickup_out);
         else std::fill(pickup_out, pickup_out + size_t(n_pickups) * frames, Real(0));
+    }
+    if (n_junctions) { // rows, compliances and statuses of the solved ones; a junction that was left out keeps its zero row
+        Real *force_out = static_cast<Real *>(force_out_v);
+        std::fill(force_out, force_out + size_t(n_junctions) * frames, Real(0));
+        const JunctionDev<Real> *jd = A.h<JunctionDev<Real>>(o_junctions);
+        for (uint32_t c = 0; c < n_coupled; ++c) {
+            const uint32_t j = jd[c].row;
+            std::copy(A.h<Real>(o_junction_force) + size_t(j) * frames, A.h<Real>(o_junction_force) + size_t(j + 1) * frames, force_out + size_t(j) * frames);
+            compliance_out[j] = A.h<double>(o_compliance)[j];
+            status_out[j] = uint8_t(A.h<uint32_t>(o_status)[j]);
+        }
     }
     const ImpactBack<Real> *back = A.h<ImpactBack<Real>>(o_back);
     for (uint32_t i = 0; i < n_impacts; ++i) {
@@ -1086,12 +1355,14 @@ int mh_bank_set_deflection_gain(mh_bank *bank, uint32_t first, uint32_t count, c
         return MH_OK;
     } catch (const std::exception &e) { return mh_guard(bank->ctx, e); }
 }
-int mh_bank_render_read(mh_bank *bank, uint32_t frames, float click_gain, uint32_t n_impacts, mh_impact *impacts, uint32_t n_renderers, const uint32_t *deal_offset,
-                        const uint32_t *deal_objects, const uint32_t *render_count, const uint32_t *tuned_count, const float *out_gain, const float *listener_gain,
-                        void *out, double *object_energy, uint32_t *object_live, uint8_t *object_silenced, double *object_modal_energy, uint32_t n_drives,
-                        const mh_drive *drives, const float *signals, uint32_t n_pickups, const mh_pickup *pickups, void *pickup_out, uint8_t *pickup_read) {
+int mh_bank_render_coupled(mh_bank *bank, uint32_t frames, float click_gain, uint32_t n_impacts, mh_impact *impacts, uint32_t n_renderers, const uint32_t *deal_offset,
+                           const uint32_t *deal_objects, const uint32_t *render_count, const uint32_t *tuned_count, const float *out_gain, const float *listener_gain,
+                           void *out, double *object_energy, uint32_t *object_live, uint8_t *object_silenced, double *object_modal_energy, uint32_t n_drives,
+                           const mh_drive *drives, const float *signals, uint32_t n_pickups, const mh_pickup *pickups, void *pickup_out, uint8_t *pickup_read,
+                           uint32_t n_junctions, const mh_junction *junctions, const float *approach, void *force_out, double *compliance_out, uint8_t *status_out) {
     if (!bank || !out || (n_impacts && !impacts) || (n_renderers && !deal_offset) || !out_gain || !listener_gain || (n_drives && (!drives || !signals))) return MH_EINVAL;
     if (n_pickups && (!pickups || !pickup_out || !pickup_read)) return MH_EINVAL;
+    if (n_junctions && (!junctions || !approach || !force_out || !compliance_out || !status_out)) return MH_EINVAL;
     if (n_renderers && deal_offset[n_renderers] && (!deal_objects || !render_count || !tuned_count || !object_energy || !object_live || !object_silenced)) return MH_EINVAL;
     if (frames == 0) return MH_OK;
     try {
@@ -1099,11 +1370,20 @@ int mh_bank_render_read(mh_bank *bank, uint32_t frames, float click_gain, uint32
         HIP_CHECK(hipSetDevice(bank->ctx->device));
         auto go = [&](auto &B) {
             render_impl(B, frames, click_gain, n_impacts, impacts, n_renderers, deal_offset, deal_objects, render_count, tuned_count, out_gain, listener_gain, out, object_energy,
-                        object_live, object_silenced, object_modal_energy, n_drives, drives, signals, n_pickups, pickups, pickup_out, pickup_read);
+                        object_live, object_silenced, object_modal_energy, n_drives, drives, signals, n_pickups, pickups, pickup_out, pickup_read, n_junctions, junctions, approach,
+                        force_out, compliance_out, status_out);
         };
         if (bank->dbl) go(*bank->d); else go(*bank->f);
         return MH_OK;
     } catch (const std::exception &e) { return mh_guard(bank->ctx, e); }
+}
+int mh_bank_render_read(mh_bank *bank, uint32_t frames, float click_gain, uint32_t n_impacts, mh_impact *impacts, uint32_t n_renderers, const uint32_t *deal_offset,
+                        const uint32_t *deal_objects, const uint32_t *render_count, const uint32_t *tuned_count, const float *out_gain, const float *listener_gain,
+                        void *out, double *object_energy, uint32_t *object_live, uint8_t *object_silenced, double *object_modal_energy, uint32_t n_drives,
+                        const mh_drive *drives, const float *signals, uint32_t n_pickups, const mh_pickup *pickups, void *pickup_out, uint8_t *pickup_read) {
+    return mh_bank_render_coupled(bank, frames, click_gain, n_impacts, impacts, n_renderers, deal_offset, deal_objects, render_count, tuned_count, out_gain, listener_gain, out,
+                                  object_energy, object_live, object_silenced, object_modal_energy, n_drives, drives, signals, n_pickups, pickups, pickup_out, pickup_read, 0, nullptr,
+                                  nullptr, nullptr, nullptr, nullptr);
 }
 int mh_bank_render_driven(mh_bank *bank, uint32_t frames, float click_gain, uint32_t n_impacts, mh_impact *impacts, uint32_t n_renderers, const uint32_t *deal_offset,
                           const uint32_t *deal_objects, const uint32_t *render_count, const uint32_t *tuned_count, const float *out_gain, const float *listener_gain,
@@ -1120,6 +1400,7 @@ int mh_bank_render(mh_bank *bank, uint32_t frames, float click_gain, uint32_t n_
 }
 uint32_t mh_drive_struct_size(void) { return uint32_t(sizeof(mh_drive)); }
 uint32_t mh_pickup_struct_size(void) { return uint32_t(sizeof(mh_pickup)); }
+uint32_t mh_junction_struct_size(void) { return uint32_t(sizeof(mh_junction)); }
 int mh_bank_read_state(const mh_bank *bank, uint32_t first, uint32_t count, double *state_re, double *state_im) {
     if (!bank || (count && (!state_re || !state_im))) return MH_EINVAL;
     try {

@@ -94,6 +94,23 @@ __device__ __forceinline__ double mh_wave_sum(double x) { // over the 64 lanes
     x = mh_row_sum(x);
     return (mh_lane_value(x, 0) + mh_lane_value(x, 16)) + (mh_lane_value(x, 32) + mh_lane_value(x, 48));
 }
+// The same tree on floats (the fp32 resonator bank's junction sums, mh_bank.hip): one DPP move per stage.
+template <int CTRL> __device__ __forceinline__ float mh_dpp_move(float x) {
+    const int b = __float_as_int(x);
+    return __int_as_float(__builtin_amdgcn_update_dpp(b, b, CTRL, 0xF, 0xF, false));
+}
+__device__ __forceinline__ float mh_row_sum(float x) { // over each aligned group of sixteen lanes
+    x += mh_dpp_move<MH_DPP_QUAD_XOR1>(x);
+    x += mh_dpp_move<MH_DPP_QUAD_XOR2>(x);
+    x += mh_dpp_move<MH_DPP_ROW_HALF_MIRROR>(x);
+    x += mh_dpp_move<MH_DPP_ROW_MIRROR>(x);
+    return x;
+}
+__device__ __forceinline__ float mh_lane_value(float x, int lane) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), lane)); }
+__device__ __forceinline__ float mh_wave_sum(float x) { // over the 64 lanes
+    x = mh_row_sum(x);
+    return (mh_lane_value(x, 0) + mh_lane_value(x, 16)) + (mh_lane_value(x, 32) + mh_lane_value(x, 48));
+}
 // 1 / x and (sqrt x, 1 / sqrt x) from the hardware's estimates (v_rcp_f64, v_rsq_f64: ~26 bits) and two Newton / Goldschmidt steps: a dozen
 // dependent instructions where the IEEE division and square root sequences take thirty to forty each.  For the serial stretches of the
 // one-workgroup dense kernels (a pivot, a Householder reflector, a Cholesky column per step), where that latency is the step's time.

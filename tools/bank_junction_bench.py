@@ -1,0 +1,200 @@
+"""Junction benchmark of the resonator bank: `objects` x 256 modes at 48 kHz, 512-frame blocks, fp32, one drive on every object in every
+block (every object renders its tuned set), J contact junctions (Scene.render_coupled), J = 0, 1, 16, 64, one- and two-sided, K C = 10,
+the exciter dipping in and out of the surface.
+
+    python tools/bank_junction_bench.py --junctions 16 --sides 2             one measurement, one JSON line
+    python tools/bank_junction_bench.py --entry replay --junctions 16 --sides 2 --forces F [--tree T]
+                                                                             the same scene through render_driven with the force rows
+                                                                             saved in F (by a --save-forces run) replayed as drives: the
+                                                                             open-loop cost of the same excitation, on this tree or on a
+                                                                             built checkout T (the parent commit has no render_coupled)
+    python tools/bank_junction_bench.py --against T [--runs 3]               the whole comparison with a built checkout T of the parent
+                                                                             commit, interleaved, every run a fresh process
+                                                                             -> profiles/bank_junctions.json
+
+The comparison also runs the unchanged tools/bank_bench.py of both trees (all_live.ms_per_block).  Kernel times per block are the
+library's kernel-class timers: class 2 the resonator kernel of the objects off the junctions, class 6 the coupled kernel.  The coupled
+kernel is one workgroup per junction running a serial chain per frame; `coupled_cycles_per_frame` is its time over the block's frames at
+the 2.4 GHz engine clock."""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SR, BLOCK, POINTS, MODES = 48000.0, 512, 4, 256
+ENGINE_MHZ = 2400.0
+JUNCTIONS = (0, 1, 16, 64)
+NORMAL = (0.25, -1.0, 0.5)
+
+
+def sides_of(j, sides):
+    """The objects of junction j: j itself (one-sided), or 2j and 2j + 1."""
+    return (j,) if sides == 1 else (2 * j, 2 * j + 1)
+
+
+def measure(tree, entry, junctions, sides, objects, blocks, renderers, forces_path, save_forces):
+    sys.path.insert(0, tree)
+    from mesheditor_amd import bank as hipbank
+    from tools import bank_bench
+    assert junctions * sides <= objects
+    sc = bank_bench.build(objects, MODES, renderers)
+    out = np.zeros(BLOCK, np.float32)
+    drives = [hipbank.Drive(o, o % POINTS, 1.0, 0.5, 0.125) for o in range(objects)]
+    signals = (0.01 * np.random.default_rng(1).standard_normal((objects, BLOCK))).astype(np.float32)
+    peak_force, kept = [0.0], []
+    if entry == "coupled":
+        side = lambda o, sign: hipbank.JunctionSide.of(o, 1, (1.0, 0.0, 0.0), tuple(sign * v for v in NORMAL), 2.0)
+        make = lambda k: (hipbank.Junction * max(junctions, 1))(*[hipbank.Junction.of(side(sides_of(j, sides)[0], 1.0), side(sides_of(j, sides)[1], -1.0) if sides == 2 else None, k[j])
+                                                                    for j in range(junctions)])
+        rows = (hipbank.Drive * objects)(*drives)
+        none = np.zeros((junctions, BLOCK), np.float32)
+        # the compliances and the size of the free deflection, from two blocks with K = 0
+        comp = np.ones(junctions)
+        if junctions:
+            _, _, _, comp, status = sc.render_coupled(out, rows, signals, [], make([0.0] * junctions), none)
+            assert (status == 1).all() and (comp > 0).all()
+            picks = (hipbank.Pickup * junctions)(*[hipbank.Pickup.of(sides_of(j, sides)[0], 1, (1.0, 0.0, 0.0), NORMAL, 2.0, 1) for j in range(junctions)])
+            reads, _ = sc.render_read(out, rows, signals, picks)
+            free = np.abs(reads).max(axis=1)
+            t = np.arange(BLOCK)
+            u = np.array([(free[j] * (np.sin(2 * np.pi * t / 256.0 + j) + 0.1)).astype(np.float32) for j in range(junctions)])  # periodic in the block
+        contacts = make([10.0 / c for c in comp]) if junctions else []
+        u = u if junctions else none
+
+        def block():
+            _, _, forces, _, status = sc.render_coupled(out, rows, signals, [], contacts, u)
+            if junctions:
+                assert (status == 1).all()
+                peak_force[0] = max(peak_force[0], float(np.abs(forces).max()))
+                kept[:] = [forces]
+    else:
+        replayed = np.load(forces_path) if junctions else np.zeros((0, BLOCK), np.float32)
+        assert replayed.shape == (junctions, BLOCK)
+        for j in range(junctions):
+            for i, o in enumerate(sides_of(j, sides)):
+                sign = 1.0 if i == 0 else -1.0
+                drives.append(hipbank.Drive(o, 1, *(sign * v for v in NORMAL)))
+        rows = (hipbank.Drive * len(drives))(*drives)
+        signals = np.concatenate([signals] + [replayed[j:j + 1] for j in range(junctions) for _ in range(sides)]).astype(np.float32)
+
+        def block():
+            sc.render_driven(out, rows, signals)
+    for _ in range(8):
+        block()
+    sc.time_kernels(True)
+    times, peak = [], 0.0
+    for _ in range(blocks):
+        out[:] = 0
+        t0 = time.perf_counter()
+        block()
+        times.append(time.perf_counter() - t0)
+        peak = max(peak, float(np.abs(out).max()))
+    k = sc.kernel_stats(2)
+    kj = sc.kernel_stats(6) if entry == "coupled" else {"launches": 0, "total_ms": 0.0}
+    sc.time_kernels(False)
+    tuned, live, ring = sc.object_state()
+    assert np.isfinite(peak) and peak > 0 and (ring == 1).all() and int(live.sum()) == objects * MODES
+    assert entry != "coupled" or junctions == 0 or (np.isfinite(peak_force[0]) and peak_force[0] > 0)
+    if save_forces and junctions:
+        np.save(save_forces, kept[0].astype(np.float32))
+    sc.close()
+    t = np.array(times)
+    coupled_us = 1e3 * kj["total_ms"] / max(1, kj["launches"])
+    return {"entry": entry, "junctions": junctions, "sides": sides, "objects": objects, "modes_per_object": MODES, "blocks": blocks, "ms_per_block": 1e3 * float(t.mean()),
+            "ms_per_block_median": 1e3 * float(np.median(t)), "ms_per_block_p99": 1e3 * float(np.quantile(t, 0.99)), "kernel_us_per_block": 1e3 * k["total_ms"] / max(1, k["launches"]),
+            "coupled_kernel_us_per_block": coupled_us, "coupled_us_per_frame": coupled_us / BLOCK, "coupled_cycles_per_frame": coupled_us / BLOCK * ENGINE_MHZ,
+            "real_time_ms_per_block": 1e3 * BLOCK / SR}
+
+
+def child(args, limit=300):
+    """One measurement in a fresh process under a time limit; anything but a clean exit ends the comparison."""
+    p = subprocess.run(["timeout", "-k", "10", str(limit), sys.executable] + args, capture_output=True, text=True)
+    if p.returncode != 0:
+        sys.stderr.write(p.stdout[-2000:] + p.stderr[-4000:])
+        raise SystemExit("a measurement ended with status %d: %s" % (p.returncode, " ".join(args)))
+    return json.loads(p.stdout.strip().splitlines()[-1])
+
+
+def compare(parent, runs, objects, blocks, renderers, out_path, all_live):
+    me = os.path.abspath(__file__)
+    common = ["--objects", str(objects), "--blocks", str(blocks), "--renderers", str(renderers)]
+    result = {"workload": f"{objects} objects x {MODES} modes @48k, {BLOCK}-frame blocks, fp32, {renderers} renderers, one drive on every object and J junctions (K C = 10) in every block",
+              "runs_each": runs, "all_live": {"parent": [], "new": []}, "j0": {"parent_driven": [], "new_coupled": []}, "junctions": {}}
+
+    def save():
+        os.makedirs(os.path.dirname(out_path), exist_ok=True)
+        with open(out_path, "w") as f:
+            json.dump(result, f, indent=1)
+    q = subprocess.run(["timeout", "-k", "10", "300", sys.executable, "-c", "import torch; p = torch.cuda.get_device_properties(0); print(p.name, p.gcnArchName, '%d CUs' % p.multi_processor_count, '|', torch.version.hip)"], capture_output=True, text=True)
+    if q.returncode != 0:
+        raise SystemExit("no GPU to measure on: " + q.stderr[-2000:])
+    result["device"], result["hip"] = (v.strip() for v in q.stdout.strip().splitlines()[-1].split("|"))
+    for _ in range(runs if all_live else 0):  # the unchanged all-live benchmark, both trees, interleaved
+        for name, tree in (("parent", parent), ("new", HERE)):
+            r = child([os.path.join(tree, "tools", "bank_bench.py")], 600)
+            result["all_live"][name].append({"ms_per_block": r["all_live"]["ms_per_block"], "kernel_us_per_block": r["all_live"]["kernel_us_per_block"],
+                                             "steady_ms_per_block": r["steady_state"]["ms_per_block"]})
+            save()
+    scratch = tempfile.mkdtemp(prefix="junction_forces_")
+    for _ in range(runs):
+        result["j0"]["parent_driven"].append(child([me, "--entry", "replay", "--junctions", "0", "--tree", parent] + common))
+        result["j0"]["new_coupled"].append(child([me, "--entry", "coupled", "--junctions", "0"] + common))
+        save()
+        for sides in (1, 2):
+            for j in JUNCTIONS[1:]:
+                forces = os.path.join(scratch, "f_%d_%d.npy" % (j, sides))
+                row = result["junctions"].setdefault("%d x %d-sided" % (j, sides), {"coupled": [], "parent_replay": []})
+                row["coupled"].append(child([me, "--entry", "coupled", "--junctions", str(j), "--sides", str(sides), "--save-forces", forces] + common))
+                row["parent_replay"].append(child([me, "--entry", "replay", "--junctions", str(j), "--sides", str(sides), "--forces", forces, "--tree", parent] + common))
+                save()
+
+    def med(rows, key):
+        return float(np.median([r[key] for r in rows])) if rows else None
+    a, j0 = result["all_live"], result["j0"]
+    spread = lambda rows, key: (max(r[key] for r in rows) / min(r[key] for r in rows)) if rows else None
+    result["summary"] = {
+        "all_live_parent_ms": [r["ms_per_block"] for r in a["parent"]], "all_live_new_ms": [r["ms_per_block"] for r in a["new"]],
+        "all_live_parent_spread_max_over_min": spread(a["parent"], "ms_per_block"),
+        "all_live_new_median_over_parent_median": (med(a["new"], "ms_per_block") / med(a["parent"], "ms_per_block")) if a["parent"] else None,
+        "j0_parent_driven_ms": [r["ms_per_block"] for r in j0["parent_driven"]], "j0_new_coupled_ms": [r["ms_per_block"] for r in j0["new_coupled"]],
+        "j0_parent_spread_max_over_min": spread(j0["parent_driven"], "ms_per_block"),
+        "j0_new_median_over_parent_median": med(j0["new_coupled"], "ms_per_block") / med(j0["parent_driven"], "ms_per_block"),
+        "real_time_ms_per_block": 1e3 * BLOCK / SR,
+        "junctions": {name: {"coupled_ms_per_block": med(row["coupled"], "ms_per_block"), "parent_replay_ms_per_block": med(row["parent_replay"], "ms_per_block"),
+                             "coupled_kernel_us_per_block": med(row["coupled"], "coupled_kernel_us_per_block"), "main_kernel_us_per_block": med(row["coupled"], "kernel_us_per_block"),
+                             "parent_replay_kernel_us_per_block": med(row["parent_replay"], "kernel_us_per_block"),
+                             "coupled_cycles_per_frame": med(row["coupled"], "coupled_cycles_per_frame")} for name, row in result["junctions"].items()}}
+    save()
+    print(json.dumps(result["summary"]))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--entry", choices=["coupled", "replay"], default="coupled")
+    ap.add_argument("--junctions", type=int, default=16)
+    ap.add_argument("--sides", type=int, choices=[1, 2], default=1)
+    ap.add_argument("--objects", type=int, default=128)
+    ap.add_argument("--blocks", type=int, default=1000)
+    ap.add_argument("--renderers", type=int, default=4)
+    ap.add_argument("--tree", default=HERE, help="built checkout whose library is measured (replay only on one without junctions)")
+    ap.add_argument("--forces", help="replay: the force rows a --save-forces run wrote")
+    ap.add_argument("--save-forces", help="coupled: write the last block's force rows here (.npy)")
+    ap.add_argument("--against", help="built checkout of the parent commit: run the whole comparison")
+    ap.add_argument("--runs", type=int, default=3)
+    ap.add_argument("--no-all-live", action="store_true", help="skip tools/bank_bench.py of both trees")
+    ap.add_argument("--out", default=os.path.join(HERE, "profiles", "bank_junctions.json"))
+    a = ap.parse_args()
+    if a.against:
+        compare(os.path.abspath(a.against), a.runs, a.objects, a.blocks, a.renderers, a.out, not a.no_all_live)
+    else:
+        print(json.dumps(measure(os.path.abspath(a.tree), a.entry, a.junctions, a.sides, a.objects, a.blocks, a.renderers, a.forces, a.save_forces)))
+
+
+if __name__ == "__main__":
+    main()
