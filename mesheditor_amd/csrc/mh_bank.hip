@@ -84,6 +84,11 @@ __global__ void k_bank_forces(ImpactDev<Real> *__restrict__ impacts, uint32_t n_
     back[i] = {left, phase_re, phase_im, z1, z2}; // what the host takes back, written where it reads it (pinned memory)
 }
 
+// A float sample as the bank takes it from a caller: one that is not finite is 0.
+template<typename Real> __device__ __forceinline__ Real finite_or_zero(float v) {
+    return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u ? Real(v) : Real(0); // exponent all ones: Inf or NaN
+}
+
 // Force rows of the caller's drives (mh_bank_render_driven): the float signals become `Real` rows that follow the impacts' rows in
 // `force`, so the resonator kernel addresses both kinds alike.  A sample that is not finite is rendered as 0 -- one NaN would ring in
 // the state for ever.  No curve, no click filter, no state: a drive lasts for the block it was passed with.
@@ -91,8 +96,7 @@ template<typename Real>
 __global__ void __launch_bounds__(256) k_bank_drive_rows(const float *__restrict__ signals, size_t n, Real *__restrict__ rows) {
     const size_t i = size_t(blockIdx.x) * 256 + threadIdx.x;
     if (i >= n) return;
-    const float v = signals[i];
-    rows[i] = (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u ? Real(v) : Real(0); // exponent all ones: Inf or NaN
+    rows[i] = finite_or_zero<Real>(signals[i]);
 }
 
 template<typename Real> struct BankCols {
@@ -116,18 +120,6 @@ __device__ __forceinline__ double lane_bcast(double v, uint32_t l) {
     const long long b = __double_as_longlong(v);
     const int lo = __builtin_amdgcn_readlane(int(b), int(l)), hi = __builtin_amdgcn_readlane(int(b >> 32), int(l));
     return __longlong_as_double((long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo));
-}
-// Sum of the 8 lanes of a chunk, lane 0..7 in order, valid in the chunk's first lane (ModalAudio.cpp:121-128).
-template<typename Real> __device__ __forceinline__ Real chunk_sum_in_order(Real term) {
-    Real acc = Real(0) + term;
-    acc += row_shl<1>(term);
-    acc += row_shl<2>(term);
-    acc += row_shl<3>(term);
-    acc += row_shl<4>(term);
-    acc += row_shl<5>(term);
-    acc += row_shl<6>(term);
-    acc += row_shl<7>(term);
-    return acc;
 }
 
 // One wave = 128 consecutive modes of one dealt object = 16 chunks, two adjacent modes per lane: the resonator arithmetic is
@@ -154,10 +146,123 @@ template<typename Real> __device__ __forceinline__ Real chunk_sum_in_order(Real 
 // Waves of objects without a pickup take no part in any of it.
 constexpr int MODES_PER_WAVE = 2 * WAVE;
 constexpr uint32_t IMP_REG = 2, ROWS_REG = 8, ROWS_MAX = 12;
-template<typename Real> struct PickupDev { // a pickup the block reads: its record, and where its partial rows begin
-    uint32_t p0, p1, p2, advance;
+constexpr uint32_t PITCH = MODES_PER_WAVE + 2, CHUNKS = MODES_PER_WAVE / LANES; // a turn-around tile's row; chunks of a wave
+constexpr uint32_t waves_of(uint32_t count) { return (count + MODES_PER_WAVE - 1) / MODES_PER_WAVE; }
+template<typename Real> using PairOf = Real __attribute__((ext_vector_type(2)));
+
+// A lane's share of a wave: two adjacent modes of one dealt object -- state, coefficients and output phases, zero where the object
+// renders no such mode -- and where the wave's chunks go.  `count` is what the wave renders of the object: 0 for a wave that holds
+// nothing (nothing is loaded or stored for it).
+template<typename Real> struct WaveLane {
+    uint32_t k0, stride, shape0, k; // the object's first mode, its mode count, its first shape entry; this lane's modes: k, k + 1
+    bool live[2];
+    uint32_t chunk0, chunks_here; // global index of this wave's first chunk; how many of its chunks hold a rendered mode
+    PairOf<Real> z_re, z_im, c_re, c_im, p_re, p_im;
+    Real mix_gain;
+};
+template<typename Real>
+__device__ __forceinline__ WaveLane<Real> load_wave(const BankCols<Real> &b, const uint32_t *deal_objects, const uint32_t *chunk_base, const Real *out_gain,
+                                                    const Real *listener_gain, uint32_t dealt, uint32_t first_mode, uint32_t count, uint32_t lane) {
+    const uint32_t o = deal_objects[dealt];
+    WaveLane<Real> w{};
+    w.k0 = b.mode_offset[o], w.stride = b.mode_count[o], w.shape0 = b.shape_offset[o];
+    w.k = first_mode + 2 * lane;
+    w.live[0] = w.k < count, w.live[1] = w.k + 1 < count;
+    w.chunk0 = chunk_base[dealt] + first_mode / LANES;
+    w.chunks_here = min(CHUNKS, (count - first_mode + LANES - 1) / LANES);
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+        if (w.live[h]) {
+            w.z_re[h] = b.state_re[w.k0 + w.k + h]; w.z_im[h] = b.state_im[w.k0 + w.k + h];
+            w.c_re[h] = b.coeff_re[w.k0 + w.k + h]; w.c_im[h] = b.coeff_im[w.k0 + w.k + h];
+            w.p_im[h] = b.phase_im[w.k0 + w.k + h]; w.p_re[h] = b.phase_re[w.k0 + w.k + h];
+        }
+    w.mix_gain = out_gain[o] * listener_gain[o];
+    return w;
+}
+// Gain pair of a force row -- an impact or a drive -- on this lane's modes (ImpactGainRow, ModalAudio.h:182-188); zero on padded modes.
+template<typename Real> __device__ __forceinline__ Real row_gain_of(const BankCols<Real> &b, const WaveLane<Real> &w, const ImpactDev<Real> &im, int h) { // w.live[h] only
+    const uint32_t base = w.shape0 + im.ex_pos * w.stride + w.k + h;
+    return b.rad_gain[w.k0 + w.k + h] * (b.shape_x[base] * im.jx + b.shape_y[base] * im.jy + b.shape_z[base] * im.jz);
+}
+template<typename Real> __device__ __forceinline__ PairOf<Real> row_gain(const BankCols<Real> &b, const WaveLane<Real> &w, const ImpactDev<Real> &im) {
+    return {w.live[0] ? row_gain_of(b, w, im, 0) : Real(0), w.live[1] ? row_gain_of(b, w, im, 1) : Real(0)};
+}
+// Three shape points blended along a direction: where a pickup reads and where a junction's side touches.  Per mode
+// along = (w0 s[p0] + w1 s[p1] + w2 s[p2]) . n and read = scale * along * DeflectionGain; a read that looks `advance` free steps ahead
+// (0, 1 or 2) has the gains of that row of ModeReadGains::Fill: read, 0; read c_re, read c_im; read (c_re^2 - c_im^2), read (2 c_re c_im).
+template<typename Real> struct BlendDev {
+    uint32_t p0, p1, p2;
     Real w0, w1, w2, nx, ny, nz, scale;
-    uint32_t first_row;
+};
+template<typename Real> struct BlendRead {
+    Real along, read;
+};
+template<typename Real>
+__device__ __forceinline__ BlendRead<Real> blend_read(const BankCols<Real> &b, const WaveLane<Real> &w, const BlendDev<Real> &p, const Real *defl_gain, int h) { // w.live[h] only
+    const uint32_t i0 = w.shape0 + p.p0 * w.stride + w.k + h, i1 = w.shape0 + p.p1 * w.stride + w.k + h, i2 = w.shape0 + p.p2 * w.stride + w.k + h;
+    const Real sx = p.w0 * b.shape_x[i0] + p.w1 * b.shape_x[i1] + p.w2 * b.shape_x[i2];
+    const Real sy = p.w0 * b.shape_y[i0] + p.w1 * b.shape_y[i1] + p.w2 * b.shape_y[i2];
+    const Real sz = p.w0 * b.shape_z[i0] + p.w1 * b.shape_z[i1] + p.w2 * b.shape_z[i2];
+    const Real along = sx * p.nx + sy * p.ny + sz * p.nz;
+    return {along, p.scale * along * defl_gain[w.k0 + w.k + h]};
+}
+template<typename Real> struct ReadGains {
+    Real im, re; // on Im z and on Re z
+};
+template<typename Real> __device__ __forceinline__ ReadGains<Real> read_gains(Real read, Real cr, Real ci, uint32_t advance) {
+    return {advance == 0 ? read : advance == 1 ? read * cr : read * (cr * cr - ci * ci), advance == 0 ? Real(0) : advance == 1 ? read * ci : read * (Real(2) * cr * ci)};
+}
+// The turn-around's sums, after a tile's samples and the caller's barrier: lane = (chunk group, sample) -- sample lane % TS of the
+// WAVE / TS groups' chunks -- adds each of its chunks' 8 terms in mode order 0..7 from the tile [sample][mode] and stores the partial signal.
+// (The loops sit in a lambda called on the spot: hipcc unrolls a lambda's loops before it inlines it and a named function's after, and in
+// the second form every mode kernel takes two more vector registers -- profiles/bank_refactor_resources.txt.)
+template<uint32_t TS, typename Real>
+__device__ __forceinline__ void chunk_sums(const Real *tile, const WaveLane<Real> &w, uint32_t lane, uint32_t s0, uint32_t sn, Real *partial, uint32_t frames) {
+    constexpr uint32_t PER_GROUP = CHUNKS / (WAVE / TS);
+    const uint32_t group = lane / TS, ts = lane % TS;
+    if (ts >= sn) return;
+    [&] {
+        const Real *row = tile + ts * PITCH + group * (PER_GROUP * LANES);
+#pragma unroll
+        for (uint32_t c = 0; c < PER_GROUP; ++c) {
+            Real acc = 0;
+#pragma unroll
+            for (uint32_t l = 0; l < LANES; l += 2) {
+                const PairOf<Real> v = *reinterpret_cast<const PairOf<Real> *>(row + c * LANES + l);
+                acc += v.x;
+                acc += v.y;
+            }
+            const uint32_t chunk = PER_GROUP * group + c;
+            if (chunk < w.chunks_here) partial[size_t(w.chunk0 + chunk) * frames + s0 + ts] = acc * w.mix_gain;
+        }
+    }();
+}
+// A wave's epilogue: the states go back, and every chunk's energy is written.
+template<typename Real> __device__ __forceinline__ void store_wave(const BankCols<Real> &b, const WaveLane<Real> &w, uint32_t lane, Real *chunk_energy) {
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+        if (w.live[h]) {
+            b.state_re[w.k0 + w.k + h] = w.z_re[h];
+            b.state_im[w.k0 + w.k + h] = w.z_im[h];
+        }
+    // chunk energy: sum over the chunk's valid modes in order (padded modes hold zero state); a chunk is four lanes' pairs
+    const PairOf<Real> e = w.z_re * w.z_re + w.z_im * w.z_im;
+    const Real e0 = w.live[0] ? e.x : Real(0), e1 = w.live[1] ? e.y : Real(0);
+    Real chunk = Real(0) + e0;
+    chunk += e1;
+    chunk += row_shl<1>(e0);
+    chunk += row_shl<1>(e1);
+    chunk += row_shl<2>(e0);
+    chunk += row_shl<2>(e1);
+    chunk += row_shl<3>(e0);
+    chunk += row_shl<3>(e1);
+    if ((lane & (LANES / 2 - 1)) == 0 && lane / (LANES / 2) < w.chunks_here) chunk_energy[w.chunk0 + lane / (LANES / 2)] = chunk;
+}
+
+template<typename Real> struct PickupDev { // a pickup the block reads: its record, and where its partial rows begin
+    BlendDev<Real> at;
+    uint32_t advance, first_row;
 };
 template<typename Real> struct ReadArgs {
     const Real *defl_gain; // DeflectionGain column
@@ -174,50 +279,24 @@ __device__ __forceinline__ void bank_modes(const BankCols<Real> &b, const WaveDe
                                            const Real *__restrict__ out_gain, const Real *__restrict__ listener_gain, uint32_t frames,
                                            Real *__restrict__ partial, Real *__restrict__ chunk_energy, Real *__restrict__ gain_scratch, uint32_t max_imp,
                                            const ReadArgs<Real> &rd = {}) {
-    typedef Real Pair __attribute__((ext_vector_type(2)));
-    constexpr uint32_t TS = 32, PITCH = MODES_PER_WAVE + 2, CHUNKS = MODES_PER_WAVE / LANES;
+    typedef PairOf<Real> Pair;
+    constexpr uint32_t TS = 32;
     __shared__ __attribute__((aligned(16))) Real s_term[TS * PITCH];
     const WaveDesc wd = waves[blockIdx.x];
     const uint32_t lane = threadIdx.x;
-    const uint32_t o = deal_objects[wd.dealt];
-    const uint32_t count = render_count[wd.dealt];
-    const uint32_t k0 = b.mode_offset[o], stride = b.mode_count[o], shape0 = b.shape_offset[o];
-    const uint32_t k = wd.first_mode + 2 * lane; // this lane's modes: k, k + 1
-    const bool live[2] = {k < count, k + 1 < count};
-    const uint32_t chunk0 = chunk_base[wd.dealt] + wd.first_mode / LANES; // global index of this wave's first chunk
-    const uint32_t chunks_here = min(CHUNKS, (count - wd.first_mode + LANES - 1) / LANES);
-    Pair z_re = {0, 0}, z_im = {0, 0}, c_re = {0, 0}, c_im = {0, 0}, p_re = {0, 0}, p_im = {0, 0};
-#pragma unroll
-    for (int h = 0; h < 2; ++h)
-        if (live[h]) {
-            z_re[h] = b.state_re[k0 + k + h]; z_im[h] = b.state_im[k0 + k + h];
-            c_re[h] = b.coeff_re[k0 + k + h]; c_im[h] = b.coeff_im[k0 + k + h];
-            p_im[h] = b.phase_im[k0 + k + h]; p_re[h] = b.phase_re[k0 + k + h];
-        }
+    WaveLane<Real> w = load_wave(b, deal_objects, chunk_base, out_gain, listener_gain, wd.dealt, wd.first_mode, render_count[wd.dealt], lane);
     const uint32_t i0 = imp_ptr[wd.dealt], n_imp = imp_ptr[wd.dealt + 1] - i0;
-    // Hoisted impact gains (ImpactGainRow, ModalAudio.h:182-188); zero on padded modes.  The first IMP_REG impacts of
-    // the object live in registers, further ones (rare) in a scratch row.
+    // Hoisted impact gains (row_gain).  The first IMP_REG impacts of the object live in registers, further ones (rare) in a scratch row.
     Pair g_reg[IMP_REG] = {};
     uint32_t f_row[IMP_REG] = {};
     Real *g_mem = gain_scratch + size_t(blockIdx.x) * max_imp * MODES_PER_WAVE;
     const bool many_rows = MANY && (!READ || rd.rows_loop) && n_imp > IMP_REG && n_imp <= ROWS_MAX; // run_rows computes its own gains
-    auto gain_of = [&](uint32_t t) {
-        Pair g = {0, 0};
-        const ImpactDev<Real> &im = impacts[imp_idx[i0 + t]];
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-            if (live[h]) {
-                const uint32_t base = shape0 + im.ex_pos * stride + k + h;
-                g[h] = b.rad_gain[k0 + k + h] * (b.shape_x[base] * im.jx + b.shape_y[base] * im.jy + b.shape_z[base] * im.jz);
-            }
-        return g;
-    };
+    auto gain_of = [&](uint32_t t) { return row_gain(b, w, impacts[imp_idx[i0 + t]]); };
     for (uint32_t t = 0; t < (many_rows ? 0u : n_imp); ++t) {
         const Pair g = gain_of(t);
         if (t < IMP_REG) { g_reg[t] = g; f_row[t] = imp_idx[i0 + t]; }
         else *reinterpret_cast<Pair *>(g_mem + size_t(t) * MODES_PER_WAVE + 2 * lane) = g;
     }
-    const Real mix_gain = out_gain[o] * listener_gain[o];
     const uint32_t half = lane / TS, ts = lane % TS; // turn-around mapping: chunks 8*half .. 8*half+7 of sample ts
     // pickups of this wave's object: the state tiles and the staged gains (see above); none of it exists in the other entries
     __shared__ __attribute__((aligned(16))) Real s_zim[READ ? TS * PITCH : 1], s_zre[READ ? TS * PITCH : 1];
@@ -231,15 +310,10 @@ __device__ __forceinline__ void bank_modes(const BankCols<Real> &b, const WaveDe
             Pair g_im = {0, 0}, g_re = {0, 0};
 #pragma unroll
             for (int h = 0; h < 2; ++h)
-                if (live[h]) {
-                    const uint32_t a = shape0 + pk.p0 * stride + k + h, bb = shape0 + pk.p1 * stride + k + h, c = shape0 + pk.p2 * stride + k + h;
-                    const Real sx = pk.w0 * b.shape_x[a] + pk.w1 * b.shape_x[bb] + pk.w2 * b.shape_x[c];
-                    const Real sy = pk.w0 * b.shape_y[a] + pk.w1 * b.shape_y[bb] + pk.w2 * b.shape_y[c];
-                    const Real sz = pk.w0 * b.shape_z[a] + pk.w1 * b.shape_z[bb] + pk.w2 * b.shape_z[c];
-                    const Real read = pk.scale * (sx * pk.nx + sy * pk.ny + sz * pk.nz) * rd.defl_gain[k0 + k + h];
-                    const Real cr = c_re[h], ci = c_im[h];
-                    g_im[h] = pk.advance == 0 ? read : pk.advance == 1 ? read * cr : read * (cr * cr - ci * ci);
-                    g_re[h] = pk.advance == 0 ? Real(0) : pk.advance == 1 ? read * ci : read * (Real(2) * cr * ci);
+                if (w.live[h]) {
+                    const ReadGains<Real> g = read_gains(blend_read(b, w, pk.at, rd.defl_gain, h).read, w.c_re[h], w.c_im[h], pk.advance);
+                    g_im[h] = g.im;
+                    g_re[h] = g.re;
                 }
             *reinterpret_cast<Pair *>(s_pick + (2 * q) * MODES_PER_WAVE + 2 * lane) = g_im;
             *reinterpret_cast<Pair *>(s_pick + (2 * q + 1) * MODES_PER_WAVE + 2 * lane) = g_re;
@@ -267,34 +341,22 @@ __device__ __forceinline__ void bank_modes(const BankCols<Real> &b, const WaveDe
 
     // one sample of this lane's two resonators; their output terms go to the turn-around tile
     auto step = [&](const Pair &excite, uint32_t ds) {
-        const Pair re = z_re * c_re - z_im * c_im + excite;
-        z_im = z_re * c_im + z_im * c_re;
-        z_re = re;
-        *reinterpret_cast<Pair *>(s_term + ds * PITCH + 2 * lane) = p_im * z_im + p_re * re;
+        const Pair re = w.z_re * w.c_re - w.z_im * w.c_im + excite;
+        w.z_im = w.z_re * w.c_im + w.z_im * w.c_re;
+        w.z_re = re;
+        *reinterpret_cast<Pair *>(s_term + ds * PITCH + 2 * lane) = w.p_im * w.z_im + w.p_re * re;
         if constexpr (READ)
             if (n_pick) {
-                *reinterpret_cast<Pair *>(s_zim + ds * PITCH + 2 * lane) = z_im;
+                *reinterpret_cast<Pair *>(s_zim + ds * PITCH + 2 * lane) = w.z_im;
                 *reinterpret_cast<Pair *>(s_zre + ds * PITCH + 2 * lane) = re;
             }
     };
     // after a tile's samples: every chunk's 8 terms added in mode order, sample ts of chunks 8*half .. 8*half+7 per lane
     auto turn_around = [&](uint32_t s0, uint32_t sn) {
         __syncthreads();
-        if (ts < sn) {
-            const Real *row = s_term + ts * PITCH + half * (CHUNKS / 2 * LANES);
-#pragma unroll
-            for (uint32_t c = 0; c < CHUNKS / 2; ++c) {
-                Real acc = 0;
-#pragma unroll
-                for (uint32_t l = 0; l < LANES; l += 2) {
-                    const Pair v = *reinterpret_cast<const Pair *>(row + c * LANES + l);
-                    acc += v.x;
-                    acc += v.y;
-                }
-                const uint32_t chunk = CHUNKS / 2 * half + c;
-                if (chunk < chunks_here) partial[size_t(chunk0 + chunk) * frames + s0 + ts] = acc * mix_gain;
-            }
-            if constexpr (READ) {
+        chunk_sums<TS>(s_term, w, lane, s0, sn, partial, frames);
+        if constexpr (READ) {
+            if (ts < sn) {
                 uint32_t q = 0;
                 for (; q + 4 <= n_pick; q += 4) read_group(std::integral_constant<uint32_t, 4>{}, q, s0);
                 if (n_pick - q == 3) read_group(std::integral_constant<uint32_t, 3>{}, q, s0);
@@ -405,25 +467,11 @@ __device__ __forceinline__ void bank_modes(const BankCols<Real> &b, const WaveDe
         else if (n_imp == 2) run(T2{}, std::false_type{});
         else run(T2{}, std::true_type{});
     }
-#pragma unroll
-    for (int h = 0; h < 2; ++h)
-        if (live[h]) {
-            b.state_re[k0 + k + h] = z_re[h];
-            b.state_im[k0 + k + h] = z_im[h];
-        }
-    // chunk energy: sum over the chunk's valid modes in order (padded modes hold zero state); a chunk is four lanes' pairs
-    const Pair e = z_re * z_re + z_im * z_im;
-    const Real e0 = live[0] ? e.x : Real(0), e1 = live[1] ? e.y : Real(0);
-    Real chunk = Real(0) + e0;
-    chunk += e1;
-    chunk += row_shl<1>(e0);
-    chunk += row_shl<1>(e1);
-    chunk += row_shl<2>(e0);
-    chunk += row_shl<2>(e1);
-    chunk += row_shl<3>(e0);
-    chunk += row_shl<3>(e1);
-    if ((lane & (LANES / 2 - 1)) == 0 && lane / (LANES / 2) < chunks_here) chunk_energy[chunk0 + lane / (LANES / 2)] = chunk;
+    store_wave(b, w, lane, chunk_energy);
 }
+// What every mode kernel takes, the coupled one below included (render_impl: launch_modes).  Separate parameters, not a struct: only a
+// kernel's own parameter can be __restrict__, and without it the coupled kernel loses a wave of occupancy in fp32 and spills scalar
+// registers in fp64 (its wave-uniform loads are no longer known to be unclobbered).
 #define BANK_MODES_PARAMS                                                                                                                                  \
     BankCols<Real> b, const WaveDesc *__restrict__ waves, const uint32_t *__restrict__ deal_objects, const uint32_t *__restrict__ render_count,          \
         const uint32_t *__restrict__ chunk_base, const uint32_t *__restrict__ imp_ptr, const uint32_t *__restrict__ imp_idx,                             \
@@ -453,8 +501,6 @@ __global__ void __launch_bounds__(256) k_bank_read_rows(const Real *__restrict__
     for (uint32_t r = 0; r < d.n_rows; ++r) acc += rows[size_t(d.first_row + r) * frames + s];
     out_host[size_t(blockIdx.y) * frames + s] = acc;
 }
-#undef BANK_MODES_PARAMS
-#undef BANK_MODES_ARGS
 
 // Contact junctions (mh_bank_render_coupled; contract in modalhip.h).  ONE WORKGROUP PER JUNCTION, one wave per 128
 // modes of each side (side a's waves first, then side b's), modes in registers two per lane as in bank_modes; the waves of a junction's
@@ -472,8 +518,8 @@ __global__ void __launch_bounds__(256) k_bank_read_rows(const Real *__restrict__
 // loads of forces and gains stay off the serial chain.
 constexpr uint32_t JUNCTION_WAVES = MH_JUNCTION_MODES / MODES_PER_WAVE;
 template<typename Real> struct JunctionSideDev {
-    uint32_t dealt, waves, p0, p1, p2, pad;
-    Real w0, w1, w2, nx, ny, nz, scale;
+    uint32_t dealt, waves;
+    BlendDev<Real> at;
 };
 template<typename Real> struct JunctionDev {
     JunctionSideDev<Real> side[2]; // side[1].waves = 0: one-sided
@@ -494,14 +540,9 @@ template<typename Real> size_t coupled_lds(uint32_t waves) {
 }
 __device__ __forceinline__ float fma_real(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 __device__ __forceinline__ double fma_real(double a, double b, double c) { return __builtin_fma(a, b, c); }
-template<typename Real>
-__global__ void __launch_bounds__(JUNCTION_WAVES *WAVE)
-    k_bank_modes_coupled(BankCols<Real> b, const uint32_t *__restrict__ deal_objects, const uint32_t *__restrict__ render_count, const uint32_t *__restrict__ chunk_base,
-                         const uint32_t *__restrict__ imp_ptr, const uint32_t *__restrict__ imp_idx, const ImpactDev<Real> *__restrict__ impacts,
-                         const Real *__restrict__ force, const Real *__restrict__ out_gain, const Real *__restrict__ listener_gain, uint32_t frames,
-                         Real *__restrict__ partial, Real *__restrict__ chunk_energy, Real *__restrict__ gain_scratch, uint32_t max_imp, CoupledArgs<Real> ca) {
-    typedef Real Pair __attribute__((ext_vector_type(2)));
-    constexpr uint32_t TS = coupled_tile<Real>(), PITCH = MODES_PER_WAVE + 2, CHUNKS = MODES_PER_WAVE / LANES, GROUPS = WAVE / TS, PER_GROUP = CHUNKS / GROUPS;
+template<typename Real> __global__ void __launch_bounds__(JUNCTION_WAVES *WAVE) k_bank_modes_coupled(BANK_MODES_PARAMS, CoupledArgs<Real> ca) { // (`waves`: the main launch's, not read here)
+    typedef PairOf<Real> Pair;
+    constexpr uint32_t TS = coupled_tile<Real>();
     extern __shared__ __attribute__((aligned(16))) unsigned char coupled_mem[];
     Real *s_slot = reinterpret_cast<Real *>(coupled_mem); // [2][JUNCTION_WAVES]
     const uint32_t wave = threadIdx.x / WAVE, lane = threadIdx.x % WAVE;
@@ -511,30 +552,17 @@ __global__ void __launch_bounds__(JUNCTION_WAVES *WAVE)
     const bool active = wave < n_w;
     const JunctionSideDev<Real> S = J.side[active && wave >= waves_a ? 1 : 0];
     const uint32_t first_mode = active ? (wave - (wave >= waves_a ? waves_a : 0u)) * MODES_PER_WAVE : 0u;
-    const uint32_t o = deal_objects[S.dealt];
-    const uint32_t count = active ? render_count[S.dealt] : 0u; // an idle wave has no live mode: nothing below loads or stores for it
-    const uint32_t k0 = b.mode_offset[o], stride = b.mode_count[o], shape0 = b.shape_offset[o];
-    const uint32_t k = first_mode + 2 * lane;
-    const bool live[2] = {k < count, k + 1 < count};
-    const uint32_t chunk0 = chunk_base[S.dealt] + first_mode / LANES;
-    const uint32_t chunks_here = active ? min(CHUNKS, (count - first_mode + LANES - 1) / LANES) : 0u;
-    Pair z_re = {0, 0}, z_im = {0, 0}, c_re = {0, 0}, c_im = {0, 0}, p_re = {0, 0}, p_im = {0, 0};
+    // an idle wave has no live mode: nothing below loads or stores for it
+    WaveLane<Real> w = load_wave(b, deal_objects, chunk_base, out_gain, listener_gain, S.dealt, first_mode, active ? render_count[S.dealt] : 0u, lane);
     Pair a = {0, 0}, g_im = {0, 0}, g_re = {0, 0}; // the junction's drive gain and its advance-1 read row
 #pragma unroll
     for (int h = 0; h < 2; ++h)
-        if (live[h]) {
-            z_re[h] = b.state_re[k0 + k + h]; z_im[h] = b.state_im[k0 + k + h];
-            c_re[h] = b.coeff_re[k0 + k + h]; c_im[h] = b.coeff_im[k0 + k + h];
-            p_im[h] = b.phase_im[k0 + k + h]; p_re[h] = b.phase_re[k0 + k + h];
-            const uint32_t i0s = shape0 + S.p0 * stride + k + h, i1s = shape0 + S.p1 * stride + k + h, i2s = shape0 + S.p2 * stride + k + h;
-            const Real sx = S.w0 * b.shape_x[i0s] + S.w1 * b.shape_x[i1s] + S.w2 * b.shape_x[i2s];
-            const Real sy = S.w0 * b.shape_y[i0s] + S.w1 * b.shape_y[i1s] + S.w2 * b.shape_y[i2s];
-            const Real sz = S.w0 * b.shape_z[i0s] + S.w1 * b.shape_z[i1s] + S.w2 * b.shape_z[i2s];
-            const Real along = sx * S.nx + sy * S.ny + sz * S.nz;
-            a[h] = b.rad_gain[k0 + k + h] * along;
-            const Real read = S.scale * along * ca.defl_gain[k0 + k + h];
-            g_im[h] = read * c_re[h];
-            g_re[h] = read * c_im[h];
+        if (w.live[h]) {
+            const BlendRead<Real> point = blend_read(b, w, S.at, ca.defl_gain, h);
+            a[h] = b.rad_gain[w.k0 + w.k + h] * point.along;
+            const ReadGains<Real> g = read_gains(point.read, w.c_re[h], w.c_im[h], 1u);
+            g_im[h] = g.im;
+            g_re[h] = g.re;
         }
     // the object's force rows: gains of the first IMP_REG in registers, of further ones in this wave's scratch rows (a lane reads back
     // what it wrote)
@@ -542,18 +570,10 @@ __global__ void __launch_bounds__(JUNCTION_WAVES *WAVE)
     Pair g_reg[IMP_REG] = {};
     Real *g_mem = gain_scratch + size_t(J.first_wave + wave) * max_imp * MODES_PER_WAVE;
     for (uint32_t t = 0; t < n_imp; ++t) {
-        Pair g = {0, 0};
-        const ImpactDev<Real> &im = impacts[imp_idx[i0 + t]];
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-            if (live[h]) {
-                const uint32_t base = shape0 + im.ex_pos * stride + k + h;
-                g[h] = b.rad_gain[k0 + k + h] * (b.shape_x[base] * im.jx + b.shape_y[base] * im.jy + b.shape_z[base] * im.jz);
-            }
+        const Pair g = row_gain(b, w, impacts[imp_idx[i0 + t]]);
         if (t < IMP_REG) g_reg[t] = g;
         else *reinterpret_cast<Pair *>(g_mem + size_t(t) * MODES_PER_WAVE + 2 * lane) = g;
     }
-    const Real mix_gain = out_gain[o] * listener_gain[o];
     // a sum over the junction's modes: the lane's part -> the wave (DPP tree) -> the waves in ascending order from +0; the same bits in
     // every lane of every wave.  One barrier.
     auto junction_sum = [&](Real mine, uint32_t buffer) {
@@ -579,17 +599,13 @@ __global__ void __launch_bounds__(JUNCTION_WAVES *WAVE)
         ca.compliance_out[J.row] = double(compliance);
         ca.status_out[J.row] = solved ? MH_JUNCTION_SOLVED : MH_JUNCTION_REFUSED;
     }
-    const uint32_t group = lane / TS, ts = lane % TS; // turn-around mapping: chunks PER_GROUP*group .. of sample ts
     const float *u_row = ca.approach + size_t(J.row) * frames;
     Real *f_row = ca.force_out + size_t(J.row) * frames;
     for (uint32_t s0 = 0; s0 < frames; s0 += TS) {
         const uint32_t sn = min(TS, frames - s0);
         // this tile's approach samples, lane = sample (not finite: 0, as a drive's)
         Real u_tile = 0;
-        if (lane < sn) {
-            const float v = u_row[s0 + lane];
-            u_tile = (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u ? Real(v) : Real(0);
-        }
+        if (lane < sn) u_tile = finite_or_zero<Real>(u_row[s0 + lane]);
         // the tile's excitation, parked where the output terms will go
         for (uint32_t ds = 0; ds < sn; ++ds) {
             Pair excite = {0, 0};
@@ -602,64 +618,31 @@ __global__ void __launch_bounds__(JUNCTION_WAVES *WAVE)
         Real f_tile = 0;
         for (uint32_t ds = 0; ds < sn; ++ds) {
             const Pair excite = *reinterpret_cast<const Pair *>(s_term + ds * PITCH + 2 * lane); // what this lane parked
-            const Pair re = z_re * c_re - z_im * c_im + excite;
-            z_im = z_re * c_im + z_im * c_re;
-            const Real mine = fma_real(g_re.y, re.y, fma_real(g_im.y, z_im.y, fma_real(g_re.x, re.x, fma_real(g_im.x, z_im.x, zero))));
+            const Pair re = w.z_re * w.c_re - w.z_im * w.c_im + excite;
+            w.z_im = w.z_re * w.c_im + w.z_im * w.c_re;
+            const Real mine = fma_real(g_re.y, re.y, fma_real(g_im.y, w.z_im.y, fma_real(g_re.x, re.x, fma_real(g_im.x, w.z_im.x, zero))));
             const Real d = junction_sum(mine, (s0 + ds) & 1u);
             const Real x = lane_bcast(u_tile, ds) - d;
             const Real reach = bilateral ? x : (x > Real(0) ? x : Real(0));
             const Real f = solved ? (stiffness * reach) / denom : Real(0);
-            z_re = re + a * f;
-            *reinterpret_cast<Pair *>(s_term + ds * PITCH + 2 * lane) = p_im * z_im + p_re * z_re;
+            w.z_re = re + a * f;
+            *reinterpret_cast<Pair *>(s_term + ds * PITCH + 2 * lane) = w.p_im * w.z_im + w.p_re * w.z_re;
             if (lane == ds) f_tile = f;
         }
         if (wave == 0 && lane < sn) f_row[s0 + lane] = f_tile;
         // the turn-around of bank_modes: every chunk's 8 terms added in mode order
         mh_lds_writes_landed();
         __syncthreads();
-        if (ts < sn) {
-            const Real *row = s_term + ts * PITCH + group * (PER_GROUP * LANES);
-#pragma unroll
-            for (uint32_t c = 0; c < PER_GROUP; ++c) {
-                Real acc = 0;
-#pragma unroll
-                for (uint32_t l = 0; l < LANES; l += 2) {
-                    const Pair v = *reinterpret_cast<const Pair *>(row + c * LANES + l);
-                    acc += v.x;
-                    acc += v.y;
-                }
-                const uint32_t chunk = PER_GROUP * group + c;
-                if (chunk < chunks_here) partial[size_t(chunk0 + chunk) * frames + s0 + ts] = acc * mix_gain;
-            }
-        }
+        chunk_sums<TS>(s_term, w, lane, s0, sn, partial, frames);
         __syncthreads();
     }
-#pragma unroll
-    for (int h = 0; h < 2; ++h)
-        if (live[h]) {
-            b.state_re[k0 + k + h] = z_re[h];
-            b.state_im[k0 + k + h] = z_im[h];
-        }
-    // chunk energy, as in bank_modes
-    const Pair e = z_re * z_re + z_im * z_im;
-    const Real e0 = live[0] ? e.x : Real(0), e1 = live[1] ? e.y : Real(0);
-    Real chunk = Real(0) + e0;
-    chunk += e1;
-    chunk += row_shl<1>(e0);
-    chunk += row_shl<1>(e1);
-    chunk += row_shl<2>(e0);
-    chunk += row_shl<2>(e1);
-    chunk += row_shl<3>(e0);
-    chunk += row_shl<3>(e1);
-    if ((lane & (LANES / 2 - 1)) == 0 && lane / (LANES / 2) < chunks_here) chunk_energy[chunk0 + lane / (LANES / 2)] = chunk;
+    store_wave(b, w, lane, chunk_energy);
 }
+#undef BANK_MODES_PARAMS
+#undef BANK_MODES_ARGS
 
 // Per dealt object (one wave each): energy, audible prefix, whole-object silence (ModalAudio.cpp:132-146).  Loads are
 // lane-parallel; every sum runs in the reference's order through wave-uniform lane broadcasts.
-struct PerDeviceOnceBank { // hipFuncSetAttribute once per (kernel, device)
-    std::once_flag flag[64];
-    template<typename F> void run(int device, F &&f) { std::call_once(flag[device >= 0 && device < 64 ? device : 0], std::forward<F>(f)); }
-};
 template<typename Real> struct ObjectPassArgs {
     BankCols<Real> b;
     const uint32_t *deal_objects, *render_count, *chunk_base, *imp_ptr;
@@ -919,7 +902,20 @@ template<typename Real> struct BankImpl {
     BankCols<Real> cols() {
         return {coeff_re, coeff_im, state_re, state_im, rad_gain, phase_im, phase_re, shape_x, shape_y, shape_z, mode_offset, mode_count, shape_offset};
     }
+    // The shape entries object o holds (positions x modes): an index a kernel follows into its shape columns must stay below this
+    // (the read would leave the shape buffer).
+    uint64_t shapes_held(uint32_t o) const { return uint64_t(o + 1 < n_objects ? h_shape_offset[o + 1] : n_shapes) - h_shape_offset[o]; }
+    // A blend (a pickup's, a junction side's) the kernels may follow on its object, which the bank has: three points inside the object's
+    // shape columns; finite weights, direction and scale.
+    template<typename Record> bool blend_ok(const Record &m) const {
+        bool ok = std::isfinite(m.nx) && std::isfinite(m.ny) && std::isfinite(m.nz) && std::isfinite(m.scale);
+        for (int c = 0; c < 3; ++c) ok = ok && std::isfinite(m.weights[c]) && (uint64_t(m.points[c]) + 1) * h_mode_count[m.object] <= shapes_held(m.object);
+        return ok;
+    }
 };
+template<typename Real, typename Record> BlendDev<Real> blend_dev(const Record &m) {
+    return {m.points[0], m.points[1], m.points[2], Real(m.weights[0]), Real(m.weights[1]), Real(m.weights[2]), Real(m.nx), Real(m.ny), Real(m.nz), Real(m.scale)};
+}
 
 template<typename T> void ensure(mh_context *ctx, DevArray<T> &a, size_t n) {
     if (a.count < n) a.reset(ctx, n + n / 4 + 16);
@@ -944,7 +940,7 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
     Real *out = static_cast<Real *>(out_v);
     const uint32_t n_dealt = n_renderers ? deal_offset[n_renderers] : 0;
     uint32_t n_waves = 0;
-    for (uint32_t d = 0; d < n_dealt; ++d) n_waves += (render_count[d] + MODES_PER_WAVE - 1) / MODES_PER_WAVE;
+    for (uint32_t d = 0; d < n_dealt; ++d) n_waves += waves_of(render_count[d]);
     // ---- arena layout: [upload only | both ways | download only] ----
     Arena &A = B.arena;
     A.used = 0;
@@ -984,15 +980,11 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
         auto side_ok = [&](const mh_junction_side &sd) {
             if (sd.object >= B.n_objects || B.h_mode_count[sd.object] == 0 || B.dealt_of_object[sd.object] < 0 || render_count[B.dealt_of_object[sd.object]] == 0) return false;
             if (B.on_junction[sd.object]) return false; // one junction per object
-            const uint64_t shapes_end = sd.object + 1 < B.n_objects ? B.h_shape_offset[sd.object + 1] : B.n_shapes, held = shapes_end - B.h_shape_offset[sd.object];
-            bool ok = std::isfinite(sd.nx) && std::isfinite(sd.ny) && std::isfinite(sd.nz) && std::isfinite(sd.scale);
-            for (int c = 0; c < 3; ++c) ok = ok && std::isfinite(sd.weights[c]) && (uint64_t(sd.points[c]) + 1) * B.h_mode_count[sd.object] <= held;
-            return ok;
+            return B.blend_ok(sd);
         };
         auto side_dev = [&](const mh_junction_side &sd) {
             const uint32_t d = uint32_t(B.dealt_of_object[sd.object]);
-            return JunctionSideDev<Real>{d, (render_count[d] + MODES_PER_WAVE - 1) / MODES_PER_WAVE, sd.points[0], sd.points[1], sd.points[2], 0, Real(sd.weights[0]), Real(sd.weights[1]),
-                                         Real(sd.weights[2]), Real(sd.nx), Real(sd.ny), Real(sd.nz), Real(sd.scale)};
+            return JunctionSideDev<Real>{d, waves_of(render_count[d]), blend_dev<Real>(sd)};
         };
         for (uint32_t j = 0; j < n_junctions; ++j) {
             const mh_junction &m = junctions[j];
@@ -1032,8 +1024,7 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
         for (uint32_t j = 0; j < n_drives; ++j) {
             const uint32_t o = drives[j].object;
             if (o >= B.n_objects || B.dealt_of_object[o] < 0 || B.h_mode_count[o] == 0) continue;
-            const uint64_t shapes_end = o + 1 < B.n_objects ? B.h_shape_offset[o + 1] : B.n_shapes;
-            if ((uint64_t(drives[j].ex_pos) + 1) * B.h_mode_count[o] > shapes_end - B.h_shape_offset[o]) continue;
+            if ((uint64_t(drives[j].ex_pos) + 1) * B.h_mode_count[o] > B.shapes_held(o)) continue;
             B.drive_dealt[j] = B.dealt_of_object[o];
             ++imp_ptr[B.drive_dealt[j] + 1];
             ++driven_rows;
@@ -1074,10 +1065,7 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
             pick_rows[q] = {0, 0};
             if (m.object >= B.n_objects || B.h_mode_count[m.object] == 0 || m.advance > 2) continue;
             if (n_coupled && B.on_junction[m.object]) continue; // its waves are the coupled kernel's, which reads for no pickup (in this version)
-            const uint64_t shapes_end = m.object + 1 < B.n_objects ? B.h_shape_offset[m.object + 1] : B.n_shapes, held = shapes_end - B.h_shape_offset[m.object];
-            bool ok = std::isfinite(m.nx) && std::isfinite(m.ny) && std::isfinite(m.nz) && std::isfinite(m.scale);
-            for (int c = 0; c < 3; ++c) ok = ok && std::isfinite(m.weights[c]) && (uint64_t(m.points[c]) + 1) * B.h_mode_count[m.object] <= held;
-            if (!ok || B.picks_on[m.object] >= MH_PICKUPS_PER_OBJECT) continue;
+            if (!B.blend_ok(m) || B.picks_on[m.object] >= MH_PICKUPS_PER_OBJECT) continue;
             ++B.picks_on[m.object];
             pickup_read[q] = 1;
             const int32_t d = B.dealt_of_object[m.object];
@@ -1092,9 +1080,8 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
             const int32_t d = B.pick_dealt[q];
             if (d < 0) continue;
             const mh_pickup &m = pickups[q];
-            pick_rows[q] = {read_row_count, 2 * ((render_count[d] + MODES_PER_WAVE - 1) / MODES_PER_WAVE)}; // a row per (wave, half) of the object
-            pick_dev[B.pick_fill[d]++] = {m.points[0], m.points[1], m.points[2], m.advance, Real(m.weights[0]), Real(m.weights[1]), Real(m.weights[2]),
-                                          Real(m.nx), Real(m.ny), Real(m.nz), Real(m.scale), read_row_count};
+            pick_rows[q] = {read_row_count, 2 * waves_of(render_count[d])}; // a row per (wave, half) of the object
+            pick_dev[B.pick_fill[d]++] = {blend_dev<Real>(m), m.advance, read_row_count};
             read_row_count += pick_rows[q].n_rows;
             picked_modes += render_count[d];
         }
@@ -1142,16 +1129,19 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
         ensure(ctx, B.partial, size_t(n_chunks + 1) * frames);
         ensure(ctx, B.chunk_energy, n_chunks + 1);
         ensure(ctx, B.gain_scratch, size_t(n_waves + 1) * max_imp * MODES_PER_WAVE);
-        const uint32_t *d_deal = A.d<uint32_t>(o_deal), *d_count = A.d<uint32_t>(o_count), *d_chunk_base = A.d<uint32_t>(o_chunk_base), *d_imp_ptr = A.d<uint32_t>(o_imp_ptr);
+        // a mode kernel's launch: the common arguments (BANK_MODES_PARAMS), the launch's own scratch gain rows, then what only that kernel takes
+        auto launch_modes = [&](auto *kernel, uint32_t grid, uint32_t block, size_t lds, Real *scratch, auto... more) {
+            kernel<<<grid, block, lds, st>>>(B.cols(), A.d<WaveDesc>(o_waves), A.d<uint32_t>(o_deal), A.d<uint32_t>(o_count), A.d<uint32_t>(o_chunk_base), A.d<uint32_t>(o_imp_ptr),
+                                             A.d<uint32_t>(o_imp_idx), d_impacts, B.force, d_out_gain, d_listener, frames, B.partial, B.chunk_energy, scratch, max_imp, more...);
+            KERNEL_CHECK();
+        };
         if (n_coupled) { // the junctions' objects: a launch of their own, one workgroup per junction
             ensure(ctx, B.junction_gain, size_t(coupled_waves + JUNCTION_WAVES) * max_imp * MODES_PER_WAVE);
-            static PerDeviceOnceBank attr;
+            static PerDeviceOnce attr;
             attr.run(ctx->device, [] { HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_bank_modes_coupled<Real>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); });
             const CoupledArgs<Real> ca{B.defl_gain, A.d<JunctionDev<Real>>(o_junctions), A.d<float>(o_approach), A.hd<Real>(o_junction_force), A.hd<double>(o_compliance), A.hd<uint32_t>(o_status)};
             TimedLaunch timed(ctx, MH_KERNEL_JUNCTION, double(n_coupled) * double(frames));
-            k_bank_modes_coupled<Real><<<n_coupled, widest_junction * WAVE, coupled_lds<Real>(widest_junction), st>>>(B.cols(), d_deal, d_count, d_chunk_base, d_imp_ptr, A.d<uint32_t>(o_imp_idx), d_impacts, B.force, d_out_gain,
-                                                                                                                    d_listener, frames, B.partial, B.chunk_energy, B.junction_gain, max_imp, ca);
-            KERNEL_CHECK();
+            launch_modes(&k_bank_modes_coupled<Real>, n_coupled, widest_junction * WAVE, coupled_lds<Real>(widest_junction), B.junction_gain, ca);
         }
         if (main_waves) {
             uint64_t rendered_modes = 0;
@@ -1166,14 +1156,10 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
             if (picks_dealt) { // a block with pickups some dealt object carries: the entry that also reads
                 ensure(ctx, B.read_rows, size_t(read_row_count + 1) * frames);
                 const ReadArgs<Real> rd{B.defl_gain, A.d<uint32_t>(o_pick_ptr), A.d<PickupDev<Real>>(o_pick_dev), B.read_rows, rows_loop ? 1u : 0u};
-                k_bank_modes_read<Real><<<main_waves, WAVE, 0, st>>>(B.cols(), A.d<WaveDesc>(o_waves), d_deal, d_count, d_chunk_base, d_imp_ptr, A.d<uint32_t>(o_imp_idx), d_impacts,
-                                                                 B.force, d_out_gain, d_listener, frames, B.partial, B.chunk_energy, B.gain_scratch, max_imp, rd);
+                launch_modes(&k_bank_modes_read<Real>, main_waves, WAVE, 0, B.gain_scratch, rd);
             } else {
-                auto *modes_kernel = rows_loop ? &k_bank_modes_rows<Real> : &k_bank_modes<Real>;
-                modes_kernel<<<main_waves, WAVE, 0, st>>>(B.cols(), A.d<WaveDesc>(o_waves), d_deal, d_count, d_chunk_base, d_imp_ptr, A.d<uint32_t>(o_imp_idx), d_impacts,
-                                                      B.force, d_out_gain, d_listener, frames, B.partial, B.chunk_energy, B.gain_scratch, max_imp);
+                launch_modes(rows_loop ? &k_bank_modes_rows<Real> : &k_bank_modes<Real>, main_waves, WAVE, 0, B.gain_scratch);
             }
-            KERNEL_CHECK();
         }
     } else if (n_renderers) {
         HIP_CHECK(hipMemsetAsync(B.rout.get(), 0, size_t(n_renderers) * frames * sizeof(Real), st));
@@ -1193,7 +1179,7 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
         const uint32_t object_slices = n_dealt ? div_up(n_dealt, strips * (1024 / WAVE)) : 0;
         ObjectPassArgs<Real> objects{B.cols(), A.d<uint32_t>(o_deal), A.d<uint32_t>(o_count), A.d<uint32_t>(o_chunk_base), A.d<uint32_t>(n_coupled ? o_excited : o_imp_ptr), d_out_gain, B.chunk_energy, n_dealt,
                                      A.hd<double>(o_energy), A.hd<uint32_t>(o_live), A.hd<uint8_t>(o_silenced), A.d<uint32_t>(o_tuned), A.hd<double>(o_modal)};
-        static PerDeviceOnceBank attr;
+        static PerDeviceOnce attr;
         attr.run(ctx->device, [] { HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_bank_post<Real, SW>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); });
         k_bank_post<Real, SW><<<dim3(strips, sum_slices + object_slices), 1024, bank_post_lds<Real, SW>(), st>>>(B.partial, A.d<uint32_t>(o_rcp), n_dealt ? n_renderers : 0, frames, B.rout, B.click, streamed_clicks,
                                                                                         d_out, objects);

@@ -529,6 +529,14 @@ inline int mh_guard(mh_context *ctx, const std::exception &e) {
 
 inline unsigned div_up(size_t a, size_t b) { return unsigned((a + b - 1) / b); }
 
+// hipFuncSetAttribute once per (kernel, device): function attributes are per device, and first calls may race between the host
+// threads of concurrent solves -- a per-call-site table of once-flags indexed by the context's device.
+struct PerDeviceOnce {
+    static constexpr int MaxDevices = 64;
+    std::once_flag flag[MaxDevices];
+    template<typename F> void run(int device, F &&f) { std::call_once(flag[device >= 0 && device < MaxDevices ? device : 0], std::forward<F>(f)); }
+};
+
 // ---- stage entry points implemented across the .hip files ----
 void mh_phase_shared_lock(int device);   // mh_eigs.hip: device work of other entry points keeps out of an exclusive factorisation phase
 void mh_phase_shared_unlock(int device); // ON THE SAME DEVICE (one lock per device; no-ops with MH_CONCURRENT_SOLVES=0)

@@ -12,14 +12,6 @@
 
 #include <map>
 
-// hipFuncSetAttribute once per (kernel, device): function attributes are per device, and first calls may race between the host
-// threads of concurrent solves -- a per-call-site table of once-flags indexed by the context's device.
-struct PerDeviceOnce {
-    static constexpr int MaxDevices = 64;
-    std::once_flag flag[MaxDevices];
-    template<typename F> void run(int device, F &&f) { std::call_once(flag[device >= 0 && device < MaxDevices ? device : 0], std::forward<F>(f)); }
-};
-
 // MH_TEST=own_gemm (A/B hook, round 5): the wide Gram blocks and basis updates of the 200-mode configuration through OUR kernels
 // (k_gram_blocked cut into 160 x 80 blocks, k_combine in 256-column chunks) instead of the vendor's dgemm -- profiles/r05_config3_gemm_ab.txt
 static bool mh_test_own_gemm() {

@@ -18,14 +18,6 @@
 
 namespace {
 constexpr int TB = 256;
-struct PerDeviceOnce { // hipFuncSetAttribute once per (kernel, device)
-    std::mutex m;
-    bool done[64] = {};
-    template<typename F> void run(int device, F &&f) {
-        std::lock_guard<std::mutex> l(m);
-        if (!done[unsigned(device) % 64]) f(), done[unsigned(device) % 64] = true;
-    }
-};
 
 __global__ void k_element_quality(const double *__restrict__ pts, const uint32_t *__restrict__ elem_ref, uint32_t stride, uint32_t nt, float *__restrict__ q, float threshold,
                                   uint32_t *__restrict__ summary) {
