@@ -314,7 +314,30 @@ int mh_bank_render_read(mh_bank *, uint32_t frames, float click_gain, uint32_t n
  * rendered modes (each side's count rounded up to whole waves).  MH_JUNCTION_MODES = 1024 is what one workgroup holds: eight waves' output
  * tiles (16 640 B each) fill the 160 KiB of LDS; the registers (78 / 103 VGPRs in fp32 / fp64, nothing spilled, of the 256 a wave of an
  * eight-wave workgroup may take) would allow more.
- * In this version a pickup on an object that is on a junction's side is left out (pickup_read = 0, a zero row). */
+ * In this version a pickup on an object that is on a junction's side is left out (pickup_read = 0, a zero row).
+ *
+ * The Hertzian law, flags & MH_JUNCTION_HERTZ: `stiffness` is K in N/m^1.5 and the junction obeys f = K * delta^(3/2), the law of
+ * ContactModel (modal/contact.hpp).  Steps 1, 2, 3 and 5 are the ones above, bit for bit -- the free step, d, C, Re z = Re z~ + a*f[s], the
+ * output term, the summation orders, the force row written in the bank's precision.  Step 4 becomes the implicit solve of the law:
+ *   4h. x = u[s] - d.  If x > 0 fails (a NaN included): f[s] = 0.  Otherwise, with c = K*C formed once per block in the bank's precision,
+ *       y is the root of  y + c*y*sqrt(y) = x  -- the compression of frame s + 1, since y = x - C*f -- and f[s] = (K*y)*sqrt(y).
+ * So, as with the linear law, f[s] = K*max(u[s] - sum read[k]*Im z[s+1][k], 0)^(3/2) holds as an identity; the solve is what keeps a stiff
+ * contact from overshooting.  The root is found by one fixed expression tree (the bits depend on it), every operation rounded to the bank's
+ * precision, nothing contracted, no trip count that depends on data:
+ *   y = x;
+ *   if (c > 0) { g = cbrt(x / c); g = g*g; if (g < x) y = g; }       x and (x/c)^(2/3) both bound the root from above, and the smaller is
+ *                                                                    within a factor 2 of it
+ *   four times:  r = sqrt(y);  y = y - ((y + (c*y)*r) - x) / (1 + (1.5*c)*r);
+ *   f = (K*y)*sqrt(y);
+ * (Newton's steps on a convex increasing function from above: four of them leave f within 2.6 eps of the exact root's in float and in
+ * double over c*sqrt(x) = 1e-8 ... 1e8; three are enough in float only.  A start value off by 1e-3 changes nothing, so cbrt need not be
+ * correctly rounded.  x = 0, c = 0 (then y = x) and c = 1e30 give finite results.)  x is taken to be finite: u is (a sample that is not
+ * is 0), and d is while the state is; where u[s] - d overflows the bank's precision, f[s] is not finite -- as the linear law's is not.
+ * Status of a Hertz junction: MH_JUNCTION_REFUSED when C < 0, or C or K*C is not finite (1 + K*C plays no part); C = 0 is solved, f = K*x^1.5.
+ * A refused junction gives a zero row and its objects render as with K = 0, as above.
+ * MH_JUNCTION_HERTZ | MH_JUNCTION_BILATERAL is left out (status 0, a zero row, C = 0): the law has no tension branch.  Every other
+ * left-out kind is as above.  Not in this version: a damped (Hunt-Crossley) or hysteretic law, state between blocks, friction, roughness,
+ * other exponents. */
 typedef struct {
     uint32_t object;
     uint32_t points[3];
@@ -324,11 +347,12 @@ typedef struct {
 } mh_junction_side;
 typedef struct {
     mh_junction_side a, b;
-    float stiffness; /* K */
+    float stiffness; /* K: N/m for the linear law, N/m^1.5 with MH_JUNCTION_HERTZ */
     uint32_t flags;
 } mh_junction;
 #define MH_NO_OBJECT 0xffffffffu
 #define MH_JUNCTION_BILATERAL 1u
+#define MH_JUNCTION_HERTZ 2u
 #define MH_JUNCTION_MODES 1024
 enum { MH_JUNCTION_LEFT_OUT = 0, MH_JUNCTION_SOLVED = 1, MH_JUNCTION_REFUSED = 2 };
 /* sizeof(mh_junction) as this library was built */

@@ -57,6 +57,7 @@ class Junction(C.Structure):  # mh_junction
 
 
 NO_OBJECT, JUNCTION_BILATERAL, JUNCTION_MODES = 0xffffffff, 1, 1024  # MH_NO_OBJECT, MH_JUNCTION_BILATERAL, MH_JUNCTION_MODES
+JUNCTION_HERTZ = 2  # MH_JUNCTION_HERTZ
 
 
 def build(force=False):

@@ -65,8 +65,12 @@ struct ModalPickup {
 // and the returned force rows: include/modalhip.h, mh_junction).  A side is a pickup's contact point and a drive's direction in one record:
 // (Nx, Ny, Nz) is the direction in which the junction pushes that side; Coupling is the caller's factor, which the render multiplies by
 // the object's DeflectionScale.  Passed with the block it acts in; no state between blocks.
+// Flags bit 1, ModalJunctionHertz: the Hertzian law f = K delta^(3/2) of ContactModel (modal/contact.hpp) instead of the linear spring,
+// with Stiffness = K in N/m^1.5 (ContactStiffness(inv_modulus, curvature) = (4/3) E* sqrt(R) gives it), solved implicitly per frame by the
+// fixed Newton iteration of modalhip.h.  Unilateral only: a junction with both bits set is left out.
 constexpr uint32_t NoModalObject{0xffffffffu};
 constexpr uint32_t ModalJunctionBilateral{1};
+constexpr uint32_t ModalJunctionHertz{2};
 struct ModalJunctionSide {
     uint32_t Object{NoModalObject};
     uint32_t Points[3]{0, 0, 0};
@@ -238,15 +242,15 @@ void RenderModalRead(ModalAudio64 &, std::span<const ModalDrive> drives, const f
 // Not in the reference: RenderModalRead with contact junctions.  `approach` holds junctions.size() rows of frame_count samples (the rigid
 // indentation the caller's physics imposes; a sample that is not finite counts as 0), `forces` receives as many rows of the contact force
 // (written, not added to), `compliances` (nullable) the compliance C of each junction and `statuses` (nullable) one byte each: 0 = left
-// out (row of zeros), 1 = solved, 2 = refused (1 + K C is not a finite number above 0: no force, the objects render as with K = 0).  An
-// object on a side of a junction that is not left out is excited for the block like one with a drive: it rings, is dealt at and renders
-// its tuned mode count, is not silenced, and leaves the block with LiveModeCount = TunedModeCount.  Left out, and exciting nothing: a
-// side naming no object of the bank (B.Object = NoModalObject is the one-sided junction, not that), an object without modes or without
-// tuned modes, a point its shape columns do not cover, a weight, direction component, coupling or stiffness that is not finite, a
-// negative stiffness, both sides the same object, an object already on a side of an earlier junction of the call that was kept (one
-// junction per object in this version), and sides that together take more than MH_JUNCTION_MODES / 128 waves of 128 tuned modes
-// (modalhip.h).  A pickup on an object that is on a kept junction's side is left out in this version.  Without junctions this is
-// RenderModalRead.
+// out (row of zeros), 1 = solved, 2 = refused (1 + K C is not a finite number above 0 -- Hertz: C < 0, or C or K C not finite --: no
+// force, the objects render as with K = 0).  An object on a side of a junction that is not left out is excited for the block like one with
+// a drive: it rings, is dealt at and renders its tuned mode count, is not silenced, and leaves the block with LiveModeCount =
+// TunedModeCount.  Left out, and exciting nothing: a side naming no object of the bank (B.Object = NoModalObject is the one-sided
+// junction, not that), an object without modes or without tuned modes, a point its shape columns do not cover, a weight, direction
+// component, coupling or stiffness that is not finite, a negative stiffness, ModalJunctionHertz together with ModalJunctionBilateral, both
+// sides the same object, an object already on a side of an earlier junction of the call that was kept (one junction per object in this
+// version), and sides that together take more than MH_JUNCTION_MODES / 128 waves of 128 tuned modes (modalhip.h).  A pickup on an object
+// that is on a kept junction's side is left out in this version.  Without junctions this is RenderModalRead.
 void RenderModalCoupled(ModalAudio &, std::span<const ModalDrive> drives, const float *signals, std::span<const ModalPickup> pickups, float *reads,
                         std::span<const ModalJunction> junctions, const float *approach, float *forces, float *out, uint32_t frame_count, uint8_t *read_flags = nullptr,
                         double *compliances = nullptr, uint8_t *statuses = nullptr);

@@ -10,10 +10,10 @@
 // renderer's feedback reads (ReadDeflection / ReadRow over ModeReadGains: the object's modal displacement at the contact point along the
 // contact normal, the point blended between three excitation positions) exist as ModalPickup / RenderModalRead, one row of reads per
 // pickup and block.  The per-sample contact solve (a sample's force depending on the displacement read in the same sample) exists as
-// ModalJunction / RenderModalCoupled: one linear, unilateral or bilateral contact spring per junction between two bank objects or an
-// object and an exciter the caller moves, solved implicitly per frame on the device (the reference's one-channel SolveChannelStep with a
-// linear law).  What is still absent is the model on top of them: contact tracking and voices, several contacts on one object (the
-// reference's shared solve), the non-linear laws and the damping of a contact, tangential channels, the rigid-body recoil and air-load
+// ModalJunction / RenderModalCoupled: one contact per junction between two bank objects or an object and an exciter the caller moves --
+// a linear spring, unilateral or bilateral, or (ModalJunctionHertz) the Hertzian law f = K delta^1.5 -- solved implicitly per frame on
+// the device (the reference's one-channel SolveChannelStep).  What is still absent is the model on top of them: contact tracking and
+// voices, several contacts on one object (the reference's shared solve), the damping of a contact, tangential channels, the rigid-body recoil and air-load
 // filters of RenderObjectCoupled, and the roughness / friction signal generators.
 #pragma once
 #include "bank.hpp"

@@ -578,6 +578,7 @@ void RenderBlock(Audio &m, std::span<const ModalDrive> drives, const float *sign
         const bool two_sided = v.B.Object != NoModalObject;
         if (!std::isfinite(v.Stiffness) || v.Stiffness < 0 || !side_ok(v.A) || (two_sided && (v.A.Object == v.B.Object || !side_ok(v.B)))) continue;
         if (side_waves(v.A) + (two_sided ? side_waves(v.B) : 0u) > MH_JUNCTION_MODES / 128) continue;
+        if ((v.Flags & ModalJunctionHertz) && (v.Flags & ModalJunctionBilateral)) continue; // the Hertz law is unilateral
         mh_junction_side none{};
         none.object = MH_NO_OBJECT;
         d.Junctions.push_back({side_record(v.A), two_sided ? side_record(v.B) : none, v.Stiffness, v.Flags});

@@ -540,7 +540,32 @@ template<typename Real> size_t coupled_lds(uint32_t waves) {
 }
 __device__ __forceinline__ float fma_real(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 __device__ __forceinline__ double fma_real(double a, double b, double c) { return __builtin_fma(a, b, c); }
-template<typename Real> __global__ void __launch_bounds__(JUNCTION_WAVES *WAVE) k_bank_modes_coupled(BANK_MODES_PARAMS, CoupledArgs<Real> ca) { // (`waves`: the main launch's, not read here)
+__device__ __forceinline__ float sqrt_real(float v) { return __builtin_sqrtf(v); }
+__device__ __forceinline__ double sqrt_real(double v) { return __builtin_sqrt(v); }
+__device__ __forceinline__ float cbrt_real(float v) { return cbrtf(v); }
+__device__ __forceinline__ double cbrt_real(double v) { return cbrt(v); }
+// Step 4 of a Hertz junction (modalhip.h, MH_JUNCTION_HERTZ): the root y of y + c y sqrt(y) = x by the header's expression tree -- the
+// smaller of the two upper bounds x and (x / c)^(2/3), then four Newton steps, nothing contracted, no trip count that depends on data --
+// and f = (K y) sqrt(y).  c = K C and c15 = 1.5 c are formed once per block.  Wave-uniform: every lane has the same x, c, K.
+template<typename Real> __device__ __forceinline__ Real hertz_force(Real x, Real c, Real c15, Real k) {
+    if (!(x > Real(0))) return Real(0); // open, or a NaN
+    Real y = x;
+    if (c > Real(0)) {
+        Real g = cbrt_real(x / c);
+        g = g * g;
+        if (g < x) y = g;
+    }
+#pragma unroll
+    for (int step = 0; step < 4; ++step) {
+        const Real r = sqrt_real(y);
+        y = y - ((y + (c * y) * r) - x) / (Real(1) + c15 * r);
+    }
+    return (k * y) * sqrt_real(y);
+}
+// HERTZ = false (k_bank_modes_coupled<Real>): every junction is a linear spring -- the entry of a call without a Hertz junction, instruction
+// for instruction what it was before the parameter.  HERTZ = true: a junction with MH_JUNCTION_HERTZ takes hertz_force, a linear one the
+// same expression as in the other entry through one workgroup-uniform branch.
+template<typename Real, bool HERTZ = false> __global__ void __launch_bounds__(JUNCTION_WAVES *WAVE) k_bank_modes_coupled(BANK_MODES_PARAMS, CoupledArgs<Real> ca) { // (`waves`: the main launch's, not read here)
     typedef PairOf<Real> Pair;
     constexpr uint32_t TS = coupled_tile<Real>();
     extern __shared__ __attribute__((aligned(16))) unsigned char coupled_mem[];
@@ -592,7 +617,16 @@ template<typename Real> __global__ void __launch_bounds__(JUNCTION_WAVES *WAVE) 
     const Real zero = 0;
     const Real compliance = junction_sum(fma_real(g_re.y, a.y, fma_real(g_re.x, a.x, zero)), 1);
     const Real denom_k = Real(1) + J.k * compliance;
-    const bool solved = denom_k > Real(0) && denom_k <= std::numeric_limits<Real>::max(); // a finite number above 0 (a NaN fails both)
+    bool solved = denom_k > Real(0) && denom_k <= std::numeric_limits<Real>::max(); // a finite number above 0 (a NaN fails both)
+    bool hertz = false; // workgroup-uniform
+    Real kc = 0, kc15 = 0; // Hertz: c = K C and 1.5 c, once per block
+    if constexpr (HERTZ) {
+        hertz = (J.flags & MH_JUNCTION_HERTZ) != 0;
+        kc = J.k * compliance;
+        kc15 = Real(1.5) * kc;
+        const Real most = std::numeric_limits<Real>::max();
+        if (hertz) solved = compliance >= Real(0) && compliance <= most && kc >= Real(0) && kc <= most; // C and K C finite and not below 0
+    }
     const Real stiffness = solved ? J.k : Real(0), denom = solved ? denom_k : Real(1);
     const bool bilateral = (J.flags & MH_JUNCTION_BILATERAL) != 0;
     if (threadIdx.x == 0) {
@@ -624,7 +658,9 @@ template<typename Real> __global__ void __launch_bounds__(JUNCTION_WAVES *WAVE) 
             const Real d = junction_sum(mine, (s0 + ds) & 1u);
             const Real x = lane_bcast(u_tile, ds) - d;
             const Real reach = bilateral ? x : (x > Real(0) ? x : Real(0));
-            const Real f = solved ? (stiffness * reach) / denom : Real(0);
+            Real f = solved ? (stiffness * reach) / denom : Real(0);
+            if constexpr (HERTZ)
+                if (hertz) f = solved ? hertz_force(x, kc, kc15, J.k) : Real(0);
             w.z_re = re + a * f;
             *reinterpret_cast<Pair *>(s_term + ds * PITCH + 2 * lane) = w.p_im * w.z_im + w.p_re * w.z_re;
             if (lane == ds) f_tile = f;
@@ -638,6 +674,9 @@ template<typename Real> __global__ void __launch_bounds__(JUNCTION_WAVES *WAVE) 
     }
     store_wave(b, w, lane, chunk_energy);
 }
+// The launch of a call with a kept Hertz junction: the same kernel with the solve compiled in.  (An instantiation, not a wrapper around a
+// shared body: with the body in a function of its own the linear entry keeps its resource report but not its register assignment.)
+template<typename Real> constexpr auto k_bank_modes_coupled_hertz = &k_bank_modes_coupled<Real, true>;
 #undef BANK_MODES_PARAMS
 #undef BANK_MODES_ARGS
 
@@ -974,6 +1013,7 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
         if (deal_objects[d] < B.n_objects) B.dealt_of_object[deal_objects[d]] = int32_t(d);
     // ---- junctions: the ones the coupled kernel may follow, one workgroup each; everything else is left out with a zero row ----
     uint32_t n_coupled = 0, coupled_waves = 0, widest_junction = 0;
+    bool any_hertz = false; // a kept junction with MH_JUNCTION_HERTZ: the call takes the entry that has the solve
     if (n_junctions) {
         JunctionDev<Real> *jd = A.h<JunctionDev<Real>>(o_junctions);
         B.on_junction.assign(B.n_objects, 0);
@@ -992,12 +1032,14 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
             compliance_out[j] = 0;
             const bool two_sided = m.b.object != MH_NO_OBJECT;
             if (!std::isfinite(m.stiffness) || m.stiffness < 0 || !side_ok(m.a) || (two_sided && (m.a.object == m.b.object || !side_ok(m.b)))) continue;
+            if ((m.flags & MH_JUNCTION_HERTZ) && (m.flags & MH_JUNCTION_BILATERAL)) continue; // the Hertz law is unilateral
             JunctionDev<Real> dev{{side_dev(m.a), two_sided ? side_dev(m.b) : JunctionSideDev<Real>{}}, Real(m.stiffness), m.flags, j, coupled_waves};
             const uint32_t w = dev.side[0].waves + dev.side[1].waves;
             if (w > JUNCTION_WAVES) continue; // more modes than one workgroup holds
             B.on_junction[m.a.object] = 1;
             if (two_sided) B.on_junction[m.b.object] = 1;
             jd[n_coupled++] = dev;
+            any_hertz = any_hertz || (m.flags & MH_JUNCTION_HERTZ) != 0;
             coupled_waves += w;
             widest_junction = std::max(widest_junction, w);
         }
@@ -1138,10 +1180,13 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
         if (n_coupled) { // the junctions' objects: a launch of their own, one workgroup per junction
             ensure(ctx, B.junction_gain, size_t(coupled_waves + JUNCTION_WAVES) * max_imp * MODES_PER_WAVE);
             static PerDeviceOnce attr;
-            attr.run(ctx->device, [] { HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_bank_modes_coupled<Real>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); });
+            attr.run(ctx->device, [] {
+                HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_bank_modes_coupled<Real>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+                HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_bank_modes_coupled_hertz<Real>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            });
             const CoupledArgs<Real> ca{B.defl_gain, A.d<JunctionDev<Real>>(o_junctions), A.d<float>(o_approach), A.hd<Real>(o_junction_force), A.hd<double>(o_compliance), A.hd<uint32_t>(o_status)};
             TimedLaunch timed(ctx, MH_KERNEL_JUNCTION, double(n_coupled) * double(frames));
-            launch_modes(&k_bank_modes_coupled<Real>, n_coupled, widest_junction * WAVE, coupled_lds<Real>(widest_junction), B.junction_gain, ca);
+            launch_modes(any_hertz ? k_bank_modes_coupled_hertz<Real> : &k_bank_modes_coupled<Real>, n_coupled, widest_junction * WAVE, coupled_lds<Real>(widest_junction), B.junction_gain, ca);
         }
         if (main_waves) {
             uint64_t rendered_modes = 0;

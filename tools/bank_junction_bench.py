@@ -12,6 +12,12 @@ the exciter dipping in and out of the surface.
                                                                              commit, interleaved, every run a fresh process
                                                                              -> profiles/bank_junctions.json
 
+    python tools/bank_junction_bench.py --law hertz --junctions 16            the same with Hertz junctions (f = K delta^1.5, K chosen so that
+                                                                             K C sqrt(x0) = 10 at the approach's peak x0)
+    python tools/bank_junction_bench.py --laws-against T [--runs 3]          the all-linear calls of a built checkout T of the parent commit and
+                                                                             of this tree, and this tree's Hertz calls, J = 1, 16, 64, interleaved,
+                                                                             every run a fresh process -> profiles/bank_hertz.json
+
 The comparison also runs the unchanged tools/bank_bench.py of both trees (all_live.ms_per_block).  Kernel times per block are the
 library's kernel-class timers: class 2 the resonator kernel of the objects off the junctions, class 6 the coupled kernel.  The coupled
 kernel is one workgroup per junction running a serial chain per frame; `coupled_cycles_per_frame` is its time over the block's frames at
@@ -38,7 +44,7 @@ def sides_of(j, sides):
     return (j,) if sides == 1 else (2 * j, 2 * j + 1)
 
 
-def measure(tree, entry, junctions, sides, objects, blocks, renderers, forces_path, save_forces):
+def measure(tree, entry, junctions, sides, objects, blocks, renderers, forces_path, save_forces, law="linear"):
     sys.path.insert(0, tree)
     from mesheditor_amd import bank as hipbank
     from tools import bank_bench
@@ -50,7 +56,8 @@ def measure(tree, entry, junctions, sides, objects, blocks, renderers, forces_pa
     peak_force, kept = [0.0], []
     if entry == "coupled":
         side = lambda o, sign: hipbank.JunctionSide.of(o, 1, (1.0, 0.0, 0.0), tuple(sign * v for v in NORMAL), 2.0)
-        make = lambda k: (hipbank.Junction * max(junctions, 1))(*[hipbank.Junction.of(side(sides_of(j, sides)[0], 1.0), side(sides_of(j, sides)[1], -1.0) if sides == 2 else None, k[j])
+        flag = {"hertz": True} if law == "hertz" else {}  # (a tree from before the Hertz law takes no such argument)
+        make = lambda k: (hipbank.Junction * max(junctions, 1))(*[hipbank.Junction.of(side(sides_of(j, sides)[0], 1.0), side(sides_of(j, sides)[1], -1.0) if sides == 2 else None, k[j], **flag)
                                                                     for j in range(junctions)])
         rows = (hipbank.Drive * objects)(*drives)
         none = np.zeros((junctions, BLOCK), np.float32)
@@ -64,7 +71,8 @@ def measure(tree, entry, junctions, sides, objects, blocks, renderers, forces_pa
             free = np.abs(reads).max(axis=1)
             t = np.arange(BLOCK)
             u = np.array([(free[j] * (np.sin(2 * np.pi * t / 256.0 + j) + 0.1)).astype(np.float32) for j in range(junctions)])  # periodic in the block
-        contacts = make([10.0 / c for c in comp]) if junctions else []
+        # linear: K C = 10; Hertz: K C sqrt(x0) = 10 at the approach's peak x0
+        contacts = make([10.0 / (c * (np.sqrt(float(u[j].max())) if law == "hertz" else 1.0)) for j, c in enumerate(comp)]) if junctions else []
         u = u if junctions else none
 
         def block():
@@ -106,7 +114,7 @@ def measure(tree, entry, junctions, sides, objects, blocks, renderers, forces_pa
     sc.close()
     t = np.array(times)
     coupled_us = 1e3 * kj["total_ms"] / max(1, kj["launches"])
-    return {"entry": entry, "junctions": junctions, "sides": sides, "objects": objects, "modes_per_object": MODES, "blocks": blocks, "ms_per_block": 1e3 * float(t.mean()),
+    return {"entry": entry, "law": law, "junctions": junctions, "sides": sides, "objects": objects, "modes_per_object": MODES, "blocks": blocks, "ms_per_block": 1e3 * float(t.mean()),
             "ms_per_block_median": 1e3 * float(np.median(t)), "ms_per_block_p99": 1e3 * float(np.quantile(t, 0.99)), "kernel_us_per_block": 1e3 * k["total_ms"] / max(1, k["launches"]),
             "coupled_kernel_us_per_block": coupled_us, "coupled_us_per_frame": coupled_us / BLOCK, "coupled_cycles_per_frame": coupled_us / BLOCK * ENGINE_MHZ,
             "real_time_ms_per_block": 1e3 * BLOCK / SR}
@@ -174,6 +182,46 @@ def compare(parent, runs, objects, blocks, renderers, out_path, all_live):
     print(json.dumps(result["summary"]))
 
 
+def compare_laws(parent, runs, objects, blocks, renderers, out_path):
+    """The all-linear calls of the parent and of this tree (the same kernels: the new figures have to land within the parent's own spread)
+    and this tree's Hertz calls beside them."""
+    me = os.path.abspath(__file__)
+    common = ["--objects", str(objects), "--blocks", str(blocks), "--renderers", str(renderers)]
+    result = {"workload": f"{objects} objects x {MODES} modes @48k, {BLOCK}-frame blocks, fp32, {renderers} renderers, one drive on every object and J junctions in every block "
+                          "(linear: K C = 10; Hertz: K C sqrt(x0) = 10)", "runs_each": runs, "junctions": {}}
+
+    def save():
+        os.makedirs(os.path.dirname(out_path), exist_ok=True)
+        with open(out_path, "w") as f:
+            json.dump(result, f, indent=1)
+    q = subprocess.run(["timeout", "-k", "10", "300", sys.executable, "-c", "import torch; p = torch.cuda.get_device_properties(0); print(p.name, p.gcnArchName, '%d CUs' % p.multi_processor_count, '|', torch.version.hip)"], capture_output=True, text=True)
+    if q.returncode != 0:
+        raise SystemExit("no GPU to measure on: " + q.stderr[-2000:])
+    result["device"], result["hip"] = (v.strip() for v in q.stdout.strip().splitlines()[-1].split("|"))
+    for _ in range(runs):
+        for sides in (1, 2):
+            for j in JUNCTIONS[1:]:
+                row = result["junctions"].setdefault("%d x %d-sided" % (j, sides), {"parent_linear": [], "new_linear": [], "new_hertz": []})
+                shape = ["--entry", "coupled", "--junctions", str(j), "--sides", str(sides)] + common
+                row["parent_linear"].append(child([me, "--tree", parent, "--law", "linear"] + shape))
+                row["new_linear"].append(child([me, "--law", "linear"] + shape))
+                row["new_hertz"].append(child([me, "--law", "hertz"] + shape))
+                save()
+    med = lambda rows, key: float(np.median([r[key] for r in rows]))
+    spread = lambda rows, key: max(r[key] for r in rows) / min(r[key] for r in rows)
+    result["summary"] = {name: {"parent_linear_ms_per_block": [r["ms_per_block"] for r in row["parent_linear"]], "new_linear_ms_per_block": [r["ms_per_block"] for r in row["new_linear"]],
+                                "parent_spread_max_over_min": spread(row["parent_linear"], "ms_per_block"),
+                                "new_linear_median_over_parent_median": med(row["new_linear"], "ms_per_block") / med(row["parent_linear"], "ms_per_block"),
+                                "hertz_ms_per_block": med(row["new_hertz"], "ms_per_block"), "linear_ms_per_block": med(row["new_linear"], "ms_per_block"),
+                                "parent_linear_coupled_cycles_per_frame": med(row["parent_linear"], "coupled_cycles_per_frame"),
+                                "linear_coupled_cycles_per_frame": med(row["new_linear"], "coupled_cycles_per_frame"),
+                                "hertz_coupled_cycles_per_frame": med(row["new_hertz"], "coupled_cycles_per_frame"),
+                                "hertz_over_linear_cycles_per_frame": med(row["new_hertz"], "coupled_cycles_per_frame") / med(row["new_linear"], "coupled_cycles_per_frame")}
+                         for name, row in result["junctions"].items()}
+    save()
+    print(json.dumps(result["summary"]))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--entry", choices=["coupled", "replay"], default="coupled")
@@ -185,15 +233,20 @@ def main():
     ap.add_argument("--tree", default=HERE, help="built checkout whose library is measured (replay only on one without junctions)")
     ap.add_argument("--forces", help="replay: the force rows a --save-forces run wrote")
     ap.add_argument("--save-forces", help="coupled: write the last block's force rows here (.npy)")
+    ap.add_argument("--law", choices=["linear", "hertz"], default="linear", help="coupled: the junctions' law")
+    ap.add_argument("--laws-against", help="built checkout of the parent commit: its all-linear calls, this tree's, and this tree's Hertz calls -> profiles/bank_hertz.json")
     ap.add_argument("--against", help="built checkout of the parent commit: run the whole comparison")
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--no-all-live", action="store_true", help="skip tools/bank_bench.py of both trees")
     ap.add_argument("--out", default=os.path.join(HERE, "profiles", "bank_junctions.json"))
     a = ap.parse_args()
-    if a.against:
+    if a.laws_against:
+        out = a.out if a.out != ap.get_default("out") else os.path.join(HERE, "profiles", "bank_hertz.json")
+        compare_laws(os.path.abspath(a.laws_against), a.runs, a.objects, a.blocks, a.renderers, out)
+    elif a.against:
         compare(os.path.abspath(a.against), a.runs, a.objects, a.blocks, a.renderers, a.out, not a.no_all_live)
     else:
-        print(json.dumps(measure(os.path.abspath(a.tree), a.entry, a.junctions, a.sides, a.objects, a.blocks, a.renderers, a.forces, a.save_forces)))
+        print(json.dumps(measure(os.path.abspath(a.tree), a.entry, a.junctions, a.sides, a.objects, a.blocks, a.renderers, a.forces, a.save_forces, a.law)))
 
 
 if __name__ == "__main__":
