@@ -310,7 +310,7 @@ int mh_bank_render_read(mh_bank *, uint32_t frames, float click_gain, uint32_t n
  * Left out (status 0, a zero row, C = 0; it excites nothing, like a dropped drive): a side naming no object of the bank, an object that is
  * not dealt, has no modes or renders none, a point beyond the object's shape columns, a weight, direction component, scale or K that is
  * not finite, K < 0, both sides the same object, an object already on a side of an earlier junction of the call that was not left out
- * (one junction per object in this version), and a junction whose sides together take more than MH_JUNCTION_MODES / 128 waves of 128
+ * (one junction per object, unless both junctions carry MH_JUNCTION_SHARED: "Groups" below), and a junction whose sides together take more than MH_JUNCTION_MODES / 128 waves of 128
  * rendered modes (each side's count rounded up to whole waves).  MH_JUNCTION_MODES = 1024 is what one workgroup holds: eight waves' output
  * tiles (16 640 B each) fill the 160 KiB of LDS; the registers (78 / 103 VGPRs in fp32 / fp64, nothing spilled, of the 256 a wave of an
  * eight-wave workgroup may take) would allow more.
@@ -337,7 +337,50 @@ int mh_bank_render_read(mh_bank *, uint32_t frames, float click_gain, uint32_t n
  * A refused junction gives a zero row and its objects render as with K = 0, as above.
  * MH_JUNCTION_HERTZ | MH_JUNCTION_BILATERAL is left out (status 0, a zero row, C = 0): the law has no tension branch.  Every other
  * left-out kind is as above.  Not in this version: a damped (Hunt-Crossley) or hysteretic law, state between blocks, friction, roughness,
- * other exponents. */
+ * other exponents.
+ *
+ * Groups, flags & MH_JUNCTION_SHARED: several junctions on one object (a bowl on three points, a table under several objects, a bar on two
+ * supports under a mallet).  A junction with the flag may name an object that is already on a side of an earlier kept junction, provided
+ * that junction carries the flag too.  A junction without it is treated as above: it is left out when it names an object of a kept
+ * junction, and a later flagged junction on one of its objects is left out.  The kept flagged junctions of a call fall into connected
+ * components over the objects they name (two junctions are connected when they share an object; an exciter side connects nothing).
+ * A component of one junction is an ordinary junction -- the five steps above, linear or Hertz, bit for bit: the flag on a lone junction
+ * changes nothing.  A component of 2 ... MH_JUNCTION_GROUP junctions is a GROUP of n members i = 0 ... n-1 in call order, solved together:
+ *   1, 2. as above per member: d_i sums over member i's own sides, side a's modes, then side b's (DESIGN.md section 3c's order).
+ *   3.  a matrix, constant over the block:  C_ij = sum over the objects o on a side of both i and j -- side a of i, then side b of i --
+ *       of sum_k g_re_{i,o}[k] * a_{j,o}[k]  (a force f_j at frame s moves member i's prediction by C_ij f_j).  C_ii is the C of step 3
+ *       above and what compliance_out[i] returns.
+ *   4.  x_i = u_i[s] - d_i.  f is the solution of:  y = x - C f;  f_i = K_i max(y_i, 0)  (bilateral: f_i = K_i y_i)  for every member at
+ *       once, so that every member's force meets its law at the displacement of frame s + 1.  With f = K y this is (I + C diag(K)) y = x
+ *       on the members in contact.  TuneModalObject makes C a positive diagonal times a Gram matrix, so I + C diag(K) is a P-matrix (its
+ *       principal minors are those of I + diag(K) C, all above 0) and the problem has exactly one solution.  It is found by enumerating
+ *       the active sets, with no trip count that depends on data:
+ *       Per block, for each subset A of the members that contains every bilateral one (bit i of the mask = member i; at most 16):
+ *         M_A = (I + C_AA diag(K_A))^-1 in the bank's precision by the elimination of [B | I] over the members of A without pivoting, in
+ *         ascending order:  B_ij = C_ij*K_j, plus 1 on the diagonal (1 + C_ii*K_i);  for p in A ascending: r = 1 / B_pp; row p of both
+ *         halves times r;  for every i != p in A: t = B_ip; row i = row i - t * row p.  Nothing contracted.
+ *       Per frame, for each such A:  y_i = sum_{j in A} M_ij*x_j (ascending j, from +0) and f_i = K_i*y_i on A, f_i = +0 off it.  A is
+ *         CONSISTENT when y_j > 0 for every unilateral j in A and  x_j - sum_{i in A} C_ji*f_i > 0  (ascending i, from +0) fails for
+ *         every j outside A.  Taken: the consistent subset of lowest mask.  The empty set is consistent exactly when no x_j > 0: a group
+ *         out of contact gives exact zeros.
+ *       If rounding leaves no subset consistent (x within a rounding of a boundary between two active sets, where both neighbours fail by
+ *         that rounding): the subset that fails by least is taken -- the largest over its members of -y_j (unilateral j in A) and of the
+ *         residual above (j outside A), above 0; lowest mask among equals -- with f_j = K_j*max(y_j, 0) on its unilateral members.  (The
+ *         full set's clamped candidate, the obvious last resort, jumps there: tests/test_bank_groups_cpu.py.)
+ *   5.  On each object  Re z[k] = (...((Re z~[k] + a_{j1}[k]*f_{j1}) + a_{j2}[k]*f_{j2})...)  over the members with a side on it, in
+ *       ascending call order; the frame's output term is formed from that state.
+ * M_{i} of a single member is formed by the same elimination, 1 / (1 + C_ii*K_i) times x and then times K_i: not the bits of step 4's
+ * (K*x) / (1 + K*C).  A lone junction never takes this path, and a group compared with itself (other members dead) does on both sides.
+ * Status: every member of a group gets MH_JUNCTION_REFUSED when a C_ij or C_ij*K_j is not finite or a pivot of an M_A is not a finite
+ * number above 0 -- zero rows, the objects render as with K = 0 -- and MH_JUNCTION_SOLVED otherwise; compliance_out[i] = C_ii either way.
+ * Left out (status 0, a zero row, C = 0, excites nothing), decided in call order: a flagged junction that would make a component larger
+ * than MH_JUNCTION_GROUP; one with which the component's distinct objects would take more than MH_JUNCTION_MODES / 128 waves of 128
+ * rendered modes (each object counted once, however many sides name it); one with MH_JUNCTION_HERTZ that would join a component of more
+ * than one junction, and one that would join a component that holds a Hertz junction (the Hertz solve in more than one dimension is not in
+ * this version); a flagged junction on an object of a kept unflagged one.  Two junctions between the same pair of objects, at different
+ * points, are a legal group.  Pickups on a junction's object stay left out.  MH_JUNCTION_GROUP = 4 is what a wave's registers hold: one
+ * gain triple per member per lane, 195 VGPRs in fp64 (118 in fp32), nothing in scratch.  Not in this version, as above: damped laws,
+ * friction, roughness, state between blocks. */
 typedef struct {
     uint32_t object;
     uint32_t points[3];
@@ -353,7 +396,9 @@ typedef struct {
 #define MH_NO_OBJECT 0xffffffffu
 #define MH_JUNCTION_BILATERAL 1u
 #define MH_JUNCTION_HERTZ 2u
+#define MH_JUNCTION_SHARED 4u
 #define MH_JUNCTION_MODES 1024
+#define MH_JUNCTION_GROUP 4 /* the most junctions one group may hold */
 enum { MH_JUNCTION_LEFT_OUT = 0, MH_JUNCTION_SOLVED = 1, MH_JUNCTION_REFUSED = 2 };
 /* sizeof(mh_junction) as this library was built */
 uint32_t mh_junction_struct_size(void);

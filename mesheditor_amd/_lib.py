@@ -58,6 +58,7 @@ class Junction(C.Structure):  # mh_junction
 
 NO_OBJECT, JUNCTION_BILATERAL, JUNCTION_MODES = 0xffffffff, 1, 1024  # MH_NO_OBJECT, MH_JUNCTION_BILATERAL, MH_JUNCTION_MODES
 JUNCTION_HERTZ = 2  # MH_JUNCTION_HERTZ
+JUNCTION_SHARED, JUNCTION_GROUP = 4, 4  # MH_JUNCTION_SHARED, MH_JUNCTION_GROUP
 
 
 def build(force=False):

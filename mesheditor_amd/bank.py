@@ -46,19 +46,21 @@ class JunctionSide(C.Structure):  # ModalJunctionSide, modal/bank.hpp (mh_juncti
         return cls(obj, (C.c_uint32 * 3)(*pts), (C.c_float * 3)(*weights), direction[0], direction[1], direction[2], coupling)
 
 
-NO_OBJECT, JUNCTION_BILATERAL, JUNCTION_HERTZ = 0xffffffff, 1, 2  # NoModalObject, ModalJunctionBilateral, ModalJunctionHertz
+NO_OBJECT, JUNCTION_BILATERAL, JUNCTION_HERTZ, JUNCTION_SHARED = 0xffffffff, 1, 2, 4  # NoModalObject, ModalJunctionBilateral, ModalJunctionHertz, ModalJunctionShared
 
 
 class Junction(C.Structure):  # ModalJunction, modal/bank.hpp (mh_junction of modalhip.h field for field)
     _fields_ = [("a", JunctionSide), ("b", JunctionSide), ("stiffness", C.c_float), ("flags", C.c_uint32)]
 
     @classmethod
-    def of(cls, a, b=None, stiffness=0.0, bilateral=False, hertz=False):
+    def of(cls, a, b=None, stiffness=0.0, bilateral=False, hertz=False, shared=False):
         """a, b: JunctionSide records or the arguments of JunctionSide.of as tuples; b = None: one-sided (an exciter the caller moves).
-        hertz: f = K delta^1.5 with `stiffness` in N/m^1.5 instead of the linear spring (unilateral only: with bilateral it is left out)."""
+        hertz: f = K delta^1.5 with `stiffness` in N/m^1.5 instead of the linear spring (unilateral only: with bilateral it is left out).
+        shared: the junction may name an object that an earlier kept junction with shared=True names; up to four linear junctions that
+        share objects in this way are one group, solved together in every frame (modalhip.h, MH_JUNCTION_SHARED)."""
         side = lambda v: v if isinstance(v, JunctionSide) else JunctionSide.of(*v)
         none = JunctionSide(NO_OBJECT, (C.c_uint32 * 3)(0, 0, 0), (C.c_float * 3)(1, 0, 0), 0.0, 0.0, 0.0, 1.0)
-        return cls(side(a), side(b) if b is not None else none, stiffness, (JUNCTION_BILATERAL if bilateral else 0) | (JUNCTION_HERTZ if hertz else 0))
+        return cls(side(a), side(b) if b is not None else none, stiffness, (JUNCTION_BILATERAL if bilateral else 0) | (JUNCTION_HERTZ if hertz else 0) | (JUNCTION_SHARED if shared else 0))
 
 
 def lib():

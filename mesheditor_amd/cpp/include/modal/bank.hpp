@@ -68,9 +68,13 @@ struct ModalPickup {
 // Flags bit 1, ModalJunctionHertz: the Hertzian law f = K delta^(3/2) of ContactModel (modal/contact.hpp) instead of the linear spring,
 // with Stiffness = K in N/m^1.5 (ContactStiffness(inv_modulus, curvature) = (4/3) E* sqrt(R) gives it), solved implicitly per frame by the
 // fixed Newton iteration of modalhip.h.  Unilateral only: a junction with both bits set is left out.
+// Flags bit 2, ModalJunctionShared: the junction may name an object that an earlier kept junction with the same bit names.  The kept
+// junctions that share objects in this way -- up to MH_JUNCTION_GROUP of them, linear, their distinct objects within one workgroup's
+// waves -- are a group and are solved together per frame (modalhip.h, "Groups"); on a junction that shares nothing the bit changes nothing.
 constexpr uint32_t NoModalObject{0xffffffffu};
 constexpr uint32_t ModalJunctionBilateral{1};
 constexpr uint32_t ModalJunctionHertz{2};
+constexpr uint32_t ModalJunctionShared{4};
 struct ModalJunctionSide {
     uint32_t Object{NoModalObject};
     uint32_t Points[3]{0, 0, 0};
@@ -248,9 +252,15 @@ void RenderModalRead(ModalAudio64 &, std::span<const ModalDrive> drives, const f
 // TunedModeCount.  Left out, and exciting nothing: a side naming no object of the bank (B.Object = NoModalObject is the one-sided
 // junction, not that), an object without modes or without tuned modes, a point its shape columns do not cover, a weight, direction
 // component, coupling or stiffness that is not finite, a negative stiffness, ModalJunctionHertz together with ModalJunctionBilateral, both
-// sides the same object, an object already on a side of an earlier junction of the call that was kept (one junction per object in this
-// version), and sides that together take more than MH_JUNCTION_MODES / 128 waves of 128 tuned modes (modalhip.h).  A pickup on an object
-// that is on a kept junction's side is left out in this version.  Without junctions this is RenderModalRead.
+// sides the same object, an object already on a side of an earlier junction of the call that was kept (one junction per object, unless
+// both junctions carry ModalJunctionShared), and sides that together take more than MH_JUNCTION_MODES / 128 waves of 128 tuned modes
+// (modalhip.h).  Junctions with ModalJunctionShared that share objects form a group, which is solved together in every frame: every
+// member's force meets its law at the next frame's displacement at once.  Left out among those, in call order: the junction that would
+// be a group's fifth (MH_JUNCTION_GROUP is 4), the one with which the group's distinct objects would take more than
+// MH_JUNCTION_MODES / 128 waves, a Hertz junction that would join another junction, and any junction that would join a Hertz one.  The
+// decision is taken here and again by the device entry, from one definition (modalhip_groups.hpp); every kept junction counts as an
+// excitation of its objects.  A pickup on an object that is on a kept junction's side is left out in this version.  Without junctions
+// this is RenderModalRead.
 void RenderModalCoupled(ModalAudio &, std::span<const ModalDrive> drives, const float *signals, std::span<const ModalPickup> pickups, float *reads,
                         std::span<const ModalJunction> junctions, const float *approach, float *forces, float *out, uint32_t frame_count, uint8_t *read_flags = nullptr,
                         double *compliances = nullptr, uint8_t *statuses = nullptr);

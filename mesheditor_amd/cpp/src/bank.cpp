@@ -12,6 +12,7 @@
 #include "modal/bank.hpp"
 
 #include "modalhip.h"
+#include "modalhip_groups.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -564,7 +565,7 @@ void RenderBlock(Audio &m, std::span<const ModalDrive> drives, const float *sign
     d.Approach.clear();
     d.OnJunction.assign(n_objects, 0);
     auto side_ok = [&](const ModalJunctionSide &v) {
-        if (v.Object >= n_objects || b.ModeCount[v.Object] == 0 || b.TunedModeCount[v.Object] == 0 || d.OnJunction[v.Object]) return false;
+        if (v.Object >= n_objects || b.ModeCount[v.Object] == 0 || b.TunedModeCount[v.Object] == 0) return false;
         bool ok = std::isfinite(v.Nx) && std::isfinite(v.Ny) && std::isfinite(v.Nz) && std::isfinite(v.Coupling);
         for (int c = 0; c < 3; ++c) ok = ok && std::isfinite(v.Weights[c]) && HasExcitationPosition(b, v.Object, v.Points[c]);
         return ok;
@@ -573,12 +574,15 @@ void RenderBlock(Audio &m, std::span<const ModalDrive> drives, const float *sign
     auto side_record = [&](const ModalJunctionSide &v) {
         return mh_junction_side{v.Object, {v.Points[0], v.Points[1], v.Points[2]}, {v.Weights[0], v.Weights[1], v.Weights[2]}, v.Nx, v.Ny, v.Nz, float(Real(v.Coupling) * b.DeflectionScale[v.Object])};
     };
+    // (one junction per object, unless both carry ModalJunctionShared: then they form a group -- the decision of modalhip_groups.hpp, which
+    // the device entry takes again)
+    MhJunctionGroups grouping(n_objects);
     for (size_t j = 0; j < junctions.size(); ++j) {
         const ModalJunction &v = junctions[j];
         const bool two_sided = v.B.Object != NoModalObject;
         if (!std::isfinite(v.Stiffness) || v.Stiffness < 0 || !side_ok(v.A) || (two_sided && (v.A.Object == v.B.Object || !side_ok(v.B)))) continue;
-        if (side_waves(v.A) + (two_sided ? side_waves(v.B) : 0u) > MH_JUNCTION_MODES / 128) continue;
         if ((v.Flags & ModalJunctionHertz) && (v.Flags & ModalJunctionBilateral)) continue; // the Hertz law is unilateral
+        if (grouping.add(uint32_t(j), v.Flags, v.A.Object, side_waves(v.A), two_sided ? v.B.Object : MH_NO_OBJECT, two_sided ? side_waves(v.B) : 0u) < 0) continue;
         mh_junction_side none{};
         none.object = MH_NO_OBJECT;
         d.Junctions.push_back({side_record(v.A), two_sided ? side_record(v.B) : none, v.Stiffness, v.Flags});

@@ -8,6 +8,7 @@
 // so the signal equals the CPU restatement's sample for sample, for fp32 (the reference's bank) and fp64 alike.
 // The sequential part (ordered accumulation) is a separate pass over per-chunk partial signals staged in HBM.
 #include "mh_common.h"
+#include "../../include/modalhip_groups.hpp"
 
 #include <algorithm>
 #include <limits>
@@ -677,6 +678,268 @@ template<typename Real, bool HERTZ = false> __global__ void __launch_bounds__(JU
 // The launch of a call with a kept Hertz junction: the same kernel with the solve compiled in.  (An instantiation, not a wrapper around a
 // shared body: with the body in a function of its own the linear entry keeps its resource report but not its register assignment.)
 template<typename Real> constexpr auto k_bank_modes_coupled_hertz = &k_bank_modes_coupled<Real, true>;
+
+// Groups of junctions that share objects (MH_JUNCTION_SHARED; contract in modalhip.h).  ONE WORKGROUP PER GROUP, one
+// wave per 128 modes of each DISTINCT object of the group (the objects in the order the members name them, side a before side b), modes
+// in registers two per lane; a wave holds one gain triple (a, g_im, g_re) per member that has a side on its object -- up to
+// MH_JUNCTION_GROUP -- and zeros for the others.  The launch has as many waves as the largest group of the call; a wave beyond a group's
+// own holds no modes and takes part in every barrier.
+// Per frame: the free step -> per member on the wave's object the lane's part of d_i (the four multiply-adds of the coupled kernel) ->
+// mh_wave_sum -> one LDS slot per (member, place of the wave in that member's order: side a's waves, then side b's) -> barrier -> every
+// wave adds each member's slots from +0 in that order, forms x and runs the group's solve: lane m (and every lane with m = lane % 16)
+// holds the inverse M_A of the subset A with bit mask m, formed once per block, and computes A's candidate and whether it is consistent;
+// a ballot over lanes 0 .. 15, its lowest set bit and one lane read per member give every lane of every wave the same f.  Then
+// Re z += a_i f_i for the members on the wave's object in ascending order, and the output term goes to the wave's turn-around tile.
+// The matrix C takes MH_JUNCTION_GROUP such reductions ahead of the loop (column j in round j).  The slots are double-buffered by parity
+// (round j: buffer j % 2; frame s: buffer s % 2 -- the last round uses the odd buffer, frame 0 the even one) as in the coupled kernel.
+// Barriers: 1 + MH_JUNCTION_GROUP + frames + 2 per tile, executed by every wave whatever it holds -- a function of `frames` alone.
+constexpr uint32_t GROUP = MH_JUNCTION_GROUP, GROUP_SETS = 1u << GROUP, NO_SLOT = 0xffffffffu;
+template<typename Real> struct GroupMemberDev {
+    BlendDev<Real> at[2];
+    Real k;
+    uint32_t flags, row, slot[2]; // row: the caller's index; slot: the side's object among the group's, NO_SLOT for an exciter
+};
+template<typename Real> struct GroupDev {
+    GroupMemberDev<Real> member[GROUP]; // in call order
+    uint32_t n, n_objects, first_wave, n_waves; // first_wave: into the gain scratch
+    uint32_t dealt[JUNCTION_WAVES], wave0[JUNCTION_WAVES], waves[JUNCTION_WAVES]; // per distinct object: the dealt object, its first wave in the workgroup, its waves
+};
+template<typename Real> struct GroupedArgs {
+    const Real *defl_gain;
+    const GroupDev<Real> *groups;
+    const float *approach; // [caller's junction][frames]
+    Real *force_out; // [caller's junction][frames], where the host reads it
+    double *compliance_out;
+    uint32_t *status_out;
+};
+template<typename Real> size_t grouped_lds(uint32_t waves) {
+    return 2 * GROUP * JUNCTION_WAVES * sizeof(Real) + size_t(waves) * coupled_tile<Real>() * (MODES_PER_WAVE + 2) * sizeof(Real);
+}
+template<typename Real> __global__ void __launch_bounds__(JUNCTION_WAVES *WAVE) k_bank_modes_grouped(BANK_MODES_PARAMS, GroupedArgs<Real> ga) { // (`waves`: the main launch's, not read here)
+    typedef PairOf<Real> Pair;
+    constexpr uint32_t TS = coupled_tile<Real>();
+    extern __shared__ __attribute__((aligned(16))) unsigned char grouped_mem[];
+    Real *s_slot = reinterpret_cast<Real *>(grouped_mem); // [2][GROUP][JUNCTION_WAVES]
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE), lane = threadIdx.x % WAVE, block_waves = blockDim.x / WAVE;
+    Real *s_term = s_slot + 2 * GROUP * JUNCTION_WAVES + size_t(wave) * TS * PITCH; // this wave's tile, [sample][mode]
+    const GroupDev<Real> *__restrict__ G = ga.groups + blockIdx.x;
+    const uint32_t n = G->n;
+    // this wave's object among the group's; an idle wave has no live mode: nothing below loads or stores for it
+    const bool active = wave < G->n_waves;
+    uint32_t slot = 0;
+    for (uint32_t o = 1; o < G->n_objects; ++o)
+        if (active && wave >= G->wave0[o]) slot = o; // (wave0 ascends with the object)
+    const uint32_t wave_in_object = active ? wave - G->wave0[slot] : 0u, dealt = G->dealt[slot];
+    WaveLane<Real> w = load_wave(b, deal_objects, chunk_base, out_gain, listener_gain, dealt, wave_in_object * MODES_PER_WAVE, active ? render_count[dealt] : 0u, lane);
+    // per member: is a side of it on this wave's object, the wave's place in the member's summation order, its gains here
+    uint32_t on = 0, place[GROUP] = {}, bilateral = 0;
+    Pair a[GROUP] = {}, g_im[GROUP] = {}, g_re[GROUP] = {};
+    Real k[GROUP] = {};
+#pragma unroll
+    for (uint32_t i = 0; i < GROUP; ++i) {
+        if (i >= n) continue;
+        const GroupMemberDev<Real> *M = G->member + i;
+        const uint32_t sa = M->slot[0], sb = M->slot[1], waves_a = G->waves[sa];
+        k[i] = M->k;
+        if (M->flags & MH_JUNCTION_BILATERAL) bilateral |= 1u << i;
+        if (!active || (sa != slot && sb != slot)) continue;
+        const uint32_t sd = sa == slot ? 0u : 1u;
+        on |= 1u << i;
+        place[i] = (sd ? waves_a : 0u) + wave_in_object;
+        const BlendDev<Real> at = M->at[sd];
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+            if (w.live[h]) {
+                const BlendRead<Real> point = blend_read(b, w, at, ga.defl_gain, h);
+                a[i][h] = b.rad_gain[w.k0 + w.k + h] * point.along;
+                const ReadGains<Real> g = read_gains(point.read, w.c_re[h], w.c_im[h], 1u);
+                g_im[i][h] = g.im;
+                g_re[i][h] = g.re;
+            }
+    }
+    on = __builtin_amdgcn_readfirstlane(on);
+    // the object's force rows, as in the coupled kernel
+    const uint32_t i0 = imp_ptr[dealt], n_imp = active ? imp_ptr[dealt + 1] - i0 : 0u;
+    Pair g_reg[IMP_REG] = {};
+    Real *g_mem = gain_scratch + size_t(G->first_wave + wave) * max_imp * MODES_PER_WAVE;
+    for (uint32_t t = 0; t < n_imp; ++t) {
+        const Pair g = row_gain(b, w, impacts[imp_idx[i0 + t]]);
+        if (t < IMP_REG) g_reg[t] = g;
+        else *reinterpret_cast<Pair *>(g_mem + size_t(t) * MODES_PER_WAVE + 2 * lane) = g;
+    }
+    // one sum per member over that member's modes: the lane's part -> the wave (DPP tree) -> the member's waves in its order from +0; the
+    // same bits in every lane of every wave.  One barrier.
+    auto member_sums = [&](const Real (&mine)[GROUP], uint32_t buffer, Real (&sum)[GROUP]) {
+#pragma unroll
+        for (uint32_t i = 0; i < GROUP; ++i)
+            if (on >> i & 1u) {
+                const Real ws = mh_wave_sum(mine[i]);
+                if (lane == 0) s_slot[(buffer * GROUP + i) * JUNCTION_WAVES + place[i]] = ws;
+            }
+        mh_lds_writes_landed();
+        __syncthreads();
+#pragma unroll
+        for (uint32_t i = 0; i < GROUP; ++i) {
+            Real v[JUNCTION_WAVES];
+#pragma unroll
+            for (uint32_t p = 0; p < JUNCTION_WAVES; ++p) v[p] = s_slot[(buffer * GROUP + i) * JUNCTION_WAVES + p];
+            Real acc = 0;
+#pragma unroll
+            for (uint32_t p = 0; p < JUNCTION_WAVES; ++p) acc = acc + v[p]; // a slot beyond the member's waves holds the +0 it was given: the same bits as not adding it
+            sum[i] = acc;
+        }
+    };
+    const Real zero = 0, most = std::numeric_limits<Real>::max();
+    // every slot starts as +0; the ones beyond a member's waves stay that way (acc, begun at +0, is never -0: acc + (+0) is acc)
+    if (threadIdx.x < 2 * GROUP * JUNCTION_WAVES) s_slot[threadIdx.x] = zero;
+    mh_lds_writes_landed();
+    __syncthreads();
+    // step 3: C[i][j], column j in round j; an object that is not on a side of both contributes +0.
+    // Step 4, per block: lane m holds the subset A with mask m = lane % 16.  What it keeps for the block is one matrix W: row i of
+    // M_A = (I + C_AA diag(K_A))^-1 (its columns in A) for a member of A, row i of C for one outside it -- built column by column as C
+    // arrives, then eliminated in place over the rows and columns of A, without pivoting, in ascending order: column p, once eliminated,
+    // receives column p of the inverse, which is the unit column until then, so the operations and their operands are those of the
+    // elimination of [B | I].
+    const uint32_t mask = lane % GROUP_SETS, full = (1u << n) - 1u;
+    const bool admissible = lane < GROUP_SETS && mask <= full && (mask & bilateral) == bilateral;
+    bool numbers_ok = true; // workgroup-uniform: every C_ij and C_ij K_j of the group is finite
+    Real W[GROUP][GROUP], c_own[GROUP];
+#pragma unroll
+    for (uint32_t j = 0; j < GROUP; ++j) {
+        Real mine[GROUP], col[GROUP];
+#pragma unroll
+        for (uint32_t i = 0; i < GROUP; ++i) mine[i] = (on >> j & 1u) ? fma_real(g_re[i].y, a[j].y, fma_real(g_re[i].x, a[j].x, zero)) : zero;
+        member_sums(mine, j & 1u, col);
+#pragma unroll
+        for (uint32_t i = 0; i < GROUP; ++i) {
+            const Real kc = col[i] * k[j];
+            if (i < n && j < n) numbers_ok = numbers_ok && col[i] >= -most && col[i] <= most && kc >= -most && kc <= most;
+            W[i][j] = (mask >> i & 1u) ? ((mask >> j & 1u) ? (i == j ? Real(1) + kc : kc) : zero) : col[i];
+            if (i == j) c_own[i] = col[i];
+        }
+    }
+    bool pivots_ok = true;
+#pragma unroll
+    for (uint32_t p = 0; p < GROUP; ++p) {
+        const bool in_p = mask >> p & 1u;
+        const Real pivot = W[p][p];
+        pivots_ok = pivots_ok && (!in_p || (pivot > Real(0) && pivot <= most)); // a finite number above 0 (a NaN fails both)
+        const Real r = Real(1) / pivot;
+        W[p][p] = in_p ? Real(1) : W[p][p];
+#pragma unroll
+        for (uint32_t j = 0; j < GROUP; ++j) W[p][j] = in_p ? W[p][j] * r : W[p][j];
+#pragma unroll
+        for (uint32_t i = 0; i < GROUP; ++i) {
+            if (i == p) continue;
+            const bool both = in_p && (mask >> i & 1u);
+            const Real t = W[i][p];
+            W[i][p] = both ? Real(0) : W[i][p];
+#pragma unroll
+            for (uint32_t j = 0; j < GROUP; ++j) W[i][j] = both ? W[i][j] - t * W[p][j] : W[i][j];
+        }
+    }
+    const bool solved = numbers_ok && __builtin_amdgcn_ballot_w64(admissible && !pivots_ok) == 0;
+    if (threadIdx.x == 0)
+        for (uint32_t i = 0; i < n; ++i) {
+            ga.compliance_out[G->member[i].row] = double(c_own[i]);
+            ga.status_out[G->member[i].row] = solved ? MH_JUNCTION_SOLVED : MH_JUNCTION_REFUSED;
+        }
+    for (uint32_t s0 = 0; s0 < frames; s0 += TS) {
+        const uint32_t sn = min(TS, frames - s0);
+        // this tile's approach samples, lane = sample (not finite: 0, as a drive's)
+        Real u_tile[GROUP] = {};
+#pragma unroll
+        for (uint32_t i = 0; i < GROUP; ++i)
+            if (i < n && lane < sn) u_tile[i] = finite_or_zero<Real>(ga.approach[size_t(G->member[i].row) * frames + s0 + lane]);
+        // the tile's excitation, parked where the output terms will go
+        for (uint32_t ds = 0; ds < sn; ++ds) {
+            Pair excite = {0, 0};
+            for (uint32_t t = 0; t < n_imp; ++t) {
+                const Real f = force[size_t(imp_idx[i0 + t]) * frames + s0 + ds];
+                excite += f * (t < IMP_REG ? g_reg[t] : *reinterpret_cast<const Pair *>(g_mem + size_t(t) * MODES_PER_WAVE + 2 * lane));
+            }
+            *reinterpret_cast<Pair *>(s_term + ds * PITCH + 2 * lane) = excite;
+        }
+        Real f_tile[GROUP] = {};
+        for (uint32_t ds = 0; ds < sn; ++ds) {
+            const Pair excite = *reinterpret_cast<const Pair *>(s_term + ds * PITCH + 2 * lane); // what this lane parked
+            const Pair re = w.z_re * w.c_re - w.z_im * w.c_im + excite;
+            w.z_im = w.z_re * w.c_im + w.z_im * w.c_re;
+            Real mine[GROUP], d[GROUP], x[GROUP];
+#pragma unroll
+            for (uint32_t i = 0; i < GROUP; ++i)
+                mine[i] = fma_real(g_re[i].y, re.y, fma_real(g_im[i].y, w.z_im.y, fma_real(g_re[i].x, re.x, fma_real(g_im[i].x, w.z_im.x, zero))));
+            member_sums(mine, (s0 + ds) & 1u, d);
+#pragma unroll
+            for (uint32_t i = 0; i < GROUP; ++i) x[i] = lane_bcast(u_tile[i], ds) - d[i];
+            // this lane's subset: its candidate, and whether it is consistent
+            Real y[GROUP], f[GROUP];
+            bool consistent = admissible;
+            Real miss = 0; // by how much the subset fails: the largest -y_j of a unilateral member, or residual of a member outside it, above 0
+#pragma unroll
+            for (uint32_t i = 0; i < GROUP; ++i) {
+                Real acc = 0;
+#pragma unroll
+                for (uint32_t j = 0; j < GROUP; ++j) acc = (mask >> j & 1u) ? acc + W[i][j] * x[j] : acc;
+                y[i] = acc;
+                f[i] = (mask >> i & 1u) ? k[i] * acc : zero;
+            }
+#pragma unroll
+            for (uint32_t j = 0; j < GROUP; ++j) {
+                Real push = 0;
+#pragma unroll
+                for (uint32_t i = 0; i < GROUP; ++i) push = (mask >> i & 1u) ? push + W[j][i] * f[i] : push;
+                const bool inside = mask >> j & 1u;
+                const Real over = inside ? ((bilateral >> j & 1u) ? zero : zero - y[j]) : x[j] - push;
+                const bool fits = inside ? ((bilateral >> j & 1u) || y[j] > Real(0)) : !(over > Real(0));
+                consistent = consistent && fits;
+                miss = over > miss ? over : miss;
+            }
+            uint64_t found = __builtin_amdgcn_ballot_w64(consistent);
+            const bool clamp = found == 0; // no subset consistent (rounding, on a boundary between two of them): the one that fails by least, clamped
+            if (clamp) {
+                Real least = admissible ? miss : most; // over lanes 0 .. 15: one row of the DPP tree
+                Real other = mh_dpp_move<MH_DPP_QUAD_XOR1>(least);
+                least = other < least ? other : least;
+                other = mh_dpp_move<MH_DPP_QUAD_XOR2>(least);
+                least = other < least ? other : least;
+                other = mh_dpp_move<MH_DPP_ROW_HALF_MIRROR>(least);
+                least = other < least ? other : least;
+                other = mh_dpp_move<MH_DPP_ROW_MIRROR>(least);
+                least = other < least ? other : least;
+                found = __builtin_amdgcn_ballot_w64(admissible && miss == least);
+            }
+            const uint32_t taken = found ? uint32_t(__builtin_ctzll(found)) : full; // (found = 0: a NaN; the full set stands in)
+            Real f_now[GROUP];
+#pragma unroll
+            for (uint32_t i = 0; i < GROUP; ++i) {
+                // (off the lane's subset y[i] is a product with a row of C, not a displacement: the force there is +0, clamped or not)
+                const Real clamped = (mask >> i & 1u) ? ((bilateral >> i & 1u) ? f[i] : k[i] * (y[i] > Real(0) ? y[i] : zero)) : zero;
+                f_now[i] = solved ? lane_bcast(clamp ? clamped : f[i], taken) : zero;
+            }
+            // step 5: the members on this wave's object, in ascending order
+            Pair z = re;
+#pragma unroll
+            for (uint32_t i = 0; i < GROUP; ++i)
+                if (on >> i & 1u) z = z + a[i] * f_now[i];
+            w.z_re = z;
+            *reinterpret_cast<Pair *>(s_term + ds * PITCH + 2 * lane) = w.p_im * w.z_im + w.p_re * w.z_re;
+#pragma unroll
+            for (uint32_t i = 0; i < GROUP; ++i)
+                if (lane == ds) f_tile[i] = f_now[i];
+        }
+        // member i's row: one store per tile, by wave i of the launch (or the wave that stands for it in a smaller one)
+#pragma unroll
+        for (uint32_t i = 0; i < GROUP; ++i)
+            if (i < n && wave == i % block_waves && lane < sn) ga.force_out[size_t(G->member[i].row) * frames + s0 + lane] = f_tile[i];
+        // the turn-around of bank_modes: every chunk's 8 terms added in mode order
+        mh_lds_writes_landed();
+        __syncthreads();
+        chunk_sums<TS>(s_term, w, lane, s0, sn, partial, frames);
+        __syncthreads();
+    }
+    store_wave(b, w, lane, chunk_energy);
+}
 #undef BANK_MODES_PARAMS
 #undef BANK_MODES_ARGS
 
@@ -933,6 +1196,7 @@ template<typename Real> struct BankImpl {
     std::vector<int32_t> pick_dealt;
     DevArray<Real> junction_gain; // the coupled kernel's scratch gain rows
     std::vector<uint8_t> on_junction; // per object: on a side of a junction of this call that was not left out
+    std::vector<uint32_t> kept_rows; // the caller's indices of those junctions
     // per-block scratch
     Arena arena;
     DevArray<Real> force, click, partial, chunk_energy, gain_scratch, rout;
@@ -993,6 +1257,7 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
     const size_t o_signals = A.take(size_t(n_drives) * frames * sizeof(float));
     const size_t o_pick_ptr = A.take((n_dealt + 2) * 4), o_pick_dev = A.take((n_pickups + 1) * sizeof(PickupDev<Real>)), o_pick_rows = A.take((n_pickups + 1) * sizeof(PickupRows));
     const size_t o_excited = A.take((n_dealt + 1) * 4), o_junctions = A.take((n_junctions + 1) * sizeof(JunctionDev<Real>)), o_approach = A.take(size_t(n_junctions) * frames * sizeof(float));
+    const size_t o_groups = A.take((n_junctions / 2 + 1) * sizeof(GroupDev<Real>));
     const size_t both_end = A.used;
     // (written by the kernels straight into the pinned arena -- no copy back: the host sees them once the block's last kernel has
     // raised the sequence number)
@@ -1013,19 +1278,24 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
         if (deal_objects[d] < B.n_objects) B.dealt_of_object[deal_objects[d]] = int32_t(d);
     // ---- junctions: the ones the coupled kernel may follow, one workgroup each; everything else is left out with a zero row ----
     uint32_t n_coupled = 0, coupled_waves = 0, widest_junction = 0;
+    uint32_t n_groups = 0, widest_group = 0, grouped_members = 0; // components of two or more junctions: k_bank_modes_grouped, one workgroup each
     bool any_hertz = false; // a kept junction with MH_JUNCTION_HERTZ: the call takes the entry that has the solve
+    B.kept_rows.clear();
     if (n_junctions) {
         JunctionDev<Real> *jd = A.h<JunctionDev<Real>>(o_junctions);
+        GroupDev<Real> *gd = A.h<GroupDev<Real>>(o_groups);
         B.on_junction.assign(B.n_objects, 0);
         auto side_ok = [&](const mh_junction_side &sd) {
             if (sd.object >= B.n_objects || B.h_mode_count[sd.object] == 0 || B.dealt_of_object[sd.object] < 0 || render_count[B.dealt_of_object[sd.object]] == 0) return false;
-            if (B.on_junction[sd.object]) return false; // one junction per object
             return B.blend_ok(sd);
         };
+        auto side_waves = [&](const mh_junction_side &sd) { return waves_of(render_count[B.dealt_of_object[sd.object]]); };
         auto side_dev = [&](const mh_junction_side &sd) {
             const uint32_t d = uint32_t(B.dealt_of_object[sd.object]);
             return JunctionSideDev<Real>{d, waves_of(render_count[d]), blend_dev<Real>(sd)};
         };
+        // which junctions are kept, and which share objects (modalhip_groups.hpp: one junction per object unless both carry MH_JUNCTION_SHARED)
+        MhJunctionGroups grouping(B.n_objects);
         for (uint32_t j = 0; j < n_junctions; ++j) {
             const mh_junction &m = junctions[j];
             status_out[j] = MH_JUNCTION_LEFT_OUT;
@@ -1033,23 +1303,63 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
             const bool two_sided = m.b.object != MH_NO_OBJECT;
             if (!std::isfinite(m.stiffness) || m.stiffness < 0 || !side_ok(m.a) || (two_sided && (m.a.object == m.b.object || !side_ok(m.b)))) continue;
             if ((m.flags & MH_JUNCTION_HERTZ) && (m.flags & MH_JUNCTION_BILATERAL)) continue; // the Hertz law is unilateral
-            JunctionDev<Real> dev{{side_dev(m.a), two_sided ? side_dev(m.b) : JunctionSideDev<Real>{}}, Real(m.stiffness), m.flags, j, coupled_waves};
-            const uint32_t w = dev.side[0].waves + dev.side[1].waves;
-            if (w > JUNCTION_WAVES) continue; // more modes than one workgroup holds
+            if (grouping.add(j, m.flags, m.a.object, side_waves(m.a), m.b.object, two_sided ? side_waves(m.b) : 0u) < 0) continue;
             B.on_junction[m.a.object] = 1;
             if (two_sided) B.on_junction[m.b.object] = 1;
+            B.kept_rows.push_back(j);
+        }
+        // a component of one junction is an ordinary junction: the coupled kernel, one workgroup each, in call order
+        for (const uint32_t j : B.kept_rows) {
+            const mh_junction &m = junctions[j];
+            if (grouping.components[grouping.of_object[m.a.object]].members.size() != 1) continue;
+            const bool two_sided = m.b.object != MH_NO_OBJECT;
+            JunctionDev<Real> dev{{side_dev(m.a), two_sided ? side_dev(m.b) : JunctionSideDev<Real>{}}, Real(m.stiffness), m.flags, j, coupled_waves};
+            const uint32_t w = dev.side[0].waves + dev.side[1].waves;
             jd[n_coupled++] = dev;
             any_hertz = any_hertz || (m.flags & MH_JUNCTION_HERTZ) != 0;
             coupled_waves += w;
             widest_junction = std::max(widest_junction, w);
         }
+        // a larger one is a group: its distinct objects in the order its members name them, a wave per 128 rendered modes of each
+        for (const auto &comp : grouping.components) {
+            if (comp.members.size() < 2) continue;
+            GroupDev<Real> g{};
+            g.n = uint32_t(comp.members.size());
+            g.first_wave = coupled_waves;
+            uint32_t object_of_slot[JUNCTION_WAVES];
+            auto slot_of = [&](const mh_junction_side &sd) {
+                for (uint32_t s = 0; s < g.n_objects; ++s)
+                    if (object_of_slot[s] == sd.object) return s;
+                if (g.n_objects == JUNCTION_WAVES) mh_throw(MH_EINVAL, "a junction group of more than %u objects", JUNCTION_WAVES); // (the grouping admits none)
+                const uint32_t s = g.n_objects++, d = uint32_t(B.dealt_of_object[sd.object]);
+                object_of_slot[s] = sd.object;
+                g.dealt[s] = d, g.wave0[s] = g.n_waves, g.waves[s] = waves_of(render_count[d]);
+                g.n_waves += g.waves[s];
+                return s;
+            };
+            for (uint32_t i = 0; i < g.n; ++i) {
+                const mh_junction &m = junctions[comp.members[i]];
+                const bool two_sided = m.b.object != MH_NO_OBJECT;
+                GroupMemberDev<Real> &dev = g.member[i];
+                dev.k = Real(m.stiffness), dev.flags = m.flags, dev.row = comp.members[i];
+                dev.slot[0] = slot_of(m.a), dev.at[0] = blend_dev<Real>(m.a);
+                dev.slot[1] = two_sided ? slot_of(m.b) : NO_SLOT;
+                if (two_sided) dev.at[1] = blend_dev<Real>(m.b);
+            }
+            if (g.n_waves > JUNCTION_WAVES) mh_throw(MH_EINVAL, "a junction group of %u waves", g.n_waves); // (the grouping admits none)
+            gd[n_groups++] = g;
+            grouped_members += g.n;
+            coupled_waves += g.n_waves;
+            widest_group = std::max(widest_group, g.n_waves);
+        }
     }
+    const bool any_junction = n_coupled || n_groups;
     chunk_base[0] = 0;
     uint32_t main_waves = 0; // the main launch's waves: every dealt object that is not on a junction's side
     for (uint32_t d = 0; d < n_dealt; ++d) {
         const uint32_t count = render_count[d];
         chunk_base[d + 1] = chunk_base[d] + (count + LANES - 1) / LANES;
-        if (!(n_coupled && deal_objects[d] < B.n_objects && B.on_junction[deal_objects[d]]))
+        if (!(any_junction && deal_objects[d] < B.n_objects && B.on_junction[deal_objects[d]]))
             for (uint32_t k = 0; k < count; k += MODES_PER_WAVE) waves[main_waves++] = {d, k};
         imp_ptr[d + 1] = 0;
     }
@@ -1085,7 +1395,7 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
     }
     // an object on a junction's side is excited for the block as one with a drive is: where the per-object pass asks "has it rows", it
     // sees one more for such an object (a list of its own: the kernels' row lists stay what they are)
-    if (n_coupled) {
+    if (any_junction) {
         uint32_t *excited = A.h<uint32_t>(o_excited);
         excited[0] = 0;
         for (uint32_t d = 0; d < n_dealt; ++d)
@@ -1106,7 +1416,7 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
             pickup_read[q] = 0;
             pick_rows[q] = {0, 0};
             if (m.object >= B.n_objects || B.h_mode_count[m.object] == 0 || m.advance > 2) continue;
-            if (n_coupled && B.on_junction[m.object]) continue; // its waves are the coupled kernel's, which reads for no pickup (in this version)
+            if (any_junction && B.on_junction[m.object]) continue; // its waves are the coupled kernel's, which reads for no pickup (in this version)
             if (!B.blend_ok(m) || B.picks_on[m.object] >= MH_PICKUPS_PER_OBJECT) continue;
             ++B.picks_on[m.object];
             pickup_read[q] = 1;
@@ -1150,7 +1460,7 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
         himp[n_impacts + j] = {m.object, m.ex_pos, 0, 0, Real(m.jx), Real(m.jy), Real(m.jz), 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     }
     if (n_drives) std::copy(signals, signals + size_t(n_drives) * frames, A.h<float>(o_signals));
-    if (n_coupled) std::copy(approach, approach + size_t(n_junctions) * frames, A.h<float>(o_approach));
+    if (any_junction) std::copy(approach, approach + size_t(n_junctions) * frames, A.h<float>(o_approach));
     HIP_CHECK(hipMemcpyAsync(A.dev, A.host, both_end, hipMemcpyHostToDevice, st));
     // ---- device passes ----
     Real *d_out_gain = A.d<Real>(o_out_gain), *d_listener = A.d<Real>(o_listener), *d_out = A.d<Real>(o_out);
@@ -1188,6 +1498,14 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
             TimedLaunch timed(ctx, MH_KERNEL_JUNCTION, double(n_coupled) * double(frames));
             launch_modes(any_hertz ? k_bank_modes_coupled_hertz<Real> : &k_bank_modes_coupled<Real>, n_coupled, widest_junction * WAVE, coupled_lds<Real>(widest_junction), B.junction_gain, ca);
         }
+        if (n_groups) { // the groups' objects: a launch of their own, one workgroup per group
+            ensure(ctx, B.junction_gain, size_t(coupled_waves + JUNCTION_WAVES) * max_imp * MODES_PER_WAVE);
+            static PerDeviceOnce attr;
+            attr.run(ctx->device, [] { HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_bank_modes_grouped<Real>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); });
+            const GroupedArgs<Real> ga{B.defl_gain, A.d<GroupDev<Real>>(o_groups), A.d<float>(o_approach), A.hd<Real>(o_junction_force), A.hd<double>(o_compliance), A.hd<uint32_t>(o_status)};
+            TimedLaunch timed(ctx, MH_KERNEL_JUNCTION, double(grouped_members) * double(frames));
+            launch_modes(&k_bank_modes_grouped<Real>, n_groups, widest_group * WAVE, grouped_lds<Real>(widest_group), B.junction_gain, ga);
+        }
         if (main_waves) {
             uint64_t rendered_modes = 0;
             for (uint32_t d = 0; d < n_dealt; ++d) rendered_modes += render_count[d];
@@ -1222,7 +1540,7 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
         constexpr int SW = 16;
         const uint32_t strips = div_up(frames, SW), sum_slices = (n_dealt ? n_renderers : 0) + (streamed_clicks ? 1 : 0);
         const uint32_t object_slices = n_dealt ? div_up(n_dealt, strips * (1024 / WAVE)) : 0;
-        ObjectPassArgs<Real> objects{B.cols(), A.d<uint32_t>(o_deal), A.d<uint32_t>(o_count), A.d<uint32_t>(o_chunk_base), A.d<uint32_t>(n_coupled ? o_excited : o_imp_ptr), d_out_gain, B.chunk_energy, n_dealt,
+        ObjectPassArgs<Real> objects{B.cols(), A.d<uint32_t>(o_deal), A.d<uint32_t>(o_count), A.d<uint32_t>(o_chunk_base), A.d<uint32_t>(any_junction ? o_excited : o_imp_ptr), d_out_gain, B.chunk_energy, n_dealt,
                                      A.hd<double>(o_energy), A.hd<uint32_t>(o_live), A.hd<uint8_t>(o_silenced), A.d<uint32_t>(o_tuned), A.hd<double>(o_modal)};
         static PerDeviceOnce attr;
         attr.run(ctx->device, [] { HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_bank_post<Real, SW>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); });
@@ -1248,9 +1566,7 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
     if (n_junctions) { // rows, compliances and statuses of the solved ones; a junction that was left out keeps its zero row
         Real *force_out = static_cast<Real *>(force_out_v);
         std::fill(force_out, force_out + size_t(n_junctions) * frames, Real(0));
-        const JunctionDev<Real> *jd = A.h<JunctionDev<Real>>(o_junctions);
-        for (uint32_t c = 0; c < n_coupled; ++c) {
-            const uint32_t j = jd[c].row;
+        for (const uint32_t j : B.kept_rows) {
             std::copy(A.h<Real>(o_junction_force) + size_t(j) * frames, A.h<Real>(o_junction_force) + size_t(j + 1) * frames, force_out + size_t(j) * frames);
             compliance_out[j] = A.h<double>(o_compliance)[j];
             status_out[j] = uint8_t(A.h<uint32_t>(o_status)[j]);

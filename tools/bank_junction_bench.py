@@ -18,6 +18,19 @@ the exciter dipping in and out of the surface.
                                                                              of this tree, and this tree's Hertz calls, J = 1, 16, 64, interleaved,
                                                                              every run a fresh process -> profiles/bank_hertz.json
 
+    python tools/bank_junction_bench.py --members 3 --junctions 48            16 groups of three junctions (MH_JUNCTION_SHARED): exciter junctions at
+                                                                             three points of each of 16 objects, solved together per frame;
+                                                                             with --ungrouped the same 48 junctions on 48 objects of their own
+                                                                             (no flag: the coupled kernel, the like-for-like the parent renders)
+    python tools/bank_junction_bench.py --groups --against T [--runs 3]      the unchanged paths -- J = 0 and the all-linear ungrouped calls J = 1, 16,
+                                                                             64 of a built checkout T of the parent commit and of this tree, and
+                                                                             tools/bank_bench.py of both, interleaved, every run a fresh process --
+                                                                             and this tree's groups, G = 1, 16, 64 of n = 2, 3, 4, beside the same
+                                                                             junctions ungrouped (256 objects) -> profiles/bank_groups.json
+
+(The coupled kernel and the group kernel are timed under one kernel class, 6: a block that holds lone junctions AND groups makes two
+launches of it, and `coupled_kernel_us_per_block`, the class total over its launch count, is then per launch.  No mode here mixes the two.)
+
 The comparison also runs the unchanged tools/bank_bench.py of both trees (all_live.ms_per_block).  Kernel times per block are the
 library's kernel-class timers: class 2 the resonator kernel of the objects off the junctions, class 6 the coupled kernel.  The coupled
 kernel is one workgroup per junction running a serial chain per frame; `coupled_cycles_per_frame` is its time over the block's frames at
@@ -44,20 +57,28 @@ def sides_of(j, sides):
     return (j,) if sides == 1 else (2 * j, 2 * j + 1)
 
 
-def measure(tree, entry, junctions, sides, objects, blocks, renderers, forces_path, save_forces, law="linear"):
+def measure(tree, entry, junctions, sides, objects, blocks, renderers, forces_path, save_forces, law="linear", members=0, ungrouped=False):
+    """members >= 2: the junctions are groups of `members` exciter junctions, junction q at point q % members of object q // members with
+    the shared flag -- or, ungrouped, of object q without it."""
     sys.path.insert(0, tree)
     from mesheditor_amd import bank as hipbank
     from tools import bank_bench
     assert junctions * sides <= objects
+    if members:
+        assert entry == "coupled" and sides == 1 and law == "linear" and 2 <= members <= POINTS and junctions % members == 0
+    where = lambda q: (q, 1) if not members else ((q, q % members) if ungrouped else (q // members, q % members))  # (object, point) of junction q's side a
     sc = bank_bench.build(objects, MODES, renderers)
     out = np.zeros(BLOCK, np.float32)
     drives = [hipbank.Drive(o, o % POINTS, 1.0, 0.5, 0.125) for o in range(objects)]
     signals = (0.01 * np.random.default_rng(1).standard_normal((objects, BLOCK))).astype(np.float32)
     peak_force, kept = [0.0], []
     if entry == "coupled":
-        side = lambda o, sign: hipbank.JunctionSide.of(o, 1, (1.0, 0.0, 0.0), tuple(sign * v for v in NORMAL), 2.0)
+        side = lambda o, sign, point=1: hipbank.JunctionSide.of(o, point, (1.0, 0.0, 0.0), tuple(sign * v for v in NORMAL), 2.0)
         flag = {"hertz": True} if law == "hertz" else {}  # (a tree from before the Hertz law takes no such argument)
-        make = lambda k: (hipbank.Junction * max(junctions, 1))(*[hipbank.Junction.of(side(sides_of(j, sides)[0], 1.0), side(sides_of(j, sides)[1], -1.0) if sides == 2 else None, k[j], **flag)
+        if members and not ungrouped:
+            flag = {"shared": True}
+        first = lambda j: side(where(j)[0], 1.0, where(j)[1]) if members else side(sides_of(j, sides)[0], 1.0)
+        make = lambda k: (hipbank.Junction * max(junctions, 1))(*[hipbank.Junction.of(first(j), side(sides_of(j, sides)[1], -1.0) if sides == 2 else None, k[j], **flag)
                                                                     for j in range(junctions)])
         rows = (hipbank.Drive * objects)(*drives)
         none = np.zeros((junctions, BLOCK), np.float32)
@@ -66,7 +87,7 @@ def measure(tree, entry, junctions, sides, objects, blocks, renderers, forces_pa
         if junctions:
             _, _, _, comp, status = sc.render_coupled(out, rows, signals, [], make([0.0] * junctions), none)
             assert (status == 1).all() and (comp > 0).all()
-            picks = (hipbank.Pickup * junctions)(*[hipbank.Pickup.of(sides_of(j, sides)[0], 1, (1.0, 0.0, 0.0), NORMAL, 2.0, 1) for j in range(junctions)])
+            picks = (hipbank.Pickup * junctions)(*[hipbank.Pickup.of(where(j)[0] if members else sides_of(j, sides)[0], where(j)[1], (1.0, 0.0, 0.0), NORMAL, 2.0, 1) for j in range(junctions)])
             reads, _ = sc.render_read(out, rows, signals, picks)
             free = np.abs(reads).max(axis=1)
             t = np.arange(BLOCK)
@@ -114,7 +135,7 @@ def measure(tree, entry, junctions, sides, objects, blocks, renderers, forces_pa
     sc.close()
     t = np.array(times)
     coupled_us = 1e3 * kj["total_ms"] / max(1, kj["launches"])
-    return {"entry": entry, "law": law, "junctions": junctions, "sides": sides, "objects": objects, "modes_per_object": MODES, "blocks": blocks, "ms_per_block": 1e3 * float(t.mean()),
+    return {"entry": entry, "law": law, "junctions": junctions, "sides": sides, "members": members, "grouped": bool(members) and not ungrouped, "objects": objects, "modes_per_object": MODES, "blocks": blocks, "ms_per_block": 1e3 * float(t.mean()),
             "ms_per_block_median": 1e3 * float(np.median(t)), "ms_per_block_p99": 1e3 * float(np.quantile(t, 0.99)), "kernel_us_per_block": 1e3 * k["total_ms"] / max(1, k["launches"]),
             "coupled_kernel_us_per_block": coupled_us, "coupled_us_per_frame": coupled_us / BLOCK, "coupled_cycles_per_frame": coupled_us / BLOCK * ENGINE_MHZ,
             "real_time_ms_per_block": 1e3 * BLOCK / SR}
@@ -222,6 +243,56 @@ def compare_laws(parent, runs, objects, blocks, renderers, out_path):
     print(json.dumps(result["summary"]))
 
 
+def compare_groups(parent, runs, objects, blocks, renderers, out_path, all_live):
+    """The unchanged paths of the parent and of this tree -- the same kernels: the new figures have to land within the parent's own spread --
+    and this tree's groups beside the same junctions ungrouped."""
+    me = os.path.abspath(__file__)
+    common = ["--objects", str(objects), "--blocks", str(blocks), "--renderers", str(renderers)]
+    result = {"workload": f"{objects} objects x {MODES} modes @48k, {BLOCK}-frame blocks, fp32, {renderers} renderers, one drive on every object in every block; J ungrouped one-sided "
+                          "junctions, or G groups of n exciter junctions on one object each (K C = 10)", "runs_each": runs, "all_live": {"parent": [], "new": []},
+              "j0": {"parent_driven": [], "new_coupled": []}, "ungrouped": {}, "groups": {}}
+
+    def save():
+        os.makedirs(os.path.dirname(out_path), exist_ok=True)
+        with open(out_path, "w") as f:
+            json.dump(result, f, indent=1)
+    q = subprocess.run(["timeout", "-k", "10", "300", sys.executable, "-c", "import torch; p = torch.cuda.get_device_properties(0); print(p.name, p.gcnArchName, '%d CUs' % p.multi_processor_count, '|', torch.version.hip)"], capture_output=True, text=True)
+    if q.returncode != 0:
+        raise SystemExit("no GPU to measure on: " + q.stderr[-2000:])
+    result["device"], result["hip"] = (v.strip() for v in q.stdout.strip().splitlines()[-1].split("|"))
+    for _ in range(runs):
+        for name, tree in (("parent", parent), ("new", HERE)) if all_live else ():
+            r = child([os.path.join(tree, "tools", "bank_bench.py")], 600)
+            result["all_live"][name].append({"ms_per_block": r["all_live"]["ms_per_block"], "kernel_us_per_block": r["all_live"]["kernel_us_per_block"]})
+        result["j0"]["parent_driven"].append(child([me, "--entry", "replay", "--junctions", "0", "--tree", parent] + common))
+        result["j0"]["new_coupled"].append(child([me, "--entry", "coupled", "--junctions", "0"] + common))
+        for j in JUNCTIONS[1:]:
+            row = result["ungrouped"].setdefault("J = %d" % j, {"parent": [], "new": []})
+            row["parent"].append(child([me, "--tree", parent, "--junctions", str(j)] + common))
+            row["new"].append(child([me, "--junctions", str(j)] + common))
+            save()
+        for n in (2, 3, 4):
+            for g in (1, 16, 64):
+                row = result["groups"].setdefault("G = %d, n = %d" % (g, n), {"grouped": [], "ungrouped": []})
+                row["grouped"].append(child([me, "--members", str(n), "--junctions", str(g * n)] + common))
+                row["ungrouped"].append(child([me, "--members", str(n), "--junctions", str(g * n), "--ungrouped"] + common))
+                save()
+    med = lambda rows, key: float(np.median([r[key] for r in rows])) if rows else None
+    spread = lambda rows, key: (max(r[key] for r in rows) / min(r[key] for r in rows)) if rows else None
+    pair = lambda old, new: {"parent_ms_per_block": [r["ms_per_block"] for r in old], "new_ms_per_block": [r["ms_per_block"] for r in new], "parent_spread_max_over_min": spread(old, "ms_per_block"),
+                             "new_median_over_parent_median": (med(new, "ms_per_block") / med(old, "ms_per_block")) if old else None,
+                             "parent_kernel_us_per_block": med(old, "kernel_us_per_block"), "new_kernel_us_per_block": med(new, "kernel_us_per_block"),
+                             "parent_coupled_kernel_us_per_block": med(old, "coupled_kernel_us_per_block"), "new_coupled_kernel_us_per_block": med(new, "coupled_kernel_us_per_block")}
+    result["summary"] = {"real_time_ms_per_block": 1e3 * BLOCK / SR, "all_live": pair(result["all_live"]["parent"], result["all_live"]["new"]) if all_live else None,
+                         "j0": pair(result["j0"]["parent_driven"], result["j0"]["new_coupled"]), "ungrouped": {name: pair(row["parent"], row["new"]) for name, row in result["ungrouped"].items()},
+                         "groups": {name: {"grouped_ms_per_block": med(row["grouped"], "ms_per_block"), "ungrouped_ms_per_block": med(row["ungrouped"], "ms_per_block"),
+                                           "grouped_kernel_us_per_block": med(row["grouped"], "coupled_kernel_us_per_block"), "ungrouped_kernel_us_per_block": med(row["ungrouped"], "coupled_kernel_us_per_block"),
+                                           "grouped_cycles_per_frame": med(row["grouped"], "coupled_cycles_per_frame"), "ungrouped_cycles_per_frame": med(row["ungrouped"], "coupled_cycles_per_frame")}
+                                    for name, row in result["groups"].items()}}
+    save()
+    print(json.dumps(result["summary"]))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--entry", choices=["coupled", "replay"], default="coupled")
@@ -236,6 +307,9 @@ def main():
     ap.add_argument("--law", choices=["linear", "hertz"], default="linear", help="coupled: the junctions' law")
     ap.add_argument("--laws-against", help="built checkout of the parent commit: its all-linear calls, this tree's, and this tree's Hertz calls -> profiles/bank_hertz.json")
     ap.add_argument("--against", help="built checkout of the parent commit: run the whole comparison")
+    ap.add_argument("--members", type=int, default=0, help="coupled: the junctions are groups of this many exciter junctions on one object each (2 ... 4)")
+    ap.add_argument("--ungrouped", action="store_true", help="with --members: the same junctions on objects of their own, without the shared flag")
+    ap.add_argument("--groups", action="store_true", help="with --against: the unchanged paths of both trees and this tree's groups -> profiles/bank_groups.json")
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--no-all-live", action="store_true", help="skip tools/bank_bench.py of both trees")
     ap.add_argument("--out", default=os.path.join(HERE, "profiles", "bank_junctions.json"))
@@ -243,10 +317,13 @@ def main():
     if a.laws_against:
         out = a.out if a.out != ap.get_default("out") else os.path.join(HERE, "profiles", "bank_hertz.json")
         compare_laws(os.path.abspath(a.laws_against), a.runs, a.objects, a.blocks, a.renderers, out)
+    elif a.against and a.groups:
+        out = a.out if a.out != ap.get_default("out") else os.path.join(HERE, "profiles", "bank_groups.json")
+        compare_groups(os.path.abspath(a.against), a.runs, a.objects if a.objects != ap.get_default("objects") else 256, a.blocks, a.renderers, out, not a.no_all_live)
     elif a.against:
         compare(os.path.abspath(a.against), a.runs, a.objects, a.blocks, a.renderers, a.out, not a.no_all_live)
     else:
-        print(json.dumps(measure(os.path.abspath(a.tree), a.entry, a.junctions, a.sides, a.objects, a.blocks, a.renderers, a.forces, a.save_forces, a.law)))
+        print(json.dumps(measure(os.path.abspath(a.tree), a.entry, a.junctions, a.sides, a.objects, a.blocks, a.renderers, a.forces, a.save_forces, a.law, a.members, a.ungrouped)))
 
 
 if __name__ == "__main__":
