@@ -286,7 +286,7 @@ int mh_bank_render_read(mh_bank *, uint32_t frames, float click_gain, uint32_t n
  * surface renderer, SolveChannelStep in src/audio/surface/, with a linear law): a unilateral -- or, MH_JUNCTION_BILATERAL, bilateral --
  * linear spring of stiffness K between a contact point on one bank object (side a) and either a second bank object (side b) or an
  * exciter the caller moves (b.object = MH_NO_OBJECT), solved implicitly once per frame inside the render call.  Passed with the block it
- * acts in; no state between blocks.
+ * acts in; no state between blocks (but a damped junction's carry: "Contact damping" below).
  * A side is a pickup's contact point and a drive's direction in one record; (nx, ny, nz) is the direction in which the junction pushes
  * that side.  Per mode k of the side's object, in the bank's precision, with `shape` the pickup's blend (above):
  *   a[k]    = RadiationGain[k] * (shape_x*nx + shape_y*ny + shape_z*nz)            the drive gain (weights {1,0,0}: a drive's gain, bit for bit)
@@ -336,8 +336,8 @@ int mh_bank_render_read(mh_bank *, uint32_t frames, float click_gain, uint32_t n
  * Status of a Hertz junction: MH_JUNCTION_REFUSED when C < 0, or C or K*C is not finite (1 + K*C plays no part); C = 0 is solved, f = K*x^1.5.
  * A refused junction gives a zero row and its objects render as with K = 0, as above.
  * MH_JUNCTION_HERTZ | MH_JUNCTION_BILATERAL is left out (status 0, a zero row, C = 0): the law has no tension branch.  Every other
- * left-out kind is as above.  Not in this version: a damped (Hunt-Crossley) or hysteretic law, state between blocks, friction, roughness,
- * other exponents.
+ * left-out kind is as above.  Not in this version: a hysteretic law, friction, roughness, other exponents (the damped -- Hunt-Crossley --
+ * law and its state between blocks: "Contact damping" below).
  *
  * Groups, flags & MH_JUNCTION_SHARED: several junctions on one object (a bowl on three points, a table under several objects, a bar on two
  * supports under a mallet).  A junction with the flag may name an object that is already on a side of an earlier kept junction, provided
@@ -379,8 +379,53 @@ int mh_bank_render_read(mh_bank *, uint32_t frames, float click_gain, uint32_t n
  * than one junction, and one that would join a component that holds a Hertz junction (the Hertz solve in more than one dimension is not in
  * this version); a flagged junction on an object of a kept unflagged one.  Two junctions between the same pair of objects, at different
  * points, are a legal group.  Pickups on a junction's object stay left out.  MH_JUNCTION_GROUP = 4 is what a wave's registers hold: one
- * gain triple per member per lane, 195 VGPRs in fp64 (118 in fp32), nothing in scratch.  Not in this version, as above: damped laws,
- * friction, roughness, state between blocks. */
+ * gain triple per member per lane, 195 VGPRs in fp64 (118 in fp32), nothing in scratch.  Not in this version, as above: damping in
+ * groups, friction, roughness.
+ *
+ * Contact damping, flags & MH_JUNCTION_DAMPED (mh_bank_render_damped only: mh_bank_render_coupled ignores the bit): the Hunt-Crossley
+ * term of the reference's surface renderer (DampingFactor = 1.5 (1 - e) ContactDamping, src/audio/surface/).  The junction obeys
+ *     f = K * phi(y) * max(1 + l*(y - y_p), 0),    phi(y) = max(y, 0), or max(y, 0)^1.5 with MH_JUNCTION_HERTZ,
+ * where y = x - C*f is the compression of frame s + 1 (the quantity step 4 is implicit in), y_p the compression the previous frame's
+ * solve left (signed: a negative value is a gap) and l >= 0 the damping in 1/m per frame (damping[j]; a caller with D in s/m passes
+ * l = D * sample rate).  The max(..., 0) is the non-adhesion clamp: a contact that opens faster than 1/l per frame gives no force.
+ * Steps 1, 2, 3 and 5 stay bit for bit; step 4 becomes the implicit solve of this law, so that f[s] = K phi(y[s]) max(1 + l (y[s] -
+ * y[s-1]), 0) holds as an identity.  One fixed expression tree per law, every operation rounded to the bank's precision, nothing
+ * contracted, no trip count that depends on data; c = K*C and cl = c*l are formed once per block; min(a, b) is b < a ? b : a; on a frame
+ * without history (below) l = 0, cl = 0 and y_p = 0 in every expression:
+ *   4d. x = u[s] - d.  If x > 0 fails (a NaN included): f = +0, y = x.  Otherwise m_x = 1 + l*(x - y_p); if m_x > 0 fails: f = +0, y = x
+ *       (exact, not a heuristic: g(y) = y + c phi(y) max(1 + l (y - y_p), 0) - x is convex and increasing, and its root lies above the
+ *       kink y_p - 1/l exactly when m_x > 0).  Otherwise, with m0 = 1 - l*y_p:
+ *       linear:  B = 1 + c*m0;  r = sqrt(B*B + (4*cl)*x);  y = min(x, B >= 0 ? (2*x)/(B + r) : (r - B)/(2*cl));
+ *                (B < 0 implies cl > 0; x bounds the root from above.  Where B*B overflows -- |c*(1 - l*y_p)| above 1.8e19 in float, 1.3e154
+ *                in double, far outside any physical damping -- the min keeps y and f finite and f >= 0, NOT accurate: r is infinite there,
+ *                so y = 0 and f = 0 for B >= 0, and y = x for B < 0.  The quadratic is not rescaled: its bits in the range that occurs
+ *                are what the tree above gives.)
+ *                m = 1 + l*(y - y_p);  if (!(m > 0)) m = 0;  f = (K*y)*m;
+ *       Hertz:   big = the largest finite number;  p5 = cl > 0 ? exp2(0.4*log2(x/cl)) : big;
+ *                if (m0 >= 0) { cm = c*m0;  t = cbrt(x/cm);  g = cm > 0 ? t*t : big;  y = min(min(x, g), p5); }
+ *                else         { ylo = -m0/l;  lin = x/((cl*ylo)*sqrt(ylo));  y = min(x, ylo + min(lin, p5)); }
+ *                six times:   r = sqrt(y);  m = 1 + l*(y - y_p);  q = (c*y)*r;
+ *                             y = y - ((y + q*m) - x) / ((1 + ((1.5*c)*r)*m) + q*l);
+ *                m = 1 + l*(y - y_p);  if (!(m > 0)) m = 0;  f = ((K*y)*sqrt(y))*m;
+ *       Every candidate start bounds the root from above (x; the roots of the equation with one of its terms alone), so Newton's steps
+ *       descend on a convex increasing function.  Measured in float and in double over c (Hertz: c sqrt(x)) = 1e-8 ... 1e8, x = 1e-12 ... 1,
+ *       l*x = 0 and 1e-6 ... 1e6, y_p/x in [-3, 3], against bisection in long double, as |f - f*| over K phi(y*) (1 + l (|y*| + |y_p|))
+ *       (the plain relative error of f means nothing where 1 + l (y - y_p) cancels): tests/test_bank_damped_cpu.py holds the figures.  exp2,
+ *       log2 and cbrt need not be correctly rounded (a start off by 1e-3 changes nothing).  The final clamp on m is needed: rounding can
+ *       leave m one rounding below 0.
+ * State: one value per junction, `carry` ([n_junctions], the bank's precision, in and out).  On entry a value that is not finite means
+ * "no history": frame 0 is solved with l = 0 and y_p = 0 and its y starts the history.  On return: the last frame's y -- the root
+ * itself, never x - C*f, which loses every digit on a stiff contact -- for a damped junction that was solved; a quiet NaN for every other
+ * junction (undamped, left out, refused).  With frames = 0 the carry comes back unchanged.
+ * With the bit set and l = 0 the junction takes the damped tree and returns a carry; its bits need not be those of the undamped law.
+ * Status: MH_JUNCTION_REFUSED (a zero row, the objects render as with K = 0, carry NaN) for a damped junction, linear or Hertz, when
+ * C < 0, or C, K*C or K*C*l is not finite (1 + K*C plays no part).  Left out (status 0, a zero row, C = 0, carry NaN, the bits of the call
+ * without the junction): a damped junction whose l is not finite or below 0; MH_JUNCTION_DAMPED | MH_JUNCTION_BILATERAL (the clamp has no
+ * tension branch); a damped junction that would join a component of more than one junction, and a junction that would join a component
+ * that holds a damped one (decided with the groups, modalhip_groups.hpp).  A lone damped junction with MH_JUNCTION_SHARED is an ordinary
+ * damped junction.  Every junction without the bit keeps its bits beside a damped one, and a call in which no kept junction has the bit
+ * launches what mh_bank_render_coupled launches.
+ * Not in this version: damping in groups, a bilateral damped law, hysteretic laws, friction and roughness, pickups on junction objects. */
 typedef struct {
     uint32_t object;
     uint32_t points[3];
@@ -397,6 +442,7 @@ typedef struct {
 #define MH_JUNCTION_BILATERAL 1u
 #define MH_JUNCTION_HERTZ 2u
 #define MH_JUNCTION_SHARED 4u
+#define MH_JUNCTION_DAMPED 8u
 #define MH_JUNCTION_MODES 1024
 #define MH_JUNCTION_GROUP 4 /* the most junctions one group may hold */
 enum { MH_JUNCTION_LEFT_OUT = 0, MH_JUNCTION_SOLVED = 1, MH_JUNCTION_REFUSED = 2 };
@@ -412,6 +458,16 @@ int mh_bank_render_coupled(mh_bank *, uint32_t frames, float click_gain, uint32_
                            const mh_drive *drives, const float *signals, uint32_t n_pickups, const mh_pickup *pickups, void *pickup_out,
                            uint8_t *pickup_read, uint32_t n_junctions, const mh_junction *junctions, const float *approach, void *force_out,
                            double *compliance_out, uint8_t *status_out);
+/* mh_bank_render_coupled with contact damping: `damping` ([n_junctions] float, l in 1/m per frame, read only for junctions with
+ * MH_JUNCTION_DAMPED) and `carry` ([n_junctions] in the bank's precision, in and out) as described under "Contact damping".  With no
+ * flagged junction this is mh_bank_render_coupled, plus NaN carries. */
+int mh_bank_render_damped(mh_bank *, uint32_t frames, float click_gain, uint32_t n_impacts, mh_impact *impacts,
+                          uint32_t n_renderers, const uint32_t *deal_offset, const uint32_t *deal_objects, const uint32_t *render_count,
+                          const uint32_t *tuned_count, const float *out_gain, const float *listener_gain, void *out, double *object_energy,
+                          uint32_t *object_live, uint8_t *object_silenced, double *object_modal_energy, uint32_t n_drives,
+                          const mh_drive *drives, const float *signals, uint32_t n_pickups, const mh_pickup *pickups, void *pickup_out,
+                          uint8_t *pickup_read, uint32_t n_junctions, const mh_junction *junctions, const float *approach, void *force_out,
+                          double *compliance_out, uint8_t *status_out, const float *damping, void *carry);
 /* Read back state columns (for parity tests and the modal-energy diagnostic, ModalAudio.cpp:564-577). */
 int mh_bank_read_state(const mh_bank *, uint32_t first, uint32_t count, double *state_re, double *state_im);
 

@@ -2,11 +2,13 @@
 // decision that RenderBlock (modal/bank.hpp) takes when it packs the caller's junctions and that mh_bank_render_coupled takes again
 // before a kernel follows any index.  Host code, header only.
 //
-// Junctions are offered in call order, after the checks that concern one junction alone (objects, points, numbers, Hertz with bilateral).
+// Junctions are offered in call order, after the checks that concern one junction alone (objects, points, numbers, Hertz or damped with
+// bilateral, a damping that is not a finite number from 0 up).
 // A junction without MH_JUNCTION_SHARED is kept when none of its objects is on a kept junction, and its sides take no more than
 // MH_JUNCTION_MODES / 128 waves.  One with the flag may join the kept flagged junctions its objects are on: they and it become one
 // component, unless that component would hold more than MH_JUNCTION_GROUP junctions, its distinct objects would take more waves than a
-// workgroup holds (each object counted once), or it would hold a Hertz junction beside another junction.
+// workgroup holds (each object counted once), or it would hold a Hertz junction or a damped one (MH_JUNCTION_DAMPED) beside another
+// junction.
 #ifndef MODALHIP_GROUPS_HPP
 #define MODALHIP_GROUPS_HPP
 #include "modalhip.h"
@@ -20,7 +22,7 @@ struct MhJunctionGroups {
         std::vector<uint32_t> members; // the caller's ids of its junctions, ascending; empty: merged into another component
         std::vector<uint32_t> objects; // its distinct objects
         uint32_t waves{0}; // what those objects take, each counted once
-        bool shared{false}, hertz{false};
+        bool shared{false}, hertz{false}, damped{false};
     };
     std::vector<int32_t> of_object; // the component an object is on, -1: none
     std::vector<Component> components;
@@ -31,7 +33,8 @@ struct MhJunctionGroups {
     // -1: left out.
     int32_t add(uint32_t id, uint32_t flags, uint32_t object_a, uint32_t waves_a, uint32_t object_b, uint32_t waves_b) {
         constexpr uint32_t MOST_WAVES = MH_JUNCTION_MODES / 128;
-        const bool two_sided = object_b != MH_NO_OBJECT, shared = (flags & MH_JUNCTION_SHARED) != 0, hertz = (flags & MH_JUNCTION_HERTZ) != 0;
+        const bool two_sided = object_b != MH_NO_OBJECT, shared = (flags & MH_JUNCTION_SHARED) != 0, hertz = (flags & MH_JUNCTION_HERTZ) != 0,
+                   damped = (flags & MH_JUNCTION_DAMPED) != 0;
         const int32_t ca = of_object[object_a], cb = two_sided ? of_object[object_b] : -1;
         if (!two_sided) waves_b = 0;
         if (!shared && (ca >= 0 || cb >= 0)) return -1; // one junction per object
@@ -41,13 +44,17 @@ struct MhJunctionGroups {
         // the distinct components it would join, each once: ca, then cb where that is another one
         size_t members = 1;
         uint32_t waves = 0;
-        bool hertz_inside = false;
+        bool hertz_inside = false, damped_inside = false;
         for (const int32_t c : {ca, cb == ca ? -1 : cb})
-            if (c >= 0) members += components[c].members.size(), waves += components[c].waves, hertz_inside = hertz_inside || components[c].hertz;
+            if (c >= 0) {
+                members += components[c].members.size(), waves += components[c].waves;
+                hertz_inside = hertz_inside || components[c].hertz, damped_inside = damped_inside || components[c].damped;
+            }
         if (ca < 0) waves += waves_a; // an object that is on no component yet brings its own waves
         if (two_sided && cb < 0) waves += waves_b;
         if (members > MH_JUNCTION_GROUP || waves > MOST_WAVES) return -1;
         if (members > 1 && (hertz || hertz_inside)) return -1; // no Hertz junction in a group in this version
+        if (members > 1 && (damped || damped_inside)) return -1; // and no damped one: its solve, like Hertz's, is in one dimension
         int32_t into = ca >= 0 ? ca : cb;
         if (into < 0) {
             into = int32_t(components.size());
@@ -71,6 +78,7 @@ struct MhJunctionGroups {
         c.waves = waves;
         c.shared = shared; // (every member of a component has the flag, or it is one unflagged junction)
         c.hertz = hertz; // (a Hertz junction is only ever a component of its own: the check above)
+        c.damped = damped; // (and so is a damped one)
         return into;
     }
 };

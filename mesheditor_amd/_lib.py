@@ -59,6 +59,7 @@ class Junction(C.Structure):  # mh_junction
 NO_OBJECT, JUNCTION_BILATERAL, JUNCTION_MODES = 0xffffffff, 1, 1024  # MH_NO_OBJECT, MH_JUNCTION_BILATERAL, MH_JUNCTION_MODES
 JUNCTION_HERTZ = 2  # MH_JUNCTION_HERTZ
 JUNCTION_SHARED, JUNCTION_GROUP = 4, 4  # MH_JUNCTION_SHARED, MH_JUNCTION_GROUP
+JUNCTION_DAMPED = 8  # MH_JUNCTION_DAMPED
 
 
 def build(force=False):
@@ -110,6 +111,7 @@ def lib():
         "mh_pickup_struct_size": (u32, []),
         "mh_bank_render_coupled": (i32, [vp, u32, C.c_float, u32, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp, u32, vp, vp, vp, vp, vp]),
         "mh_junction_struct_size": (u32, []),
+        "mh_bank_render_damped": (i32, [vp, u32, C.c_float, u32, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp]),
         "mh_bank_read_state": (i32, [vp, u32, u32, vp, vp]),
     }
     for name, (res, args) in sig.items():

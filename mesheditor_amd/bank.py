@@ -47,20 +47,24 @@ class JunctionSide(C.Structure):  # ModalJunctionSide, modal/bank.hpp (mh_juncti
 
 
 NO_OBJECT, JUNCTION_BILATERAL, JUNCTION_HERTZ, JUNCTION_SHARED = 0xffffffff, 1, 2, 4  # NoModalObject, ModalJunctionBilateral, ModalJunctionHertz, ModalJunctionShared
+JUNCTION_DAMPED = 8  # ModalJunctionDamped
 
 
 class Junction(C.Structure):  # ModalJunction, modal/bank.hpp (mh_junction of modalhip.h field for field)
     _fields_ = [("a", JunctionSide), ("b", JunctionSide), ("stiffness", C.c_float), ("flags", C.c_uint32)]
 
     @classmethod
-    def of(cls, a, b=None, stiffness=0.0, bilateral=False, hertz=False, shared=False):
+    def of(cls, a, b=None, stiffness=0.0, bilateral=False, hertz=False, shared=False, damped=False):
         """a, b: JunctionSide records or the arguments of JunctionSide.of as tuples; b = None: one-sided (an exciter the caller moves).
         hertz: f = K delta^1.5 with `stiffness` in N/m^1.5 instead of the linear spring (unilateral only: with bilateral it is left out).
         shared: the junction may name an object that an earlier kept junction with shared=True names; up to four linear junctions that
-        share objects in this way are one group, solved together in every frame (modalhip.h, MH_JUNCTION_SHARED)."""
+        share objects in this way are one group, solved together in every frame (modalhip.h, MH_JUNCTION_SHARED).
+        damped: Hunt-Crossley contact damping on the linear or the Hertz law (Scene.render_damped only; unilateral, and alone on its objects:
+        with bilateral, or where it would share an object, it is left out)."""
         side = lambda v: v if isinstance(v, JunctionSide) else JunctionSide.of(*v)
         none = JunctionSide(NO_OBJECT, (C.c_uint32 * 3)(0, 0, 0), (C.c_float * 3)(1, 0, 0), 0.0, 0.0, 0.0, 1.0)
-        return cls(side(a), side(b) if b is not None else none, stiffness, (JUNCTION_BILATERAL if bilateral else 0) | (JUNCTION_HERTZ if hertz else 0) | (JUNCTION_SHARED if shared else 0))
+        return cls(side(a), side(b) if b is not None else none, stiffness, (JUNCTION_BILATERAL if bilateral else 0) | (JUNCTION_HERTZ if hertz else 0) | (JUNCTION_SHARED if shared else 0) |
+                   (JUNCTION_DAMPED if damped else 0))
 
 
 def lib():
@@ -81,6 +85,7 @@ def lib():
         "mhx_enqueue": (i32, [vp, C.POINTER(Event)]), "mhx_render": (i32, [vp, vp, u32]), "mhx_render_driven": (i32, [vp, vp, u32, u32, vp, vp]),
         "mhx_render_read": (i32, [vp, vp, u32, u32, vp, vp, u32, vp, vp, vp]), "mhx_num_objects": (u32, [vp]),
         "mhx_render_coupled": (i32, [vp, vp, u32, u32, vp, vp, u32, vp, vp, vp, u32, vp, vp, vp, vp, vp]),
+        "mhx_render_damped": (i32, [vp, vp, u32, u32, vp, vp, u32, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp]),
         "mhx_active_impacts": (u32, [vp]), "mhx_modal_energy": (f64, [vp]), "mhx_render_share": (f32, [vp]), "mhx_find_object": (i32, [vp, u32]),
         "mhx_time_kernels": (i32, [vp, i32]), "mhx_kernel_class_stats": (i32, [vp, i32, C.POINTER(C.c_uint64), C.POINTER(f64), C.POINTER(f64)]),
         "mhx_column": (u32, [vp, i32, i32, vp]), "mhx_object_state": (None, [vp, vp, vp, vp]),
@@ -194,6 +199,27 @@ class Scene:
                                      len(junctions), C.cast(contacts, C.c_void_p), _p(u), _p(forces), _p(compliances), _p(statuses)):
             raise RuntimeError(self.L.mhx_last_error().decode())
         return reads, flags, forces, compliances, statuses
+
+    def render_damped(self, out, drives, signals, pickups, junctions, approach, damping, carry=None):
+        """RenderModalDamped: render_coupled with contact damping.  damping: one D in s/m per junction (float32; read for junctions with
+        damped=True, l = D * sample rate per frame); carry: one value per junction in the scene's precision -- the compression the last
+        frame of the previous block left, as this call returned it then; None or a value that is not finite: no history.  Returns
+        render_coupled's tuple plus the new carry (NaN for every junction that is not a solved damped one)."""
+        assert out.dtype == self.dtype and out.flags["C_CONTIGUOUS"]
+        rows = drives if isinstance(drives, C.Array) else (Drive * max(len(drives), 1))(*[v if isinstance(v, Drive) else Drive(*v) for v in drives])
+        sig = np.ascontiguousarray(signals, np.float32).reshape(len(drives), len(out))
+        probes = pickups if isinstance(pickups, C.Array) else (Pickup * max(len(pickups), 1))(*pickups)
+        contacts = junctions if isinstance(junctions, C.Array) else (Junction * max(len(junctions), 1))(*junctions)
+        n = len(junctions)
+        u = np.ascontiguousarray(approach, np.float32).reshape(n, len(out))
+        rates = np.ascontiguousarray(damping, np.float32).reshape(n)
+        state = np.full(n, np.nan, self.dtype) if carry is None else np.array(carry, self.dtype).reshape(n)
+        reads, flags = np.zeros((len(pickups), len(out)), self.dtype), np.zeros(len(pickups), np.uint8)
+        forces, compliances, statuses = np.zeros((n, len(out)), self.dtype), np.zeros(n), np.zeros(n, np.uint8)
+        if self.L.mhx_render_damped(self.h, _p(out), len(out), len(drives), C.cast(rows, C.c_void_p), _p(sig), len(pickups), C.cast(probes, C.c_void_p), _p(reads), _p(flags),
+                                    n, C.cast(contacts, C.c_void_p), _p(u), _p(forces), _p(compliances), _p(statuses), _p(rates), _p(state)):
+            raise RuntimeError(self.L.mhx_last_error().decode())
+        return reads, flags, forces, compliances, statuses, state
 
     def time_kernels(self, enable=True):
         """HIP-event timing of the bank's kernels on its device context (measurement aid)."""

@@ -64,17 +64,22 @@ struct ModalPickup {
 // (B.Object = NoModalObject), solved implicitly once per frame inside the render call (RenderModalCoupled; the contract, its five steps
 // and the returned force rows: include/modalhip.h, mh_junction).  A side is a pickup's contact point and a drive's direction in one record:
 // (Nx, Ny, Nz) is the direction in which the junction pushes that side; Coupling is the caller's factor, which the render multiplies by
-// the object's DeflectionScale.  Passed with the block it acts in; no state between blocks.
+// the object's DeflectionScale.  Passed with the block it acts in; no state between blocks but a damped junction's carry (below).
 // Flags bit 1, ModalJunctionHertz: the Hertzian law f = K delta^(3/2) of ContactModel (modal/contact.hpp) instead of the linear spring,
 // with Stiffness = K in N/m^1.5 (ContactStiffness(inv_modulus, curvature) = (4/3) E* sqrt(R) gives it), solved implicitly per frame by the
 // fixed Newton iteration of modalhip.h.  Unilateral only: a junction with both bits set is left out.
 // Flags bit 2, ModalJunctionShared: the junction may name an object that an earlier kept junction with the same bit names.  The kept
 // junctions that share objects in this way -- up to MH_JUNCTION_GROUP of them, linear, their distinct objects within one workgroup's
 // waves -- are a group and are solved together per frame (modalhip.h, "Groups"); on a junction that shares nothing the bit changes nothing.
+// Flags bit 3, ModalJunctionDamped (RenderModalDamped only; RenderModalCoupled ignores it): Hunt-Crossley contact damping on the linear or
+// the Hertz law, f = K phi(y) max(1 + l (y - y_p), 0) with y_p the previous frame's compression, solved implicitly per frame by the fixed
+// trees of modalhip.h ("Contact damping").  Unilateral only, and alone on its objects: with ModalJunctionBilateral, or where it would
+// share an object with another junction, it is left out.
 constexpr uint32_t NoModalObject{0xffffffffu};
 constexpr uint32_t ModalJunctionBilateral{1};
 constexpr uint32_t ModalJunctionHertz{2};
 constexpr uint32_t ModalJunctionShared{4};
+constexpr uint32_t ModalJunctionDamped{8};
 struct ModalJunctionSide {
     uint32_t Object{NoModalObject};
     uint32_t Points[3]{0, 0, 0};
@@ -267,6 +272,21 @@ void RenderModalCoupled(ModalAudio &, std::span<const ModalDrive> drives, const 
 void RenderModalCoupled(ModalAudio64 &, std::span<const ModalDrive> drives, const float *signals, std::span<const ModalPickup> pickups, double *reads,
                         std::span<const ModalJunction> junctions, const float *approach, double *forces, double *out, uint32_t frame_count, uint8_t *read_flags = nullptr,
                         double *compliances = nullptr, uint8_t *statuses = nullptr);
+// Not in the reference: RenderModalCoupled with contact damping (ModalJunctionDamped).  `damping` holds one D in s/m per junction (read for
+// flagged junctions only; ContactDamping(restitution, approach speed) of modal/contact.hpp gives it), which the render turns into the
+// per-frame l = float(D) * float(SampleRate), rounded once in float.  `carry` holds one value per junction in the bank's precision, in and
+// out: the compression the last frame's solve left.  A value that is not finite on entry means "no history" (the first frame is solved
+// without damping and starts it); on return a damped junction that was solved has its carry, every other junction a quiet NaN; with
+// frame_count = 0 it comes back unchanged.  Hand it to the next block's call as it is.  Left out beyond RenderModalCoupled's kinds: a
+// damped junction whose D * SampleRate is not finite or is below 0, ModalJunctionDamped with ModalJunctionBilateral, a damped junction that
+// would join a group, and a junction that would join a damped one.  Refused (status 2): a damped junction when C < 0, or C, K C or K C l is
+// not finite.  Without a flagged junction this is RenderModalCoupled, plus NaN carries.
+void RenderModalDamped(ModalAudio &, std::span<const ModalDrive> drives, const float *signals, std::span<const ModalPickup> pickups, float *reads,
+                       std::span<const ModalJunction> junctions, const float *approach, std::span<const float> damping, std::span<float> carry, float *forces, float *out,
+                       uint32_t frame_count, uint8_t *read_flags = nullptr, double *compliances = nullptr, uint8_t *statuses = nullptr);
+void RenderModalDamped(ModalAudio64 &, std::span<const ModalDrive> drives, const float *signals, std::span<const ModalPickup> pickups, double *reads,
+                       std::span<const ModalJunction> junctions, const float *approach, std::span<const float> damping, std::span<double> carry, double *forces, double *out,
+                       uint32_t frame_count, uint8_t *read_flags = nullptr, double *compliances = nullptr, uint8_t *statuses = nullptr);
 // Not in the reference: the libmodalhip context the bank's device mirror lives on (created on demand), for callers that
 // time its kernels (mh_context_time_kernels / mh_context_kernel_class_stats).
 mh_context *ModalDeviceContext(ModalAudio &);

@@ -31,4 +31,8 @@ double PunchStiffness(double inv_effective_modulus, double nominal_area);
 double EstimateContactTime(const ContactDynamics &, uint32_t excitable_index, vec3 impact_direction, double contact_speed,
                            const AcousticMaterialProperties &object_material, double object_curvature, double nominal_area, const Impactor &,
                            double scale_ratio, double combined_roughness = 0);
+// Not in the reference's ContactModel.h: the Hunt-Crossley damping D in s/m of a contact pair with restitution e at approach speed v > 0,
+// D = 1.5 max(1 - e, 0) / v -- Hunt and Crossley's relation as the reference's surface renderer sizes its damping term (DampingFactor =
+// 1.5 (1 - e) ContactDamping, src/audio/surface/SurfaceAudio.cpp).  What RenderModalDamped takes per junction (modal/bank.hpp).
+inline double ContactDamping(double restitution, double approach_speed) { return 1.5 * (1.0 - restitution > 0.0 ? 1.0 - restitution : 0.0) / approach_speed; }
 inline constexpr double MinContactTime = 2e-5, MaxContactTime = 5e-2;

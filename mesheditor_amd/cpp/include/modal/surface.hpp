@@ -12,9 +12,12 @@
 // pickup and block.  The per-sample contact solve (a sample's force depending on the displacement read in the same sample) exists as
 // ModalJunction / RenderModalCoupled: one contact per junction between two bank objects or an object and an exciter the caller moves --
 // a linear spring, unilateral or bilateral, or (ModalJunctionHertz) the Hertzian law f = K delta^1.5 -- solved implicitly per frame on
-// the device (the reference's one-channel SolveChannelStep).  What is still absent is the model on top of them: contact tracking and
-// voices, several contacts on one object (the reference's shared solve), the damping of a contact, tangential channels, the rigid-body recoil and air-load
-// filters of RenderObjectCoupled, and the roughness / friction signal generators.
+// the device (the reference's one-channel SolveChannelStep).  The damping of a contact exists as ModalJunctionDamped / RenderModalDamped:
+// the Hunt-Crossley factor max(1 + l (y - y_p), 0) on either law, sized from the pair's restitution by ContactDamping (modal/contact.hpp)
+// as the reference's surface renderer sizes its DampingFactor, with one number of state per junction carried from block to block.
+// What is still absent is the model on top of them: contact tracking and voices, damping inside a group of contacts that share an
+// object, tangential channels, the rigid-body recoil and air-load filters of RenderObjectCoupled, and the roughness / friction signal
+// generators.
 #pragma once
 #include "bank.hpp"
 

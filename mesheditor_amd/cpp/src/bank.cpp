@@ -17,6 +17,7 @@
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <limits>
 #include <queue>
 #include <stdexcept>
 #include <string>
@@ -504,6 +505,8 @@ template<typename Real> struct JunctionResults {
     Real *Forces{nullptr};
     double *Compliances{nullptr};
     uint8_t *Statuses{nullptr};
+    const float *Damping{nullptr}; // RenderModalDamped: D in s/m per junction, and the carry (in and out); null: ModalJunctionDamped is ignored
+    Real *Carry{nullptr};
 };
 
 template<typename Audio, typename Real>
@@ -577,16 +580,26 @@ void RenderBlock(Audio &m, std::span<const ModalDrive> drives, const float *sign
     // (one junction per object, unless both carry ModalJunctionShared: then they form a group -- the decision of modalhip_groups.hpp, which
     // the device entry takes again)
     MhJunctionGroups grouping(n_objects);
+    const uint32_t flag_mask = coupled.Damping ? ~0u : ~ModalJunctionDamped;
+    std::vector<float> damping; // per kept junction: l = D * SampleRate per frame, rounded once in float
+    std::vector<Real> carry;
     for (size_t j = 0; j < junctions.size(); ++j) {
         const ModalJunction &v = junctions[j];
         const bool two_sided = v.B.Object != NoModalObject;
+        const uint32_t flags = v.Flags & flag_mask;
+        const float per_frame = (flags & ModalJunctionDamped) ? coupled.Damping[j] * float(b.SampleRate) : 0.f;
         if (!std::isfinite(v.Stiffness) || v.Stiffness < 0 || !side_ok(v.A) || (two_sided && (v.A.Object == v.B.Object || !side_ok(v.B)))) continue;
         if ((v.Flags & ModalJunctionHertz) && (v.Flags & ModalJunctionBilateral)) continue; // the Hertz law is unilateral
-        if (grouping.add(uint32_t(j), v.Flags, v.A.Object, side_waves(v.A), two_sided ? v.B.Object : MH_NO_OBJECT, two_sided ? side_waves(v.B) : 0u) < 0) continue;
+        if ((flags & ModalJunctionDamped) && ((flags & ModalJunctionBilateral) || !std::isfinite(per_frame) || per_frame < 0)) continue; // so is the damped one
+        if (grouping.add(uint32_t(j), flags, v.A.Object, side_waves(v.A), two_sided ? v.B.Object : MH_NO_OBJECT, two_sided ? side_waves(v.B) : 0u) < 0) continue;
         mh_junction_side none{};
         none.object = MH_NO_OBJECT;
-        d.Junctions.push_back({side_record(v.A), two_sided ? side_record(v.B) : none, v.Stiffness, v.Flags});
+        d.Junctions.push_back({side_record(v.A), two_sided ? side_record(v.B) : none, v.Stiffness, flags});
         d.JunctionFrom.push_back(uint32_t(j));
+        if (coupled.Damping) {
+            damping.push_back(per_frame);
+            carry.push_back(coupled.Carry[j]);
+        }
         d.Approach.insert(d.Approach.end(), coupled.Approach + j * frames, coupled.Approach + (j + 1) * frames);
         auto excite = [&](uint32_t o) {
             d.OnJunction[o] = 1;
@@ -639,7 +652,14 @@ void RenderBlock(Audio &m, std::span<const ModalDrive> drives, const float *sign
         narrow_listener.assign(b.ListenerGain.begin(), b.ListenerGain.end());
         out_gain = narrow_out.data(), listener_gain = narrow_listener.data();
     }
-    if (mh_bank_render_coupled(d.Bank, frames, m.ClickGain.load(std::memory_order_relaxed), n_impacts, d.Impacts.data(), renderers, d.DealOffset.data(), d.DealObjects.data(),
+    if (coupled.Damping) {
+        damping.push_back(0.f), carry.push_back(Real(0)); // (never read: the entry wants pointers)
+        if (mh_bank_render_damped(d.Bank, frames, m.ClickGain.load(std::memory_order_relaxed), n_impacts, d.Impacts.data(), renderers, d.DealOffset.data(), d.DealObjects.data(),
+                                  d.RenderCount.data(), d.Tuned.data(), out_gain, listener_gain, out, d.Energy.data(), d.Live.data(), d.Silenced.data(), d.ModalEnergy.data(),
+                                  uint32_t(d.Drives.size()), d.Drives.data(), drive_signals, uint32_t(d.Pickups.size()), d.Pickups.data(), reads, d.PickupRead.data(), kept_junctions, d.Junctions.data(), d.Approach.data(),
+                                  junction_forces.data(), d.JunctionCompliance.data(), d.JunctionStatus.data(), damping.data(), carry.data()) != MH_OK)
+            Fail(d);
+    } else if (mh_bank_render_coupled(d.Bank, frames, m.ClickGain.load(std::memory_order_relaxed), n_impacts, d.Impacts.data(), renderers, d.DealOffset.data(), d.DealObjects.data(),
                               d.RenderCount.data(), d.Tuned.data(), out_gain, listener_gain, out, d.Energy.data(), d.Live.data(), d.Silenced.data(), d.ModalEnergy.data(),
                               uint32_t(d.Drives.size()), d.Drives.data(), drive_signals, uint32_t(d.Pickups.size()), d.Pickups.data(), reads, d.PickupRead.data(), kept_junctions, d.Junctions.data(), d.Approach.data(),
                                junction_forces.data(), d.JunctionCompliance.data(), d.JunctionStatus.data()) != MH_OK)
@@ -654,6 +674,10 @@ void RenderBlock(Audio &m, std::span<const ModalDrive> drives, const float *sign
             std::copy(junction_forces.begin() + size_t(c) * frames, junction_forces.begin() + size_t(c + 1) * frames, coupled.Forces + j * frames);
             if (coupled.Compliances) coupled.Compliances[j] = d.JunctionCompliance[c];
             if (coupled.Statuses) coupled.Statuses[j] = d.JunctionStatus[c];
+        }
+        if (coupled.Carry) { // a quiet NaN for the ones left out; a kept one's as the entry returned it (NaN unless damped and solved)
+            std::fill(coupled.Carry, coupled.Carry + junctions.size(), std::numeric_limits<Real>::quiet_NaN());
+            for (uint32_t c = 0; c < kept_junctions; ++c) coupled.Carry[d.JunctionFrom[c]] = carry[c];
         }
     }
 
@@ -749,6 +773,20 @@ void RenderModalCoupled(ModalAudio64 &m, std::span<const ModalDrive> drives, con
                         std::span<const ModalJunction> junctions, const float *approach, double *forces, double *out, uint32_t frame_count, uint8_t *read_flags, double *compliances,
                         uint8_t *statuses) {
     RenderBlock<ModalAudio64, double>(m, drives, signals, out, frame_count, pickups, reads, read_flags, {junctions, approach, forces, compliances, statuses});
+}
+void RenderModalDamped(ModalAudio &m, std::span<const ModalDrive> drives, const float *signals, std::span<const ModalPickup> pickups, float *reads,
+                       std::span<const ModalJunction> junctions, const float *approach, std::span<const float> damping, std::span<float> carry, float *forces, float *out,
+                       uint32_t frame_count, uint8_t *read_flags, double *compliances, uint8_t *statuses) {
+    if (damping.size() < junctions.size() || carry.size() < junctions.size()) throw std::invalid_argument("RenderModalDamped: a damping and a carry per junction");
+    static const float none = 0; // (no junctions: a pointer that says which entry this is)
+    RenderBlock<ModalAudio, float>(m, drives, signals, out, frame_count, pickups, reads, read_flags, {junctions, approach, forces, compliances, statuses, junctions.empty() ? &none : damping.data(), carry.data()});
+}
+void RenderModalDamped(ModalAudio64 &m, std::span<const ModalDrive> drives, const float *signals, std::span<const ModalPickup> pickups, double *reads,
+                       std::span<const ModalJunction> junctions, const float *approach, std::span<const float> damping, std::span<double> carry, double *forces, double *out,
+                       uint32_t frame_count, uint8_t *read_flags, double *compliances, uint8_t *statuses) {
+    if (damping.size() < junctions.size() || carry.size() < junctions.size()) throw std::invalid_argument("RenderModalDamped: a damping and a carry per junction");
+    static const float none = 0;
+    RenderBlock<ModalAudio64, double>(m, drives, signals, out, frame_count, pickups, reads, read_flags, {junctions, approach, forces, compliances, statuses, junctions.empty() ? &none : damping.data(), carry.data()});
 }
 mh_context *ModalDeviceContext(ModalAudio &m) { return NeedContext(m), m.Dev->Context; }
 mh_context *ModalDeviceContext(ModalAudio64 &m) { return NeedContext(m), m.Dev->Context; }

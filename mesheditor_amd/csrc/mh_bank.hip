@@ -563,10 +563,64 @@ template<typename Real> __device__ __forceinline__ Real hertz_force(Real x, Real
     }
     return (k * y) * sqrt_real(y);
 }
+__device__ __forceinline__ float exp2_real(float v) { return exp2f(v); }
+__device__ __forceinline__ double exp2_real(double v) { return exp2(v); }
+__device__ __forceinline__ float log2_real(float v) { return log2f(v); }
+__device__ __forceinline__ double log2_real(double v) { return log2(v); }
+template<typename Real> __device__ __forceinline__ Real min_real(Real a, Real b) { return b < a ? b : a; }
+// Step 4 of a damped junction (modalhip.h, MH_JUNCTION_DAMPED, 4d): the root y of y + c phi(y) max(1 + l (y - y_p), 0) = x by the header's
+// expression trees -- the linear law's closed form; Hertz: the smallest of the upper bounds, then six Newton steps -- nothing contracted, no
+// trip count that depends on data, and f = K phi(y) max(1 + l (y - y_p), 0).  c = K C, c15 = 1.5 c and cl = c l are formed once per block; on a
+// frame without history the caller passes l = 0, cl = 0, yp = 0.  Wave-uniform: every lane has the same arguments.
+template<typename Real> struct DampedStep {
+    Real f, y; // the force, and the compression the solve left: the next frame's y_p
+};
+template<typename Real> __device__ __forceinline__ DampedStep<Real> damped_force(Real x, Real c, Real c15, Real cl, Real l, Real yp, Real k, bool hertz) {
+    if (!(x > Real(0))) return {Real(0), x}; // open, or a NaN
+    if (!(Real(1) + l * (x - yp) > Real(0))) return {Real(0), x}; // it opens faster than 1 / l per frame: the root is below the clamp's kink
+    const Real m0 = Real(1) - l * yp;
+    Real y;
+    if (!hertz) {
+        const Real b = Real(1) + c * m0;
+        const Real r = sqrt_real(b * b + (Real(4) * cl) * x);
+        y = min_real(x, b >= Real(0) ? (Real(2) * x) / (b + r) : (r - b) / (Real(2) * cl));
+        Real m = Real(1) + l * (y - yp);
+        if (!(m > Real(0))) m = Real(0);
+        return {(k * y) * m, y};
+    }
+    const Real big = std::numeric_limits<Real>::max();
+    const Real p5 = cl > Real(0) ? exp2_real(Real(0.4) * log2_real(x / cl)) : big;
+    if (m0 >= Real(0)) {
+        const Real cm = c * m0, t = cbrt_real(x / cm);
+        const Real g = cm > Real(0) ? t * t : big;
+        y = min_real(min_real(x, g), p5);
+    } else {
+        const Real ylo = -m0 / l;
+        const Real lin = x / ((cl * ylo) * sqrt_real(ylo));
+        y = min_real(x, ylo + min_real(lin, p5));
+    }
+#pragma unroll
+    for (int step = 0; step < 6; ++step) {
+        const Real r = sqrt_real(y), m = Real(1) + l * (y - yp), q = (c * y) * r;
+        y = y - ((y + q * m) - x) / ((Real(1) + (c15 * r) * m) + q * l);
+    }
+    Real m = Real(1) + l * (y - yp);
+    if (!(m > Real(0))) m = Real(0);
+    return {((k * y) * sqrt_real(y)) * m, y};
+}
+// What the damped entry takes beyond CoupledArgs, by the caller's junction index: l in the bank's precision, the carry that came in and where
+// the one that goes out is written (where the host reads it).
+template<typename Real> struct DampedArgs : CoupledArgs<Real> {
+    const Real *damping, *carry_in;
+    Real *carry_out;
+};
 // HERTZ = false (k_bank_modes_coupled<Real>): every junction is a linear spring -- the entry of a call without a Hertz junction, instruction
 // for instruction what it was before the parameter.  HERTZ = true: a junction with MH_JUNCTION_HERTZ takes hertz_force, a linear one the
-// same expression as in the other entry through one workgroup-uniform branch.
-template<typename Real, bool HERTZ = false> __global__ void __launch_bounds__(JUNCTION_WAVES *WAVE) k_bank_modes_coupled(BANK_MODES_PARAMS, CoupledArgs<Real> ca) { // (`waves`: the main launch's, not read here)
+// same expression as in the other entry through one workgroup-uniform branch.  DAMPED = true (with HERTZ: k_bank_modes_coupled_damped<Real>):
+// a junction with MH_JUNCTION_DAMPED takes damped_force and keeps y_p in a register from frame to frame; every other junction the branch it
+// takes in the Hertz entry.  The parameter type depends on DAMPED, so the other two entries are what they were.
+template<typename Real, bool HERTZ = false, bool DAMPED = false> __global__ void __launch_bounds__(JUNCTION_WAVES *WAVE) k_bank_modes_coupled(BANK_MODES_PARAMS, std::conditional_t<DAMPED, DampedArgs<Real>, CoupledArgs<Real>> ca) { // (`waves`: the main launch's, not read here)
+    static_assert(!DAMPED || HERTZ, "the damped entry is the Hertz entry plus the damped solve: K C and 1.5 K C are formed under HERTZ");
     typedef PairOf<Real> Pair;
     constexpr uint32_t TS = coupled_tile<Real>();
     extern __shared__ __attribute__((aligned(16))) unsigned char coupled_mem[];
@@ -628,6 +682,19 @@ template<typename Real, bool HERTZ = false> __global__ void __launch_bounds__(JU
         const Real most = std::numeric_limits<Real>::max();
         if (hertz) solved = compliance >= Real(0) && compliance <= most && kc >= Real(0) && kc <= most; // C and K C finite and not below 0
     }
+    bool damped = false; // workgroup-uniform
+    Real lam = 0, kcl = 0, y_prev = 0, l_now = 0, cl_now = 0; // damped: l and c l; y_p; what this frame's solve takes of l and c l (0 without history)
+    if constexpr (DAMPED) {
+        damped = (J.flags & MH_JUNCTION_DAMPED) != 0;
+        if (damped) {
+            const Real most = std::numeric_limits<Real>::max();
+            lam = ca.damping[J.row];
+            kcl = kc * lam;
+            solved = compliance >= Real(0) && compliance <= most && kc >= Real(0) && kc <= most && kcl >= Real(0) && kcl <= most; // C, K C and K C l finite and not below 0
+            const Real came = ca.carry_in[J.row];
+            if (came >= -most && came <= most) y_prev = came, l_now = lam, cl_now = kcl; // a finite carry: there is a history
+        }
+    }
     const Real stiffness = solved ? J.k : Real(0), denom = solved ? denom_k : Real(1);
     const bool bilateral = (J.flags & MH_JUNCTION_BILATERAL) != 0;
     if (threadIdx.x == 0) {
@@ -661,7 +728,13 @@ template<typename Real, bool HERTZ = false> __global__ void __launch_bounds__(JU
             const Real reach = bilateral ? x : (x > Real(0) ? x : Real(0));
             Real f = solved ? (stiffness * reach) / denom : Real(0);
             if constexpr (HERTZ)
-                if (hertz) f = solved ? hertz_force(x, kc, kc15, J.k) : Real(0);
+                if (hertz && !(DAMPED && damped)) f = solved ? hertz_force(x, kc, kc15, J.k) : Real(0);
+            if constexpr (DAMPED)
+                if (damped) {
+                    const DampedStep<Real> step = damped_force(x, kc, kc15, cl_now, l_now, y_prev, J.k, hertz);
+                    f = solved ? step.f : Real(0);
+                    y_prev = step.y, l_now = lam, cl_now = kcl;
+                }
             w.z_re = re + a * f;
             *reinterpret_cast<Pair *>(s_term + ds * PITCH + 2 * lane) = w.p_im * w.z_im + w.p_re * w.z_re;
             if (lane == ds) f_tile = f;
@@ -673,11 +746,15 @@ template<typename Real, bool HERTZ = false> __global__ void __launch_bounds__(JU
         chunk_sums<TS>(s_term, w, lane, s0, sn, partial, frames);
         __syncthreads();
     }
+    if constexpr (DAMPED)
+        if (damped && threadIdx.x == 0) ca.carry_out[J.row] = y_prev; // (the host hands it on only for a solved junction)
     store_wave(b, w, lane, chunk_energy);
 }
 // The launch of a call with a kept Hertz junction: the same kernel with the solve compiled in.  (An instantiation, not a wrapper around a
 // shared body: with the body in a function of its own the linear entry keeps its resource report but not its register assignment.)
 template<typename Real> constexpr auto k_bank_modes_coupled_hertz = &k_bank_modes_coupled<Real, true>;
+// The launch of a call with a kept damped junction (MH_JUNCTION_DAMPED): the same kernel again, with both solves compiled in.
+template<typename Real> constexpr auto k_bank_modes_coupled_damped = &k_bank_modes_coupled<Real, true, true>;
 
 // Groups of junctions that share objects (MH_JUNCTION_SHARED; contract in modalhip.h).  ONE WORKGROUP PER GROUP, one
 // wave per 128 modes of each DISTINCT object of the group (the objects in the order the members name them, side a before side b), modes
@@ -1237,7 +1314,8 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
                  const uint32_t *deal_objects, const uint32_t *render_count, const uint32_t *tuned_count, const float *out_gain, const float *listener_gain,
                  void *out_v, double *object_energy, uint32_t *object_live, uint8_t *object_silenced, double *object_modal_energy, uint32_t n_drives,
                  const mh_drive *drives, const float *signals, uint32_t n_pickups, const mh_pickup *pickups, void *pickup_out_v, uint8_t *pickup_read,
-                 uint32_t n_junctions, const mh_junction *junctions, const float *approach, void *force_out_v, double *compliance_out, uint8_t *status_out) {
+                 uint32_t n_junctions, const mh_junction *junctions, const float *approach, void *force_out_v, double *compliance_out, uint8_t *status_out,
+                 const float *damping, void *carry_v) { // damping, carry_v: mh_bank_render_damped's; both null in every other entry (MH_JUNCTION_DAMPED is ignored then)
     mh_context *ctx = B.ctx;
     hipStream_t st = ctx->stream;
     Real *out = static_cast<Real *>(out_v);
@@ -1258,6 +1336,7 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
     const size_t o_pick_ptr = A.take((n_dealt + 2) * 4), o_pick_dev = A.take((n_pickups + 1) * sizeof(PickupDev<Real>)), o_pick_rows = A.take((n_pickups + 1) * sizeof(PickupRows));
     const size_t o_excited = A.take((n_dealt + 1) * 4), o_junctions = A.take((n_junctions + 1) * sizeof(JunctionDev<Real>)), o_approach = A.take(size_t(n_junctions) * frames * sizeof(float));
     const size_t o_groups = A.take((n_junctions / 2 + 1) * sizeof(GroupDev<Real>));
+    const size_t o_damping = A.take(damping ? (n_junctions + 1) * sizeof(Real) : 0), o_carry_in = A.take(damping ? (n_junctions + 1) * sizeof(Real) : 0);
     const size_t both_end = A.used;
     // (written by the kernels straight into the pinned arena -- no copy back: the host sees them once the block's last kernel has
     // raised the sequence number)
@@ -1265,6 +1344,7 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
     const size_t o_back = A.take((n_impacts + 1) * sizeof(ImpactBack<Real>));
     const size_t o_pick_out = A.take(size_t(n_pickups) * frames * sizeof(Real));
     const size_t o_junction_force = A.take(size_t(n_junctions) * frames * sizeof(Real)), o_compliance = A.take((n_junctions + 1) * 8), o_status = A.take((n_junctions + 1) * 4);
+    const size_t o_carry_out = A.take(damping ? (n_junctions + 1) * sizeof(Real) : 0);
     const size_t total = A.used;
     if (total > A.cap) {
         HIP_CHECK(hipStreamSynchronize(st));
@@ -1280,6 +1360,8 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
     uint32_t n_coupled = 0, coupled_waves = 0, widest_junction = 0;
     uint32_t n_groups = 0, widest_group = 0, grouped_members = 0; // components of two or more junctions: k_bank_modes_grouped, one workgroup each
     bool any_hertz = false; // a kept junction with MH_JUNCTION_HERTZ: the call takes the entry that has the solve
+    bool any_damped = false; // a kept junction with MH_JUNCTION_DAMPED: the entry that has both solves and the carry
+    const uint32_t flag_mask = damping ? ~0u : ~uint32_t(MH_JUNCTION_DAMPED);
     B.kept_rows.clear();
     if (n_junctions) {
         JunctionDev<Real> *jd = A.h<JunctionDev<Real>>(o_junctions);
@@ -1303,7 +1385,10 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
             const bool two_sided = m.b.object != MH_NO_OBJECT;
             if (!std::isfinite(m.stiffness) || m.stiffness < 0 || !side_ok(m.a) || (two_sided && (m.a.object == m.b.object || !side_ok(m.b)))) continue;
             if ((m.flags & MH_JUNCTION_HERTZ) && (m.flags & MH_JUNCTION_BILATERAL)) continue; // the Hertz law is unilateral
-            if (grouping.add(j, m.flags, m.a.object, side_waves(m.a), m.b.object, two_sided ? side_waves(m.b) : 0u) < 0) continue;
+            if (m.flags & flag_mask & MH_JUNCTION_DAMPED) { // the damped law is unilateral too, and its l a finite number from 0 up
+                if ((m.flags & MH_JUNCTION_BILATERAL) || !std::isfinite(damping[j]) || damping[j] < 0) continue;
+            }
+            if (grouping.add(j, m.flags & flag_mask, m.a.object, side_waves(m.a), m.b.object, two_sided ? side_waves(m.b) : 0u) < 0) continue;
             B.on_junction[m.a.object] = 1;
             if (two_sided) B.on_junction[m.b.object] = 1;
             B.kept_rows.push_back(j);
@@ -1313,10 +1398,11 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
             const mh_junction &m = junctions[j];
             if (grouping.components[grouping.of_object[m.a.object]].members.size() != 1) continue;
             const bool two_sided = m.b.object != MH_NO_OBJECT;
-            JunctionDev<Real> dev{{side_dev(m.a), two_sided ? side_dev(m.b) : JunctionSideDev<Real>{}}, Real(m.stiffness), m.flags, j, coupled_waves};
+            JunctionDev<Real> dev{{side_dev(m.a), two_sided ? side_dev(m.b) : JunctionSideDev<Real>{}}, Real(m.stiffness), m.flags & flag_mask, j, coupled_waves};
             const uint32_t w = dev.side[0].waves + dev.side[1].waves;
             jd[n_coupled++] = dev;
             any_hertz = any_hertz || (m.flags & MH_JUNCTION_HERTZ) != 0;
+            any_damped = any_damped || (dev.flags & MH_JUNCTION_DAMPED) != 0;
             coupled_waves += w;
             widest_junction = std::max(widest_junction, w);
         }
@@ -1461,6 +1547,10 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
     }
     if (n_drives) std::copy(signals, signals + size_t(n_drives) * frames, A.h<float>(o_signals));
     if (any_junction) std::copy(approach, approach + size_t(n_junctions) * frames, A.h<float>(o_approach));
+    if (any_damped) {
+        std::copy(damping, damping + n_junctions, A.h<Real>(o_damping));
+        std::copy(static_cast<const Real *>(carry_v), static_cast<const Real *>(carry_v) + n_junctions, A.h<Real>(o_carry_in));
+    }
     HIP_CHECK(hipMemcpyAsync(A.dev, A.host, both_end, hipMemcpyHostToDevice, st));
     // ---- device passes ----
     Real *d_out_gain = A.d<Real>(o_out_gain), *d_listener = A.d<Real>(o_listener), *d_out = A.d<Real>(o_out);
@@ -1493,10 +1583,16 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
             attr.run(ctx->device, [] {
                 HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_bank_modes_coupled<Real>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
                 HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_bank_modes_coupled_hertz<Real>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+                HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_bank_modes_coupled_damped<Real>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
             });
             const CoupledArgs<Real> ca{B.defl_gain, A.d<JunctionDev<Real>>(o_junctions), A.d<float>(o_approach), A.hd<Real>(o_junction_force), A.hd<double>(o_compliance), A.hd<uint32_t>(o_status)};
             TimedLaunch timed(ctx, MH_KERNEL_JUNCTION, double(n_coupled) * double(frames));
-            launch_modes(any_hertz ? k_bank_modes_coupled_hertz<Real> : &k_bank_modes_coupled<Real>, n_coupled, widest_junction * WAVE, coupled_lds<Real>(widest_junction), B.junction_gain, ca);
+            if (any_damped) {
+                const DampedArgs<Real> da{ca, A.d<Real>(o_damping), A.d<Real>(o_carry_in), A.hd<Real>(o_carry_out)};
+                launch_modes(k_bank_modes_coupled_damped<Real>, n_coupled, widest_junction * WAVE, coupled_lds<Real>(widest_junction), B.junction_gain, da);
+            } else {
+                launch_modes(any_hertz ? k_bank_modes_coupled_hertz<Real> : &k_bank_modes_coupled<Real>, n_coupled, widest_junction * WAVE, coupled_lds<Real>(widest_junction), B.junction_gain, ca);
+            }
         }
         if (n_groups) { // the groups' objects: a launch of their own, one workgroup per group
             ensure(ctx, B.junction_gain, size_t(coupled_waves + JUNCTION_WAVES) * max_imp * MODES_PER_WAVE);
@@ -1570,6 +1666,12 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
             std::copy(A.h<Real>(o_junction_force) + size_t(j) * frames, A.h<Real>(o_junction_force) + size_t(j + 1) * frames, force_out + size_t(j) * frames);
             compliance_out[j] = A.h<double>(o_compliance)[j];
             status_out[j] = uint8_t(A.h<uint32_t>(o_status)[j]);
+        }
+        if (carry_v) { // the carry of a damped junction that was solved; a quiet NaN for every other junction
+            Real *carry = static_cast<Real *>(carry_v);
+            std::fill(carry, carry + n_junctions, std::numeric_limits<Real>::quiet_NaN());
+            for (const uint32_t j : B.kept_rows)
+                if ((junctions[j].flags & MH_JUNCTION_DAMPED) && status_out[j] == MH_JUNCTION_SOLVED) carry[j] = A.h<Real>(o_carry_out)[j];
         }
     }
     const ImpactBack<Real> *back = A.h<ImpactBack<Real>>(o_back);
@@ -1702,11 +1804,13 @@ int mh_bank_set_deflection_gain(mh_bank *bank, uint32_t first, uint32_t count, c
         return MH_OK;
     } catch (const std::exception &e) { return mh_guard(bank->ctx, e); }
 }
-int mh_bank_render_coupled(mh_bank *bank, uint32_t frames, float click_gain, uint32_t n_impacts, mh_impact *impacts, uint32_t n_renderers, const uint32_t *deal_offset,
-                           const uint32_t *deal_objects, const uint32_t *render_count, const uint32_t *tuned_count, const float *out_gain, const float *listener_gain,
-                           void *out, double *object_energy, uint32_t *object_live, uint8_t *object_silenced, double *object_modal_energy, uint32_t n_drives,
-                           const mh_drive *drives, const float *signals, uint32_t n_pickups, const mh_pickup *pickups, void *pickup_out, uint8_t *pickup_read,
-                           uint32_t n_junctions, const mh_junction *junctions, const float *approach, void *force_out, double *compliance_out, uint8_t *status_out) {
+// mh_bank_render_coupled (damping = carry = null: MH_JUNCTION_DAMPED is ignored) and mh_bank_render_damped
+static int render_junctions(mh_bank *bank, uint32_t frames, float click_gain, uint32_t n_impacts, mh_impact *impacts, uint32_t n_renderers, const uint32_t *deal_offset,
+                            const uint32_t *deal_objects, const uint32_t *render_count, const uint32_t *tuned_count, const float *out_gain, const float *listener_gain,
+                            void *out, double *object_energy, uint32_t *object_live, uint8_t *object_silenced, double *object_modal_energy, uint32_t n_drives,
+                            const mh_drive *drives, const float *signals, uint32_t n_pickups, const mh_pickup *pickups, void *pickup_out, uint8_t *pickup_read,
+                            uint32_t n_junctions, const mh_junction *junctions, const float *approach, void *force_out, double *compliance_out, uint8_t *status_out,
+                            const float *damping, void *carry) {
     if (!bank || !out || (n_impacts && !impacts) || (n_renderers && !deal_offset) || !out_gain || !listener_gain || (n_drives && (!drives || !signals))) return MH_EINVAL;
     if (n_pickups && (!pickups || !pickup_out || !pickup_read)) return MH_EINVAL;
     if (n_junctions && (!junctions || !approach || !force_out || !compliance_out || !status_out)) return MH_EINVAL;
@@ -1718,11 +1822,32 @@ int mh_bank_render_coupled(mh_bank *bank, uint32_t frames, float click_gain, uin
         auto go = [&](auto &B) {
             render_impl(B, frames, click_gain, n_impacts, impacts, n_renderers, deal_offset, deal_objects, render_count, tuned_count, out_gain, listener_gain, out, object_energy,
                         object_live, object_silenced, object_modal_energy, n_drives, drives, signals, n_pickups, pickups, pickup_out, pickup_read, n_junctions, junctions, approach,
-                        force_out, compliance_out, status_out);
+                        force_out, compliance_out, status_out, damping, carry);
         };
         if (bank->dbl) go(*bank->d); else go(*bank->f);
         return MH_OK;
     } catch (const std::exception &e) { return mh_guard(bank->ctx, e); }
+}
+int mh_bank_render_coupled(mh_bank *bank, uint32_t frames, float click_gain, uint32_t n_impacts, mh_impact *impacts, uint32_t n_renderers, const uint32_t *deal_offset,
+                           const uint32_t *deal_objects, const uint32_t *render_count, const uint32_t *tuned_count, const float *out_gain, const float *listener_gain,
+                           void *out, double *object_energy, uint32_t *object_live, uint8_t *object_silenced, double *object_modal_energy, uint32_t n_drives,
+                           const mh_drive *drives, const float *signals, uint32_t n_pickups, const mh_pickup *pickups, void *pickup_out, uint8_t *pickup_read,
+                           uint32_t n_junctions, const mh_junction *junctions, const float *approach, void *force_out, double *compliance_out, uint8_t *status_out) {
+    return render_junctions(bank, frames, click_gain, n_impacts, impacts, n_renderers, deal_offset, deal_objects, render_count, tuned_count, out_gain, listener_gain, out, object_energy,
+                            object_live, object_silenced, object_modal_energy, n_drives, drives, signals, n_pickups, pickups, pickup_out, pickup_read, n_junctions, junctions, approach,
+                            force_out, compliance_out, status_out, nullptr, nullptr);
+}
+int mh_bank_render_damped(mh_bank *bank, uint32_t frames, float click_gain, uint32_t n_impacts, mh_impact *impacts, uint32_t n_renderers, const uint32_t *deal_offset,
+                          const uint32_t *deal_objects, const uint32_t *render_count, const uint32_t *tuned_count, const float *out_gain, const float *listener_gain,
+                          void *out, double *object_energy, uint32_t *object_live, uint8_t *object_silenced, double *object_modal_energy, uint32_t n_drives,
+                          const mh_drive *drives, const float *signals, uint32_t n_pickups, const mh_pickup *pickups, void *pickup_out, uint8_t *pickup_read,
+                          uint32_t n_junctions, const mh_junction *junctions, const float *approach, void *force_out, double *compliance_out, uint8_t *status_out,
+                          const float *damping, void *carry) {
+    if (n_junctions && (!damping || !carry)) return MH_EINVAL;
+    static const float no_damping = 0; // (n_junctions = 0: render_impl tells the entries apart by the pointer)
+    return render_junctions(bank, frames, click_gain, n_impacts, impacts, n_renderers, deal_offset, deal_objects, render_count, tuned_count, out_gain, listener_gain, out, object_energy,
+                            object_live, object_silenced, object_modal_energy, n_drives, drives, signals, n_pickups, pickups, pickup_out, pickup_read, n_junctions, junctions, approach,
+                            force_out, compliance_out, status_out, damping ? damping : &no_damping, carry);
 }
 int mh_bank_render_read(mh_bank *bank, uint32_t frames, float click_gain, uint32_t n_impacts, mh_impact *impacts, uint32_t n_renderers, const uint32_t *deal_offset,
                         const uint32_t *deal_objects, const uint32_t *render_count, const uint32_t *tuned_count, const float *out_gain, const float *listener_gain,

@@ -14,6 +14,11 @@ the exciter dipping in and out of the surface.
 
     python tools/bank_junction_bench.py --law hertz --junctions 16            the same with Hertz junctions (f = K delta^1.5, K chosen so that
                                                                              K C sqrt(x0) = 10 at the approach's peak x0)
+    python tools/bank_junction_bench.py --law damped --junctions 16           the same with contact damping (MH_JUNCTION_DAMPED, l x0 = 1 at the approach's
+                                                                             peak x0, the carry passed from block to block); hertz-damped: on the Hertz law
+    python tools/bank_junction_bench.py --damped-against T [--runs 3]        the all-linear and all-Hertz undamped calls of a built checkout T of the parent
+                                                                             commit and of this tree (J = 1, 16, 64, one- and two-sided), interleaved in fresh
+                                                                             processes, and this tree's damped calls beside them -> profiles/bank_damped.json
     python tools/bank_junction_bench.py --laws-against T [--runs 3]          the all-linear calls of a built checkout T of the parent commit and
                                                                              of this tree, and this tree's Hertz calls, J = 1, 16, 64, interleaved,
                                                                              every run a fresh process -> profiles/bank_hertz.json
@@ -74,7 +79,10 @@ def measure(tree, entry, junctions, sides, objects, blocks, renderers, forces_pa
     peak_force, kept = [0.0], []
     if entry == "coupled":
         side = lambda o, sign, point=1: hipbank.JunctionSide.of(o, point, (1.0, 0.0, 0.0), tuple(sign * v for v in NORMAL), 2.0)
-        flag = {"hertz": True} if law == "hertz" else {}  # (a tree from before the Hertz law takes no such argument)
+        flag = {"hertz": True} if law in ("hertz", "hertz-damped") else {}  # (a tree from before the Hertz law takes no such argument)
+        damped = law in ("damped", "hertz-damped")
+        if damped:
+            flag["damped"] = True
         if members and not ungrouped:
             flag = {"shared": True}
         first = lambda j: side(where(j)[0], 1.0, where(j)[1]) if members else side(sides_of(j, sides)[0], 1.0)
@@ -93,11 +101,16 @@ def measure(tree, entry, junctions, sides, objects, blocks, renderers, forces_pa
             t = np.arange(BLOCK)
             u = np.array([(free[j] * (np.sin(2 * np.pi * t / 256.0 + j) + 0.1)).astype(np.float32) for j in range(junctions)])  # periodic in the block
         # linear: K C = 10; Hertz: K C sqrt(x0) = 10 at the approach's peak x0
-        contacts = make([10.0 / (c * (np.sqrt(float(u[j].max())) if law == "hertz" else 1.0)) for j, c in enumerate(comp)]) if junctions else []
+        contacts = make([10.0 / (c * (np.sqrt(float(u[j].max())) if "hertz" in law else 1.0)) for j, c in enumerate(comp)]) if junctions else []
         u = u if junctions else none
+        damping = [1.0 / (float(u[j].max()) * SR) for j in range(junctions)]  # damped: D in s/m with l x0 = D SR x0 = 1
+        carry = [None]
 
         def block():
-            _, _, forces, _, status = sc.render_coupled(out, rows, signals, [], contacts, u)
+            if damped:
+                _, _, forces, _, status, carry[0] = sc.render_damped(out, rows, signals, [], contacts, u, damping, carry[0])
+            else:
+                _, _, forces, _, status = sc.render_coupled(out, rows, signals, [], contacts, u)
             if junctions:
                 assert (status == 1).all()
                 peak_force[0] = max(peak_force[0], float(np.abs(forces).max()))
@@ -243,6 +256,54 @@ def compare_laws(parent, runs, objects, blocks, renderers, out_path):
     print(json.dumps(result["summary"]))
 
 
+def compare_damped(parent, runs, objects, blocks, renderers, out_path):
+    """The all-linear and all-Hertz undamped calls of the parent and of this tree (the same kernels: the new figures have to land within the
+    parent's own spread) and this tree's damped calls beside them."""
+    me = os.path.abspath(__file__)
+    common = ["--objects", str(objects), "--blocks", str(blocks), "--renderers", str(renderers)]
+    result = {"workload": f"{objects} objects x {MODES} modes @48k, {BLOCK}-frame blocks, fp32, {renderers} renderers, one drive on every object and J junctions in every block "
+                          "(linear: K C = 10; Hertz: K C sqrt(x0) = 10; damped: l x0 = 1, the carry passed on)", "runs_each": runs, "junctions": {}}
+
+    def save():
+        os.makedirs(os.path.dirname(out_path), exist_ok=True)
+        with open(out_path, "w") as f:
+            json.dump(result, f, indent=1)
+    q = subprocess.run(["timeout", "-k", "10", "300", sys.executable, "-c", "import torch; p = torch.cuda.get_device_properties(0); print(p.name, p.gcnArchName, '%d CUs' % p.multi_processor_count, '|', torch.version.hip)"], capture_output=True, text=True)
+    if q.returncode != 0:
+        raise SystemExit("no GPU to measure on: " + q.stderr[-2000:])
+    result["device"], result["hip"] = (v.strip() for v in q.stdout.strip().splitlines()[-1].split("|"))
+    calls = (("parent_linear", parent, "linear"), ("new_linear", None, "linear"), ("parent_hertz", parent, "hertz"), ("new_hertz", None, "hertz"),
+             ("new_damped", None, "damped"), ("new_hertz_damped", None, "hertz-damped"))
+    for _ in range(runs):
+        for sides in (1, 2):
+            for j in JUNCTIONS[1:]:
+                row = result["junctions"].setdefault("%d x %d-sided" % (j, sides), {name: [] for name, _, _ in calls})
+                shape = ["--entry", "coupled", "--junctions", str(j), "--sides", str(sides)] + common
+                for name, tree, law in calls:
+                    row[name].append(child([me, "--law", law] + (["--tree", tree] if tree else []) + shape))
+                save()
+    med = lambda rows, key: float(np.median([r[key] for r in rows]))
+    spread = lambda rows, key: max(r[key] for r in rows) / min(r[key] for r in rows)
+    summary = {}
+    for name, row in result["junctions"].items():
+        entry = {"real_time_ms_per_block": 1e3 * BLOCK / SR}
+        for law in ("linear", "hertz"):
+            entry.update({"parent_%s_ms_per_block" % law: [r["ms_per_block"] for r in row["parent_" + law]], "new_%s_ms_per_block" % law: [r["ms_per_block"] for r in row["new_" + law]],
+                          "parent_%s_spread_max_over_min" % law: spread(row["parent_" + law], "ms_per_block"),
+                          "new_%s_median_over_parent_median" % law: med(row["new_" + law], "ms_per_block") / med(row["parent_" + law], "ms_per_block"),
+                          "new_%s_median_inside_parent_range" % law: bool(min(r["ms_per_block"] for r in row["parent_" + law]) <= med(row["new_" + law], "ms_per_block") <= max(r["ms_per_block"] for r in row["parent_" + law])),
+                          "new_%s_median_over_parent_slowest" % law: med(row["new_" + law], "ms_per_block") / max(r["ms_per_block"] for r in row["parent_" + law]),
+                          "parent_%s_coupled_cycles_per_frame" % law: med(row["parent_" + law], "coupled_cycles_per_frame"),
+                          "%s_coupled_cycles_per_frame" % law: med(row["new_" + law], "coupled_cycles_per_frame")})
+        for law, base in (("damped", "linear"), ("hertz_damped", "hertz")):
+            entry.update({"%s_ms_per_block" % law: med(row["new_" + law], "ms_per_block"), "%s_coupled_cycles_per_frame" % law: med(row["new_" + law], "coupled_cycles_per_frame"),
+                          "%s_over_%s_cycles_per_frame" % (law, base): med(row["new_" + law], "coupled_cycles_per_frame") / med(row["new_" + base], "coupled_cycles_per_frame")})
+        summary[name] = entry
+    result["summary"] = summary
+    save()
+    print(json.dumps(summary))
+
+
 def compare_groups(parent, runs, objects, blocks, renderers, out_path, all_live):
     """The unchanged paths of the parent and of this tree -- the same kernels: the new figures have to land within the parent's own spread --
     and this tree's groups beside the same junctions ungrouped."""
@@ -304,7 +365,8 @@ def main():
     ap.add_argument("--tree", default=HERE, help="built checkout whose library is measured (replay only on one without junctions)")
     ap.add_argument("--forces", help="replay: the force rows a --save-forces run wrote")
     ap.add_argument("--save-forces", help="coupled: write the last block's force rows here (.npy)")
-    ap.add_argument("--law", choices=["linear", "hertz"], default="linear", help="coupled: the junctions' law")
+    ap.add_argument("--law", choices=["linear", "hertz", "damped", "hertz-damped"], default="linear", help="coupled: the junctions' law")
+    ap.add_argument("--damped-against", help="built checkout of the parent commit: its undamped linear and Hertz calls, this tree's, and this tree's damped calls -> profiles/bank_damped.json")
     ap.add_argument("--laws-against", help="built checkout of the parent commit: its all-linear calls, this tree's, and this tree's Hertz calls -> profiles/bank_hertz.json")
     ap.add_argument("--against", help="built checkout of the parent commit: run the whole comparison")
     ap.add_argument("--members", type=int, default=0, help="coupled: the junctions are groups of this many exciter junctions on one object each (2 ... 4)")
@@ -314,7 +376,10 @@ def main():
     ap.add_argument("--no-all-live", action="store_true", help="skip tools/bank_bench.py of both trees")
     ap.add_argument("--out", default=os.path.join(HERE, "profiles", "bank_junctions.json"))
     a = ap.parse_args()
-    if a.laws_against:
+    if a.damped_against:
+        out = a.out if a.out != ap.get_default("out") else os.path.join(HERE, "profiles", "bank_damped.json")
+        compare_damped(os.path.abspath(a.damped_against), a.runs, a.objects, a.blocks, a.renderers, out)
+    elif a.laws_against:
         out = a.out if a.out != ap.get_default("out") else os.path.join(HERE, "profiles", "bank_hertz.json")
         compare_laws(os.path.abspath(a.laws_against), a.runs, a.objects, a.blocks, a.renderers, out)
     elif a.against and a.groups:
