@@ -314,7 +314,8 @@ int mh_bank_render_read(mh_bank *, uint32_t frames, float click_gain, uint32_t n
  * rendered modes (each side's count rounded up to whole waves).  MH_JUNCTION_MODES = 1024 is what one workgroup holds: eight waves' output
  * tiles (16 640 B each) fill the 160 KiB of LDS; the registers (78 / 103 VGPRs in fp32 / fp64, nothing spilled, of the 256 a wave of an
  * eight-wave workgroup may take) would allow more.
- * In this version a pickup on an object that is on a junction's side is left out (pickup_read = 0, a zero row).
+ * In this version a pickup on an object that is on a junction's side is left out (pickup_read = 0, a zero row); mh_bank_render_observed
+ * reads it ("Pickups on junction objects" below).
  *
  * The Hertzian law, flags & MH_JUNCTION_HERTZ: `stiffness` is K in N/m^1.5 and the junction obeys f = K * delta^(3/2), the law of
  * ContactModel (modal/contact.hpp).  Steps 1, 2, 3 and 5 are the ones above, bit for bit -- the free step, d, C, Re z = Re z~ + a*f[s], the
@@ -378,7 +379,7 @@ int mh_bank_render_read(mh_bank *, uint32_t frames, float click_gain, uint32_t n
  * rendered modes (each object counted once, however many sides name it); one with MH_JUNCTION_HERTZ that would join a component of more
  * than one junction, and one that would join a component that holds a Hertz junction (the Hertz solve in more than one dimension is not in
  * this version); a flagged junction on an object of a kept unflagged one.  Two junctions between the same pair of objects, at different
- * points, are a legal group.  Pickups on a junction's object stay left out.  MH_JUNCTION_GROUP = 4 is what a wave's registers hold: one
+ * points, are a legal group.  Pickups on a junction's object stay left out (mh_bank_render_observed reads them).  MH_JUNCTION_GROUP = 4 is what a wave's registers hold: one
  * gain triple per member per lane, 195 VGPRs in fp64 (118 in fp32), nothing in scratch.  Not in this version, as above: damping in
  * groups, friction, roughness.
  *
@@ -425,7 +426,34 @@ int mh_bank_render_read(mh_bank *, uint32_t frames, float click_gain, uint32_t n
  * that holds a damped one (decided with the groups, modalhip_groups.hpp).  A lone damped junction with MH_JUNCTION_SHARED is an ordinary
  * damped junction.  Every junction without the bit keeps its bits beside a damped one, and a call in which no kept junction has the bit
  * launches what mh_bank_render_coupled launches.
- * Not in this version: damping in groups, a bilateral damped law, hysteretic laws, friction and roughness, pickups on junction objects. */
+ * Not in this version: damping in groups, a bilateral damped law, hysteretic laws, friction and roughness, pickups on junction objects
+ * (in this entry: mh_bank_render_observed reads them, "Pickups on junction objects" below).
+ *
+ * Pickups on junction objects, mh_bank_render_observed: mh_bank_render_damped -- its parameters in its order, nothing more -- except that a
+ * pickup whose object is on a side of a KEPT junction (status solved or refused; a lone linear, Hertz or damped junction, or a member of a
+ * group) is read.  Every other pickup, and every left-out kind of mh_bank_render_read -- an unknown object or one without modes, a point
+ * beyond the shapes, a value that is not finite, advance > 2, more than MH_PICKUPS_PER_OBJECT on the object before it -- is as it is
+ * there; an object on a LEFT-OUT junction is rendered by the main launch and read there, as today.
+ * A row: frame s is the sum over the object's rendered modes of  g_im[k]*Im z[s][k] + g_re[k]*Re z[s][k],  with the pickup's gains of
+ * mh_bank_render_read (`read`, advance 0, 1 or 2) and z[s] the state AFTER step 5 of frame s:  Re z = Re z~ + sum_j a_j*f_j[s],  the state
+ * the frame's output term is formed from.  The advance is free: no contact force acts in the look-ahead.
+ * Consequence: with advance-1 pickups at a junction's own sides (same points, weights, direction and scale),
+ *     sum_sides read1[s] = d + C*f[s]      (step 2's prediction moved by the frame's force),
+ * so  u[s] - sum_sides read1[s]  is the compression y of frame s + 1, the quantity every law above is implicit in:
+ * f[s] = K*phi(u[s] - sum read1[s]) (times the damping factor for a damped junction) can be checked where it is solved, in either
+ * precision, whatever else excites the objects.  For a damped junction the last frame's value is the returned carry, up to rounding.
+ * Summation order: mh_bank_render_read's, unchanged.  Per (wave of 128 modes from the object's mode 0, half of 64
+ * modes): acc = fma(g_im[k], Im z[k], acc), then acc = fma(g_re[k], Re z[k], acc), even modes into one accumulator and odd modes into a
+ * second, k ascending from +0, the value even + odd; the partial rows are added in ascending (wave, half) order from +0.  The junction
+ * kernels cut each object into waves at the same modes 0, 128, ..., so the partition is the same and a row depends on its object's state
+ * trajectory and its own record only -- not on the deal, the renderer count, which kernel rendered the object, a tile length or anything
+ * else in the call.  This is part of the contract: a row is bit for bit the row mh_bank_render_read gives for the same trajectory.
+ * Pickups only observe: with the pickups on junction objects removed from the call, `out`, every state, the per-object results, the
+ * force rows, compliances, statuses and carries are the same bits.  A refused junction's objects render as with K = 0 and are read.
+ * With frames = 0 nothing is read and the carry comes back unchanged.  A call without a pickup on a kept junction's object launches
+ * exactly what mh_bank_render_damped launches.  mh_bank_render_coupled and mh_bank_render_damped keep leaving such pickups out.
+ * Not in this version: Hertz or damping inside groups, a bilateral damped law, friction, roughness, contact forces acting inside a
+ * pickup's look-ahead. */
 typedef struct {
     uint32_t object;
     uint32_t points[3];
@@ -468,6 +496,14 @@ int mh_bank_render_damped(mh_bank *, uint32_t frames, float click_gain, uint32_t
                           const mh_drive *drives, const float *signals, uint32_t n_pickups, const mh_pickup *pickups, void *pickup_out,
                           uint8_t *pickup_read, uint32_t n_junctions, const mh_junction *junctions, const float *approach, void *force_out,
                           double *compliance_out, uint8_t *status_out, const float *damping, void *carry);
+/* mh_bank_render_damped that also reads the pickups on objects of kept junctions: "Pickups on junction objects" above. */
+int mh_bank_render_observed(mh_bank *, uint32_t frames, float click_gain, uint32_t n_impacts, mh_impact *impacts,
+                            uint32_t n_renderers, const uint32_t *deal_offset, const uint32_t *deal_objects, const uint32_t *render_count,
+                            const uint32_t *tuned_count, const float *out_gain, const float *listener_gain, void *out, double *object_energy,
+                            uint32_t *object_live, uint8_t *object_silenced, double *object_modal_energy, uint32_t n_drives,
+                            const mh_drive *drives, const float *signals, uint32_t n_pickups, const mh_pickup *pickups, void *pickup_out,
+                            uint8_t *pickup_read, uint32_t n_junctions, const mh_junction *junctions, const float *approach, void *force_out,
+                            double *compliance_out, uint8_t *status_out, const float *damping, void *carry);
 /* Read back state columns (for parity tests and the modal-energy diagnostic, ModalAudio.cpp:564-577). */
 int mh_bank_read_state(const mh_bank *, uint32_t first, uint32_t count, double *state_re, double *state_im);
 

@@ -86,6 +86,7 @@ def lib():
         "mhx_render_read": (i32, [vp, vp, u32, u32, vp, vp, u32, vp, vp, vp]), "mhx_num_objects": (u32, [vp]),
         "mhx_render_coupled": (i32, [vp, vp, u32, u32, vp, vp, u32, vp, vp, vp, u32, vp, vp, vp, vp, vp]),
         "mhx_render_damped": (i32, [vp, vp, u32, u32, vp, vp, u32, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp]),
+        "mhx_render_observed": (i32, [vp, vp, u32, u32, vp, vp, u32, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp]),
         "mhx_active_impacts": (u32, [vp]), "mhx_modal_energy": (f64, [vp]), "mhx_render_share": (f32, [vp]), "mhx_find_object": (i32, [vp, u32]),
         "mhx_time_kernels": (i32, [vp, i32]), "mhx_kernel_class_stats": (i32, [vp, i32, C.POINTER(C.c_uint64), C.POINTER(f64), C.POINTER(f64)]),
         "mhx_column": (u32, [vp, i32, i32, vp]), "mhx_object_state": (None, [vp, vp, vp, vp]),
@@ -200,7 +201,13 @@ class Scene:
             raise RuntimeError(self.L.mhx_last_error().decode())
         return reads, flags, forces, compliances, statuses
 
-    def render_damped(self, out, drives, signals, pickups, junctions, approach, damping, carry=None):
+    def render_observed(self, out, drives, signals, pickups, junctions, approach, damping=None, carry=None):
+        """RenderModalObserved: render_damped that also reads the pickups on objects of kept junctions (render_coupled and render_damped leave
+        those out).  damping=None: zeros (no junction with damped=True is expected).  Returns render_damped's tuple."""
+        rates = np.zeros(len(junctions), np.float32) if damping is None else damping
+        return self.render_damped(out, drives, signals, pickups, junctions, approach, rates, carry, entry=self.L.mhx_render_observed)
+
+    def render_damped(self, out, drives, signals, pickups, junctions, approach, damping, carry=None, entry=None):
         """RenderModalDamped: render_coupled with contact damping.  damping: one D in s/m per junction (float32; read for junctions with
         damped=True, l = D * sample rate per frame); carry: one value per junction in the scene's precision -- the compression the last
         frame of the previous block left, as this call returned it then; None or a value that is not finite: no history.  Returns
@@ -216,7 +223,7 @@ class Scene:
         state = np.full(n, np.nan, self.dtype) if carry is None else np.array(carry, self.dtype).reshape(n)
         reads, flags = np.zeros((len(pickups), len(out)), self.dtype), np.zeros(len(pickups), np.uint8)
         forces, compliances, statuses = np.zeros((n, len(out)), self.dtype), np.zeros(n), np.zeros(n, np.uint8)
-        if self.L.mhx_render_damped(self.h, _p(out), len(out), len(drives), C.cast(rows, C.c_void_p), _p(sig), len(pickups), C.cast(probes, C.c_void_p), _p(reads), _p(flags),
+        if (entry or self.L.mhx_render_damped)(self.h, _p(out), len(out), len(drives), C.cast(rows, C.c_void_p), _p(sig), len(pickups), C.cast(probes, C.c_void_p), _p(reads), _p(flags),
                                     n, C.cast(contacts, C.c_void_p), _p(u), _p(forces), _p(compliances), _p(statuses), _p(rates), _p(state)):
             raise RuntimeError(self.L.mhx_last_error().decode())
         return reads, flags, forces, compliances, statuses, state

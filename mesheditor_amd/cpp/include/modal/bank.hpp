@@ -264,8 +264,8 @@ void RenderModalRead(ModalAudio64 &, std::span<const ModalDrive> drives, const f
 // be a group's fifth (MH_JUNCTION_GROUP is 4), the one with which the group's distinct objects would take more than
 // MH_JUNCTION_MODES / 128 waves, a Hertz junction that would join another junction, and any junction that would join a Hertz one.  The
 // decision is taken here and again by the device entry, from one definition (modalhip_groups.hpp); every kept junction counts as an
-// excitation of its objects.  A pickup on an object that is on a kept junction's side is left out in this version.  Without junctions
-// this is RenderModalRead.
+// excitation of its objects.  A pickup on an object that is on a kept junction's side is left out in this version (RenderModalObserved
+// below reads it).  Without junctions this is RenderModalRead.
 void RenderModalCoupled(ModalAudio &, std::span<const ModalDrive> drives, const float *signals, std::span<const ModalPickup> pickups, float *reads,
                         std::span<const ModalJunction> junctions, const float *approach, float *forces, float *out, uint32_t frame_count, uint8_t *read_flags = nullptr,
                         double *compliances = nullptr, uint8_t *statuses = nullptr);
@@ -287,6 +287,22 @@ void RenderModalDamped(ModalAudio &, std::span<const ModalDrive> drives, const f
 void RenderModalDamped(ModalAudio64 &, std::span<const ModalDrive> drives, const float *signals, std::span<const ModalPickup> pickups, double *reads,
                        std::span<const ModalJunction> junctions, const float *approach, std::span<const float> damping, std::span<double> carry, double *forces, double *out,
                        uint32_t frame_count, uint8_t *read_flags = nullptr, double *compliances = nullptr, uint8_t *statuses = nullptr);
+// Not in the reference: RenderModalDamped that also reads the pickups on junction objects.  A pickup on an object that is on a side of a kept
+// junction (status 1 or 2; a lone linear, Hertz or damped junction, or a member of a group) is read like any other: frame s of its row is the
+// sum over the object's rendered modes of g_im Im z[s] + g_re Re z[s], with the pickup's gains of RenderModalRead (Advance 0, 1 or 2) and z[s]
+// the state after the frame's contact force was applied -- the state the frame's output is formed from.  The advance is free: no contact
+// force acts in the look-ahead.  So Advance-1 pickups at a junction's own sides (same points, weights, direction and coupling) sum to
+// d + C f[s], and approach[s] minus that sum is the compression of frame s + 1, the quantity every law is implicit in; for a damped junction
+// the last frame's value is the returned carry, up to rounding.  The summation order is RenderModalRead's, so a row depends on its object's
+// state trajectory and its own record only.  Pickups only observe: with them removed, `out`, the bank, the forces, compliances, statuses and
+// carries are the same bits.  A refused junction's objects render as with K = 0 and are read.  Every other pickup, every left-out kind and
+// everything else is RenderModalDamped's; the older entries above keep leaving such pickups out.
+void RenderModalObserved(ModalAudio &, std::span<const ModalDrive> drives, const float *signals, std::span<const ModalPickup> pickups, float *reads,
+                         std::span<const ModalJunction> junctions, const float *approach, std::span<const float> damping, std::span<float> carry, float *forces, float *out,
+                         uint32_t frame_count, uint8_t *read_flags = nullptr, double *compliances = nullptr, uint8_t *statuses = nullptr);
+void RenderModalObserved(ModalAudio64 &, std::span<const ModalDrive> drives, const float *signals, std::span<const ModalPickup> pickups, double *reads,
+                         std::span<const ModalJunction> junctions, const float *approach, std::span<const float> damping, std::span<double> carry, double *forces, double *out,
+                         uint32_t frame_count, uint8_t *read_flags = nullptr, double *compliances = nullptr, uint8_t *statuses = nullptr);
 // Not in the reference: the libmodalhip context the bank's device mirror lives on (created on demand), for callers that
 // time its kernels (mh_context_time_kernels / mh_context_kernel_class_stats).
 mh_context *ModalDeviceContext(ModalAudio &);

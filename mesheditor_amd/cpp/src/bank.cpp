@@ -507,6 +507,7 @@ template<typename Real> struct JunctionResults {
     uint8_t *Statuses{nullptr};
     const float *Damping{nullptr}; // RenderModalDamped: D in s/m per junction, and the carry (in and out); null: ModalJunctionDamped is ignored
     Real *Carry{nullptr};
+    bool Observed{false}; // RenderModalObserved: the damped entry that also reads the pickups on junction objects
 };
 
 template<typename Audio, typename Real>
@@ -654,7 +655,7 @@ void RenderBlock(Audio &m, std::span<const ModalDrive> drives, const float *sign
     }
     if (coupled.Damping) {
         damping.push_back(0.f), carry.push_back(Real(0)); // (never read: the entry wants pointers)
-        if (mh_bank_render_damped(d.Bank, frames, m.ClickGain.load(std::memory_order_relaxed), n_impacts, d.Impacts.data(), renderers, d.DealOffset.data(), d.DealObjects.data(),
+        if ((coupled.Observed ? mh_bank_render_observed : mh_bank_render_damped)(d.Bank, frames, m.ClickGain.load(std::memory_order_relaxed), n_impacts, d.Impacts.data(), renderers, d.DealOffset.data(), d.DealObjects.data(),
                                   d.RenderCount.data(), d.Tuned.data(), out_gain, listener_gain, out, d.Energy.data(), d.Live.data(), d.Silenced.data(), d.ModalEnergy.data(),
                                   uint32_t(d.Drives.size()), d.Drives.data(), drive_signals, uint32_t(d.Pickups.size()), d.Pickups.data(), reads, d.PickupRead.data(), kept_junctions, d.Junctions.data(), d.Approach.data(),
                                   junction_forces.data(), d.JunctionCompliance.data(), d.JunctionStatus.data(), damping.data(), carry.data()) != MH_OK)
@@ -787,6 +788,20 @@ void RenderModalDamped(ModalAudio64 &m, std::span<const ModalDrive> drives, cons
     if (damping.size() < junctions.size() || carry.size() < junctions.size()) throw std::invalid_argument("RenderModalDamped: a damping and a carry per junction");
     static const float none = 0;
     RenderBlock<ModalAudio64, double>(m, drives, signals, out, frame_count, pickups, reads, read_flags, {junctions, approach, forces, compliances, statuses, junctions.empty() ? &none : damping.data(), carry.data()});
+}
+void RenderModalObserved(ModalAudio &m, std::span<const ModalDrive> drives, const float *signals, std::span<const ModalPickup> pickups, float *reads,
+                         std::span<const ModalJunction> junctions, const float *approach, std::span<const float> damping, std::span<float> carry, float *forces, float *out,
+                         uint32_t frame_count, uint8_t *read_flags, double *compliances, uint8_t *statuses) {
+    if (damping.size() < junctions.size() || carry.size() < junctions.size()) throw std::invalid_argument("RenderModalObserved: a damping and a carry per junction");
+    static const float none = 0; // (no junctions: a pointer that says which entry this is)
+    RenderBlock<ModalAudio, float>(m, drives, signals, out, frame_count, pickups, reads, read_flags, {junctions, approach, forces, compliances, statuses, junctions.empty() ? &none : damping.data(), carry.data(), true});
+}
+void RenderModalObserved(ModalAudio64 &m, std::span<const ModalDrive> drives, const float *signals, std::span<const ModalPickup> pickups, double *reads,
+                         std::span<const ModalJunction> junctions, const float *approach, std::span<const float> damping, std::span<double> carry, double *forces, double *out,
+                         uint32_t frame_count, uint8_t *read_flags, double *compliances, uint8_t *statuses) {
+    if (damping.size() < junctions.size() || carry.size() < junctions.size()) throw std::invalid_argument("RenderModalObserved: a damping and a carry per junction");
+    static const float none = 0;
+    RenderBlock<ModalAudio64, double>(m, drives, signals, out, frame_count, pickups, reads, read_flags, {junctions, approach, forces, compliances, statuses, junctions.empty() ? &none : damping.data(), carry.data(), true});
 }
 mh_context *ModalDeviceContext(ModalAudio &m) { return NeedContext(m), m.Dev->Context; }
 mh_context *ModalDeviceContext(ModalAudio64 &m) { return NeedContext(m), m.Dev->Context; }

@@ -272,6 +272,59 @@ template<typename Real> struct ReadArgs {
     Real *rows; // [partial row][frames]
     uint32_t rows_loop; // what selects k_bank_modes_rows over k_bank_modes in a call without pickups
 };
+// The gains of an object's pickups on this lane's modes, staged for the block: [pickup][im | re][mode], zero on padded modes.
+template<typename Real>
+__device__ __forceinline__ void stage_pickup_gains(const BankCols<Real> &b, const WaveLane<Real> &w, const ReadArgs<Real> &rd, uint32_t pk0, uint32_t n_pick, uint32_t lane, Real *s_pick) {
+    typedef PairOf<Real> Pair;
+    for (uint32_t q = 0; q < n_pick; ++q) {
+        const PickupDev<Real> pk = rd.pickups[pk0 + q];
+        Pair g_im = {0, 0}, g_re = {0, 0};
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+            if (w.live[h]) {
+                const ReadGains<Real> g = read_gains(blend_read(b, w, pk.at, rd.defl_gain, h).read, w.c_re[h], w.c_im[h], pk.advance);
+                g_im[h] = g.im;
+                g_re[h] = g.re;
+            }
+        *reinterpret_cast<Pair *>(s_pick + (2 * q) * MODES_PER_WAVE + 2 * lane) = g_im;
+        *reinterpret_cast<Pair *>(s_pick + (2 * q + 1) * MODES_PER_WAVE + 2 * lane) = g_re;
+    }
+}
+// The per-half sum of G pickups from q0 on, after a tile's samples and the caller's barrier: lane = (half, sample ts) adds the 64 modes of
+// its half from the state tiles [sample][mode] and the staged gains, and stores one value per pickup into the (wave, half)'s partial row.
+// (The loop sits in a lambda called on the spot, as in chunk_sums.)
+template<uint32_t G, typename Real>
+__device__ __forceinline__ void read_group(const Real *s_zim, const Real *s_zre, const Real *s_pick, const ReadArgs<Real> &rd, uint32_t pk0, uint32_t q0, uint32_t first_mode,
+                                           uint32_t half, uint32_t ts, uint32_t s0, uint32_t frames) {
+    typedef PairOf<Real> Pair;
+    [&] {
+        Pair acc[G] = {};
+        const Real *zi = s_zim + ts * PITCH + half * WAVE, *zr = s_zre + ts * PITCH + half * WAVE;
+        const Real *g = s_pick + size_t(q0) * 2 * MODES_PER_WAVE + half * WAVE;
+#pragma unroll 4
+        for (uint32_t m = 0; m < WAVE; m += 2) {
+            const Pair vi = *reinterpret_cast<const Pair *>(zi + m), vr = *reinterpret_cast<const Pair *>(zr + m);
+#pragma unroll
+            for (uint32_t j = 0; j < G; ++j) {
+                acc[j] = __builtin_elementwise_fma(*reinterpret_cast<const Pair *>(g + (2 * j) * MODES_PER_WAVE + m), vi, acc[j]);
+                acc[j] = __builtin_elementwise_fma(*reinterpret_cast<const Pair *>(g + (2 * j + 1) * MODES_PER_WAVE + m), vr, acc[j]);
+            }
+        }
+#pragma unroll
+        for (uint32_t j = 0; j < G; ++j)
+            rd.rows[(size_t(rd.pickups[pk0 + q0 + j].first_row) + 2 * (first_mode / MODES_PER_WAVE) + half) * frames + s0 + ts] = acc[j].x + acc[j].y;
+    }();
+}
+// All of an object's pickups, four at a time.
+template<typename Real>
+__device__ __forceinline__ void read_pickups(const Real *s_zim, const Real *s_zre, const Real *s_pick, const ReadArgs<Real> &rd, uint32_t pk0, uint32_t n_pick, uint32_t first_mode,
+                                             uint32_t half, uint32_t ts, uint32_t s0, uint32_t frames) {
+    uint32_t q = 0;
+    for (; q + 4 <= n_pick; q += 4) read_group<4>(s_zim, s_zre, s_pick, rd, pk0, q, first_mode, half, ts, s0, frames);
+    if (n_pick - q == 3) read_group<3>(s_zim, s_zre, s_pick, rd, pk0, q, first_mode, half, ts, s0, frames);
+    else if (n_pick - q == 2) read_group<2>(s_zim, s_zre, s_pick, rd, pk0, q, first_mode, half, ts, s0, frames);
+    else if (n_pick - q == 1) read_group<1>(s_zim, s_zre, s_pick, rd, pk0, q, first_mode, half, ts, s0, frames);
+}
 template<typename Real, bool MANY, bool READ = false>
 __device__ __forceinline__ void bank_modes(const BankCols<Real> &b, const WaveDesc *__restrict__ waves, const uint32_t *__restrict__ deal_objects,
                                            const uint32_t *__restrict__ render_count, const uint32_t *__restrict__ chunk_base,
@@ -306,40 +359,8 @@ __device__ __forceinline__ void bank_modes(const BankCols<Real> &b, const WaveDe
     if constexpr (READ) {
         pk0 = rd.pick_ptr[wd.dealt];
         n_pick = min(rd.pick_ptr[wd.dealt + 1] - pk0, uint32_t(MH_PICKUPS_PER_OBJECT));
-        for (uint32_t q = 0; q < n_pick; ++q) {
-            const PickupDev<Real> pk = rd.pickups[pk0 + q];
-            Pair g_im = {0, 0}, g_re = {0, 0};
-#pragma unroll
-            for (int h = 0; h < 2; ++h)
-                if (w.live[h]) {
-                    const ReadGains<Real> g = read_gains(blend_read(b, w, pk.at, rd.defl_gain, h).read, w.c_re[h], w.c_im[h], pk.advance);
-                    g_im[h] = g.im;
-                    g_re[h] = g.re;
-                }
-            *reinterpret_cast<Pair *>(s_pick + (2 * q) * MODES_PER_WAVE + 2 * lane) = g_im;
-            *reinterpret_cast<Pair *>(s_pick + (2 * q + 1) * MODES_PER_WAVE + 2 * lane) = g_re;
-        }
+        stage_pickup_gains(b, w, rd, pk0, n_pick, lane, s_pick);
     }
-    // G pickups from q0 on: sample ts of this lane's half of the wave's modes
-    auto read_group = [&](auto g_tag, uint32_t q0, uint32_t s0) {
-        constexpr uint32_t G = decltype(g_tag)::value;
-        Pair acc[G] = {};
-        const Real *zi = s_zim + ts * PITCH + half * WAVE, *zr = s_zre + ts * PITCH + half * WAVE;
-        const Real *g = s_pick + size_t(q0) * 2 * MODES_PER_WAVE + half * WAVE;
-#pragma unroll 4
-        for (uint32_t m = 0; m < WAVE; m += 2) {
-            const Pair vi = *reinterpret_cast<const Pair *>(zi + m), vr = *reinterpret_cast<const Pair *>(zr + m);
-#pragma unroll
-            for (uint32_t j = 0; j < G; ++j) {
-                acc[j] = __builtin_elementwise_fma(*reinterpret_cast<const Pair *>(g + (2 * j) * MODES_PER_WAVE + m), vi, acc[j]);
-                acc[j] = __builtin_elementwise_fma(*reinterpret_cast<const Pair *>(g + (2 * j + 1) * MODES_PER_WAVE + m), vr, acc[j]);
-            }
-        }
-#pragma unroll
-        for (uint32_t j = 0; j < G; ++j)
-            rd.rows[(size_t(rd.pickups[pk0 + q0 + j].first_row) + 2 * (wd.first_mode / MODES_PER_WAVE) + half) * frames + s0 + ts] = acc[j].x + acc[j].y;
-    };
-
     // one sample of this lane's two resonators; their output terms go to the turn-around tile
     auto step = [&](const Pair &excite, uint32_t ds) {
         const Pair re = w.z_re * w.c_re - w.z_im * w.c_im + excite;
@@ -357,13 +378,7 @@ __device__ __forceinline__ void bank_modes(const BankCols<Real> &b, const WaveDe
         __syncthreads();
         chunk_sums<TS>(s_term, w, lane, s0, sn, partial, frames);
         if constexpr (READ) {
-            if (ts < sn) {
-                uint32_t q = 0;
-                for (; q + 4 <= n_pick; q += 4) read_group(std::integral_constant<uint32_t, 4>{}, q, s0);
-                if (n_pick - q == 3) read_group(std::integral_constant<uint32_t, 3>{}, q, s0);
-                else if (n_pick - q == 2) read_group(std::integral_constant<uint32_t, 2>{}, q, s0);
-                else if (n_pick - q == 1) read_group(std::integral_constant<uint32_t, 1>{}, q, s0);
-            }
+            if (ts < sn) read_pickups(s_zim, s_zre, s_pick, rd, pk0, n_pick, wd.first_mode, half, ts, s0, frames);
         }
         __syncthreads();
     };
@@ -536,7 +551,7 @@ template<typename Real> struct CoupledArgs {
     uint32_t *status_out;
 };
 template<typename Real> constexpr uint32_t coupled_tile() { return sizeof(Real) == 4 ? 32 : 16; } // samples per turn-around tile: 16 640 B per wave either way
-template<typename Real> size_t coupled_lds(uint32_t waves) {
+template<typename Real> constexpr size_t coupled_lds(uint32_t waves) {
     return 2 * JUNCTION_WAVES * sizeof(Real) + size_t(waves) * coupled_tile<Real>() * (MODES_PER_WAVE + 2) * sizeof(Real);
 }
 __device__ __forceinline__ float fma_real(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
@@ -614,12 +629,35 @@ template<typename Real> struct DampedArgs : CoupledArgs<Real> {
     const Real *damping, *carry_in;
     Real *carry_out;
 };
+// Pickups on junction objects (mh_bank_render_observed; contract in modalhip.h).  A wave of a junction launch whose
+// object carries a pickup is TAPPED: it streams Im z and Re z of every frame -- the state after step 5, the one the output term is formed
+// from -- with two plain vector stores into `states`, [tapped wave][frame][Im z | Re z][128], zeros on padded modes.  Nothing waits for
+// the stores: they are off the per-frame chain.  k_bank_observe_rows then forms the (wave, half) partial rows from them in the order
+// k_bank_modes_read does.  tap: by the wave's index among the junction launches' waves (first_wave + wave); NO_TAP: not tapped.
+constexpr uint32_t NO_TAP = 0xffffffffu;
+constexpr uint32_t TAP_FRAME = 2 * MODES_PER_WAVE; // values a tapped wave stores per frame
+template<typename Real, typename Base> struct ObservedArgs : Base {
+    const uint32_t *tap;
+    Real *states;
+};
+template<typename Real, typename Base, bool OBSERVE> using JunctionArgs = std::conditional_t<OBSERVE, ObservedArgs<Real, Base>, Base>;
+// Where a tapped wave's lane stores frame 0 (its two modes of Im z; Re z is MODES_PER_WAVE further); null for a wave that is not tapped.
+template<typename Real, typename Args> __device__ __forceinline__ Real *tap_of(const Args &args, bool active, uint32_t wave_index, uint32_t frames, uint32_t lane) {
+    const uint32_t tap = active ? args.tap[wave_index] : NO_TAP;
+    return tap != NO_TAP ? args.states + size_t(tap) * frames * TAP_FRAME + 2 * lane : nullptr;
+}
+template<typename Real> __device__ __forceinline__ void tap_store(Real *tap_row, uint32_t frame, const PairOf<Real> &z_im, const PairOf<Real> &z_re) {
+    Real *at = tap_row + size_t(frame) * TAP_FRAME;
+    *reinterpret_cast<PairOf<Real> *>(at) = z_im;
+    *reinterpret_cast<PairOf<Real> *>(at + MODES_PER_WAVE) = z_re;
+}
 // HERTZ = false (k_bank_modes_coupled<Real>): every junction is a linear spring -- the entry of a call without a Hertz junction, instruction
 // for instruction what it was before the parameter.  HERTZ = true: a junction with MH_JUNCTION_HERTZ takes hertz_force, a linear one the
 // same expression as in the other entry through one workgroup-uniform branch.  DAMPED = true (with HERTZ: k_bank_modes_coupled_damped<Real>):
 // a junction with MH_JUNCTION_DAMPED takes damped_force and keeps y_p in a register from frame to frame; every other junction the branch it
-// takes in the Hertz entry.  The parameter type depends on DAMPED, so the other two entries are what they were.
-template<typename Real, bool HERTZ = false, bool DAMPED = false> __global__ void __launch_bounds__(JUNCTION_WAVES *WAVE) k_bank_modes_coupled(BANK_MODES_PARAMS, std::conditional_t<DAMPED, DampedArgs<Real>, CoupledArgs<Real>> ca) { // (`waves`: the main launch's, not read here)
+// takes in the Hertz entry.  The parameter type depends on DAMPED, so the other two entries are what they were.  OBSERVE = true: the entries
+// of mh_bank_render_observed -- tapped waves also store their states (above); the parameter type grows by the tap list and the states' base.
+template<typename Real, bool HERTZ = false, bool DAMPED = false, bool OBSERVE = false> __global__ void __launch_bounds__(JUNCTION_WAVES *WAVE) k_bank_modes_coupled(BANK_MODES_PARAMS, JunctionArgs<Real, std::conditional_t<DAMPED, DampedArgs<Real>, CoupledArgs<Real>>, OBSERVE> ca) { // (`waves`: the main launch's, not read here)
     static_assert(!DAMPED || HERTZ, "the damped entry is the Hertz entry plus the damped solve: K C and 1.5 K C are formed under HERTZ");
     typedef PairOf<Real> Pair;
     constexpr uint32_t TS = coupled_tile<Real>();
@@ -703,6 +741,8 @@ template<typename Real, bool HERTZ = false, bool DAMPED = false> __global__ void
     }
     const float *u_row = ca.approach + size_t(J.row) * frames;
     Real *f_row = ca.force_out + size_t(J.row) * frames;
+    Real *tap_row = nullptr;
+    if constexpr (OBSERVE) tap_row = tap_of<Real>(ca, active, J.first_wave + wave, frames, lane);
     for (uint32_t s0 = 0; s0 < frames; s0 += TS) {
         const uint32_t sn = min(TS, frames - s0);
         // this tile's approach samples, lane = sample (not finite: 0, as a drive's)
@@ -737,6 +777,8 @@ template<typename Real, bool HERTZ = false, bool DAMPED = false> __global__ void
                 }
             w.z_re = re + a * f;
             *reinterpret_cast<Pair *>(s_term + ds * PITCH + 2 * lane) = w.p_im * w.z_im + w.p_re * w.z_re;
+            if constexpr (OBSERVE)
+                if (tap_row) tap_store(tap_row, s0 + ds, w.z_im, w.z_re);
             if (lane == ds) f_tile = f;
         }
         if (wave == 0 && lane < sn) f_row[s0 + lane] = f_tile;
@@ -755,6 +797,10 @@ template<typename Real, bool HERTZ = false, bool DAMPED = false> __global__ void
 template<typename Real> constexpr auto k_bank_modes_coupled_hertz = &k_bank_modes_coupled<Real, true>;
 // The launch of a call with a kept damped junction (MH_JUNCTION_DAMPED): the same kernel again, with both solves compiled in.
 template<typename Real> constexpr auto k_bank_modes_coupled_damped = &k_bank_modes_coupled<Real, true, true>;
+// The launches of mh_bank_render_observed when a kept junction's object carries a pickup: the three entries again, with the taps.
+template<typename Real> constexpr auto k_bank_modes_coupled_observed = &k_bank_modes_coupled<Real, false, false, true>;
+template<typename Real> constexpr auto k_bank_modes_coupled_hertz_observed = &k_bank_modes_coupled<Real, true, false, true>;
+template<typename Real> constexpr auto k_bank_modes_coupled_damped_observed = &k_bank_modes_coupled<Real, true, true, true>;
 
 // Groups of junctions that share objects (MH_JUNCTION_SHARED; contract in modalhip.h).  ONE WORKGROUP PER GROUP, one
 // wave per 128 modes of each DISTINCT object of the group (the objects in the order the members name them, side a before side b), modes
@@ -789,10 +835,11 @@ template<typename Real> struct GroupedArgs {
     double *compliance_out;
     uint32_t *status_out;
 };
-template<typename Real> size_t grouped_lds(uint32_t waves) {
+template<typename Real> constexpr size_t grouped_lds(uint32_t waves) {
     return 2 * GROUP * JUNCTION_WAVES * sizeof(Real) + size_t(waves) * coupled_tile<Real>() * (MODES_PER_WAVE + 2) * sizeof(Real);
 }
-template<typename Real> __global__ void __launch_bounds__(JUNCTION_WAVES *WAVE) k_bank_modes_grouped(BANK_MODES_PARAMS, GroupedArgs<Real> ga) { // (`waves`: the main launch's, not read here)
+// OBSERVE = true (k_bank_modes_grouped_observed<Real>): the entry of mh_bank_render_observed, with the taps of the coupled kernel's.
+template<typename Real, bool OBSERVE = false> __global__ void __launch_bounds__(JUNCTION_WAVES *WAVE) k_bank_modes_grouped(BANK_MODES_PARAMS, JunctionArgs<Real, GroupedArgs<Real>, OBSERVE> ga) { // (`waves`: the main launch's, not read here)
     typedef PairOf<Real> Pair;
     constexpr uint32_t TS = coupled_tile<Real>();
     extern __shared__ __attribute__((aligned(16))) unsigned char grouped_mem[];
@@ -921,6 +968,8 @@ template<typename Real> __global__ void __launch_bounds__(JUNCTION_WAVES *WAVE) 
             ga.compliance_out[G->member[i].row] = double(c_own[i]);
             ga.status_out[G->member[i].row] = solved ? MH_JUNCTION_SOLVED : MH_JUNCTION_REFUSED;
         }
+    Real *tap_row = nullptr;
+    if constexpr (OBSERVE) tap_row = tap_of<Real>(ga, active, G->first_wave + wave, frames, lane);
     for (uint32_t s0 = 0; s0 < frames; s0 += TS) {
         const uint32_t sn = min(TS, frames - s0);
         // this tile's approach samples, lane = sample (not finite: 0, as a drive's)
@@ -1001,6 +1050,8 @@ template<typename Real> __global__ void __launch_bounds__(JUNCTION_WAVES *WAVE) 
                 if (on >> i & 1u) z = z + a[i] * f_now[i];
             w.z_re = z;
             *reinterpret_cast<Pair *>(s_term + ds * PITCH + 2 * lane) = w.p_im * w.z_im + w.p_re * w.z_re;
+            if constexpr (OBSERVE)
+                if (tap_row) tap_store(tap_row, s0 + ds, w.z_im, w.z_re);
 #pragma unroll
             for (uint32_t i = 0; i < GROUP; ++i)
                 if (lane == ds) f_tile[i] = f_now[i];
@@ -1017,8 +1068,39 @@ template<typename Real> __global__ void __launch_bounds__(JUNCTION_WAVES *WAVE) 
     }
     store_wave(b, w, lane, chunk_energy);
 }
+template<typename Real> constexpr auto k_bank_modes_grouped_observed = &k_bank_modes_grouped<Real, true>;
 #undef BANK_MODES_PARAMS
 #undef BANK_MODES_ARGS
+// The partial rows of the pickups on junction objects (mh_bank_render_observed), from the states the tapped waves stored: one wave per
+// (tapped wave, tile of 32 frames) stages the object's pickup gains and the tile's states as k_bank_modes_read holds them -- [pickup][im | re]
+// [mode], and Im z, Re z as [sample][mode] -- and runs the same per-half sums (read_pickups), so a row is the bits k_bank_modes_read would
+// give for the same state trajectory.  taps: the tapped waves as (dealt object, first mode); grid: (tapped waves, tiles).
+template<typename Real> constexpr size_t observe_rows_lds() { return (2 * 32 * PITCH + MH_PICKUPS_PER_OBJECT * 2 * MODES_PER_WAVE) * sizeof(Real); }
+static_assert(observe_rows_lds<double>() <= 160 * 1024, "k_bank_observe_rows: two state tiles and the staged gains within the 160 KiB of LDS");
+template<typename Real>
+__global__ void __launch_bounds__(WAVE) k_bank_observe_rows(BankCols<Real> b, const WaveDesc *__restrict__ taps, const uint32_t *__restrict__ deal_objects, const uint32_t *__restrict__ render_count,
+                                                            const uint32_t *__restrict__ chunk_base, const Real *__restrict__ out_gain, const Real *__restrict__ listener_gain, uint32_t frames,
+                                                            const Real *__restrict__ states, ReadArgs<Real> rd) {
+    typedef PairOf<Real> Pair;
+    constexpr uint32_t TS = 32;
+    __shared__ __attribute__((aligned(16))) Real s_zim[TS * PITCH], s_zre[TS * PITCH];
+    __shared__ __attribute__((aligned(16))) Real s_pick[MH_PICKUPS_PER_OBJECT * 2 * MODES_PER_WAVE]; // [pickup][im | re][mode]
+    const WaveDesc wd = taps[blockIdx.x];
+    const uint32_t lane = threadIdx.x, half = lane / TS, ts = lane % TS, s0 = blockIdx.y * TS;
+    if (s0 >= frames) return; // (wave-uniform; the grid has no such tile)
+    const uint32_t sn = min(TS, frames - s0);
+    const WaveLane<Real> w = load_wave(b, deal_objects, chunk_base, out_gain, listener_gain, wd.dealt, wd.first_mode, render_count[wd.dealt], lane);
+    const uint32_t pk0 = rd.pick_ptr[wd.dealt], n_pick = min(rd.pick_ptr[wd.dealt + 1] - pk0, uint32_t(MH_PICKUPS_PER_OBJECT));
+    stage_pickup_gains(b, w, rd, pk0, n_pick, lane, s_pick);
+    const Real *tile = states + (size_t(blockIdx.x) * frames + s0) * TAP_FRAME + 2 * lane;
+    for (uint32_t ds = 0; ds < sn; ++ds) {
+        *reinterpret_cast<Pair *>(s_zim + ds * PITCH + 2 * lane) = *reinterpret_cast<const Pair *>(tile + size_t(ds) * TAP_FRAME);
+        *reinterpret_cast<Pair *>(s_zre + ds * PITCH + 2 * lane) = *reinterpret_cast<const Pair *>(tile + size_t(ds) * TAP_FRAME + MODES_PER_WAVE);
+    }
+    mh_lds_writes_landed();
+    __syncthreads();
+    if (ts < sn) read_pickups(s_zim, s_zre, s_pick, rd, pk0, n_pick, wd.first_mode, half, ts, s0, frames);
+}
 
 // Per dealt object (one wave each): energy, audible prefix, whole-object silence (ModalAudio.cpp:132-146).  Loads are
 // lane-parallel; every sum runs in the reference's order through wave-uniform lane broadcasts.
@@ -1272,6 +1354,7 @@ template<typename Real> struct BankImpl {
     std::vector<uint32_t> h_mode_count, picks_on, pick_fill;
     std::vector<int32_t> pick_dealt;
     DevArray<Real> junction_gain; // the coupled kernel's scratch gain rows
+    DevArray<Real> tap_states; // mh_bank_render_observed: what the tapped waves store, [tapped wave][frame][Im z | Re z][128]
     std::vector<uint8_t> on_junction; // per object: on a side of a junction of this call that was not left out
     std::vector<uint32_t> kept_rows; // the caller's indices of those junctions
     // per-block scratch
@@ -1315,7 +1398,8 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
                  void *out_v, double *object_energy, uint32_t *object_live, uint8_t *object_silenced, double *object_modal_energy, uint32_t n_drives,
                  const mh_drive *drives, const float *signals, uint32_t n_pickups, const mh_pickup *pickups, void *pickup_out_v, uint8_t *pickup_read,
                  uint32_t n_junctions, const mh_junction *junctions, const float *approach, void *force_out_v, double *compliance_out, uint8_t *status_out,
-                 const float *damping, void *carry_v) { // damping, carry_v: mh_bank_render_damped's; both null in every other entry (MH_JUNCTION_DAMPED is ignored then)
+                 const float *damping, void *carry_v, bool observe) { // damping, carry_v: mh_bank_render_damped's; both null in every other entry (MH_JUNCTION_DAMPED is ignored then)
+    // observe: mh_bank_render_observed -- a pickup on a kept junction's object is read
     mh_context *ctx = B.ctx;
     hipStream_t st = ctx->stream;
     Real *out = static_cast<Real *>(out_v);
@@ -1337,6 +1421,7 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
     const size_t o_excited = A.take((n_dealt + 1) * 4), o_junctions = A.take((n_junctions + 1) * sizeof(JunctionDev<Real>)), o_approach = A.take(size_t(n_junctions) * frames * sizeof(float));
     const size_t o_groups = A.take((n_junctions / 2 + 1) * sizeof(GroupDev<Real>));
     const size_t o_damping = A.take(damping ? (n_junctions + 1) * sizeof(Real) : 0), o_carry_in = A.take(damping ? (n_junctions + 1) * sizeof(Real) : 0);
+    const size_t o_taps = A.take(observe ? (n_waves + 1) * sizeof(WaveDesc) : 0), o_tap_of = A.take(observe ? (n_waves + JUNCTION_WAVES + 1) * 4 : 0);
     const size_t both_end = A.used;
     // (written by the kernels straight into the pinned arena -- no copy back: the host sees them once the block's last kernel has
     // raised the sequence number)
@@ -1488,7 +1573,8 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
             excited[d + 1] = excited[d] + (imp_ptr[d + 1] - imp_ptr[d]) + (deal_objects[d] < B.n_objects && B.on_junction[deal_objects[d]] ? 1u : 0u);
     }
     // ---- pickups: the ones the kernel may follow, grouped by dealt object in the caller's order; everything else gets a zero row ----
-    uint32_t read_row_count = 0, picks_dealt = 0;
+    uint32_t read_row_count = 0, picks_dealt = 0, picks_main = 0; // pickups with rows; those of them whose object the main launch renders
+    uint32_t n_taps = 0; // waves of the junction launches whose object carries a pickup (mh_bank_render_observed)
     uint64_t picked_modes = 0; // a pickup adds two multiply-adds per mode-sample of its object
     if (n_pickups) {
         uint32_t *pick_ptr = A.h<uint32_t>(o_pick_ptr);
@@ -1502,7 +1588,8 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
             pickup_read[q] = 0;
             pick_rows[q] = {0, 0};
             if (m.object >= B.n_objects || B.h_mode_count[m.object] == 0 || m.advance > 2) continue;
-            if (any_junction && B.on_junction[m.object]) continue; // its waves are the coupled kernel's, which reads for no pickup (in this version)
+            const bool junction_object = any_junction && B.on_junction[m.object];
+            if (junction_object && !observe) continue; // its waves are the coupled kernel's, which reads for no pickup except in mh_bank_render_observed
             if (!B.blend_ok(m) || B.picks_on[m.object] >= MH_PICKUPS_PER_OBJECT) continue;
             ++B.picks_on[m.object];
             pickup_read[q] = 1;
@@ -1511,6 +1598,7 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
             B.pick_dealt[q] = d;
             ++pick_ptr[d + 1];
             ++picks_dealt;
+            if (!junction_object) ++picks_main;
         }
         for (uint32_t d = 0; d < n_dealt; ++d) pick_ptr[d + 1] += pick_ptr[d];
         B.pick_fill.assign(pick_ptr, pick_ptr + n_dealt + 1);
@@ -1522,6 +1610,28 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
             pick_dev[B.pick_fill[d]++] = {blend_dev<Real>(m), m.advance, read_row_count};
             read_row_count += pick_rows[q].n_rows;
             picked_modes += render_count[d];
+        }
+        // the waves of the junction launches that store their states: every wave of a junction object that carries a pickup, by its index
+        // among those launches' waves
+        if (observe && picks_dealt > picks_main) {
+            WaveDesc *taps = A.h<WaveDesc>(o_taps);
+            uint32_t *tap_of = A.h<uint32_t>(o_tap_of);
+            std::fill(tap_of, tap_of + n_waves + JUNCTION_WAVES + 1, NO_TAP);
+            auto tap_object = [&](uint32_t d, uint32_t first_wave, uint32_t object_waves) {
+                if (pick_ptr[d + 1] == pick_ptr[d]) return;
+                for (uint32_t i = 0; i < object_waves; ++i) {
+                    tap_of[first_wave + i] = n_taps;
+                    taps[n_taps++] = {d, i * uint32_t(MODES_PER_WAVE)};
+                }
+            };
+            const JunctionDev<Real> *jd = A.h<JunctionDev<Real>>(o_junctions);
+            for (uint32_t j = 0; j < n_coupled; ++j) {
+                tap_object(jd[j].side[0].dealt, jd[j].first_wave, jd[j].side[0].waves);
+                if (jd[j].side[1].waves) tap_object(jd[j].side[1].dealt, jd[j].first_wave + jd[j].side[0].waves, jd[j].side[1].waves);
+            }
+            const GroupDev<Real> *gd = A.h<GroupDev<Real>>(o_groups);
+            for (uint32_t g = 0; g < n_groups; ++g)
+                for (uint32_t o = 0; o < gd[g].n_objects; ++o) tap_object(gd[g].dealt[o], gd[g].first_wave + gd[g].wave0[o], gd[g].waves[o]);
         }
     }
     for (uint32_t q = 0; q <= n_renderers; ++q) {
@@ -1587,7 +1697,24 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
             });
             const CoupledArgs<Real> ca{B.defl_gain, A.d<JunctionDev<Real>>(o_junctions), A.d<float>(o_approach), A.hd<Real>(o_junction_force), A.hd<double>(o_compliance), A.hd<uint32_t>(o_status)};
             TimedLaunch timed(ctx, MH_KERNEL_JUNCTION, double(n_coupled) * double(frames));
-            if (any_damped) {
+            if (n_taps) { // some junction object carries a pickup: the entries that also store the tapped waves' states
+                static_assert(coupled_lds<double>(JUNCTION_WAVES) <= 160 * 1024 && coupled_lds<float>(JUNCTION_WAVES) <= 160 * 1024, "the coupled entries' LDS within the 160 KiB");
+                if (coupled_lds<Real>(widest_junction) > 160 * 1024) mh_throw(MH_EINVAL, "a junction of %u waves", widest_junction); // (none is kept)
+                static PerDeviceOnce observed_attr;
+                observed_attr.run(ctx->device, [] {
+                    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_bank_modes_coupled_observed<Real>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+                    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_bank_modes_coupled_hertz_observed<Real>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+                    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_bank_modes_coupled_damped_observed<Real>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+                });
+                ensure(ctx, B.tap_states, size_t(n_taps) * frames * TAP_FRAME);
+                if (any_damped) {
+                    const ObservedArgs<Real, DampedArgs<Real>> oa{{ca, A.d<Real>(o_damping), A.d<Real>(o_carry_in), A.hd<Real>(o_carry_out)}, A.d<uint32_t>(o_tap_of), B.tap_states};
+                    launch_modes(k_bank_modes_coupled_damped_observed<Real>, n_coupled, widest_junction * WAVE, coupled_lds<Real>(widest_junction), B.junction_gain, oa);
+                } else {
+                    const ObservedArgs<Real, CoupledArgs<Real>> oa{ca, A.d<uint32_t>(o_tap_of), B.tap_states};
+                    launch_modes(any_hertz ? k_bank_modes_coupled_hertz_observed<Real> : k_bank_modes_coupled_observed<Real>, n_coupled, widest_junction * WAVE, coupled_lds<Real>(widest_junction), B.junction_gain, oa);
+                }
+            } else if (any_damped) {
                 const DampedArgs<Real> da{ca, A.d<Real>(o_damping), A.d<Real>(o_carry_in), A.hd<Real>(o_carry_out)};
                 launch_modes(k_bank_modes_coupled_damped<Real>, n_coupled, widest_junction * WAVE, coupled_lds<Real>(widest_junction), B.junction_gain, da);
             } else {
@@ -1600,7 +1727,25 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
             attr.run(ctx->device, [] { HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_bank_modes_grouped<Real>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); });
             const GroupedArgs<Real> ga{B.defl_gain, A.d<GroupDev<Real>>(o_groups), A.d<float>(o_approach), A.hd<Real>(o_junction_force), A.hd<double>(o_compliance), A.hd<uint32_t>(o_status)};
             TimedLaunch timed(ctx, MH_KERNEL_JUNCTION, double(grouped_members) * double(frames));
-            launch_modes(&k_bank_modes_grouped<Real>, n_groups, widest_group * WAVE, grouped_lds<Real>(widest_group), B.junction_gain, ga);
+            if (n_taps) {
+                static_assert(grouped_lds<double>(JUNCTION_WAVES) <= 160 * 1024 && grouped_lds<float>(JUNCTION_WAVES) <= 160 * 1024, "the grouped entries' LDS within the 160 KiB");
+                if (grouped_lds<Real>(widest_group) > 160 * 1024) mh_throw(MH_EINVAL, "a junction group of %u waves", widest_group); // (none is kept)
+                static PerDeviceOnce observed_attr;
+                observed_attr.run(ctx->device, [] { HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_bank_modes_grouped_observed<Real>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); });
+                ensure(ctx, B.tap_states, size_t(n_taps) * frames * TAP_FRAME);
+                const ObservedArgs<Real, GroupedArgs<Real>> oa{ga, A.d<uint32_t>(o_tap_of), B.tap_states};
+                launch_modes(k_bank_modes_grouped_observed<Real>, n_groups, widest_group * WAVE, grouped_lds<Real>(widest_group), B.junction_gain, oa);
+            } else {
+                launch_modes(&k_bank_modes_grouped<Real>, n_groups, widest_group * WAVE, grouped_lds<Real>(widest_group), B.junction_gain, ga);
+            }
+        }
+        if (n_taps) { // the tapped waves' partial rows, in k_bank_modes_read's order; they join read_rows ahead of k_bank_read_rows
+            ensure(ctx, B.read_rows, size_t(read_row_count + 1) * frames);
+            const ReadArgs<Real> rd{B.defl_gain, A.d<uint32_t>(o_pick_ptr), A.d<PickupDev<Real>>(o_pick_dev), B.read_rows, 0u};
+            TimedLaunch timed(ctx, MH_KERNEL_JUNCTION, 0.0);
+            k_bank_observe_rows<Real><<<dim3(n_taps, div_up(frames, 32u)), WAVE, 0, st>>>(B.cols(), A.d<WaveDesc>(o_taps), A.d<uint32_t>(o_deal), A.d<uint32_t>(o_count), A.d<uint32_t>(o_chunk_base), d_out_gain,
+                                                                                        d_listener, frames, B.tap_states, rd);
+            KERNEL_CHECK();
         }
         if (main_waves) {
             uint64_t rendered_modes = 0;
@@ -1612,7 +1757,7 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
             // a block without drives launches what it always did; one with drives takes the launch with the many-row loop (and its
             // LDS) only when some object has more rows than the register path holds
             const bool rows_loop = driven_rows && max_imp > IMP_REG;
-            if (picks_dealt) { // a block with pickups some dealt object carries: the entry that also reads
+            if (picks_main) { // a block with pickups some dealt object of the main launch carries: the entry that also reads
                 ensure(ctx, B.read_rows, size_t(read_row_count + 1) * frames);
                 const ReadArgs<Real> rd{B.defl_gain, A.d<uint32_t>(o_pick_ptr), A.d<PickupDev<Real>>(o_pick_dev), B.read_rows, rows_loop ? 1u : 0u};
                 launch_modes(&k_bank_modes_read<Real>, main_waves, WAVE, 0, B.gain_scratch, rd);
@@ -1804,13 +1949,13 @@ int mh_bank_set_deflection_gain(mh_bank *bank, uint32_t first, uint32_t count, c
         return MH_OK;
     } catch (const std::exception &e) { return mh_guard(bank->ctx, e); }
 }
-// mh_bank_render_coupled (damping = carry = null: MH_JUNCTION_DAMPED is ignored) and mh_bank_render_damped
+// mh_bank_render_coupled (damping = carry = null: MH_JUNCTION_DAMPED is ignored), mh_bank_render_damped and mh_bank_render_observed (observe)
 static int render_junctions(mh_bank *bank, uint32_t frames, float click_gain, uint32_t n_impacts, mh_impact *impacts, uint32_t n_renderers, const uint32_t *deal_offset,
                             const uint32_t *deal_objects, const uint32_t *render_count, const uint32_t *tuned_count, const float *out_gain, const float *listener_gain,
                             void *out, double *object_energy, uint32_t *object_live, uint8_t *object_silenced, double *object_modal_energy, uint32_t n_drives,
                             const mh_drive *drives, const float *signals, uint32_t n_pickups, const mh_pickup *pickups, void *pickup_out, uint8_t *pickup_read,
                             uint32_t n_junctions, const mh_junction *junctions, const float *approach, void *force_out, double *compliance_out, uint8_t *status_out,
-                            const float *damping, void *carry) {
+                            const float *damping, void *carry, bool observe = false) {
     if (!bank || !out || (n_impacts && !impacts) || (n_renderers && !deal_offset) || !out_gain || !listener_gain || (n_drives && (!drives || !signals))) return MH_EINVAL;
     if (n_pickups && (!pickups || !pickup_out || !pickup_read)) return MH_EINVAL;
     if (n_junctions && (!junctions || !approach || !force_out || !compliance_out || !status_out)) return MH_EINVAL;
@@ -1822,7 +1967,7 @@ static int render_junctions(mh_bank *bank, uint32_t frames, float click_gain, ui
         auto go = [&](auto &B) {
             render_impl(B, frames, click_gain, n_impacts, impacts, n_renderers, deal_offset, deal_objects, render_count, tuned_count, out_gain, listener_gain, out, object_energy,
                         object_live, object_silenced, object_modal_energy, n_drives, drives, signals, n_pickups, pickups, pickup_out, pickup_read, n_junctions, junctions, approach,
-                        force_out, compliance_out, status_out, damping, carry);
+                        force_out, compliance_out, status_out, damping, carry, observe);
         };
         if (bank->dbl) go(*bank->d); else go(*bank->f);
         return MH_OK;
@@ -1848,6 +1993,18 @@ int mh_bank_render_damped(mh_bank *bank, uint32_t frames, float click_gain, uint
     return render_junctions(bank, frames, click_gain, n_impacts, impacts, n_renderers, deal_offset, deal_objects, render_count, tuned_count, out_gain, listener_gain, out, object_energy,
                             object_live, object_silenced, object_modal_energy, n_drives, drives, signals, n_pickups, pickups, pickup_out, pickup_read, n_junctions, junctions, approach,
                             force_out, compliance_out, status_out, damping ? damping : &no_damping, carry);
+}
+int mh_bank_render_observed(mh_bank *bank, uint32_t frames, float click_gain, uint32_t n_impacts, mh_impact *impacts, uint32_t n_renderers, const uint32_t *deal_offset,
+                            const uint32_t *deal_objects, const uint32_t *render_count, const uint32_t *tuned_count, const float *out_gain, const float *listener_gain,
+                            void *out, double *object_energy, uint32_t *object_live, uint8_t *object_silenced, double *object_modal_energy, uint32_t n_drives,
+                            const mh_drive *drives, const float *signals, uint32_t n_pickups, const mh_pickup *pickups, void *pickup_out, uint8_t *pickup_read,
+                            uint32_t n_junctions, const mh_junction *junctions, const float *approach, void *force_out, double *compliance_out, uint8_t *status_out,
+                            const float *damping, void *carry) {
+    if (n_junctions && (!damping || !carry)) return MH_EINVAL;
+    static const float no_damping = 0; // (as in mh_bank_render_damped)
+    return render_junctions(bank, frames, click_gain, n_impacts, impacts, n_renderers, deal_offset, deal_objects, render_count, tuned_count, out_gain, listener_gain, out, object_energy,
+                            object_live, object_silenced, object_modal_energy, n_drives, drives, signals, n_pickups, pickups, pickup_out, pickup_read, n_junctions, junctions, approach,
+                            force_out, compliance_out, status_out, damping ? damping : &no_damping, carry, true);
 }
 int mh_bank_render_read(mh_bank *bank, uint32_t frames, float click_gain, uint32_t n_impacts, mh_impact *impacts, uint32_t n_renderers, const uint32_t *deal_offset,
                         const uint32_t *deal_objects, const uint32_t *render_count, const uint32_t *tuned_count, const float *out_gain, const float *listener_gain,

@@ -33,8 +33,18 @@ the exciter dipping in and out of the surface.
                                                                              and this tree's groups, G = 1, 16, 64 of n = 2, 3, 4, beside the same
                                                                              junctions ungrouped (256 objects) -> profiles/bank_groups.json
 
+    python tools/bank_junction_bench.py --pickups 4 --junctions 16 --sides 2   the call through Scene.render_observed with 4 pickups (advances 0, 1, 2 in
+                                                                             turn) on every junction object; --pickups 0: the same entry without them
+    python tools/bank_junction_bench.py --observed-against T [--runs 3]      this tree's render_observed with P = 0, 1, 2, 4, 8 pickups on every junction
+                                                                             object (16 and 64 junctions, one- and two-sided; 16 and 64 groups of 3), and the
+                                                                             unchanged paths -- render_coupled, render_damped and tools/bank_bench.py -- of a
+                                                                             built checkout T of the parent commit and of this tree, interleaved in fresh
+                                                                             processes -> profiles/bank_observed.json
+
 (The coupled kernel and the group kernel are timed under one kernel class, 6: a block that holds lone junctions AND groups makes two
-launches of it, and `coupled_kernel_us_per_block`, the class total over its launch count, is then per launch.  No mode here mixes the two.)
+launches of it, and `coupled_kernel_us_per_block`, the class total over its launch count, is then per launch.  No mode here mixes the two.
+With --pickups P > 0 the pickup rows' kernel, k_bank_observe_rows, is a second launch of the class: `junction_kernels_us_per_block`, the
+class total over the blocks, is the junction kernel and that kernel together.)
 
 The comparison also runs the unchanged tools/bank_bench.py of both trees (all_live.ms_per_block).  Kernel times per block are the
 library's kernel-class timers: class 2 the resonator kernel of the objects off the junctions, class 6 the coupled kernel.  The coupled
@@ -62,9 +72,10 @@ def sides_of(j, sides):
     return (j,) if sides == 1 else (2 * j, 2 * j + 1)
 
 
-def measure(tree, entry, junctions, sides, objects, blocks, renderers, forces_path, save_forces, law="linear", members=0, ungrouped=False):
+def measure(tree, entry, junctions, sides, objects, blocks, renderers, forces_path, save_forces, law="linear", members=0, ungrouped=False, pickups=None):
     """members >= 2: the junctions are groups of `members` exciter junctions, junction q at point q % members of object q // members with
-    the shared flag -- or, ungrouped, of object q without it."""
+    the shared flag -- or, ungrouped, of object q without it.  pickups = P (not None): the call goes through Scene.render_observed with P
+    pickups on every junction object."""
     sys.path.insert(0, tree)
     from mesheditor_amd import bank as hipbank
     from tools import bank_bench
@@ -105,9 +116,17 @@ def measure(tree, entry, junctions, sides, objects, blocks, renderers, forces_pa
         u = u if junctions else none
         damping = [1.0 / (float(u[j].max()) * SR) for j in range(junctions)]  # damped: D in s/m with l x0 = D SR x0 = 1
         carry = [None]
+        watched = sorted({where(j)[0] for j in range(junctions)} if members else {o for j in range(junctions) for o in sides_of(j, sides)})
+        probes = [hipbank.Pickup.of(o, (o + i) % POINTS, (1.0, 0.0, 0.0), NORMAL, 1.0 + 0.5 * i, i % 3) for o in watched for i in range(pickups or 0)]
+        probes = (hipbank.Pickup * len(probes))(*probes) if probes else []
+        peak_read = [0.0]
 
         def block():
-            if damped:
+            if pickups is not None:
+                reads, flags, forces, _, status, carry[0] = sc.render_observed(out, rows, signals, probes, contacts, u, damping if damped else None, carry[0])
+                assert (flags == 1).all()
+                peak_read[0] = max(peak_read[0], float(np.abs(reads).max()) if len(reads) else 0.0)
+            elif damped:
                 _, _, forces, _, status, carry[0] = sc.render_damped(out, rows, signals, [], contacts, u, damping, carry[0])
             else:
                 _, _, forces, _, status = sc.render_coupled(out, rows, signals, [], contacts, u)
@@ -143,12 +162,13 @@ def measure(tree, entry, junctions, sides, objects, blocks, renderers, forces_pa
     tuned, live, ring = sc.object_state()
     assert np.isfinite(peak) and peak > 0 and (ring == 1).all() and int(live.sum()) == objects * MODES
     assert entry != "coupled" or junctions == 0 or (np.isfinite(peak_force[0]) and peak_force[0] > 0)
+    assert not pickups or not junctions or (np.isfinite(peak_read[0]) and peak_read[0] > 0)
     if save_forces and junctions:
         np.save(save_forces, kept[0].astype(np.float32))
     sc.close()
     t = np.array(times)
     coupled_us = 1e3 * kj["total_ms"] / max(1, kj["launches"])
-    return {"entry": entry, "law": law, "junctions": junctions, "sides": sides, "members": members, "grouped": bool(members) and not ungrouped, "objects": objects, "modes_per_object": MODES, "blocks": blocks, "ms_per_block": 1e3 * float(t.mean()),
+    return {"entry": entry if pickups is None else "observed", "pickups_per_object": pickups, "junction_kernels_us_per_block": 1e3 * kj["total_ms"] / max(1, blocks), "law": law, "junctions": junctions, "sides": sides, "members": members, "grouped": bool(members) and not ungrouped, "objects": objects, "modes_per_object": MODES, "blocks": blocks, "ms_per_block": 1e3 * float(t.mean()),
             "ms_per_block_median": 1e3 * float(np.median(t)), "ms_per_block_p99": 1e3 * float(np.quantile(t, 0.99)), "kernel_us_per_block": 1e3 * k["total_ms"] / max(1, k["launches"]),
             "coupled_kernel_us_per_block": coupled_us, "coupled_us_per_frame": coupled_us / BLOCK, "coupled_cycles_per_frame": coupled_us / BLOCK * ENGINE_MHZ,
             "real_time_ms_per_block": 1e3 * BLOCK / SR}
@@ -304,6 +324,54 @@ def compare_damped(parent, runs, objects, blocks, renderers, out_path):
     print(json.dumps(summary))
 
 
+def compare_observed(parent, runs, objects, blocks, renderers, out_path, all_live):
+    """This tree's render_observed with P pickups on every junction object (one run each), and the unchanged paths of the parent and of this
+    tree, `runs` fresh processes each: the new figures may not be slower than the parent's by more than the spread of the parent's own runs."""
+    me = os.path.abspath(__file__)
+    common = ["--objects", str(objects), "--blocks", str(blocks), "--renderers", str(renderers)]
+    result = {"workload": f"{objects} objects x {MODES} modes @48k, {BLOCK}-frame blocks, fp32, {renderers} renderers, one drive on every object and J junctions (K C = 10) in every block; "
+                          "observed: through render_observed with P pickups on every junction object", "runs_each": runs, "observed": {}, "unchanged": {}, "all_live": {"parent": [], "new": []}}
+
+    def save():
+        os.makedirs(os.path.dirname(out_path), exist_ok=True)
+        with open(out_path, "w") as f:
+            json.dump(result, f, indent=1)
+    q = subprocess.run(["timeout", "-k", "10", "300", sys.executable, "-c", "import torch; p = torch.cuda.get_device_properties(0); print(p.name, p.gcnArchName, '%d CUs' % p.multi_processor_count, '|', torch.version.hip)"], capture_output=True, text=True)
+    if q.returncode != 0:
+        raise SystemExit("no GPU to measure on: " + q.stderr[-2000:])
+    result["device"], result["hip"] = (v.strip() for v in q.stdout.strip().splitlines()[-1].split("|"))
+    shapes = [("%d x %d-sided" % (j, sides), ["--junctions", str(j), "--sides", str(sides)]) for sides in (1, 2) for j in (16, 64)]
+    shapes += [("%d groups of 3" % g, ["--members", "3", "--junctions", str(3 * g)]) for g in (16, 64)]  # (every member junction counts as one towards the objects' bound)
+    for name, shape in shapes:
+        for p in (0, 1, 2, 4, 8):
+            result["observed"].setdefault(name, {})["P = %d" % p] = child([me, "--pickups", str(p)] + shape + common + (["--objects", str(max(objects, 256))] if "--members" in shape else []))
+            save()
+    for _ in range(runs):
+        for name, law, shape in (("render_coupled, 16 x 1-sided", "linear", ["--junctions", "16"]), ("render_coupled, 64 x 2-sided", "linear", ["--junctions", "64", "--sides", "2"]),
+                                 ("render_damped, 16 x 1-sided", "damped", ["--junctions", "16"]), ("render_damped, 64 x 2-sided", "damped", ["--junctions", "64", "--sides", "2"])):
+            row = result["unchanged"].setdefault(name, {"parent": [], "new": []})
+            row["parent"].append(child([me, "--tree", parent, "--law", law] + shape + common))
+            row["new"].append(child([me, "--law", law] + shape + common))
+            save()
+        for name, tree in (("parent", parent), ("new", HERE)) if all_live else ():
+            r = child([os.path.join(tree, "tools", "bank_bench.py")], 600)
+            result["all_live"][name].append({"ms_per_block": r["all_live"]["ms_per_block"], "kernel_us_per_block": r["all_live"]["kernel_us_per_block"]})
+            save()
+    med = lambda rows, key: float(np.median([r[key] for r in rows])) if rows else None
+    pair = lambda old, new: {"parent_ms_per_block": [r["ms_per_block"] for r in old], "new_ms_per_block": [r["ms_per_block"] for r in new],
+                             "parent_spread_ms": (max(r["ms_per_block"] for r in old) - min(r["ms_per_block"] for r in old)) if old else None,
+                             "new_median_minus_parent_median_ms": (med(new, "ms_per_block") - med(old, "ms_per_block")) if old else None,
+                             "parent_coupled_kernel_us_per_block": med(old, "coupled_kernel_us_per_block") if old and "coupled_kernel_us_per_block" in old[0] else None,
+                             "new_coupled_kernel_us_per_block": med(new, "coupled_kernel_us_per_block") if new and "coupled_kernel_us_per_block" in new[0] else None}
+    result["summary"] = {"real_time_ms_per_block": 1e3 * BLOCK / SR,
+                         "observed": {name: {p: {"ms_per_block": r["ms_per_block"], "ms_per_block_median": r["ms_per_block_median"], "junction_kernels_us_per_block": r["junction_kernels_us_per_block"],
+                                                 "main_kernel_us_per_block": r["kernel_us_per_block"]} for p, r in row.items()} for name, row in result["observed"].items()},
+                         "unchanged": {name: pair(row["parent"], row["new"]) for name, row in result["unchanged"].items()},
+                         "all_live": pair(result["all_live"]["parent"], result["all_live"]["new"]) if all_live else None}
+    save()
+    print(json.dumps(result["summary"]))
+
+
 def compare_groups(parent, runs, objects, blocks, renderers, out_path, all_live):
     """The unchanged paths of the parent and of this tree -- the same kernels: the new figures have to land within the parent's own spread --
     and this tree's groups beside the same junctions ungrouped."""
@@ -372,11 +440,16 @@ def main():
     ap.add_argument("--members", type=int, default=0, help="coupled: the junctions are groups of this many exciter junctions on one object each (2 ... 4)")
     ap.add_argument("--ungrouped", action="store_true", help="with --members: the same junctions on objects of their own, without the shared flag")
     ap.add_argument("--groups", action="store_true", help="with --against: the unchanged paths of both trees and this tree's groups -> profiles/bank_groups.json")
+    ap.add_argument("--pickups", type=int, default=None, help="coupled: through Scene.render_observed with this many pickups on every junction object (0 ... 8)")
+    ap.add_argument("--observed-against", help="built checkout of the parent commit: this tree's render_observed with P pickups per junction object, and the unchanged paths of both trees -> profiles/bank_observed.json")
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--no-all-live", action="store_true", help="skip tools/bank_bench.py of both trees")
     ap.add_argument("--out", default=os.path.join(HERE, "profiles", "bank_junctions.json"))
     a = ap.parse_args()
-    if a.damped_against:
+    if a.observed_against:
+        out = a.out if a.out != ap.get_default("out") else os.path.join(HERE, "profiles", "bank_observed.json")
+        compare_observed(os.path.abspath(a.observed_against), a.runs, a.objects, a.blocks, a.renderers, out, not a.no_all_live)
+    elif a.damped_against:
         out = a.out if a.out != ap.get_default("out") else os.path.join(HERE, "profiles", "bank_damped.json")
         compare_damped(os.path.abspath(a.damped_against), a.runs, a.objects, a.blocks, a.renderers, out)
     elif a.laws_against:
@@ -388,7 +461,7 @@ def main():
     elif a.against:
         compare(os.path.abspath(a.against), a.runs, a.objects, a.blocks, a.renderers, a.out, not a.no_all_live)
     else:
-        print(json.dumps(measure(os.path.abspath(a.tree), a.entry, a.junctions, a.sides, a.objects, a.blocks, a.renderers, a.forces, a.save_forces, a.law, a.members, a.ungrouped)))
+        print(json.dumps(measure(os.path.abspath(a.tree), a.entry, a.junctions, a.sides, a.objects, a.blocks, a.renderers, a.forces, a.save_forces, a.law, a.members, a.ungrouped, a.pickups)))
 
 
 if __name__ == "__main__":
