@@ -115,6 +115,11 @@ void mh_mesh_destroy(mh_mesh *);
 /* FilterDegenerate + BuildQuadMesh + ComputeElementBases + AssembleQuadratic (mesh2modes.cpp:42-60,137-165,246-264,
  * 273-327) on the device: K as 3x3 node blocks (BSR), M as one scalar per node block (M = M_node (x) I3). */
 int mh_assemble(mh_context *, const mh_mesh *, const mh_material *, mh_system **out);
+/* What mh_assemble derives from the points and tets alone (numbering, interpolation lists, element bases, block patterns, aggregates,
+ * components) is built on the first assembly with the mesh's own context and kept with the mesh; later assemblies on it only form K and M.
+ * builds: how many times that structure has been built for this mesh (0 before the first assembly and after a failed one);
+ * bytes: device memory the kept structure holds (0 while there is none).  Either pointer may be null. */
+int mh_mesh_structure_stats(const mh_mesh *, uint64_t *builds, uint64_t *bytes);
 void mh_system_destroy(mh_system *);
 int mh_system_dims(const mh_system *, uint32_t *dofs, uint32_t *node_count, uint32_t *kept_tets, uint64_t *node_blocks);
 /* QuadMesh::ElementNodes in the reference's numbering (corners, then midside ids in first-encounter order). */

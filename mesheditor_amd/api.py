@@ -94,6 +94,12 @@ class Mesh:
         self.ctx.check(self.ctx.L.mh_nearest_points(self.ctx.h, self.h, len(pos), _p(pos), _p(out)))
         return out
 
+    def structure_stats(self):
+        """(times the mesh's derived structure has been built, device bytes the kept one holds) -- include/modalhip.h: mh_mesh_structure_stats."""
+        builds, nbytes = C.c_uint64(0), C.c_uint64(0)
+        self.ctx.check(self.ctx.L.mh_mesh_structure_stats(self.h, C.byref(builds), C.byref(nbytes)))
+        return builds.value, nbytes.value
+
     def close(self):
         if self.h and self.ctx.h:
             self.ctx.L.mh_mesh_destroy(self.h)

@@ -220,6 +220,13 @@ int mh_mesh_create(mh_context *ctx, uint32_t n_points, const double *points_xyz,
     } catch (const std::exception &e) { return mh_guard(ctx, e); }
 }
 void mh_mesh_destroy(mh_mesh *m) { delete m; }
+int mh_mesh_structure_stats(const mh_mesh *m, uint64_t *builds, uint64_t *bytes) {
+    if (!m) return MH_EINVAL;
+    std::lock_guard<std::mutex> lock(m->structure_mutex);
+    if (builds) *builds = m->structure_builds.load();
+    if (bytes) *bytes = m->structure ? m->structure->device_bytes() : 0;
+    return MH_OK;
+}
 
 int mh_assemble(mh_context *ctx, const mh_mesh *mesh, const mh_material *material, mh_system **out) {
     if (!ctx || !mesh || !material || !out) return MH_EINVAL;

@@ -14,7 +14,9 @@
 #include <cstring>
 #include <iterator>
 #include <limits>
+#include <atomic>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <stdexcept>
 #include <string>
@@ -354,23 +356,30 @@ struct TimedLaunch {
     TimedLaunch &operator=(const TimedLaunch &) = delete;
 };
 
-// RAII device array bound to a context's pool.
+// RAII device array bound to a context's pool.  An ALIAS (alias_of) refers to another array's memory without owning it: it never releases
+// to the pool, and whoever makes one keeps the owner alive (mh_system holds its mesh structure by shared pointer).
 template<typename T> struct DevArray {
     mh_context *ctx{nullptr};
     T *ptr{nullptr};
     size_t count{0};
+    bool owned{true};
     DevArray() = default;
     DevArray(mh_context *c, size_t n) { reset(c, n); }
     DevArray(const DevArray &) = delete;
     DevArray &operator=(const DevArray &) = delete;
-    DevArray(DevArray &&o) noexcept : ctx(o.ctx), ptr(o.ptr), count(o.count) { o.ptr = nullptr; o.count = 0; }
+    DevArray(DevArray &&o) noexcept : ctx(o.ctx), ptr(o.ptr), count(o.count), owned(o.owned) { o.ptr = nullptr; o.count = 0; o.owned = true; }
     DevArray &operator=(DevArray &&o) noexcept {
         if (this != &o) {
             free();
-            ctx = o.ctx; ptr = o.ptr; count = o.count;
-            o.ptr = nullptr; o.count = 0;
+            ctx = o.ctx; ptr = o.ptr; count = o.count; owned = o.owned;
+            o.ptr = nullptr; o.count = 0; o.owned = true;
         }
         return *this;
+    }
+    void alias_of(const DevArray &o) {
+        free();
+        ctx = o.ctx; ptr = o.ptr; count = o.count;
+        owned = false;
     }
     ~DevArray() { free(); }
     void reset(mh_context *c, size_t n) {
@@ -384,9 +393,10 @@ template<typename T> struct DevArray {
         if (poison && ptr) (void)hipMemsetAsync(ptr, 0xff, n * sizeof(T), c->stream);
     }
     void free() {
-        if (ptr && ctx) ctx->pool.release(ptr);
+        if (ptr && ctx && owned) ctx->pool.release(ptr);
         ptr = nullptr;
         count = 0;
+        owned = true;
     }
     T *get() const { return ptr; }
     operator T *() const { return ptr; }
@@ -403,11 +413,48 @@ template<typename T> struct DevArray {
     }
 };
 
+// Everything mh_assemble derives from a mesh's points and tets alone (mh_pipeline.hip: build_structure): built the first time a system is
+// assembled on the mesh with the mesh's own context, then shared -- immutable -- by the mesh and every system assembled on it.  A system
+// may outlive its mesh, so the points are the structure's own copy.  Per level: the block pattern and the two lists k_assemble_flat reads.
+struct MhLevelStructure {
+    uint32_t n_nodes{0};
+    uint64_t n_blocks{0};
+    DevArray<uint32_t> row_ptr, col; // n_nodes + 1, n_blocks
+    DevArray<uint32_t> seg, pay;     // n_blocks + 1: first contribution of every node block; kept_tets x NN x NN: the contributions, sorted by block
+};
+struct mh_structure {
+    mh_context *ctx{nullptr};
+    uint32_t n_points{0}, kept_tets{0}, n_nodes{0}, n_edges{0};
+    DevArray<double> points;          // n_points x 3, the mesh's points
+    DevArray<uint32_t> tets;          // kept_tets x 4, the tets FilterDegenerate kept
+    DevArray<uint32_t> elem_nodes_ref, elem_nodes, elem_p1;
+    DevArray<double> elem_basis;
+    DevArray<uint32_t> perm, inv_perm;
+    bool relative{false};             // a body far from the origin: node coordinates relative to `origin`, the bounding box's corner
+    double origin[3]{0, 0, 0};
+    double node_box[6]{0, 0, 0, 0, 0, 0}; // bounding box of node_xyz (minima, maxima), from the host copy the components pass reads
+    DevArray<double> node_xyz, p1_xyz;
+    DevArray<uint32_t> parent_a, parent_b, p1_edge_ptr, p1_edge_mid, p1_corner;
+    DevArray<double> tables2, tables1, support2, support1; // shape-function integrals of the two levels (full, and on the supports)
+    MhLevelStructure L2, L1;
+    uint32_t agg_target{16}, n_agg{0};
+    DevArray<uint32_t> agg_of, agg_ptr, agg_nodes;
+    DevArray<double> agg_t;
+    uint32_t n_components{1}, unreferenced_points{0};
+    DevArray<uint32_t> node_component;
+    DevArray<double> component_centroid;
+    uint64_t device_bytes() const;   // mh_pipeline.hip: what the arrays above hold
+};
+
 struct mh_mesh {
     mh_context *ctx;
     uint32_t n_points{0}, n_tets{0};
     DevArray<double> points; // n_points x 3
     DevArray<uint32_t> tets; // n_tets x 4
+    // the derived structure, built on first assembly with this mesh's context (under the mutex: concurrent first use builds it once)
+    mutable std::mutex structure_mutex;
+    mutable std::shared_ptr<const mh_structure> structure;
+    mutable std::atomic<uint64_t> structure_builds{0};
 };
 
 // One level of the operator hierarchy: symmetric matrix in 3x3 node blocks (BSR), rows and columns in the level's
@@ -457,12 +504,15 @@ struct PatchSet {
 
 struct mh_system {
     mh_context *ctx;
+    // The mesh-only part: the arrays below that the material does not enter (everything but kval / mval and what the hierarchy and the solve
+    // make) are aliases of this structure's memory.  Nothing writes them after the structure's build.
+    std::shared_ptr<const mh_structure> structure;
     uint32_t dropped_patches[2]{0, 0}; // sliver patches dropped at the last hierarchy build (P2 level, P1 level)
     double plain_residual{-1.0}; // last solve: worst 2-norm relative residual of the returned elastic pairs when they were accepted in the Jacobi-scaled norm, else -1
     mh_material material{};
     uint32_t n_points{0}, kept_tets{0}, n_nodes{0}, n_edges{0};
     bool lmax_widened{false}; // a solve stalled and was redone with the smoothers' spectral bounds widened by a quarter (mh_eigs.hip, eigs_impl)
-    DevArray<double> points; // copy of mesh points (P1 node coordinates), reference numbering
+    DevArray<double> points; // the mesh points (P1 node coordinates), reference numbering
     DevArray<uint32_t> elem_nodes_ref; // kept_tets x 10, reference numbering
     DevArray<uint32_t> elem_nodes; // kept_tets x 10, internal numbering
     DevArray<double> elem_basis; // kept_tets x 16: four (gradient xyz, volume) quadruples = one 128-byte line per tet

@@ -61,7 +61,7 @@ std::mutex g_solve_mutex;
 //   MH_CYCLE=d2,d1,g,ratio[,ratio1]  shape of the preconditioner cycle: Chebyshev degrees of the P2 and P1 smoothers, P1 cycles per
 //                           application, spectrum ratio lmax / lmin the smoothers target; 0 or missing keeps a built-in value
 //   MH_TEST=...             test hooks, comma separated (what each forces: beside its member): sytrd_giveup, no_tridiag_wide, last_resort,
-//                           coarse_pivot, selfcheck_fail, lmax_low, potrf_chain, no_poly_start
+//                           coarse_pivot, selfcheck_fail, lmax_low, potrf_chain, no_poly_start, fresh_structure
 // Read elsewhere: MH_AGG, MH_PATCH_Q, MH_CLUSTERS, MH_CLUSTER_CAP, MH_POOL_CAP_MB; MH_TEST's poison, redzone and farzone (mh_common.h),
 // sytrd_multi, sytrd_fused and own_gemm (mh_dense.hip).
 struct Switches {
@@ -77,6 +77,7 @@ struct Switches {
     bool lmax_low = getenv("MH_TEST") && strstr(getenv("MH_TEST"), "lmax_low"); // the smoothers' spectral bounds 12 % low, below the spectrum's end (as an unconverged power iteration leaves them): the iteration stalls
     bool potrf_chain = getenv("MH_TEST") && strstr(getenv("MH_TEST"), "potrf_chain"); // the Gram blocks' Cholesky factorisations as the chain of launches they were before round 5
     bool no_poly_start = getenv("MH_TEST") && strstr(getenv("MH_TEST"), "no_poly_start"); // (A/B hook of round 5: the cold start block as rounds 1-4 had it)
+    bool fresh_structure = getenv("MH_TEST") && strstr(getenv("MH_TEST"), "fresh_structure"); // (A/B hook: every mh_assemble builds the mesh's structure anew -- mh_pipeline.hip reads it too -- and the start block's box comes from k_bbox, as before the structure was kept)
     Switches() {
         if (const char *c = getenv("MH_CYCLE")) {
             double v[5] = {0, 0, 0, 0, 0};
@@ -1713,17 +1714,24 @@ struct BlockLobpcg {
         // are bending modes of the walls -- and the Kuhn plate's block came out rank deficient (a few node layers through the thickness).
         bool with_poly = !warm && seed_rigid && !switches().no_poly_start && sys->n_components == 1 && poly_allowed;
         if (with_poly) {
-            DevArray<unsigned long long> keys(ctx, 6);
-            const unsigned long long init[6] = {~0ull, ~0ull, ~0ull, 0, 0, 0};
-            keys.upload(init, 6);
-            k_bbox<<<grid1(sys->n_nodes), TB, 0, st>>>(sys->node_xyz, sys->n_nodes, keys);
-            KERNEL_CHECK();
-            unsigned long long hk[6];
-            keys.download(hk, 6);
+            // The nodes' bounding box: the mesh structure holds it (mh_pipeline.hip: build_structure, from the host copy of node_xyz it reads
+            // anyway) -- no launch, no read-back.  MH_TEST=fresh_structure: k_bbox and its six-word read-back as before the structure
+            // was kept, and the two boxes must agree bit for bit.
             double box[6], longest = 0, shortest = 1e300;
-            for (int a = 0; a < 6; ++a) {
-                const unsigned long long u = (hk[a] >> 63) ? (hk[a] & 0x7fffffffffffffffull) : ~hk[a];
-                memcpy(&box[a], &u, sizeof(double));
+            memcpy(box, sys->structure->node_box, sizeof(box));
+            if (switches().fresh_structure) {
+                DevArray<unsigned long long> keys(ctx, 6);
+                const unsigned long long init[6] = {~0ull, ~0ull, ~0ull, 0, 0, 0};
+                keys.upload(init, 6);
+                k_bbox<<<grid1(sys->n_nodes), TB, 0, st>>>(sys->node_xyz, sys->n_nodes, keys);
+                KERNEL_CHECK();
+                unsigned long long hk[6];
+                keys.download(hk, 6);
+                for (int a = 0; a < 6; ++a) {
+                    const unsigned long long u = (hk[a] >> 63) ? (hk[a] & 0x7fffffffffffffffull) : ~hk[a];
+                    memcpy(&box[a], &u, sizeof(double));
+                }
+                if (memcmp(box, sys->structure->node_box, sizeof(box)) != 0) mh_throw(MH_EINVAL, "the structure's bounding box differs from the device's");
             }
             for (int a = 0; a < 3; ++a) longest = std::max(longest, box[3 + a] - box[a]), shortest = std::min(shortest, box[3 + a] - box[a]);
             with_poly = shortest >= 0.25 * longest;

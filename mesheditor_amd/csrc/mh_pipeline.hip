@@ -683,15 +683,16 @@ __global__ void k_fix_coarse_diag(double *__restrict__ a0, uint32_t n0, double r
 
 // ------------------------------------------------------------------------------------------------------------
 namespace {
+// The mesh-only half of a level: its block pattern and the contribution lists of the assembly kernel.
 template<int NN>
-void build_level(mh_context *ctx, CubTemp &tmp, const uint32_t *elem, uint32_t nt, uint32_t nnodes, const double *basis, const double *tables_dev,
-                 const double *support_tables_dev, const mh_material &mat, BsrLevel &lvl) {
+void build_level_structure(mh_context *ctx, CubTemp &tmp, const uint32_t *elem, uint32_t nt, uint32_t nnodes, MhLevelStructure &lvl) {
     const size_t npairs = size_t(nt) * NN * NN;
     DevArray<uint64_t> keys(ctx, npairs), keys_s(ctx, npairs);
-    DevArray<uint32_t> pay(ctx, npairs), pay_s(ctx, npairs), head(ctx, npairs), incl(ctx, npairs);
+    DevArray<uint32_t> pay(ctx, npairs), head(ctx, npairs), incl(ctx, npairs);
+    lvl.pay.reset(ctx, npairs);
     k_pairs<NN><<<div_up(npairs, TB), TB, 0, ctx->stream>>>(elem, nt, nnodes, keys, pay);
     KERNEL_CHECK();
-    sort_pairs(ctx, tmp, keys.get(), keys_s.get(), pay.get(), pay_s.get(), npairs, bit_width64(uint64_t(nnodes) * nnodes));
+    sort_pairs(ctx, tmp, keys.get(), keys_s.get(), pay.get(), lvl.pay.get(), npairs, bit_width64(uint64_t(nnodes) * nnodes));
     k_heads<<<div_up(npairs, TB), TB, 0, ctx->stream>>>(keys_s.get(), npairs, head.get());
     KERNEL_CHECK();
     inclusive_sum(ctx, tmp, head, incl, npairs);
@@ -700,13 +701,24 @@ void build_level(mh_context *ctx, CubTemp &tmp, const uint32_t *elem, uint32_t n
     lvl.n_blocks = nb;
     lvl.col.reset(ctx, nb);
     lvl.row_ptr.reset(ctx, size_t(nnodes) + 1);
-    lvl.kval.reset(ctx, size_t(nb) * 9);
-    lvl.mval.reset(ctx, nb);
-    DevArray<uint32_t> blk_row(ctx, nb), seg(ctx, size_t(nb) + 1);
-    k_block_index<<<div_up(npairs + 1, TB), TB, 0, ctx->stream>>>(keys_s, head, incl, npairs, nnodes, lvl.col, blk_row, seg);
+    lvl.seg.reset(ctx, size_t(nb) + 1);
+    DevArray<uint32_t> blk_row(ctx, nb);
+    k_block_index<<<div_up(npairs + 1, TB), TB, 0, ctx->stream>>>(keys_s, head, incl, npairs, nnodes, lvl.col, blk_row, lvl.seg);
     KERNEL_CHECK();
     k_segment_ptr<uint32_t><<<div_up(size_t(nnodes) + 1, TB), TB, 0, ctx->stream>>>(blk_row.get(), nb, nnodes, lvl.row_ptr.get());
     KERNEL_CHECK();
+}
+// The material half: K and M of a level on the structure's pattern.  One launch; no sort, no read-back, no synchronisation.
+template<int NN>
+void assemble_level(mh_context *ctx, const MhLevelStructure &ls, uint32_t nt, const double *basis, const double *tables_dev, const double *support_tables_dev,
+                    const mh_material &mat, BsrLevel &lvl) {
+    const uint32_t nb = uint32_t(ls.n_blocks);
+    lvl.n_nodes = ls.n_nodes;
+    lvl.n_blocks = ls.n_blocks;
+    lvl.col.alias_of(ls.col);
+    lvl.row_ptr.alias_of(ls.row_ptr);
+    lvl.kval.reset(ctx, size_t(nb) * 9);
+    lvl.mval.reset(ctx, nb);
     const double lambda = (mat.poisson_ratio * mat.young_modulus) / ((1 + mat.poisson_ratio) * (1 - 2 * mat.poisson_ratio));
     const double mu = mat.young_modulus / (2 * (1 + mat.poisson_ratio));
     {
@@ -718,8 +730,8 @@ void build_level(mh_context *ctx, CubTemp &tmp, const uint32_t *elem, uint32_t n
         // DESIGN.md section 5 has the measured pair.  A third form (one wave per node row, LDS-staged element data) was built in
         // between and measured slower than either (426 us; profiles/r02_ab_assembly.txt); it is gone.
         constexpr bool by_block = false; // round 1's kernel, one thread per node block: 573 us against 171 us
-        if (by_block) k_assemble<NN><<<div_up(nb, TB), TB, 0, ctx->stream>>>(seg, pay_s, nb, basis, tables_dev, mat.density, lambda, mu, lvl.kval, lvl.mval);
-        else k_assemble_flat<NN><<<div_up(nb, TB), TB, 0, ctx->stream>>>(seg, pay_s, nb, basis, support_tables_dev, mat.density, lambda, mu, lvl.kval, lvl.mval);
+        if (by_block) k_assemble<NN><<<div_up(nb, TB), TB, 0, ctx->stream>>>(ls.seg, ls.pay, nb, basis, tables_dev, mat.density, lambda, mu, lvl.kval, lvl.mval);
+        else k_assemble_flat<NN><<<div_up(nb, TB), TB, 0, ctx->stream>>>(ls.seg, ls.pay, nb, basis, support_tables_dev, mat.density, lambda, mu, lvl.kval, lvl.mval);
     }
     KERNEL_CHECK();
 }
@@ -799,13 +811,14 @@ std::vector<double> support_tables(const std::vector<double> &full, int nn) {
         }
     return out;
 }
-} // namespace
 
-void mh_build_system(mh_context *ctx, const mh_mesh *mesh, const mh_material &mat, mh_system *sys) {
+// The mesh-only part of mh_assemble: everything below is a function of the points and the tets.  (`sys` is the structure under construction.)
+std::shared_ptr<const mh_structure> build_structure(mh_context *ctx, const mh_mesh *mesh) {
+    auto built = std::make_shared<mh_structure>();
+    mh_structure *sys = built.get();
     CubTemp tmp;
     hipStream_t st = ctx->stream;
     sys->ctx = ctx;
-    sys->material = mat;
     const uint32_t npts = mesh->n_points, nt_in = mesh->n_tets;
     if (npts == 0 || nt_in == 0) mh_throw(MH_EEMPTY, "empty tet mesh");
     sys->n_points = npts;
@@ -818,7 +831,8 @@ void mh_build_system(mh_context *ctx, const mh_mesh *mesh, const mh_material &ma
     const uint32_t nt = read_u32(ctx, incl.get() + nt_in - 1);
     if (nt == 0) mh_throw(MH_EEMPTY, "every tet is degenerate");
     sys->kept_tets = nt;
-    DevArray<uint32_t> tets(ctx, size_t(nt) * 4);
+    sys->tets.reset(ctx, size_t(nt) * 4);
+    DevArray<uint32_t> &tets = sys->tets;
     k_compact_tets<<<div_up(nt_in, TB), TB, 0, st>>>(mesh->tets, flag, incl, nt_in, tets);
     KERNEL_CHECK();
 
@@ -875,6 +889,8 @@ void mh_build_system(mh_context *ctx, const mh_mesh *mesh, const mh_material &ma
     for (int d = 0; d < 3; ++d) far = std::max({far, std::fabs(lo[d]), std::fabs(hi[d])});
     const bool relative = far > 4.0 * extent;
     const double3 origin = relative ? double3{lo[0], lo[1], lo[2]} : double3{0, 0, 0};
+    sys->relative = relative;
+    sys->origin[0] = origin.x, sys->origin[1] = origin.y, sys->origin[2] = origin.z;
     const double3 key_lo = relative ? double3{0, 0, 0} : double3{lo[0], lo[1], lo[2]};
     k_node_xyz_keys<<<div_up(nn, TB), TB, 0, st>>>(mesh->points, npts, edge_key, rank_of, ne, key_lo, 1.0 / extent, origin, xyz_ref, mkey, ids);
     KERNEL_CHECK();
@@ -916,15 +932,16 @@ void mh_build_system(mh_context *ctx, const mh_mesh *mesh, const mh_material &ma
     quad_tables(tq);
     linear_tables(tl);
     const std::vector<double> sq = support_tables(tq, 10), sl = support_tables(tl, 4);
-    DevArray<double> tq_dev(ctx, tq.size()), tl_dev(ctx, tl.size()), sq_dev(ctx, sq.size()), sl_dev(ctx, sl.size());
-    tq_dev.upload(tq.data(), tq.size());
-    tl_dev.upload(tl.data(), tl.size());
-    sq_dev.upload(sq.data(), sq.size());
-    sl_dev.upload(sl.data(), sl.size());
-    sys->L2.id = 2;
-    sys->L1.id = 1;
-    build_level<10>(ctx, tmp, sys->elem_nodes, nt, nn, sys->elem_basis, tq_dev, sq_dev, mat, sys->L2);
-    build_level<4>(ctx, tmp, elem_p1, nt, npts, sys->elem_basis, tl_dev, sl_dev, mat, sys->L1);
+    sys->tables2.reset(ctx, tq.size());
+    sys->tables1.reset(ctx, tl.size());
+    sys->support2.reset(ctx, sq.size());
+    sys->support1.reset(ctx, sl.size());
+    sys->tables2.upload(tq.data(), tq.size());
+    sys->tables1.upload(tl.data(), tl.size());
+    sys->support2.upload(sq.data(), sq.size());
+    sys->support1.upload(sl.data(), sl.size());
+    build_level_structure<10>(ctx, tmp, sys->elem_nodes, nt, nn, sys->L2);
+    build_level_structure<4>(ctx, tmp, elem_p1, nt, npts, sys->L1);
 
     // --- rigid-body aggregates: connected node sets on the P1 operator's graph (graph_aggregates above)
     if (const char *e = getenv("MH_AGG")) sys->agg_target = uint32_t(std::max(2, atoi(e)));
@@ -967,6 +984,22 @@ void mh_build_system(mh_context *ctx, const mh_mesh *mesh, const mh_material &ma
             HIP_CHECK(hipMemcpyAsync(pa.data(), sys->parent_a.get(), size_t(nn) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
             HIP_CHECK(hipMemcpyAsync(xyz.data(), sys->node_xyz.get(), xyz.size() * sizeof(double), hipMemcpyDeviceToHost, st));
             HIP_CHECK(hipStreamSynchronize(st));
+            // The nodes' bounding box for the eigensolver's polynomial start block, in the total order of the doubles' bit patterns
+            // (-0 below +0): what a reduction over node_xyz on the device returns, bit for bit, for these are the same numbers.
+            {
+                const auto key = [](double v) {
+                    uint64_t u;
+                    memcpy(&u, &v, sizeof(u));
+                    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+                };
+                for (int d = 0; d < 3; ++d) sys->node_box[d] = sys->node_box[3 + d] = xyz[d];
+                for (uint32_t i = 1; i < nn; ++i)
+                    for (int d = 0; d < 3; ++d) {
+                        const double v = xyz[size_t(3) * i + d];
+                        if (key(v) < key(sys->node_box[d])) sys->node_box[d] = v;
+                        if (key(v) > key(sys->node_box[3 + d])) sys->node_box[3 + d] = v;
+                    }
+            }
             for (uint32_t i = 0; i < nn; ++i) {
                 const uint32_t c = pa[i] < npts && comp[pa[i]] != UINT32_MAX ? comp[pa[i]] : 0u;
                 node_comp[i] = c;
@@ -992,9 +1025,60 @@ void mh_build_system(mh_context *ctx, const mh_mesh *mesh, const mh_material &ma
     sys->agg_t.reset(ctx, size_t(npts) * 18);
     k_aggregate_t<<<div_up(sys->n_agg, 64), 64, 0, st>>>(sys->p1_xyz, sys->agg_ptr, sys->agg_nodes, sys->n_agg, sys->agg_t);
     KERNEL_CHECK();
-    sys->points.reset(ctx, size_t(npts) * 3);
+    sys->points.reset(ctx, size_t(npts) * 3); // (the structure's own copy: a system may outlive the mesh it was assembled on)
     HIP_CHECK(hipMemcpyAsync(sys->points.get(), mesh->points.get(), size_t(npts) * 3 * sizeof(double), hipMemcpyDeviceToDevice, st));
     HIP_CHECK(hipStreamSynchronize(st)); // host-side staging vectors (tables) must outlive their uploads
+    return built;
+}
+} // namespace
+
+uint64_t mh_structure::device_bytes() const {
+    uint64_t total = 0;
+    const auto add = [&total](const auto &a) { total += uint64_t(a.count) * sizeof(*a.ptr); };
+    add(points), add(tets), add(elem_nodes_ref), add(elem_nodes), add(elem_p1), add(elem_basis), add(perm), add(inv_perm), add(node_xyz), add(p1_xyz);
+    add(parent_a), add(parent_b), add(p1_edge_ptr), add(p1_edge_mid), add(p1_corner), add(tables2), add(tables1), add(support2), add(support1);
+    for (const MhLevelStructure *l : {&L2, &L1}) add(l->row_ptr), add(l->col), add(l->seg), add(l->pay);
+    add(agg_of), add(agg_ptr), add(agg_nodes), add(agg_t), add(node_component), add(component_centroid);
+    return total;
+}
+
+// mh_assemble: the mesh's structure -- built here on first use with the mesh's own context, reused afterwards -- and on it the material part:
+// K and M of both levels, two launches.  MH_TEST=fresh_structure (A/B hook): the structure is built anew on every call, as it was
+// before it was kept.  A context other than the mesh's builds a structure of its own that nobody keeps.  A failed build throws and
+// caches nothing.
+void mh_build_system(mh_context *ctx, const mh_mesh *mesh, const mh_material &mat, mh_system *sys) {
+    static const bool fresh = getenv("MH_TEST") && strstr(getenv("MH_TEST"), "fresh_structure");
+    std::shared_ptr<const mh_structure> kept;
+    if (mesh->ctx == ctx) {
+        std::lock_guard<std::mutex> lock(mesh->structure_mutex);
+        if (fresh || !mesh->structure) {
+            auto built = build_structure(ctx, mesh);
+            ++mesh->structure_builds;
+            mesh->structure = std::move(built);
+        }
+        kept = mesh->structure;
+    } else {
+        kept = build_structure(ctx, mesh);
+        ++mesh->structure_builds;
+    }
+    const mh_structure &s = *kept;
+    sys->structure = kept;
+    sys->ctx = ctx;
+    sys->material = mat;
+    sys->n_points = s.n_points, sys->kept_tets = s.kept_tets, sys->n_nodes = s.n_nodes, sys->n_edges = s.n_edges;
+    sys->points.alias_of(s.points);
+    sys->elem_nodes_ref.alias_of(s.elem_nodes_ref), sys->elem_nodes.alias_of(s.elem_nodes), sys->elem_p1.alias_of(s.elem_p1), sys->elem_basis.alias_of(s.elem_basis);
+    sys->perm.alias_of(s.perm), sys->inv_perm.alias_of(s.inv_perm), sys->node_xyz.alias_of(s.node_xyz), sys->p1_xyz.alias_of(s.p1_xyz);
+    sys->parent_a.alias_of(s.parent_a), sys->parent_b.alias_of(s.parent_b), sys->p1_edge_ptr.alias_of(s.p1_edge_ptr), sys->p1_edge_mid.alias_of(s.p1_edge_mid);
+    sys->p1_corner.alias_of(s.p1_corner);
+    sys->agg_target = s.agg_target, sys->n_agg = s.n_agg;
+    sys->agg_of.alias_of(s.agg_of), sys->agg_ptr.alias_of(s.agg_ptr), sys->agg_nodes.alias_of(s.agg_nodes), sys->agg_t.alias_of(s.agg_t);
+    sys->n_components = s.n_components, sys->unreferenced_points = s.unreferenced_points;
+    sys->node_component.alias_of(s.node_component), sys->component_centroid.alias_of(s.component_centroid);
+    sys->L2.id = 2;
+    sys->L1.id = 1;
+    assemble_level<10>(ctx, s.L2, s.kept_tets, s.elem_basis, s.tables2, s.support2, mat, sys->L2);
+    assemble_level<4>(ctx, s.L1, s.kept_tets, s.elem_basis, s.tables1, s.support1, mat, sys->L1);
     // --- sliver patches of the smoothers (mh_patch.hip): elements with a shape measure below 0.02 (a regular tetrahedron has 1,
     //     a Kuhn tetrahedron 0.66; MH_PATCH_Q sets the threshold, 0 disables)
     static const float patch_q = getenv("MH_PATCH_Q") ? float(atof(getenv("MH_PATCH_Q"))) : 0.02f;
