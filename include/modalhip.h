@@ -385,7 +385,7 @@ int mh_bank_render_read(mh_bank *, uint32_t frames, float click_gain, uint32_t n
  * than one junction, and one that would join a component that holds a Hertz junction (the Hertz solve in more than one dimension is not in
  * this version); a flagged junction on an object of a kept unflagged one.  Two junctions between the same pair of objects, at different
  * points, are a legal group.  Pickups on a junction's object stay left out (mh_bank_render_observed reads them).  MH_JUNCTION_GROUP = 4 is what a wave's registers hold: one
- * gain triple per member per lane, 195 VGPRs in fp64 (118 in fp32), nothing in scratch.  Not in this version, as above: damping in
+ * gain triple per member per lane, 195 VGPRs in fp64 (118 in fp32), nothing in scratch.  (Hertz in groups: mh_bank_render_mixed.)  Not in this version, as above: damping in
  * groups, friction, roughness.
  *
  * Contact damping, flags & MH_JUNCTION_DAMPED (mh_bank_render_damped only: mh_bank_render_coupled ignores the bit): the Hunt-Crossley
@@ -457,8 +457,61 @@ int mh_bank_render_read(mh_bank *, uint32_t frames, float click_gain, uint32_t n
  * force rows, compliances, statuses and carries are the same bits.  A refused junction's objects render as with K = 0 and are read.
  * With frames = 0 nothing is read and the carry comes back unchanged.  A call without a pickup on a kept junction's object launches
  * exactly what mh_bank_render_damped launches.  mh_bank_render_coupled and mh_bank_render_damped keep leaving such pickups out.
- * Not in this version: Hertz or damping inside groups, a bilateral damped law, friction, roughness, contact forces acting inside a
- * pickup's look-ahead. */
+ * Not in this version: damping inside groups (Hertz inside groups: mh_bank_render_mixed, below), a bilateral damped law, friction,
+ * roughness, contact forces acting inside a pickup's look-ahead.
+ *
+ * Hertz junctions in groups, mh_bank_render_mixed: mh_bank_render_observed -- its parameters in its order -- followed by one output,
+ * unconverged_out [n_junctions].  One difference: a kept junction with MH_JUNCTION_SHARED | MH_JUNCTION_HERTZ may be a member of a group,
+ * beside linear unilateral, bilateral and other Hertz members (the group decision of modalhip_groups.hpp with hertz_in_groups = true).
+ * Still left out, in call order, with the bits of the call without them: Hertz with bilateral, a damped junction in a group, a fifth
+ * member, a ninth wave, a flagged junction on an unflagged junction's object.  A group without a Hertz member runs the enumeration of
+ * MH_JUNCTION_SHARED, bit for bit, and a call without a Hertz junction in a group launches what mh_bank_render_observed launches.
+ * A group with a Hertz member takes the steps of MH_JUNCTION_SHARED: steps 1, 2, 3 and 5 bit for bit (the free step, d_i, C_ij and their
+ * summation orders, Re z = (...(Re z~ + a_j1 f_j1) + ...), the rows in the bank's precision).  Step 4 becomes
+ *   4m. find y with y = x - C f(y): f_j = K_j max(y_j, 0) (linear), K_j y_j (bilateral), K_j max(y_j, 0)^1.5 (Hertz).  As with every law
+ *       the force of frame s meets the law at the displacement of frame s + 1.  C = D G, a positive diagonal times a Gram matrix, so the
+ *       problem is D^-1 x in G f + D^-1 phi^-1(f), a monotone operator plus a strictly monotone diagonal one: exactly one solution when
+ *       every K_j > 0; a member with K_j = 0 has f_j = 0 and drops out.
+ *       One fixed expression tree, every operation rounded to the bank's precision, nothing contracted (the one fused multiply-add below
+ *       is written as such), no trip count that depends on data, no state between frames (a warm start would make the bits depend on
+ *       the block length).  With ck_jj = C_jj K_j (once per block), phi_j(y) = p sqrt(p) with p = max(y, 0) (Hertz), y (bilateral),
+ *       max(y, 0) (linear), phi'_j = 1.5 sqrt(p), 1, [y > 0], and f_j = K_j phi_j(y_j), kd_j = K_j phi'_j(y_j) formed after every change of y_j:
+ *         alone_j(x): Hertz: x for x <= 0, else step 4h's tree up to y (the smaller of x and cbrt(x / ck_jj)^2, taken when ck_jj > 0;
+ *                     four steps y -= ((y + (ck_jj y) sqrt(y)) - x) / (1 + (1.5 ck_jj) sqrt(y))); linear: x / (1 + ck_jj) for x > 0
+ *                     or a bilateral member, else x.
+ *         start:      y_j = alone_j(x_j), j ascending.
+ *         1 sweep:    j ascending: y_j = alone_j(x_j - s), s = sum over i != j, ascending from +0, of C_ji f_i  (Gauss-Seidel).
+ *         residual:   plain: F_i = (y_i + sum_j C_ij f_j, ascending from +0) - x_i.  In twice the precision: s = y_i, c = +0; j ascending:
+ *                     p = C_ij f_j, e = fma(C_ij, f_j, -p), (s, r) = two_sum(s, p), c = c + (r + e); then (s, r) = two_sum(s, -x_i),
+ *                     c = c + r; F_i = s + c.  two_sum(a, b): s = a + b, bb = s - a, r = (a - (s - bb)) + (b - bb).
+ *         10 steps:   J_ij = C_ij kd_j, J_ii = 1 + C_ii kd_i; J d = F by elimination without pivoting in ascending order (inv = 1 / J_pp;
+ *                     row p's later entries and r_p times inv; every later row i: t = J_ip, J_ij -= t J_pj, r_i -= t r_p), back
+ *                     substitution in descending order (d_p = (...(r_p - J_p,p+1 d_p+1) - ...)); y_j = y_j - d_j; the residual of the
+ *                     new y.  The residuals after steps 9 and 10 are the ones in twice the precision, the others plain: the last
+ *                     step is one of iterative refinement, and the residual test sees the residual itself, not its rounding.
+ *         The forces are the f_j of the last y.
+ *       The residual is written in the forces the solve returns, f_j rounded, not in C_ij K_j: the y found satisfies y = x - C f for
+ *       those very numbers, and the roundings of K phi(y) perturb the law by 1.5 u instead of being amplified by the elimination.
+ *       The group is padded to MH_JUNCTION_GROUP members with K = 0, C = 0, x = 0, which changes no bit.
+ *       The residual test of a frame: with F of the final y, some |F_i| > 16 u (|y_i| + sum_j |C_ij| |f_j| + |x_i|), u the unit roundoff.
+ *       F_i has 6 terms; the last place of y_i (1 rounding) and of each f_j (3: the root, the product, K) moves F_i by up to 2 u of
+ *       the magnitudes summed, which is how close to 0 the last step can bring it; the multiple is 8 times that.
+ *       unconverged_out[j]: for a member of a group with a Hertz member, the number of
+ *       frames of the block that failed the test; 0 for every other junction.  A correct solve on valid input returns 0 everywhere; a
+ *       count above 0 says that the block's forces are not at the law.
+ *       Accuracy (tests/test_bank_mixed_cpu.py, 36 sets of 1 000 cases): |f - f*| / max |f*| is 1.4 - 2.3 eps in every set, float32 and
+ *       float64; against the error of step 4's linear solve on the linearisation at the solution that is 0.00 - 1.19 x (4 x allowed,
+ *       2.4 x asserted).  (Sweeps, steps) = (1, 10) is a smallest pair: with 9 steps, or without the sweep, sets miss by factors of
+ *       thousands; 0, 2 and 3 sweeps need 13, 12 and 12 steps.  The tests' numpy restatement forms the product's error e by Veltkamp's
+ *       splitting where the device uses the fused multiply-add: the two are the same bits while neither the split (|C_ij|, |f_j| below
+ *       the largest number / 2^27 in fp64, / 2^12 in fp32) nor e (|C_ij f_j| above the smallest normal number times 2^53, 2^24) leaves
+ *       the format's range; outside it only the last step's correction differs, by less than the residual test resolves.
+ * Status: refused (every member, zero rows, the objects render as with K = 0) when a C_ij or C_ij K_j is not finite, a |C_ij K_j| is
+ * above the square root of the largest finite number (the elimination multiplies two entries of J), C_ii or C_ii K_i is below 0 on a Hertz
+ * member, or 1 + C_ii K_i is not a finite number above 0 on a linear one; solved otherwise.  compliance_out[i] = C_ii in both cases.
+ * k_bank_modes_grouped<Real, OBSERVE, true>: the same solve in every lane of every wave; 230 / 246 VGPRs (fp32 / fp64), nothing in scratch;
+ * 512-frame blocks on an MI355X, n = 2 ... 4: fp32 20 600 - 27 100 cycles per frame, 4.6 - 6.1 ms; fp64 24 600 - 31 200 cycles, 5.4 - 6.9 ms.
+ * Not in this version: damping inside groups, a bilateral Hertz or damped law, more than four members, friction, roughness. */
 typedef struct {
     uint32_t object;
     uint32_t points[3];
@@ -509,6 +562,14 @@ int mh_bank_render_observed(mh_bank *, uint32_t frames, float click_gain, uint32
                             const mh_drive *drives, const float *signals, uint32_t n_pickups, const mh_pickup *pickups, void *pickup_out,
                             uint8_t *pickup_read, uint32_t n_junctions, const mh_junction *junctions, const float *approach, void *force_out,
                             double *compliance_out, uint8_t *status_out, const float *damping, void *carry);
+/* mh_bank_render_observed in which a Hertz junction may join a group: "Hertz junctions in groups" above.  unconverged_out: [n_junctions]. */
+int mh_bank_render_mixed(mh_bank *, uint32_t frames, float click_gain, uint32_t n_impacts, mh_impact *impacts,
+                         uint32_t n_renderers, const uint32_t *deal_offset, const uint32_t *deal_objects, const uint32_t *render_count,
+                         const uint32_t *tuned_count, const float *out_gain, const float *listener_gain, void *out, double *object_energy,
+                         uint32_t *object_live, uint8_t *object_silenced, double *object_modal_energy, uint32_t n_drives,
+                         const mh_drive *drives, const float *signals, uint32_t n_pickups, const mh_pickup *pickups, void *pickup_out,
+                         uint8_t *pickup_read, uint32_t n_junctions, const mh_junction *junctions, const float *approach, void *force_out,
+                         double *compliance_out, uint8_t *status_out, const float *damping, void *carry, uint32_t *unconverged_out);
 /* Read back state columns (for parity tests and the modal-energy diagnostic, ModalAudio.cpp:564-577). */
 int mh_bank_read_state(const mh_bank *, uint32_t first, uint32_t count, double *state_re, double *state_im);
 

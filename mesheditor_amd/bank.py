@@ -87,6 +87,7 @@ def lib():
         "mhx_render_coupled": (i32, [vp, vp, u32, u32, vp, vp, u32, vp, vp, vp, u32, vp, vp, vp, vp, vp]),
         "mhx_render_damped": (i32, [vp, vp, u32, u32, vp, vp, u32, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp]),
         "mhx_render_observed": (i32, [vp, vp, u32, u32, vp, vp, u32, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp]),
+        "mhx_render_mixed": (i32, [vp, vp, u32, u32, vp, vp, u32, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp]),
         "mhx_active_impacts": (u32, [vp]), "mhx_modal_energy": (f64, [vp]), "mhx_render_share": (f32, [vp]), "mhx_find_object": (i32, [vp, u32]),
         "mhx_time_kernels": (i32, [vp, i32]), "mhx_kernel_class_stats": (i32, [vp, i32, C.POINTER(C.c_uint64), C.POINTER(f64), C.POINTER(f64)]),
         "mhx_column": (u32, [vp, i32, i32, vp]), "mhx_object_state": (None, [vp, vp, vp, vp]),
@@ -206,6 +207,15 @@ class Scene:
         those out).  damping=None: zeros (no junction with damped=True is expected).  Returns render_damped's tuple."""
         rates = np.zeros(len(junctions), np.float32) if damping is None else damping
         return self.render_damped(out, drives, signals, pickups, junctions, approach, rates, carry, entry=self.L.mhx_render_observed)
+
+    def render_mixed(self, out, drives, signals, pickups, junctions, approach, damping=None, carry=None):
+        """RenderModalMixed: render_observed in which a junction with shared=True and hertz=True may be a member of a group (the older entries
+        leave it out).  Returns render_observed's tuple plus `unconverged`: per junction, for a member of a group with a Hertz member, the
+        frames of the block in which the group's residual test failed (0 on valid input); 0 for every other junction."""
+        rates = np.zeros(len(junctions), np.float32) if damping is None else damping
+        counts = np.zeros(len(junctions), np.uint32)
+        entry = lambda *args: self.L.mhx_render_mixed(*args, _p(counts))
+        return self.render_damped(out, drives, signals, pickups, junctions, approach, rates, carry, entry=entry) + (counts,)
 
     def render_damped(self, out, drives, signals, pickups, junctions, approach, damping, carry=None, entry=None):
         """RenderModalDamped: render_coupled with contact damping.  damping: one D in s/m per junction (float32; read for junctions with

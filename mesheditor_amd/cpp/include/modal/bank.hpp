@@ -303,6 +303,20 @@ void RenderModalObserved(ModalAudio &, std::span<const ModalDrive> drives, const
 void RenderModalObserved(ModalAudio64 &, std::span<const ModalDrive> drives, const float *signals, std::span<const ModalPickup> pickups, double *reads,
                          std::span<const ModalJunction> junctions, const float *approach, std::span<const float> damping, std::span<double> carry, double *forces, double *out,
                          uint32_t frame_count, uint8_t *read_flags = nullptr, double *compliances = nullptr, uint8_t *statuses = nullptr);
+// Hertz junctions in groups (modalhip.h, mh_bank_render_mixed): RenderModalObserved -- its parameters in its order, then
+// `unconverged`, one count per junction -- except that a kept junction with ModalJunctionShared | ModalJunctionHertz may be a member of a
+// group, beside linear unilateral, bilateral and other Hertz members.  Such a group's step 4 is the header's step 4m: y = x - C f(y) with
+// every member's own law, by a fixed tree (each member alone, one Gauss-Seidel sweep, ten Newton steps, the last one from a residual
+// summed in twice the working precision).  unconverged[j]: for a member
+// of a group with a Hertz member, the frames of the block in which the group's final residual test failed -- 0 on valid input --; 0 for
+// every other junction.  Still left out: Hertz with bilateral, a damped junction in a group, a fifth member, a ninth wave, a flagged
+// junction on an unflagged junction's object.  A group without a Hertz member, every other junction and every older entry are what they were.
+void RenderModalMixed(ModalAudio &, std::span<const ModalDrive> drives, const float *signals, std::span<const ModalPickup> pickups, float *reads,
+                      std::span<const ModalJunction> junctions, const float *approach, std::span<const float> damping, std::span<float> carry, float *forces, float *out,
+                      uint32_t frame_count, std::span<uint32_t> unconverged, uint8_t *read_flags = nullptr, double *compliances = nullptr, uint8_t *statuses = nullptr);
+void RenderModalMixed(ModalAudio64 &, std::span<const ModalDrive> drives, const float *signals, std::span<const ModalPickup> pickups, double *reads,
+                      std::span<const ModalJunction> junctions, const float *approach, std::span<const float> damping, std::span<double> carry, double *forces, double *out,
+                      uint32_t frame_count, std::span<uint32_t> unconverged, uint8_t *read_flags = nullptr, double *compliances = nullptr, uint8_t *statuses = nullptr);
 // Not in the reference: the libmodalhip context the bank's device mirror lives on (created on demand), for callers that
 // time its kernels (mh_context_time_kernels / mh_context_kernel_class_stats).
 mh_context *ModalDeviceContext(ModalAudio &);

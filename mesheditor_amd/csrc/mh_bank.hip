@@ -838,8 +838,61 @@ template<typename Real> struct GroupedArgs {
 template<typename Real> constexpr size_t grouped_lds(uint32_t waves) {
     return 2 * GROUP * JUNCTION_WAVES * sizeof(Real) + size_t(waves) * coupled_tile<Real>() * (MODES_PER_WAVE + 2) * sizeof(Real);
 }
+// A group with a Hertz member (mh_bank_render_mixed; contract in modalhip.h, step 4m).  What its entries take beyond
+// GroupedArgs: where a member's count of frames that failed the residual test goes (where the host reads it), by the caller's index.
+template<typename Real> struct MixedArgs : GroupedArgs<Real> {
+    uint32_t *unconverged_out;
+};
+constexpr int MIXED_SWEEPS = 1, MIXED_STEPS = 10, MIXED_REFINED = 1; // step 4m's Gauss-Seidel sweeps, its Newton steps, and those of them that start from a residual in twice the precision
+// a + b and a b as the rounded result and its rounding error, both exact (Knuth's six operations; one fused multiply-add).
+template<typename Real> __device__ __forceinline__ Real two_sum(Real a, Real b, Real &err) {
+    const Real s = a + b, bb = s - a;
+    err = (a - (s - bb)) + (b - bb);
+    return s;
+}
+template<typename Real> __device__ __forceinline__ Real two_product(Real a, Real b, Real &err) {
+    const Real p = a * b;
+    err = fma_real(a, b, -p);
+    return p;
+}
+// Step 4m, a member alone: the root y of y + c phi(y) = x.  Hertz: step 4h's tree (hertz_force's) up to y; linear: x / (1 + c), for x > 0
+// only unless bilateral; an open member keeps y = x.  c15 = 1.5 c.
+template<typename Real> __device__ __forceinline__ Real mixed_alone(Real x, Real c, Real c15, bool hertz, bool bilateral) {
+    if (hertz) {
+        if (!(x > Real(0))) return x;
+        Real y = x;
+        if (c > Real(0)) {
+            Real g = cbrt_real(x / c);
+            g = g * g;
+            if (g < x) y = g;
+        }
+#pragma unroll
+        for (int step = 0; step < 4; ++step) {
+            const Real r = sqrt_real(y);
+            y = y - ((y + (c * y) * r) - x) / (Real(1) + c15 * r);
+        }
+        return y;
+    }
+    return bilateral || x > Real(0) ? x / (Real(1) + c) : x;
+}
+// Step 4m, the laws: phi(y) and phi'(y) of a member.
+template<typename Real> __device__ __forceinline__ void mixed_law(Real y, bool hertz, bool bilateral, Real &phi, Real &dphi) {
+    const Real pos = y > Real(0) ? y : Real(0);
+    if (hertz) {
+        const Real r = sqrt_real(pos);
+        phi = pos * r;
+        dphi = Real(1.5) * r;
+    } else {
+        phi = bilateral ? y : pos;
+        dphi = bilateral || y > Real(0) ? Real(1) : Real(0);
+    }
+}
 // OBSERVE = true (k_bank_modes_grouped_observed<Real>): the entry of mh_bank_render_observed, with the taps of the coupled kernel's.
-template<typename Real, bool OBSERVE = false> __global__ void __launch_bounds__(JUNCTION_WAVES *WAVE) k_bank_modes_grouped(BANK_MODES_PARAMS, JunctionArgs<Real, GroupedArgs<Real>, OBSERVE> ga) { // (`waves`: the main launch's, not read here)
+// MIXED = true (k_bank_modes_grouped_mixed<Real>, ..._mixed_observed<Real>): the entries of mh_bank_render_mixed for the groups with a Hertz
+// member -- step 4 is step 4m, the same solve in every lane of every wave (its inputs are the same bits everywhere), no subset per lane,
+// no ballot; what the block keeps is C in registers, J is rebuilt from it every Newton step.  The parameter type depends on
+// MIXED, and the enumeration's matrix W is not formed: the other entries are what they were.
+template<typename Real, bool OBSERVE = false, bool MIXED = false> __global__ void __launch_bounds__(JUNCTION_WAVES *WAVE) k_bank_modes_grouped(BANK_MODES_PARAMS, JunctionArgs<Real, std::conditional_t<MIXED, MixedArgs<Real>, GroupedArgs<Real>>, OBSERVE> ga) { // (`waves`: the main launch's, not read here)
     typedef PairOf<Real> Pair;
     constexpr uint32_t TS = coupled_tile<Real>();
     extern __shared__ __attribute__((aligned(16))) unsigned char grouped_mem[];
@@ -856,7 +909,7 @@ template<typename Real, bool OBSERVE = false> __global__ void __launch_bounds__(
     const uint32_t wave_in_object = active ? wave - G->wave0[slot] : 0u, dealt = G->dealt[slot];
     WaveLane<Real> w = load_wave(b, deal_objects, chunk_base, out_gain, listener_gain, dealt, wave_in_object * MODES_PER_WAVE, active ? render_count[dealt] : 0u, lane);
     // per member: is a side of it on this wave's object, the wave's place in the member's summation order, its gains here
-    uint32_t on = 0, place[GROUP] = {}, bilateral = 0;
+    uint32_t on = 0, place[GROUP] = {}, bilateral = 0, hertz = 0;
     Pair a[GROUP] = {}, g_im[GROUP] = {}, g_re[GROUP] = {};
     Real k[GROUP] = {};
 #pragma unroll
@@ -866,6 +919,8 @@ template<typename Real, bool OBSERVE = false> __global__ void __launch_bounds__(
         const uint32_t sa = M->slot[0], sb = M->slot[1], waves_a = G->waves[sa];
         k[i] = M->k;
         if (M->flags & MH_JUNCTION_BILATERAL) bilateral |= 1u << i;
+        if constexpr (MIXED)
+            if (M->flags & MH_JUNCTION_HERTZ) hertz |= 1u << i;
         if (!active || (sa != slot && sb != slot)) continue;
         const uint32_t sd = sa == slot ? 0u : 1u;
         on |= 1u << i;
@@ -938,13 +993,29 @@ template<typename Real, bool OBSERVE = false> __global__ void __launch_bounds__(
         for (uint32_t i = 0; i < GROUP; ++i) {
             const Real kc = col[i] * k[j];
             if (i < n && j < n) numbers_ok = numbers_ok && col[i] >= -most && col[i] <= most && kc >= -most && kc <= most;
-            W[i][j] = (mask >> i & 1u) ? ((mask >> j & 1u) ? (i == j ? Real(1) + kc : kc) : zero) : col[i];
+            if constexpr (MIXED) {
+                W[i][j] = col[i]; // step 4m keeps C alone
+                const Real range = sqrt_real(most); // and J multiplies two entries: |C_ij K_j| within the square root of the largest number
+                if (i < n && j < n) numbers_ok = numbers_ok && kc >= -range && kc <= range;
+            }
+            if constexpr (!MIXED) W[i][j] = (mask >> i & 1u) ? ((mask >> j & 1u) ? (i == j ? Real(1) + kc : kc) : zero) : col[i];
             if (i == j) c_own[i] = col[i];
         }
     }
     bool pivots_ok = true;
+    Real ckd[GROUP] = {}, ck15[GROUP] = {}; // step 4m: ck_jj = C_jj K_j and 1.5 ck_jj, once per block
+    if constexpr (MIXED) {
+        // a Hertz member: C_ii and C_ii K_i not below 0, as in step 4h; a linear one: 1 + C_ii K_i a finite number above 0, as in step 4
 #pragma unroll
-    for (uint32_t p = 0; p < GROUP; ++p) {
+        for (uint32_t i = 0; i < GROUP; ++i) {
+            ckd[i] = W[i][i] * k[i];
+            ck15[i] = Real(1.5) * ckd[i];
+            const Real denom = Real(1) + ckd[i];
+            if (i < n) pivots_ok = pivots_ok && ((hertz >> i & 1u) ? (W[i][i] >= Real(0) && ckd[i] >= Real(0)) : (denom > Real(0) && denom <= most));
+        }
+    }
+#pragma unroll
+    for (uint32_t p = 0; p < GROUP && !MIXED; ++p) {
         const bool in_p = mask >> p & 1u;
         const Real pivot = W[p][p];
         pivots_ok = pivots_ok && (!in_p || (pivot > Real(0) && pivot <= most)); // a finite number above 0 (a NaN fails both)
@@ -962,7 +1033,8 @@ template<typename Real, bool OBSERVE = false> __global__ void __launch_bounds__(
             for (uint32_t j = 0; j < GROUP; ++j) W[i][j] = both ? W[i][j] - t * W[p][j] : W[i][j];
         }
     }
-    const bool solved = numbers_ok && __builtin_amdgcn_ballot_w64(admissible && !pivots_ok) == 0;
+    const bool solved = numbers_ok && (MIXED ? pivots_ok : __builtin_amdgcn_ballot_w64(admissible && !pivots_ok) == 0);
+    uint32_t unconverged = 0; // step 4m: frames of the block that failed the residual test
     if (threadIdx.x == 0)
         for (uint32_t i = 0; i < n; ++i) {
             ga.compliance_out[G->member[i].row] = double(c_own[i]);
@@ -998,6 +1070,109 @@ template<typename Real, bool OBSERVE = false> __global__ void __launch_bounds__(
             member_sums(mine, (s0 + ds) & 1u, d);
 #pragma unroll
             for (uint32_t i = 0; i < GROUP; ++i) x[i] = lane_bcast(u_tile[i], ds) - d[i];
+            Real f_now[GROUP];
+            if constexpr (MIXED) {
+                // step 4m (modalhip.h): each member alone, MIXED_SWEEPS Gauss-Seidel sweeps, MIXED_STEPS Newton steps, the residual test
+                Real y[GROUP], f[GROUP], kd[GROUP], F[GROUP]; // kd: K phi'
+                auto law = [&](uint32_t j) {
+                    Real phi, dphi;
+                    mixed_law(y[j], hertz >> j & 1u, bilateral >> j & 1u, phi, dphi);
+                    f[j] = k[j] * phi;
+                    kd[j] = k[j] * dphi;
+                };
+#pragma unroll
+                for (uint32_t j = 0; j < GROUP; ++j) {
+                    y[j] = mixed_alone(x[j], ckd[j], ck15[j], hertz >> j & 1u, bilateral >> j & 1u);
+                    law(j);
+                }
+#pragma unroll 1
+                for (int sweep = 0; sweep < MIXED_SWEEPS; ++sweep) {
+#pragma unroll
+                    for (uint32_t j = 0; j < GROUP; ++j) {
+                        Real acc = 0;
+#pragma unroll
+                        for (uint32_t i = 0; i < GROUP; ++i)
+                            if (i != j) acc = acc + W[j][i] * f[i];
+                        y[j] = mixed_alone(x[j] - acc, ckd[j], ck15[j], hertz >> j & 1u, bilateral >> j & 1u);
+                        law(j);
+                    }
+                }
+                // F_i = (y_i + sum_j C_ij f_j) - x_i; twice: the sum carried in twice the working precision
+                auto residual = [&](bool twice) {
+#pragma unroll
+                    for (uint32_t i = 0; i < GROUP; ++i) {
+                        if (!twice) {
+                            Real acc = 0;
+#pragma unroll
+                            for (uint32_t j = 0; j < GROUP; ++j) acc = acc + W[i][j] * f[j];
+                            F[i] = (y[i] + acc) - x[i];
+                        } else {
+                            Real sum = y[i], low = 0, r, e;
+#pragma unroll
+                            for (uint32_t j = 0; j < GROUP; ++j) {
+                                const Real p = two_product(W[i][j], f[j], e);
+                                sum = two_sum(sum, p, r);
+                                low = low + (r + e);
+                            }
+                            sum = two_sum(sum, -x[i], r);
+                            low = low + r;
+                            F[i] = sum + low;
+                        }
+                    }
+                };
+                residual(MIXED_STEPS <= MIXED_REFINED);
+#pragma unroll 1
+                for (int step = 0; step < MIXED_STEPS; ++step) {
+                    // J = I + C diag(K phi'), eliminated without pivoting in ascending order; back substitution in descending order
+                    Real Jm[GROUP][GROUP], r[GROUP], d[GROUP];
+#pragma unroll
+                    for (uint32_t i = 0; i < GROUP; ++i) {
+#pragma unroll
+                        for (uint32_t j = 0; j < GROUP; ++j) Jm[i][j] = i == j ? Real(1) + W[i][j] * kd[j] : W[i][j] * kd[j];
+                        r[i] = F[i];
+                    }
+#pragma unroll
+                    for (uint32_t p = 0; p < GROUP; ++p) {
+                        const Real inv = Real(1) / Jm[p][p];
+#pragma unroll
+                        for (uint32_t j = p + 1; j < GROUP; ++j) Jm[p][j] = Jm[p][j] * inv;
+                        r[p] = r[p] * inv;
+#pragma unroll
+                        for (uint32_t i = p + 1; i < GROUP; ++i) {
+                            const Real t = Jm[i][p];
+#pragma unroll
+                            for (uint32_t j = p + 1; j < GROUP; ++j) Jm[i][j] = Jm[i][j] - t * Jm[p][j];
+                            r[i] = r[i] - t * r[p];
+                        }
+                    }
+#pragma unroll
+                    for (int p = int(GROUP) - 1; p >= 0; --p) {
+                        Real acc = r[p];
+#pragma unroll
+                        for (int j = p + 1; j < int(GROUP); ++j) acc = acc - Jm[p][j] * d[j];
+                        d[p] = acc;
+                    }
+#pragma unroll
+                    for (uint32_t j = 0; j < GROUP; ++j) {
+                        y[j] = y[j] - d[j];
+                        law(j);
+                    }
+                    residual(step + 1 >= MIXED_STEPS - MIXED_REFINED);
+                }
+                // the residual test: |F_i| against 16 u (|y_i| + sum_j |C_ij f_j| + |x_i|)
+                bool met = true;
+#pragma unroll
+                for (uint32_t i = 0; i < GROUP; ++i) {
+                    Real acc = 0;
+#pragma unroll
+                    for (uint32_t j = 0; j < GROUP; ++j) acc = acc + __builtin_fabs(W[i][j]) * __builtin_fabs(f[j]);
+                    const Real mag = (__builtin_fabs(y[i]) + acc) + __builtin_fabs(x[i]);
+                    met = met && __builtin_fabs(F[i]) <= (Real(16) * (std::numeric_limits<Real>::epsilon() * Real(0.5))) * mag;
+                }
+                if (solved && !met) ++unconverged;
+#pragma unroll
+                for (uint32_t i = 0; i < GROUP; ++i) f_now[i] = solved ? f[i] : zero;
+            } else {
             // this lane's subset: its candidate, and whether it is consistent
             Real y[GROUP], f[GROUP];
             bool consistent = admissible;
@@ -1036,12 +1211,12 @@ template<typename Real, bool OBSERVE = false> __global__ void __launch_bounds__(
                 found = __builtin_amdgcn_ballot_w64(admissible && miss == least);
             }
             const uint32_t taken = found ? uint32_t(__builtin_ctzll(found)) : full; // (found = 0: a NaN; the full set stands in)
-            Real f_now[GROUP];
 #pragma unroll
             for (uint32_t i = 0; i < GROUP; ++i) {
                 // (off the lane's subset y[i] is a product with a row of C, not a displacement: the force there is +0, clamped or not)
                 const Real clamped = (mask >> i & 1u) ? ((bilateral >> i & 1u) ? f[i] : k[i] * (y[i] > Real(0) ? y[i] : zero)) : zero;
                 f_now[i] = solved ? lane_bcast(clamp ? clamped : f[i], taken) : zero;
+            }
             }
             // step 5: the members on this wave's object, in ascending order
             Pair z = re;
@@ -1066,9 +1241,14 @@ template<typename Real, bool OBSERVE = false> __global__ void __launch_bounds__(
         chunk_sums<TS>(s_term, w, lane, s0, sn, partial, frames);
         __syncthreads();
     }
+    if constexpr (MIXED)
+        if (threadIdx.x == 0)
+            for (uint32_t i = 0; i < n; ++i) ga.unconverged_out[G->member[i].row] = unconverged;
     store_wave(b, w, lane, chunk_energy);
 }
 template<typename Real> constexpr auto k_bank_modes_grouped_observed = &k_bank_modes_grouped<Real, true>;
+template<typename Real> constexpr auto k_bank_modes_grouped_mixed = &k_bank_modes_grouped<Real, false, true>;
+template<typename Real> constexpr auto k_bank_modes_grouped_mixed_observed = &k_bank_modes_grouped<Real, true, true>;
 #undef BANK_MODES_PARAMS
 #undef BANK_MODES_ARGS
 // The partial rows of the pickups on junction objects (mh_bank_render_observed), from the states the tapped waves stored: one wave per
@@ -1357,6 +1537,8 @@ template<typename Real> struct BankImpl {
     DevArray<Real> tap_states; // mh_bank_render_observed: what the tapped waves store, [tapped wave][frame][Im z | Re z][128]
     std::vector<uint8_t> on_junction; // per object: on a side of a junction of this call that was not left out
     std::vector<uint32_t> kept_rows; // the caller's indices of those junctions
+    std::vector<uint32_t> mixed_rows; // mh_bank_render_mixed: those of them that are members of a group with a Hertz member
+    std::vector<GroupDev<Real>> mixed_groups; // and those groups, until they take their place behind the other groups
     // per-block scratch
     Arena arena;
     DevArray<Real> force, click, partial, chunk_energy, gain_scratch, rout;
@@ -1398,8 +1580,10 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
                  void *out_v, double *object_energy, uint32_t *object_live, uint8_t *object_silenced, double *object_modal_energy, uint32_t n_drives,
                  const mh_drive *drives, const float *signals, uint32_t n_pickups, const mh_pickup *pickups, void *pickup_out_v, uint8_t *pickup_read,
                  uint32_t n_junctions, const mh_junction *junctions, const float *approach, void *force_out_v, double *compliance_out, uint8_t *status_out,
-                 const float *damping, void *carry_v, bool observe) { // damping, carry_v: mh_bank_render_damped's; both null in every other entry (MH_JUNCTION_DAMPED is ignored then)
+                 const float *damping, void *carry_v, bool observe, uint32_t *unconverged_out) { // damping, carry_v: mh_bank_render_damped's; both null in every other entry (MH_JUNCTION_DAMPED is ignored then)
     // observe: mh_bank_render_observed -- a pickup on a kept junction's object is read
+    // unconverged_out: mh_bank_render_mixed -- a Hertz junction may join a group (step 4m); null in every other entry
+    const bool mixed = unconverged_out != nullptr;
     mh_context *ctx = B.ctx;
     hipStream_t st = ctx->stream;
     Real *out = static_cast<Real *>(out_v);
@@ -1430,6 +1614,7 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
     const size_t o_pick_out = A.take(size_t(n_pickups) * frames * sizeof(Real));
     const size_t o_junction_force = A.take(size_t(n_junctions) * frames * sizeof(Real)), o_compliance = A.take((n_junctions + 1) * 8), o_status = A.take((n_junctions + 1) * 4);
     const size_t o_carry_out = A.take(damping ? (n_junctions + 1) * sizeof(Real) : 0);
+    const size_t o_unconverged = A.take(mixed ? (n_junctions + 1) * 4 : 0);
     const size_t total = A.used;
     if (total > A.cap) {
         HIP_CHECK(hipStreamSynchronize(st));
@@ -1444,6 +1629,9 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
     // ---- junctions: the ones the coupled kernel may follow, one workgroup each; everything else is left out with a zero row ----
     uint32_t n_coupled = 0, coupled_waves = 0, widest_junction = 0;
     uint32_t n_groups = 0, widest_group = 0, grouped_members = 0; // components of two or more junctions: k_bank_modes_grouped, one workgroup each
+    uint32_t n_mixed = 0, widest_mixed = 0, mixed_members = 0; // those of them with a Hertz member (mh_bank_render_mixed): the entries with step 4m; they follow the others in the list
+    B.mixed_rows.clear();
+    B.mixed_groups.clear();
     bool any_hertz = false; // a kept junction with MH_JUNCTION_HERTZ: the call takes the entry that has the solve
     bool any_damped = false; // a kept junction with MH_JUNCTION_DAMPED: the entry that has both solves and the carry
     const uint32_t flag_mask = damping ? ~0u : ~uint32_t(MH_JUNCTION_DAMPED);
@@ -1473,7 +1661,7 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
             if (m.flags & flag_mask & MH_JUNCTION_DAMPED) { // the damped law is unilateral too, and its l a finite number from 0 up
                 if ((m.flags & MH_JUNCTION_BILATERAL) || !std::isfinite(damping[j]) || damping[j] < 0) continue;
             }
-            if (grouping.add(j, m.flags & flag_mask, m.a.object, side_waves(m.a), m.b.object, two_sided ? side_waves(m.b) : 0u) < 0) continue;
+            if (grouping.add(j, m.flags & flag_mask, m.a.object, side_waves(m.a), m.b.object, two_sided ? side_waves(m.b) : 0u, mixed) < 0) continue;
             B.on_junction[m.a.object] = 1;
             if (two_sided) B.on_junction[m.b.object] = 1;
             B.kept_rows.push_back(j);
@@ -1518,13 +1706,22 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
                 if (two_sided) dev.at[1] = blend_dev<Real>(m.b);
             }
             if (g.n_waves > JUNCTION_WAVES) mh_throw(MH_EINVAL, "a junction group of %u waves", g.n_waves); // (the grouping admits none)
+            coupled_waves += g.n_waves;
+            if (comp.hertz) { // parked until the others are known
+                B.mixed_groups.push_back(g);
+                ++n_mixed;
+                mixed_members += g.n;
+                widest_mixed = std::max(widest_mixed, g.n_waves);
+                B.mixed_rows.insert(B.mixed_rows.end(), comp.members.begin(), comp.members.end());
+                continue;
+            }
             gd[n_groups++] = g;
             grouped_members += g.n;
-            coupled_waves += g.n_waves;
             widest_group = std::max(widest_group, g.n_waves);
         }
+        std::copy(B.mixed_groups.begin(), B.mixed_groups.end(), gd + n_groups);
     }
-    const bool any_junction = n_coupled || n_groups;
+    const bool any_junction = n_coupled || n_groups || n_mixed;
     chunk_base[0] = 0;
     uint32_t main_waves = 0; // the main launch's waves: every dealt object that is not on a junction's side
     for (uint32_t d = 0; d < n_dealt; ++d) {
@@ -1630,7 +1827,7 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
                 if (jd[j].side[1].waves) tap_object(jd[j].side[1].dealt, jd[j].first_wave + jd[j].side[0].waves, jd[j].side[1].waves);
             }
             const GroupDev<Real> *gd = A.h<GroupDev<Real>>(o_groups);
-            for (uint32_t g = 0; g < n_groups; ++g)
+            for (uint32_t g = 0; g < n_groups + n_mixed; ++g)
                 for (uint32_t o = 0; o < gd[g].n_objects; ++o) tap_object(gd[g].dealt[o], gd[g].first_wave + gd[g].wave0[o], gd[g].waves[o]);
         }
     }
@@ -1739,6 +1936,24 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
                 launch_modes(&k_bank_modes_grouped<Real>, n_groups, widest_group * WAVE, grouped_lds<Real>(widest_group), B.junction_gain, ga);
             }
         }
+        if (n_mixed) { // the groups with a Hertz member (mh_bank_render_mixed): the entries with step 4m, one workgroup per group
+            ensure(ctx, B.junction_gain, size_t(coupled_waves + JUNCTION_WAVES) * max_imp * MODES_PER_WAVE);
+            static PerDeviceOnce attr;
+            attr.run(ctx->device, [] {
+                HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_bank_modes_grouped_mixed<Real>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+                HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_bank_modes_grouped_mixed_observed<Real>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            });
+            if (grouped_lds<Real>(widest_mixed) > 160 * 1024) mh_throw(MH_EINVAL, "a junction group of %u waves", widest_mixed); // (none is kept)
+            const MixedArgs<Real> ma{{B.defl_gain, A.d<GroupDev<Real>>(o_groups) + n_groups, A.d<float>(o_approach), A.hd<Real>(o_junction_force), A.hd<double>(o_compliance), A.hd<uint32_t>(o_status)}, A.hd<uint32_t>(o_unconverged)};
+            TimedLaunch timed(ctx, MH_KERNEL_JUNCTION, double(mixed_members) * double(frames));
+            if (n_taps) {
+                ensure(ctx, B.tap_states, size_t(n_taps) * frames * TAP_FRAME);
+                const ObservedArgs<Real, MixedArgs<Real>> oa{ma, A.d<uint32_t>(o_tap_of), B.tap_states};
+                launch_modes(k_bank_modes_grouped_mixed_observed<Real>, n_mixed, widest_mixed * WAVE, grouped_lds<Real>(widest_mixed), B.junction_gain, oa);
+            } else {
+                launch_modes(k_bank_modes_grouped_mixed<Real>, n_mixed, widest_mixed * WAVE, grouped_lds<Real>(widest_mixed), B.junction_gain, ma);
+            }
+        }
         if (n_taps) { // the tapped waves' partial rows, in k_bank_modes_read's order; they join read_rows ahead of k_bank_read_rows
             ensure(ctx, B.read_rows, size_t(read_row_count + 1) * frames);
             const ReadArgs<Real> rd{B.defl_gain, A.d<uint32_t>(o_pick_ptr), A.d<PickupDev<Real>>(o_pick_dev), B.read_rows, 0u};
@@ -1811,6 +2026,10 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
             std::copy(A.h<Real>(o_junction_force) + size_t(j) * frames, A.h<Real>(o_junction_force) + size_t(j + 1) * frames, force_out + size_t(j) * frames);
             compliance_out[j] = A.h<double>(o_compliance)[j];
             status_out[j] = uint8_t(A.h<uint32_t>(o_status)[j]);
+        }
+        if (mixed) { // a member of a group with a Hertz member: its frames that failed the residual test; 0 for every other junction
+            std::fill(unconverged_out, unconverged_out + n_junctions, 0u);
+            for (const uint32_t j : B.mixed_rows) unconverged_out[j] = A.h<uint32_t>(o_unconverged)[j];
         }
         if (carry_v) { // the carry of a damped junction that was solved; a quiet NaN for every other junction
             Real *carry = static_cast<Real *>(carry_v);
@@ -1955,7 +2174,7 @@ static int render_junctions(mh_bank *bank, uint32_t frames, float click_gain, ui
                             void *out, double *object_energy, uint32_t *object_live, uint8_t *object_silenced, double *object_modal_energy, uint32_t n_drives,
                             const mh_drive *drives, const float *signals, uint32_t n_pickups, const mh_pickup *pickups, void *pickup_out, uint8_t *pickup_read,
                             uint32_t n_junctions, const mh_junction *junctions, const float *approach, void *force_out, double *compliance_out, uint8_t *status_out,
-                            const float *damping, void *carry, bool observe = false) {
+                            const float *damping, void *carry, bool observe = false, uint32_t *unconverged_out = nullptr) {
     if (!bank || !out || (n_impacts && !impacts) || (n_renderers && !deal_offset) || !out_gain || !listener_gain || (n_drives && (!drives || !signals))) return MH_EINVAL;
     if (n_pickups && (!pickups || !pickup_out || !pickup_read)) return MH_EINVAL;
     if (n_junctions && (!junctions || !approach || !force_out || !compliance_out || !status_out)) return MH_EINVAL;
@@ -1967,7 +2186,7 @@ static int render_junctions(mh_bank *bank, uint32_t frames, float click_gain, ui
         auto go = [&](auto &B) {
             render_impl(B, frames, click_gain, n_impacts, impacts, n_renderers, deal_offset, deal_objects, render_count, tuned_count, out_gain, listener_gain, out, object_energy,
                         object_live, object_silenced, object_modal_energy, n_drives, drives, signals, n_pickups, pickups, pickup_out, pickup_read, n_junctions, junctions, approach,
-                        force_out, compliance_out, status_out, damping, carry, observe);
+                        force_out, compliance_out, status_out, damping, carry, observe, unconverged_out);
         };
         if (bank->dbl) go(*bank->d); else go(*bank->f);
         return MH_OK;
@@ -2005,6 +2224,20 @@ int mh_bank_render_observed(mh_bank *bank, uint32_t frames, float click_gain, ui
     return render_junctions(bank, frames, click_gain, n_impacts, impacts, n_renderers, deal_offset, deal_objects, render_count, tuned_count, out_gain, listener_gain, out, object_energy,
                             object_live, object_silenced, object_modal_energy, n_drives, drives, signals, n_pickups, pickups, pickup_out, pickup_read, n_junctions, junctions, approach,
                             force_out, compliance_out, status_out, damping ? damping : &no_damping, carry, true);
+}
+int mh_bank_render_mixed(mh_bank *bank, uint32_t frames, float click_gain, uint32_t n_impacts, mh_impact *impacts, uint32_t n_renderers, const uint32_t *deal_offset,
+                         const uint32_t *deal_objects, const uint32_t *render_count, const uint32_t *tuned_count, const float *out_gain, const float *listener_gain,
+                         void *out, double *object_energy, uint32_t *object_live, uint8_t *object_silenced, double *object_modal_energy, uint32_t n_drives,
+                         const mh_drive *drives, const float *signals, uint32_t n_pickups, const mh_pickup *pickups, void *pickup_out, uint8_t *pickup_read,
+                         uint32_t n_junctions, const mh_junction *junctions, const float *approach, void *force_out, double *compliance_out, uint8_t *status_out,
+                         const float *damping, void *carry, uint32_t *unconverged_out) {
+    if (n_junctions && (!damping || !carry || !unconverged_out)) return MH_EINVAL;
+    static const float no_damping = 0; // (as in mh_bank_render_damped)
+    static uint32_t no_count = 0; // (n_junctions = 0: render_impl tells the entries apart by the pointer; nothing is written through it)
+    if (unconverged_out) std::fill(unconverged_out, unconverged_out + n_junctions, 0u);
+    return render_junctions(bank, frames, click_gain, n_impacts, impacts, n_renderers, deal_offset, deal_objects, render_count, tuned_count, out_gain, listener_gain, out, object_energy,
+                            object_live, object_silenced, object_modal_energy, n_drives, drives, signals, n_pickups, pickups, pickup_out, pickup_read, n_junctions, junctions, approach,
+                            force_out, compliance_out, status_out, damping ? damping : &no_damping, carry, true, unconverged_out ? unconverged_out : &no_count);
 }
 int mh_bank_render_read(mh_bank *bank, uint32_t frames, float click_gain, uint32_t n_impacts, mh_impact *impacts, uint32_t n_renderers, const uint32_t *deal_offset,
                         const uint32_t *deal_objects, const uint32_t *render_count, const uint32_t *tuned_count, const float *out_gain, const float *listener_gain,
