@@ -385,8 +385,8 @@ int mh_bank_render_read(mh_bank *, uint32_t frames, float click_gain, uint32_t n
  * than one junction, and one that would join a component that holds a Hertz junction (the Hertz solve in more than one dimension is not in
  * this version); a flagged junction on an object of a kept unflagged one.  Two junctions between the same pair of objects, at different
  * points, are a legal group.  Pickups on a junction's object stay left out (mh_bank_render_observed reads them).  MH_JUNCTION_GROUP = 4 is what a wave's registers hold: one
- * gain triple per member per lane, 195 VGPRs in fp64 (118 in fp32), nothing in scratch.  (Hertz in groups: mh_bank_render_mixed.)  Not in this version, as above: damping in
- * groups, friction, roughness.
+ * gain triple per member per lane, 195 VGPRs in fp64 (118 in fp32), nothing in scratch.  (Hertz in groups: mh_bank_render_mixed; damping in groups:
+ * mh_bank_render_damped_groups.)  Not in this version, as above: friction, roughness.
  *
  * Contact damping, flags & MH_JUNCTION_DAMPED (mh_bank_render_damped only: mh_bank_render_coupled ignores the bit): the Hunt-Crossley
  * term of the reference's surface renderer (DampingFactor = 1.5 (1 - e) ContactDamping, src/audio/surface/).  The junction obeys
@@ -431,7 +431,7 @@ int mh_bank_render_read(mh_bank *, uint32_t frames, float click_gain, uint32_t n
  * that holds a damped one (decided with the groups, modalhip_groups.hpp).  A lone damped junction with MH_JUNCTION_SHARED is an ordinary
  * damped junction.  Every junction without the bit keeps its bits beside a damped one, and a call in which no kept junction has the bit
  * launches what mh_bank_render_coupled launches.
- * Not in this version: damping in groups, a bilateral damped law, hysteretic laws, friction and roughness, pickups on junction objects
+ * Not in this version: a bilateral damped law (damping in groups: mh_bank_render_damped_groups, below), hysteretic laws, friction and roughness, pickups on junction objects
  * (in this entry: mh_bank_render_observed reads them, "Pickups on junction objects" below).
  *
  * Pickups on junction objects, mh_bank_render_observed: mh_bank_render_damped -- its parameters in its order, nothing more -- except that a
@@ -457,7 +457,8 @@ int mh_bank_render_read(mh_bank *, uint32_t frames, float click_gain, uint32_t n
  * force rows, compliances, statuses and carries are the same bits.  A refused junction's objects render as with K = 0 and are read.
  * With frames = 0 nothing is read and the carry comes back unchanged.  A call without a pickup on a kept junction's object launches
  * exactly what mh_bank_render_damped launches.  mh_bank_render_coupled and mh_bank_render_damped keep leaving such pickups out.
- * Not in this version: damping inside groups (Hertz inside groups: mh_bank_render_mixed, below), a bilateral damped law, friction,
+ * Not in this version: a bilateral damped law (Hertz inside groups: mh_bank_render_mixed, damping inside groups:
+ * mh_bank_render_damped_groups, below), friction,
  * roughness, contact forces acting inside a pickup's look-ahead.
  *
  * Hertz junctions in groups, mh_bank_render_mixed: mh_bank_render_observed -- its parameters in its order -- followed by one output,
@@ -511,7 +512,70 @@ int mh_bank_render_read(mh_bank *, uint32_t frames, float click_gain, uint32_t n
  * member, or 1 + C_ii K_i is not a finite number above 0 on a linear one; solved otherwise.  compliance_out[i] = C_ii in both cases.
  * k_bank_modes_grouped<Real, OBSERVE, true>: the same solve in every lane of every wave; 230 / 246 VGPRs (fp32 / fp64), nothing in scratch;
  * 512-frame blocks on an MI355X, n = 2 ... 4: fp32 20 600 - 27 100 cycles per frame, 4.6 - 6.1 ms; fp64 24 600 - 31 200 cycles, 5.4 - 6.9 ms.
- * Not in this version: damping inside groups, a bilateral Hertz or damped law, more than four members, friction, roughness. */
+ * Not in this version: a bilateral Hertz or damped law, more than four members, friction, roughness (damping inside groups:
+ * mh_bank_render_damped_groups, next).
+ *
+ * Damped junctions in groups, mh_bank_render_damped_groups: mh_bank_render_mixed -- its parameters in its order and nothing more.  One
+ * difference: a kept junction with MH_JUNCTION_SHARED | MH_JUNCTION_DAMPED, linear or Hertz, may be a member of a group, beside linear
+ * unilateral, bilateral, Hertz and other damped members (the group decision of modalhip_groups.hpp with damped_in_groups = true).
+ * Still left out, in call order, with the bits of the call without them: damped with bilateral, an l (damping[j]) that is not finite or
+ * below 0, Hertz with bilateral, a fifth member, a ninth wave, a flagged junction on an unflagged junction's object.  A group with a
+ * Hertz member and no damped one runs step 4m's kernel bit for bit, a linear group the enumeration of MH_JUNCTION_SHARED, a lone damped
+ * junction k_bank_modes_coupled_damped: a call without a damped junction in a group launches exactly what mh_bank_render_mixed launches.
+ * A group with a damped member takes steps 1, 2, 3 and 5 of MH_JUNCTION_SHARED bit for bit.  Step 4 becomes
+ *   4g. find y with y = x - C f(y): f_j = K_j phi_j(y_j) max(1 + l_j (y_j - y_p,j), 0) on a damped member, phi_j = max(y, 0) or
+ *       max(y, 0)^1.5 (MH_JUNCTION_HERTZ); step 4m's law on every other member.  y_p,j is the compression that member's solve left in the
+ *       previous frame.  For l >= 0 each f_j is continuous and nondecreasing in y_j (on y >= 0 a product of two factors that are not below
+ *       0 and do not decrease; 0 elsewhere), so with C = D G two solutions y, y' give sum_j df_j dy_j / D_j + df' G df = 0 with both terms
+ *       >= 0: G df = 0, then dy = -C df = 0 -- exactly one solution, as in step 4m.
+ *       The carry: one value of state per damped member, through `carry` in and out, with step 4d's meaning.  Not finite on entry: no
+ *       history for this member -- frame 0 is solved with l_j = 0, y_p,j = 0 and its y_j starts the history.  On return: the last frame's
+ *       y_j of the final iterate (never x - C f), for a damped member of a solved group; a quiet NaN for every other junction; frames = 0
+ *       leaves it alone.  The solve keeps no other state between frames: one block of N frames and two of N / 2 with the carry passed
+ *       on are the same bits.
+ *       One fixed expression tree as in step 4m: every operation rounded to the bank's precision, nothing contracted, no trip count
+ *       that depends on data.  With ck_jj = C_jj K_j, c15_jj = 1.5 ck_jj (once per block), l_j and y_p,j as this frame takes them (0
+ *       without history), (phi_j, phi'_j) of step 4m, kp = K_j phi_j(y_j), kq = K_j phi'_j(y_j), formed after every change of y_j:
+ *         law_j:      not damped: f_j = kp, kd_j = kq.  Damped: m = 1 + l_j (y_j - y_p,j); for m > 0 f_j = kp m, kd_j = kq m + kp l_j;
+ *                     otherwise f_j = +0, kd_j = 0.
+ *         alone_j(x): damped: step 4d's tree up to y, with c = ck_jj, c15 = c15_jj, cl = ck_jj l_j (x for x <= 0 or 1 + l_j (x - y_p,j)
+ *                     <= 0; linear: the closed form; Hertz: the smallest of the upper bounds, six Newton steps); else step 4m's alone_j.
+ *         start:      y_j = alone_j(x_j), j ascending.
+ *         1 sweep:    j ascending: y_j = alone_j(x_j - s), s = sum over i != j, ascending from +0, of C_ji f_i.
+ *         residual:   step 4m's, plain and in twice the precision, in the f_j above.
+ *         8 steps:    J_ij = C_ij kd_j, J_ii = 1 + C_ii kd_i; J d = F by step 4m's elimination; t_j = y_j - d_j.  In steps 1 - 6 a
+ *                     member that is not bilateral with kd_j = 0 or t_j > 2 y_j takes y_j = alone_j(t_j + C_jj (f_j + kd_j (t_j - y_j)))
+ *                     -- its own tree at its row's linearised right-hand side, x_j - sum_{i != j} C_ji (f_i + kd_i dy_i): from below the
+ *                     root Newton's iteration on a convex law lands far above it and creeps back by 0.6 per step, and an open or clamped
+ *                     member (kd = 0) comes back at x_j - s --; every other member, and every member in steps 7 and 8, y_j = t_j.
+ *                     Then law_j and the residual of the new y: plain after steps 1 - 5, in twice the precision after steps 6, 7
+ *                     and 8 -- the last two steps are iterative refinement.
+ *         The forces are the f_j of the last y; the carries its y_j.
+ *       The final clamp on m is step 4d's: m <= 0 gives f_j = +0.  The group is padded to MH_JUNCTION_GROUP members with K = 0, C = 0,
+ *       x = 0, which changes no bit.
+ *       The residual test of a frame: some |F_i| > 32 u (|y_i| + sum_j |C_ij| s_j + |x_i|), with s_j = kp (1 + l_j (|y_j| + |y_p,j|)) on
+ *       a damped member and |f_j| on every other.  A damped f_j has 7 roundings where step 4m's has 3: the root, the product and K
+ *       (kp), then y - y_p, times l, plus 1 -- each within u of l (|y| + |y_p|) or of 1 + l (|y| + |y_p|), whatever m cancels to -- and
+ *       the product kp m; the last place of y_j moves m by another u l |y_j|.  That is 8 u s_j per member against step 4m's 4 u |f_j|:
+ *       the sum the last step can reach is 4 u of the magnitudes, and the multiple is 8 times that as in step 4m.  (With |f_j| in the
+ *       place of s_j a stiff member whose m has cancelled to 1e-4 settles at 1e3 u and fails a test it has met.)
+ *       unconverged_out[j]: for a member of a group with a Hertz or a damped member, the frames of the block that failed its test.
+ *       Accuracy (tests/test_bank_damped_groups_cpu.py, section 3h's 36 sets of 1 000 cases with about half the unilateral members
+ *       damped, l |x| = 0 and 1e-3 ... 1e3, y_p / x in [-3, 3]): |f - f*| / max_j s_j(y*) against the error of step 4's linear solve on
+ *       the linearisation at the solution is at most 1.31 x (4 x allowed, 2.62 x asserted); the largest final |F_i| is 3.5 u of the
+ *       magnitudes summed.  (Sweeps, steps, refined) = (1, 8, 2) is a smallest triple: with 7 steps 6 cases of 36 000 fail the residual
+ *       test, without the sweep 12 (and a set misses the margin by 3.7e5), with one refined step 3.  Without the step through alone_j
+ *       19 steps are needed.
+ * Status: step 4m's conditions with a damped member counted as a Hertz one (C_ii and C_ii K_i not below 0), plus, on a damped member,
+ * C_ii K_i l_i a finite number not below 0 and every |C_ij K_j l_j| within the square root of the largest finite number (kd_j holds
+ * K_j phi l_j, and the elimination multiplies two entries of J; what kd_j becomes beyond that depends on y and cannot be decided per
+ * block).  A refused group: every member status 2, zero rows, NaN carries, the objects render as with K = 0.
+ * k_bank_modes_grouped<Real, OBSERVE, true, true>: C, K, ck, c15, l and the iterate in scalar registers, y_p per member in registers from frame to
+ * frame, no barrier, LDS slot or global access per frame beyond step 4m's; the carries are written once after the loop.  Resources:
+ * profiles/bank_damped_groups_resources.txt.  512-frame blocks on an MI355X, n = 2 ... 4: fp32 35 500 - 45 200 cycles per frame, 7.8 - 10.0 ms;
+ * fp64 47 600 - 58 900 cycles, 10.4 - 12.8 ms: beyond the 10.67 ms of real time for n = 3 and 4.
+ * Not in this version: a bilateral damped or Hertz law, more than four members, friction, roughness, hysteretic laws, a warm start of the
+ * Newton iteration from the previous frame (the bits would depend on the block length). */
 typedef struct {
     uint32_t object;
     uint32_t points[3];
@@ -570,6 +634,14 @@ int mh_bank_render_mixed(mh_bank *, uint32_t frames, float click_gain, uint32_t 
                          const mh_drive *drives, const float *signals, uint32_t n_pickups, const mh_pickup *pickups, void *pickup_out,
                          uint8_t *pickup_read, uint32_t n_junctions, const mh_junction *junctions, const float *approach, void *force_out,
                          double *compliance_out, uint8_t *status_out, const float *damping, void *carry, uint32_t *unconverged_out);
+/* mh_bank_render_mixed in which a damped junction may join a group as well: "Damped junctions in groups" above. */
+int mh_bank_render_damped_groups(mh_bank *, uint32_t frames, float click_gain, uint32_t n_impacts, mh_impact *impacts,
+                                 uint32_t n_renderers, const uint32_t *deal_offset, const uint32_t *deal_objects, const uint32_t *render_count,
+                                 const uint32_t *tuned_count, const float *out_gain, const float *listener_gain, void *out, double *object_energy,
+                                 uint32_t *object_live, uint8_t *object_silenced, double *object_modal_energy, uint32_t n_drives,
+                                 const mh_drive *drives, const float *signals, uint32_t n_pickups, const mh_pickup *pickups, void *pickup_out,
+                                 uint8_t *pickup_read, uint32_t n_junctions, const mh_junction *junctions, const float *approach, void *force_out,
+                                 double *compliance_out, uint8_t *status_out, const float *damping, void *carry, uint32_t *unconverged_out);
 /* Read back state columns (for parity tests and the modal-energy diagnostic, ModalAudio.cpp:564-577). */
 int mh_bank_read_state(const mh_bank *, uint32_t first, uint32_t count, double *state_re, double *state_im);
 

@@ -9,7 +9,9 @@
 // component, unless that component would hold more than MH_JUNCTION_GROUP junctions, its distinct objects would take more waves than a
 // workgroup holds (each object counted once), or it would hold a Hertz junction or a damped one (MH_JUNCTION_DAMPED) beside another
 // junction.  mh_bank_render_mixed alone offers its junctions with hertz_in_groups = true: a Hertz junction then joins a group as a linear one
-// does (Component::hertz: the group has a Hertz member and takes step 4m); a damped one still stays alone.
+// does (Component::hertz: the group has a Hertz member and takes step 4m); a damped one still stays alone.  mh_bank_render_damped_groups
+// alone offers them with damped_in_groups = true as well: a damped junction then joins too (Component::damped: the group has a damped
+// member and takes step 4g).
 #ifndef MODALHIP_GROUPS_HPP
 #define MODALHIP_GROUPS_HPP
 #include "modalhip.h"
@@ -31,8 +33,10 @@ struct MhJunctionGroups {
     explicit MhJunctionGroups(uint32_t n_objects) : of_object(n_objects, -1) {}
 
     // Offers junction `id` (ids ascend with the call order).  object_b = MH_NO_OBJECT: one-sided.  Returns the component it was kept in, or
-    // -1: left out.  hertz_in_groups: mh_bank_render_mixed's decision; false: every other entry's.
-    int32_t add(uint32_t id, uint32_t flags, uint32_t object_a, uint32_t waves_a, uint32_t object_b, uint32_t waves_b, bool hertz_in_groups = false) {
+    // -1: left out.  hertz_in_groups: mh_bank_render_mixed's decision; damped_in_groups: mh_bank_render_damped_groups's; false: every other
+    // entry's.
+    int32_t add(uint32_t id, uint32_t flags, uint32_t object_a, uint32_t waves_a, uint32_t object_b, uint32_t waves_b, bool hertz_in_groups = false,
+                bool damped_in_groups = false) {
         constexpr uint32_t MOST_WAVES = MH_JUNCTION_MODES / 128;
         const bool two_sided = object_b != MH_NO_OBJECT, shared = (flags & MH_JUNCTION_SHARED) != 0, hertz = (flags & MH_JUNCTION_HERTZ) != 0,
                    damped = (flags & MH_JUNCTION_DAMPED) != 0;
@@ -55,7 +59,7 @@ struct MhJunctionGroups {
         if (two_sided && cb < 0) waves += waves_b;
         if (members > MH_JUNCTION_GROUP || waves > MOST_WAVES) return -1;
         if (members > 1 && (hertz || hertz_inside) && !hertz_in_groups) return -1; // a Hertz junction in a group: mh_bank_render_mixed only
-        if (members > 1 && (damped || damped_inside)) return -1; // and no damped one: its solve, like Hertz's, is in one dimension
+        if (members > 1 && (damped || damped_inside) && !damped_in_groups) return -1; // a damped one in a group: mh_bank_render_damped_groups only
         int32_t into = ca >= 0 ? ca : cb;
         if (into < 0) {
             into = int32_t(components.size());
@@ -79,7 +83,7 @@ struct MhJunctionGroups {
         c.waves = waves;
         c.shared = shared; // (every member of a component has the flag, or it is one unflagged junction)
         c.hertz = hertz || hertz_inside; // (without hertz_in_groups a Hertz junction is only ever a component of its own: the check above)
-        c.damped = damped; // (and so is a damped one)
+        c.damped = damped || damped_inside; // (and so is a damped one without damped_in_groups)
         return into;
     }
 };

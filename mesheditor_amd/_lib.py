@@ -115,6 +115,7 @@ def lib():
         "mh_bank_render_damped": (i32, [vp, u32, C.c_float, u32, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp]),
         "mh_bank_render_observed": (i32, [vp, u32, C.c_float, u32, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp]),
         "mh_bank_render_mixed": (i32, [vp, u32, C.c_float, u32, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "mh_bank_render_damped_groups": (i32, [vp, u32, C.c_float, u32, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp]),
         "mh_bank_read_state": (i32, [vp, u32, u32, vp, vp]),
     }
     for name, (res, args) in sig.items():

@@ -88,6 +88,7 @@ def lib():
         "mhx_render_damped": (i32, [vp, vp, u32, u32, vp, vp, u32, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp]),
         "mhx_render_observed": (i32, [vp, vp, u32, u32, vp, vp, u32, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp]),
         "mhx_render_mixed": (i32, [vp, vp, u32, u32, vp, vp, u32, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "mhx_render_damped_groups": (i32, [vp, vp, u32, u32, vp, vp, u32, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp]),
         "mhx_active_impacts": (u32, [vp]), "mhx_modal_energy": (f64, [vp]), "mhx_render_share": (f32, [vp]), "mhx_find_object": (i32, [vp, u32]),
         "mhx_time_kernels": (i32, [vp, i32]), "mhx_kernel_class_stats": (i32, [vp, i32, C.POINTER(C.c_uint64), C.POINTER(f64), C.POINTER(f64)]),
         "mhx_column": (u32, [vp, i32, i32, vp]), "mhx_object_state": (None, [vp, vp, vp, vp]),
@@ -215,6 +216,16 @@ class Scene:
         rates = np.zeros(len(junctions), np.float32) if damping is None else damping
         counts = np.zeros(len(junctions), np.uint32)
         entry = lambda *args: self.L.mhx_render_mixed(*args, _p(counts))
+        return self.render_damped(out, drives, signals, pickups, junctions, approach, rates, carry, entry=entry) + (counts,)
+
+    def render_damped_groups(self, out, drives, signals, pickups, junctions, approach, damping=None, carry=None):
+        """RenderModalDampedGroups: render_mixed in which a junction with shared=True and damped=True, linear or Hertz, may be a member of a
+        group as well (the older entries leave it out).  Returns render_mixed's tuple: the carry holds, for a damped member of a solved
+        group, the compression its last frame's solve left (pass it to the next block), and `unconverged` counts the members of a group
+        with a Hertz or a damped member."""
+        rates = np.zeros(len(junctions), np.float32) if damping is None else damping
+        counts = np.zeros(len(junctions), np.uint32)
+        entry = lambda *args: self.L.mhx_render_damped_groups(*args, _p(counts))
         return self.render_damped(out, drives, signals, pickups, junctions, approach, rates, carry, entry=entry) + (counts,)
 
     def render_damped(self, out, drives, signals, pickups, junctions, approach, damping, carry=None, entry=None):

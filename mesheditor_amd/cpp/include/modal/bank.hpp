@@ -317,6 +317,20 @@ void RenderModalMixed(ModalAudio &, std::span<const ModalDrive> drives, const fl
 void RenderModalMixed(ModalAudio64 &, std::span<const ModalDrive> drives, const float *signals, std::span<const ModalPickup> pickups, double *reads,
                       std::span<const ModalJunction> junctions, const float *approach, std::span<const float> damping, std::span<double> carry, double *forces, double *out,
                       uint32_t frame_count, std::span<uint32_t> unconverged, uint8_t *read_flags = nullptr, double *compliances = nullptr, uint8_t *statuses = nullptr);
+// Damped junctions in groups (modalhip.h, mh_bank_render_damped_groups): RenderModalMixed -- its parameters in its
+// order -- except that a kept junction with ModalJunctionShared | ModalJunctionDamped, linear or Hertz, may be a member of a group as well,
+// beside linear unilateral, bilateral, Hertz and other damped members.  Such a group's step 4 is the header's step 4g: step 4m's tree with
+// f = K phi(y) max(1 + l (y - y_p), 0) on the damped members.  carry: one value per junction, in and out, with RenderModalDamped's meaning
+// (not finite: no history; a quiet NaN comes back for every junction that is not a solved damped one); unconverged[j] counts the frames of
+// a member of a group with a Hertz or a damped member that failed the residual test.  Still left out: damped or Hertz with bilateral, a
+// damping that is not a finite number from 0 up, a fifth member, a ninth wave, a flagged junction on an unflagged junction's object.
+// Every other junction, every other group and every older entry are what they were.
+void RenderModalDampedGroups(ModalAudio &, std::span<const ModalDrive> drives, const float *signals, std::span<const ModalPickup> pickups, float *reads,
+                             std::span<const ModalJunction> junctions, const float *approach, std::span<const float> damping, std::span<float> carry, float *forces, float *out,
+                             uint32_t frame_count, std::span<uint32_t> unconverged, uint8_t *read_flags = nullptr, double *compliances = nullptr, uint8_t *statuses = nullptr);
+void RenderModalDampedGroups(ModalAudio64 &, std::span<const ModalDrive> drives, const float *signals, std::span<const ModalPickup> pickups, double *reads,
+                             std::span<const ModalJunction> junctions, const float *approach, std::span<const float> damping, std::span<double> carry, double *forces, double *out,
+                             uint32_t frame_count, std::span<uint32_t> unconverged, uint8_t *read_flags = nullptr, double *compliances = nullptr, uint8_t *statuses = nullptr);
 // Not in the reference: the libmodalhip context the bank's device mirror lives on (created on demand), for callers that
 // time its kernels (mh_context_time_kernels / mh_context_kernel_class_stats).
 mh_context *ModalDeviceContext(ModalAudio &);

@@ -509,6 +509,7 @@ template<typename Real> struct JunctionResults {
     Real *Carry{nullptr};
     bool Observed{false}; // RenderModalObserved: the damped entry that also reads the pickups on junction objects
     uint32_t *Unconverged{nullptr}; // RenderModalMixed: the observed entry in which a Hertz junction may join a group; per junction, its frames that failed the residual test
+    bool DampedInGroups{false}; // RenderModalDampedGroups: the mixed entry in which a damped junction may join a group as well
 };
 
 template<typename Audio, typename Real>
@@ -593,7 +594,7 @@ void RenderBlock(Audio &m, std::span<const ModalDrive> drives, const float *sign
         if (!std::isfinite(v.Stiffness) || v.Stiffness < 0 || !side_ok(v.A) || (two_sided && (v.A.Object == v.B.Object || !side_ok(v.B)))) continue;
         if ((v.Flags & ModalJunctionHertz) && (v.Flags & ModalJunctionBilateral)) continue; // the Hertz law is unilateral
         if ((flags & ModalJunctionDamped) && ((flags & ModalJunctionBilateral) || !std::isfinite(per_frame) || per_frame < 0)) continue; // so is the damped one
-        if (grouping.add(uint32_t(j), flags, v.A.Object, side_waves(v.A), two_sided ? v.B.Object : MH_NO_OBJECT, two_sided ? side_waves(v.B) : 0u, coupled.Unconverged != nullptr) < 0) continue;
+        if (grouping.add(uint32_t(j), flags, v.A.Object, side_waves(v.A), two_sided ? v.B.Object : MH_NO_OBJECT, two_sided ? side_waves(v.B) : 0u, coupled.Unconverged != nullptr, coupled.DampedInGroups) < 0) continue;
         mh_junction_side none{};
         none.object = MH_NO_OBJECT;
         d.Junctions.push_back({side_record(v.A), two_sided ? side_record(v.B) : none, v.Stiffness, flags});
@@ -658,7 +659,7 @@ void RenderBlock(Audio &m, std::span<const ModalDrive> drives, const float *sign
     if (coupled.Unconverged) {
         unconverged.assign(kept_junctions + 1, 0u);
         damping.push_back(0.f), carry.push_back(Real(0)); // (never read: the entry wants pointers)
-        if (mh_bank_render_mixed(d.Bank, frames, m.ClickGain.load(std::memory_order_relaxed), n_impacts, d.Impacts.data(), renderers, d.DealOffset.data(), d.DealObjects.data(),
+        if ((coupled.DampedInGroups ? mh_bank_render_damped_groups : mh_bank_render_mixed)(d.Bank, frames, m.ClickGain.load(std::memory_order_relaxed), n_impacts, d.Impacts.data(), renderers, d.DealOffset.data(), d.DealObjects.data(),
                                  d.RenderCount.data(), d.Tuned.data(), out_gain, listener_gain, out, d.Energy.data(), d.Live.data(), d.Silenced.data(), d.ModalEnergy.data(),
                                  uint32_t(d.Drives.size()), d.Drives.data(), drive_signals, uint32_t(d.Pickups.size()), d.Pickups.data(), reads, d.PickupRead.data(), kept_junctions, d.Junctions.data(), d.Approach.data(),
                                  junction_forces.data(), d.JunctionCompliance.data(), d.JunctionStatus.data(), damping.data(), carry.data(), unconverged.data()) != MH_OK)
@@ -832,6 +833,22 @@ void RenderModalMixed(ModalAudio64 &m, std::span<const ModalDrive> drives, const
     static const float none = 0;
     static uint32_t no_count = 0;
     RenderBlock<ModalAudio64, double>(m, drives, signals, out, frame_count, pickups, reads, read_flags, {junctions, approach, forces, compliances, statuses, junctions.empty() ? &none : damping.data(), carry.data(), true, junctions.empty() ? &no_count : unconverged.data()});
+}
+void RenderModalDampedGroups(ModalAudio &m, std::span<const ModalDrive> drives, const float *signals, std::span<const ModalPickup> pickups, float *reads,
+                             std::span<const ModalJunction> junctions, const float *approach, std::span<const float> damping, std::span<float> carry, float *forces, float *out,
+                             uint32_t frame_count, std::span<uint32_t> unconverged, uint8_t *read_flags, double *compliances, uint8_t *statuses) {
+    if (damping.size() < junctions.size() || carry.size() < junctions.size() || unconverged.size() < junctions.size()) throw std::invalid_argument("RenderModalDampedGroups: a damping, a carry and a count per junction");
+    static const float none = 0; // (no junctions: pointers that say which entry this is)
+    static uint32_t no_count = 0;
+    RenderBlock<ModalAudio, float>(m, drives, signals, out, frame_count, pickups, reads, read_flags, {junctions, approach, forces, compliances, statuses, junctions.empty() ? &none : damping.data(), carry.data(), true, junctions.empty() ? &no_count : unconverged.data(), true});
+}
+void RenderModalDampedGroups(ModalAudio64 &m, std::span<const ModalDrive> drives, const float *signals, std::span<const ModalPickup> pickups, double *reads,
+                             std::span<const ModalJunction> junctions, const float *approach, std::span<const float> damping, std::span<double> carry, double *forces, double *out,
+                             uint32_t frame_count, std::span<uint32_t> unconverged, uint8_t *read_flags, double *compliances, uint8_t *statuses) {
+    if (damping.size() < junctions.size() || carry.size() < junctions.size() || unconverged.size() < junctions.size()) throw std::invalid_argument("RenderModalDampedGroups: a damping, a carry and a count per junction");
+    static const float none = 0;
+    static uint32_t no_count = 0;
+    RenderBlock<ModalAudio64, double>(m, drives, signals, out, frame_count, pickups, reads, read_flags, {junctions, approach, forces, compliances, statuses, junctions.empty() ? &none : damping.data(), carry.data(), true, junctions.empty() ? &no_count : unconverged.data(), true});
 }
 mh_context *ModalDeviceContext(ModalAudio &m) { return NeedContext(m), m.Dev->Context; }
 mh_context *ModalDeviceContext(ModalAudio64 &m) { return NeedContext(m), m.Dev->Context; }

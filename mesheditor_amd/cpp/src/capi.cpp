@@ -203,6 +203,25 @@ int mhx_render_mixed(mhx_scene *s, void *out, uint32_t frames, uint32_t n_drives
         return 0;
     } catch (const std::exception &e) { g_error = e.what(); return 1; }
 }
+// RenderModalDampedGroups: mhx_render_mixed's parameters
+int mhx_render_damped_groups(mhx_scene *s, void *out, uint32_t frames, uint32_t n_drives, const ModalDrive *drives, const float *signals, uint32_t n_pickups,
+                             const ModalPickup *pickups, void *reads, uint8_t *read_flags, uint32_t n_junctions, const ModalJunction *junctions, const float *approach,
+                             void *forces, double *compliances, uint8_t *statuses, const float *damping, void *carry, uint32_t *unconverged) {
+    try {
+        const std::span<const ModalDrive> list(drives, n_drives);
+        const std::span<const ModalPickup> probes(pickups, n_pickups);
+        const std::span<const ModalJunction> contacts(junctions, n_junctions);
+        const std::span<const float> rates(damping, n_junctions);
+        const std::span<uint32_t> counts(unconverged, n_junctions);
+        if (s->dbl)
+            RenderModalDampedGroups(s->audio64, list, signals, probes, static_cast<double *>(reads), contacts, approach, rates, std::span<double>(static_cast<double *>(carry), n_junctions),
+                                    static_cast<double *>(forces), static_cast<double *>(out), frames, counts, read_flags, compliances, statuses);
+        else
+            RenderModalDampedGroups(s->audio, list, signals, probes, static_cast<float *>(reads), contacts, approach, rates, std::span<float>(static_cast<float *>(carry), n_junctions),
+                                    static_cast<float *>(forces), static_cast<float *>(out), frames, counts, read_flags, compliances, statuses);
+        return 0;
+    } catch (const std::exception &e) { g_error = e.what(); return 1; }
+}
 // Kernel timing of the scene's device context: enable / read one class (modalhip.h MH_KERNEL_*)
 int mhx_time_kernels(mhx_scene *s, int enable) {
     try {

@@ -844,6 +844,14 @@ template<typename Real> struct MixedArgs : GroupedArgs<Real> {
     uint32_t *unconverged_out;
 };
 constexpr int MIXED_SWEEPS = 1, MIXED_STEPS = 10, MIXED_REFINED = 1; // step 4m's Gauss-Seidel sweeps, its Newton steps, and those of them that start from a residual in twice the precision
+// A group with a damped member (mh_bank_render_damped_groups; contract in modalhip.h, step 4g).  What its entries take
+// beyond MixedArgs, by the caller's junction index: l in the bank's precision, the carry that came in and where the one that goes out is
+// written (where the host reads it).
+template<typename Real> struct DampedGroupArgs : MixedArgs<Real> {
+    const Real *damping, *carry_in;
+    Real *carry_out;
+};
+constexpr int DAMPED_SWEEPS = 1, DAMPED_STEPS = 8, DAMPED_REFINED = 2; // step 4g's counts, as step 4m's
 // a + b and a b as the rounded result and its rounding error, both exact (Knuth's six operations; one fused multiply-add).
 template<typename Real> __device__ __forceinline__ Real two_sum(Real a, Real b, Real &err) {
     const Real s = a + b, bb = s - a;
@@ -875,6 +883,36 @@ template<typename Real> __device__ __forceinline__ Real mixed_alone(Real x, Real
     }
     return bilateral || x > Real(0) ? x / (Real(1) + c) : x;
 }
+// Step 4g, a damped member alone: the root y of y + c phi(y) max(1 + l (y - y_p), 0) = x by step 4d's trees -- damped_force's up to y, the
+// force left to the caller, so that nothing of it lives across the group's Newton loop.  cl = c l.
+template<typename Real> __device__ __forceinline__ Real damped_root(Real x, Real c, Real c15, Real cl, Real l, Real yp, bool hertz) {
+    if (!(x > Real(0))) return x; // open, or a NaN
+    if (!(Real(1) + l * (x - yp) > Real(0))) return x; // below the clamp's kink
+    const Real m0 = Real(1) - l * yp;
+    if (!hertz) {
+        const Real b = Real(1) + c * m0;
+        const Real r = sqrt_real(b * b + (Real(4) * cl) * x);
+        return min_real(x, b >= Real(0) ? (Real(2) * x) / (b + r) : (r - b) / (Real(2) * cl));
+    }
+    const Real big = std::numeric_limits<Real>::max();
+    const Real p5 = cl > Real(0) ? exp2_real(Real(0.4) * log2_real(x / cl)) : big;
+    Real y;
+    if (m0 >= Real(0)) {
+        const Real cm = c * m0, t = cbrt_real(x / cm);
+        const Real g = cm > Real(0) ? t * t : big;
+        y = min_real(min_real(x, g), p5);
+    } else {
+        const Real ylo = -m0 / l;
+        const Real lin = x / ((cl * ylo) * sqrt_real(ylo));
+        y = min_real(x, ylo + min_real(lin, p5));
+    }
+#pragma unroll
+    for (int step = 0; step < 6; ++step) {
+        const Real r = sqrt_real(y), m = Real(1) + l * (y - yp), q = (c * y) * r;
+        y = y - ((y + q * m) - x) / ((Real(1) + (c15 * r) * m) + q * l);
+    }
+    return y;
+}
 // Step 4m, the laws: phi(y) and phi'(y) of a member.
 template<typename Real> __device__ __forceinline__ void mixed_law(Real y, bool hertz, bool bilateral, Real &phi, Real &dphi) {
     const Real pos = y > Real(0) ? y : Real(0);
@@ -887,12 +925,165 @@ template<typename Real> __device__ __forceinline__ void mixed_law(Real y, bool h
         dphi = bilateral || y > Real(0) ? Real(1) : Real(0);
     }
 }
+// A value that is the same bits in every lane, handed to the compiler as such (it then lives in scalar registers): what a group's block
+// keeps for step 4g -- C, K, C_jj K_j, l -- is wave-uniform, and so are x and y_p of every frame.
+__device__ __forceinline__ float wave_uniform(float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); }
+__device__ __forceinline__ double wave_uniform(double v) {
+    const uint64_t bits = __builtin_bit_cast(uint64_t, v);
+    const uint32_t lo = __builtin_amdgcn_readfirstlane(uint32_t(bits)), hi = __builtin_amdgcn_readfirstlane(uint32_t(bits >> 32));
+    return __builtin_bit_cast(double, uint64_t(hi) << 32 | lo);
+}
+// Step 4g (modalhip.h, mh_bank_render_damped_groups): what a group with a damped member keeps for the block, all of it wave-uniform.
+template<typename Real> struct DampedGroup {
+    Real c[GROUP][GROUP], k[GROUP], ck[GROUP], ck15[GROUP], lam[GROUP]; // C, K, ck_jj = C_jj K_j, 1.5 ck_jj, l (0 on a member that is not damped)
+    uint32_t hertz, bilateral, damped; // bit masks over the members
+};
+// Step 4g of one frame: step 4m's tree -- each member alone, DAMPED_SWEEPS Gauss-Seidel sweeps, DAMPED_STEPS Newton steps, the last
+// DAMPED_REFINED from a residual in twice the precision, the residual test -- with the damped law on the damped members.  known: the
+// damped members with a history (the others take l = 0, y_p = 0); y_prev: y_p in, the compression this frame's solve left out.  Returns
+// whether the residual test is met; f: the forces of the last y.  The same bits in every lane.
+template<typename Real> __device__ __forceinline__ bool damped_group_solve(const DampedGroup<Real> &g, const Real (&x)[GROUP], uint32_t known, Real (&y_prev)[GROUP], Real (&f)[GROUP]) {
+    const Real zero = 0;
+    Real y[GROUP], kd[GROUP], F[GROUP], l_now[GROUP]; // kd: df / dy; l_now: what this frame's solve takes of l
+#pragma unroll
+    for (uint32_t j = 0; j < GROUP; ++j) l_now[j] = (known >> j & 1u) ? g.lam[j] : zero;
+    auto law = [&](uint32_t j) {
+        Real phi, dphi;
+        mixed_law(y[j], g.hertz >> j & 1u, g.bilateral >> j & 1u, phi, dphi);
+        f[j] = g.k[j] * phi;
+        kd[j] = g.k[j] * dphi;
+        if (g.damped >> j & 1u) { // f = (K phi) m, f' = (K phi') m + (K phi) l for m = 1 + l (y - y_p) > 0; else +0 and 0
+            const Real m = Real(1) + l_now[j] * (y[j] - y_prev[j]), kp = f[j];
+            const bool closed = m > Real(0);
+            kd[j] = closed ? kd[j] * m + kp * l_now[j] : zero;
+            f[j] = closed ? kp * m : zero;
+        }
+        f[j] = wave_uniform(f[j]), kd[j] = wave_uniform(kd[j]); // (the iterate lives in scalar registers between the steps: the wave's gains keep their vector registers)
+    };
+    auto alone = [&](uint32_t j, Real xs) {
+        if (g.damped >> j & 1u) return damped_root(xs, g.ck[j], g.ck15[j], g.ck[j] * l_now[j], l_now[j], y_prev[j], (g.hertz >> j & 1u) != 0);
+        return mixed_alone(xs, g.ck[j], g.ck15[j], g.hertz >> j & 1u, g.bilateral >> j & 1u);
+    };
+#pragma unroll
+    for (uint32_t j = 0; j < GROUP; ++j) y[j] = zero, f[j] = zero, kd[j] = zero;
+    // pass -1 is the start, each member alone at x_j; the sweeps follow in the same loop, so that the members' trees are compiled once
+#pragma unroll 1
+    for (int sweep = -1; sweep < DAMPED_SWEEPS; ++sweep) {
+#pragma unroll
+        for (uint32_t j = 0; j < GROUP; ++j) {
+            Real acc = 0;
+#pragma unroll
+            for (uint32_t i = 0; i < GROUP; ++i)
+                if (i != j) acc = acc + g.c[j][i] * f[i];
+            y[j] = wave_uniform(alone(j, wave_uniform(sweep < 0 ? x[j] : x[j] - acc)));
+            law(j);
+            __builtin_amdgcn_sched_barrier(0); // one member's tree at a time: their temporaries are not to be live side by side
+        }
+    }
+    // F_i = (y_i + sum_j C_ij f_j) - x_i; twice: the sum carried in twice the working precision (step 4m's)
+    auto residual = [&](bool twice) {
+#pragma unroll
+        for (uint32_t i = 0; i < GROUP; ++i) {
+            if (!twice) {
+                Real acc = 0;
+#pragma unroll
+                for (uint32_t j = 0; j < GROUP; ++j) acc = acc + g.c[i][j] * f[j];
+                F[i] = wave_uniform((y[i] + acc) - x[i]);
+            } else {
+                Real sum = y[i], low = 0, r, e;
+#pragma unroll
+                for (uint32_t j = 0; j < GROUP; ++j) {
+                    const Real p = two_product(g.c[i][j], f[j], e);
+                    sum = two_sum(sum, p, r);
+                    low = low + (r + e);
+                }
+                sum = two_sum(sum, -x[i], r);
+                low = low + r;
+                F[i] = wave_uniform(sum + low);
+            }
+        }
+    };
+    residual(DAMPED_STEPS <= DAMPED_REFINED);
+#pragma unroll 1
+    for (int step = 0; step < DAMPED_STEPS; ++step) {
+        // J = I + C diag(kd), eliminated without pivoting in ascending order; back substitution in descending order (step 4m's)
+        Real Jm[GROUP][GROUP], r[GROUP], d[GROUP];
+#pragma unroll
+        for (uint32_t i = 0; i < GROUP; ++i) {
+#pragma unroll
+            for (uint32_t j = 0; j < GROUP; ++j) Jm[i][j] = i == j ? Real(1) + g.c[i][j] * kd[j] : g.c[i][j] * kd[j];
+            r[i] = F[i];
+        }
+#pragma unroll
+        for (uint32_t p = 0; p < GROUP; ++p) {
+            const Real inv = Real(1) / Jm[p][p];
+#pragma unroll
+            for (uint32_t j = p + 1; j < GROUP; ++j) Jm[p][j] = Jm[p][j] * inv;
+            r[p] = r[p] * inv;
+#pragma unroll
+            for (uint32_t i = p + 1; i < GROUP; ++i) {
+                const Real t = Jm[i][p];
+#pragma unroll
+                for (uint32_t j = p + 1; j < GROUP; ++j) Jm[i][j] = Jm[i][j] - t * Jm[p][j];
+                r[i] = r[i] - t * r[p];
+            }
+        }
+#pragma unroll
+        for (int p = int(GROUP) - 1; p >= 0; --p) {
+            Real acc = r[p];
+#pragma unroll
+            for (int j = p + 1; j < int(GROUP); ++j) acc = acc - Jm[p][j] * d[j];
+            d[p] = acc;
+        }
+        // a unilateral member that was open or clamped (kd = 0), or whose step more than doubles y, takes its own tree at its row's
+        // linearised right-hand side instead: from below the root Newton's iteration on a convex law lands far above it and creeps
+        // back.  Not in the refined steps.
+#pragma unroll
+        for (uint32_t j = 0; j < GROUP; ++j) {
+            Real moved = y[j] - d[j];
+            if (step < DAMPED_STEPS - DAMPED_REFINED && !(g.bilateral >> j & 1u) && (kd[j] == zero || moved > Real(2) * y[j]))
+                moved = alone(j, wave_uniform(moved + g.c[j][j] * (f[j] + kd[j] * (moved - y[j]))));
+            y[j] = wave_uniform(moved);
+            law(j);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        residual(step + 1 >= DAMPED_STEPS - DAMPED_REFINED);
+    }
+    // the residual test: |F_i| against 32 u (|y_i| + sum_j |C_ij| s_j + |x_i|), s_j = K phi(y) (1 + l (|y| + |y_p|)) on a damped member, |f_j| on every other
+    Real size[GROUP];
+#pragma unroll
+    for (uint32_t j = 0; j < GROUP; ++j) {
+        size[j] = __builtin_fabs(f[j]);
+        if (g.damped >> j & 1u) {
+            Real phi, dphi;
+            mixed_law(y[j], g.hertz >> j & 1u, false, phi, dphi);
+            size[j] = (g.k[j] * phi) * (Real(1) + l_now[j] * (__builtin_fabs(y[j]) + __builtin_fabs(y_prev[j])));
+        }
+    }
+    bool met = true;
+#pragma unroll
+    for (uint32_t i = 0; i < GROUP; ++i) {
+        Real acc = 0;
+#pragma unroll
+        for (uint32_t j = 0; j < GROUP; ++j) acc = acc + __builtin_fabs(g.c[i][j]) * size[j];
+        const Real mag = (__builtin_fabs(y[i]) + acc) + __builtin_fabs(x[i]);
+        met = met && __builtin_fabs(F[i]) <= (Real(32) * (std::numeric_limits<Real>::epsilon() * Real(0.5))) * mag;
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < GROUP; ++j)
+        if (g.damped >> j & 1u) y_prev[j] = wave_uniform(y[j]);
+    return met;
+}
 // OBSERVE = true (k_bank_modes_grouped_observed<Real>): the entry of mh_bank_render_observed, with the taps of the coupled kernel's.
 // MIXED = true (k_bank_modes_grouped_mixed<Real>, ..._mixed_observed<Real>): the entries of mh_bank_render_mixed for the groups with a Hertz
 // member -- step 4 is step 4m, the same solve in every lane of every wave (its inputs are the same bits everywhere), no subset per lane,
 // no ballot; what the block keeps is C in registers, J is rebuilt from it every Newton step.  The parameter type depends on
 // MIXED, and the enumeration's matrix W is not formed: the other entries are what they were.
-template<typename Real, bool OBSERVE = false, bool MIXED = false> __global__ void __launch_bounds__(JUNCTION_WAVES *WAVE) k_bank_modes_grouped(BANK_MODES_PARAMS, JunctionArgs<Real, std::conditional_t<MIXED, MixedArgs<Real>, GroupedArgs<Real>>, OBSERVE> ga) { // (`waves`: the main launch's, not read here)
+// DAMPED = true, with MIXED (k_bank_modes_grouped_damped<Real>, ..._damped_observed<Real>): the entries of mh_bank_render_damped_groups for
+// the groups with a damped member -- step 4 is step 4g: step 4m's tree with the damped law on the damped members, y_p per member in
+// registers from frame to frame, the carries written once after the loop.  No barrier, LDS slot or global access per frame beyond step 4m's.
+template<typename Real, bool OBSERVE = false, bool MIXED = false, bool DAMPED = false> __global__ void __launch_bounds__(JUNCTION_WAVES *WAVE) k_bank_modes_grouped(BANK_MODES_PARAMS, JunctionArgs<Real, std::conditional_t<DAMPED, DampedGroupArgs<Real>, std::conditional_t<MIXED, MixedArgs<Real>, GroupedArgs<Real>>>, OBSERVE> ga) { // (`waves`: the main launch's, not read here)
+    static_assert(!DAMPED || MIXED, "the damped entry is the mixed entry plus the damped law");
     typedef PairOf<Real> Pair;
     constexpr uint32_t TS = coupled_tile<Real>();
     extern __shared__ __attribute__((aligned(16))) unsigned char grouped_mem[];
@@ -912,15 +1103,25 @@ template<typename Real, bool OBSERVE = false, bool MIXED = false> __global__ voi
     uint32_t on = 0, place[GROUP] = {}, bilateral = 0, hertz = 0;
     Pair a[GROUP] = {}, g_im[GROUP] = {}, g_re[GROUP] = {};
     Real k[GROUP] = {};
+    uint32_t damped = 0, known = 0; // step 4g: the damped members, and those of them with a history
+    Real lam[GROUP] = {}, y_prev[GROUP] = {}; // their l and y_p (0 without history)
 #pragma unroll
     for (uint32_t i = 0; i < GROUP; ++i) {
         if (i >= n) continue;
         const GroupMemberDev<Real> *M = G->member + i;
         const uint32_t sa = M->slot[0], sb = M->slot[1], waves_a = G->waves[sa];
         k[i] = M->k;
+        if constexpr (DAMPED) k[i] = wave_uniform(k[i]);
         if (M->flags & MH_JUNCTION_BILATERAL) bilateral |= 1u << i;
         if constexpr (MIXED)
             if (M->flags & MH_JUNCTION_HERTZ) hertz |= 1u << i;
+        if constexpr (DAMPED)
+            if (M->flags & MH_JUNCTION_DAMPED) {
+                damped |= 1u << i;
+                lam[i] = wave_uniform(ga.damping[M->row]);
+                const Real came = wave_uniform(ga.carry_in[M->row]), top = std::numeric_limits<Real>::max();
+                if (came >= -top && came <= top) y_prev[i] = came, known |= 1u << i; // a finite carry: there is a history
+            }
         if (!active || (sa != slot && sb != slot)) continue;
         const uint32_t sd = sa == slot ? 0u : 1u;
         on |= 1u << i;
@@ -939,11 +1140,12 @@ template<typename Real, bool OBSERVE = false, bool MIXED = false> __global__ voi
     on = __builtin_amdgcn_readfirstlane(on);
     // the object's force rows, as in the coupled kernel
     const uint32_t i0 = imp_ptr[dealt], n_imp = active ? imp_ptr[dealt + 1] - i0 : 0u;
+    constexpr uint32_t REG_ROWS = DAMPED ? 0u : IMP_REG; // (step 4g's entries keep every row's gains in the scratch rows: the registers go to the members' gains)
     Pair g_reg[IMP_REG] = {};
     Real *g_mem = gain_scratch + size_t(G->first_wave + wave) * max_imp * MODES_PER_WAVE;
     for (uint32_t t = 0; t < n_imp; ++t) {
         const Pair g = row_gain(b, w, impacts[imp_idx[i0 + t]]);
-        if (t < IMP_REG) g_reg[t] = g;
+        if (t < REG_ROWS) g_reg[t] = g;
         else *reinterpret_cast<Pair *>(g_mem + size_t(t) * MODES_PER_WAVE + 2 * lane) = g;
     }
     // one sum per member over that member's modes: the lane's part -> the wave (DPP tree) -> the member's waves in its order from +0; the
@@ -995,8 +1197,13 @@ template<typename Real, bool OBSERVE = false, bool MIXED = false> __global__ voi
             if (i < n && j < n) numbers_ok = numbers_ok && col[i] >= -most && col[i] <= most && kc >= -most && kc <= most;
             if constexpr (MIXED) {
                 W[i][j] = col[i]; // step 4m keeps C alone
+                if constexpr (DAMPED) W[i][j] = wave_uniform(col[i]); // (step 4g keeps it in scalar registers from here on)
                 const Real range = sqrt_real(most); // and J multiplies two entries: |C_ij K_j| within the square root of the largest number
                 if (i < n && j < n) numbers_ok = numbers_ok && kc >= -range && kc <= range;
+                if constexpr (DAMPED) { // and kd_j = K_j (phi' m + phi l_j): |C_ij K_j l_j| within it as well
+                    const Real kcl = kc * lam[j];
+                    if (i < n && j < n && (damped >> j & 1u)) numbers_ok = numbers_ok && kcl >= -range && kcl <= range;
+                }
             }
             if constexpr (!MIXED) W[i][j] = (mask >> i & 1u) ? ((mask >> j & 1u) ? (i == j ? Real(1) + kc : kc) : zero) : col[i];
             if (i == j) c_own[i] = col[i];
@@ -1010,8 +1217,13 @@ template<typename Real, bool OBSERVE = false, bool MIXED = false> __global__ voi
         for (uint32_t i = 0; i < GROUP; ++i) {
             ckd[i] = W[i][i] * k[i];
             ck15[i] = Real(1.5) * ckd[i];
+            if constexpr (DAMPED) ckd[i] = wave_uniform(ckd[i]), ck15[i] = wave_uniform(ck15[i]);
             const Real denom = Real(1) + ckd[i];
             if (i < n) pivots_ok = pivots_ok && ((hertz >> i & 1u) ? (W[i][i] >= Real(0) && ckd[i] >= Real(0)) : (denom > Real(0) && denom <= most));
+            if constexpr (DAMPED) { // a damped member: C_ii, C_ii K_i and C_ii K_i l_i not below 0, as in step 4d
+                const Real cl = ckd[i] * lam[i];
+                if (i < n && (damped >> i & 1u)) pivots_ok = pivots_ok && W[i][i] >= Real(0) && ckd[i] >= Real(0) && cl >= Real(0) && cl <= most;
+            }
         }
     }
 #pragma unroll
@@ -1035,6 +1247,18 @@ template<typename Real, bool OBSERVE = false, bool MIXED = false> __global__ voi
     }
     const bool solved = numbers_ok && (MIXED ? pivots_ok : __builtin_amdgcn_ballot_w64(admissible && !pivots_ok) == 0);
     uint32_t unconverged = 0; // step 4m: frames of the block that failed the residual test
+    DampedGroup<Real> dg; // step 4g: the block's constants as wave-uniform values
+    if constexpr (DAMPED) {
+#pragma unroll
+        for (uint32_t i = 0; i < GROUP; ++i) {
+#pragma unroll
+            for (uint32_t j = 0; j < GROUP; ++j) dg.c[i][j] = wave_uniform(W[i][j]);
+            dg.k[i] = wave_uniform(k[i]), dg.ck[i] = wave_uniform(ckd[i]), dg.ck15[i] = wave_uniform(ck15[i]), dg.lam[i] = wave_uniform(lam[i]);
+            y_prev[i] = wave_uniform(y_prev[i]);
+        }
+        dg.hertz = __builtin_amdgcn_readfirstlane(hertz), dg.bilateral = __builtin_amdgcn_readfirstlane(bilateral), dg.damped = __builtin_amdgcn_readfirstlane(damped);
+        known = __builtin_amdgcn_readfirstlane(known);
+    }
     if (threadIdx.x == 0)
         for (uint32_t i = 0; i < n; ++i) {
             ga.compliance_out[G->member[i].row] = double(c_own[i]);
@@ -1045,16 +1269,17 @@ template<typename Real, bool OBSERVE = false, bool MIXED = false> __global__ voi
     for (uint32_t s0 = 0; s0 < frames; s0 += TS) {
         const uint32_t sn = min(TS, frames - s0);
         // this tile's approach samples, lane = sample (not finite: 0, as a drive's)
-        Real u_tile[GROUP] = {};
+        using Approach = std::conditional_t<DAMPED, float, Real>; // (step 4g's entries keep the approach as the float it came as: the same bits once widened, half the registers in fp64)
+        Approach u_tile[GROUP] = {};
 #pragma unroll
         for (uint32_t i = 0; i < GROUP; ++i)
-            if (i < n && lane < sn) u_tile[i] = finite_or_zero<Real>(ga.approach[size_t(G->member[i].row) * frames + s0 + lane]);
+            if (i < n && lane < sn) u_tile[i] = finite_or_zero<Approach>(ga.approach[size_t(G->member[i].row) * frames + s0 + lane]);
         // the tile's excitation, parked where the output terms will go
         for (uint32_t ds = 0; ds < sn; ++ds) {
             Pair excite = {0, 0};
             for (uint32_t t = 0; t < n_imp; ++t) {
                 const Real f = force[size_t(imp_idx[i0 + t]) * frames + s0 + ds];
-                excite += f * (t < IMP_REG ? g_reg[t] : *reinterpret_cast<const Pair *>(g_mem + size_t(t) * MODES_PER_WAVE + 2 * lane));
+                excite += f * (t < REG_ROWS ? g_reg[t] : *reinterpret_cast<const Pair *>(g_mem + size_t(t) * MODES_PER_WAVE + 2 * lane));
             }
             *reinterpret_cast<Pair *>(s_term + ds * PITCH + 2 * lane) = excite;
         }
@@ -1069,9 +1294,19 @@ template<typename Real, bool OBSERVE = false, bool MIXED = false> __global__ voi
                 mine[i] = fma_real(g_re[i].y, re.y, fma_real(g_im[i].y, w.z_im.y, fma_real(g_re[i].x, re.x, fma_real(g_im[i].x, w.z_im.x, zero))));
             member_sums(mine, (s0 + ds) & 1u, d);
 #pragma unroll
-            for (uint32_t i = 0; i < GROUP; ++i) x[i] = lane_bcast(u_tile[i], ds) - d[i];
+            for (uint32_t i = 0; i < GROUP; ++i) x[i] = Real(lane_bcast(u_tile[i], ds)) - d[i];
             Real f_now[GROUP];
-            if constexpr (MIXED) {
+            if constexpr (DAMPED) {
+                // step 4g (modalhip.h): damped_group_solve; y_p and the history mask go from frame to frame in registers
+                Real xs[GROUP], f[GROUP];
+#pragma unroll
+                for (uint32_t i = 0; i < GROUP; ++i) xs[i] = wave_uniform(x[i]);
+                const bool met = damped_group_solve(dg, xs, known, y_prev, f);
+                known = dg.damped;
+                if (solved && !met) ++unconverged;
+#pragma unroll
+                for (uint32_t i = 0; i < GROUP; ++i) f_now[i] = solved ? f[i] : zero;
+            } else if constexpr (MIXED) {
                 // step 4m (modalhip.h): each member alone, MIXED_SWEEPS Gauss-Seidel sweeps, MIXED_STEPS Newton steps, the residual test
                 Real y[GROUP], f[GROUP], kd[GROUP], F[GROUP]; // kd: K phi'
                 auto law = [&](uint32_t j) {
@@ -1244,11 +1479,17 @@ template<typename Real, bool OBSERVE = false, bool MIXED = false> __global__ voi
     if constexpr (MIXED)
         if (threadIdx.x == 0)
             for (uint32_t i = 0; i < n; ++i) ga.unconverged_out[G->member[i].row] = unconverged;
+    if constexpr (DAMPED)
+        if (threadIdx.x == 0)
+            for (uint32_t i = 0; i < n; ++i)
+                if (damped >> i & 1u) ga.carry_out[G->member[i].row] = y_prev[i]; // (the host hands it on only for a solved group)
     store_wave(b, w, lane, chunk_energy);
 }
 template<typename Real> constexpr auto k_bank_modes_grouped_observed = &k_bank_modes_grouped<Real, true>;
 template<typename Real> constexpr auto k_bank_modes_grouped_mixed = &k_bank_modes_grouped<Real, false, true>;
 template<typename Real> constexpr auto k_bank_modes_grouped_mixed_observed = &k_bank_modes_grouped<Real, true, true>;
+template<typename Real> constexpr auto k_bank_modes_grouped_damped = &k_bank_modes_grouped<Real, false, true, true>;
+template<typename Real> constexpr auto k_bank_modes_grouped_damped_observed = &k_bank_modes_grouped<Real, true, true, true>;
 #undef BANK_MODES_PARAMS
 #undef BANK_MODES_ARGS
 // The partial rows of the pickups on junction objects (mh_bank_render_observed), from the states the tapped waves stored: one wave per
@@ -1539,6 +1780,7 @@ template<typename Real> struct BankImpl {
     std::vector<uint32_t> kept_rows; // the caller's indices of those junctions
     std::vector<uint32_t> mixed_rows; // mh_bank_render_mixed: those of them that are members of a group with a Hertz member
     std::vector<GroupDev<Real>> mixed_groups; // and those groups, until they take their place behind the other groups
+    std::vector<GroupDev<Real>> damped_groups; // mh_bank_render_damped_groups: the groups with a damped member, which follow those (their members are in mixed_rows too)
     // per-block scratch
     Arena arena;
     DevArray<Real> force, click, partial, chunk_energy, gain_scratch, rout;
@@ -1580,9 +1822,10 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
                  void *out_v, double *object_energy, uint32_t *object_live, uint8_t *object_silenced, double *object_modal_energy, uint32_t n_drives,
                  const mh_drive *drives, const float *signals, uint32_t n_pickups, const mh_pickup *pickups, void *pickup_out_v, uint8_t *pickup_read,
                  uint32_t n_junctions, const mh_junction *junctions, const float *approach, void *force_out_v, double *compliance_out, uint8_t *status_out,
-                 const float *damping, void *carry_v, bool observe, uint32_t *unconverged_out) { // damping, carry_v: mh_bank_render_damped's; both null in every other entry (MH_JUNCTION_DAMPED is ignored then)
+                 const float *damping, void *carry_v, bool observe, uint32_t *unconverged_out, bool damped_in_groups) { // damping, carry_v: mh_bank_render_damped's; both null in every other entry (MH_JUNCTION_DAMPED is ignored then)
     // observe: mh_bank_render_observed -- a pickup on a kept junction's object is read
     // unconverged_out: mh_bank_render_mixed -- a Hertz junction may join a group (step 4m); null in every other entry
+    // damped_in_groups: mh_bank_render_damped_groups -- the mixed entry in which a damped junction may join a group as well (step 4g)
     const bool mixed = unconverged_out != nullptr;
     mh_context *ctx = B.ctx;
     hipStream_t st = ctx->stream;
@@ -1630,8 +1873,10 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
     uint32_t n_coupled = 0, coupled_waves = 0, widest_junction = 0;
     uint32_t n_groups = 0, widest_group = 0, grouped_members = 0; // components of two or more junctions: k_bank_modes_grouped, one workgroup each
     uint32_t n_mixed = 0, widest_mixed = 0, mixed_members = 0; // those of them with a Hertz member (mh_bank_render_mixed): the entries with step 4m; they follow the others in the list
+    uint32_t n_damped_groups = 0, widest_damped = 0, damped_members = 0; // and those with a damped member (mh_bank_render_damped_groups): the entries with step 4g; they come last
     B.mixed_rows.clear();
     B.mixed_groups.clear();
+    B.damped_groups.clear();
     bool any_hertz = false; // a kept junction with MH_JUNCTION_HERTZ: the call takes the entry that has the solve
     bool any_damped = false; // a kept junction with MH_JUNCTION_DAMPED: the entry that has both solves and the carry
     const uint32_t flag_mask = damping ? ~0u : ~uint32_t(MH_JUNCTION_DAMPED);
@@ -1661,7 +1906,7 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
             if (m.flags & flag_mask & MH_JUNCTION_DAMPED) { // the damped law is unilateral too, and its l a finite number from 0 up
                 if ((m.flags & MH_JUNCTION_BILATERAL) || !std::isfinite(damping[j]) || damping[j] < 0) continue;
             }
-            if (grouping.add(j, m.flags & flag_mask, m.a.object, side_waves(m.a), m.b.object, two_sided ? side_waves(m.b) : 0u, mixed) < 0) continue;
+            if (grouping.add(j, m.flags & flag_mask, m.a.object, side_waves(m.a), m.b.object, two_sided ? side_waves(m.b) : 0u, mixed, damped_in_groups) < 0) continue;
             B.on_junction[m.a.object] = 1;
             if (two_sided) B.on_junction[m.b.object] = 1;
             B.kept_rows.push_back(j);
@@ -1707,6 +1952,14 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
             }
             if (g.n_waves > JUNCTION_WAVES) mh_throw(MH_EINVAL, "a junction group of %u waves", g.n_waves); // (the grouping admits none)
             coupled_waves += g.n_waves;
+            if (comp.damped) { // (a group has a damped member through mh_bank_render_damped_groups only)
+                B.damped_groups.push_back(g);
+                ++n_damped_groups;
+                damped_members += g.n;
+                widest_damped = std::max(widest_damped, g.n_waves);
+                B.mixed_rows.insert(B.mixed_rows.end(), comp.members.begin(), comp.members.end());
+                continue;
+            }
             if (comp.hertz) { // parked until the others are known
                 B.mixed_groups.push_back(g);
                 ++n_mixed;
@@ -1720,8 +1973,9 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
             widest_group = std::max(widest_group, g.n_waves);
         }
         std::copy(B.mixed_groups.begin(), B.mixed_groups.end(), gd + n_groups);
+        std::copy(B.damped_groups.begin(), B.damped_groups.end(), gd + n_groups + n_mixed);
     }
-    const bool any_junction = n_coupled || n_groups || n_mixed;
+    const bool any_junction = n_coupled || n_groups || n_mixed || n_damped_groups;
     chunk_base[0] = 0;
     uint32_t main_waves = 0; // the main launch's waves: every dealt object that is not on a junction's side
     for (uint32_t d = 0; d < n_dealt; ++d) {
@@ -1827,7 +2081,7 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
                 if (jd[j].side[1].waves) tap_object(jd[j].side[1].dealt, jd[j].first_wave + jd[j].side[0].waves, jd[j].side[1].waves);
             }
             const GroupDev<Real> *gd = A.h<GroupDev<Real>>(o_groups);
-            for (uint32_t g = 0; g < n_groups + n_mixed; ++g)
+            for (uint32_t g = 0; g < n_groups + n_mixed + n_damped_groups; ++g)
                 for (uint32_t o = 0; o < gd[g].n_objects; ++o) tap_object(gd[g].dealt[o], gd[g].first_wave + gd[g].wave0[o], gd[g].waves[o]);
         }
     }
@@ -1854,7 +2108,7 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
     }
     if (n_drives) std::copy(signals, signals + size_t(n_drives) * frames, A.h<float>(o_signals));
     if (any_junction) std::copy(approach, approach + size_t(n_junctions) * frames, A.h<float>(o_approach));
-    if (any_damped) {
+    if (any_damped || n_damped_groups) {
         std::copy(damping, damping + n_junctions, A.h<Real>(o_damping));
         std::copy(static_cast<const Real *>(carry_v), static_cast<const Real *>(carry_v) + n_junctions, A.h<Real>(o_carry_in));
     }
@@ -1952,6 +2206,25 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
                 launch_modes(k_bank_modes_grouped_mixed_observed<Real>, n_mixed, widest_mixed * WAVE, grouped_lds<Real>(widest_mixed), B.junction_gain, oa);
             } else {
                 launch_modes(k_bank_modes_grouped_mixed<Real>, n_mixed, widest_mixed * WAVE, grouped_lds<Real>(widest_mixed), B.junction_gain, ma);
+            }
+        }
+        if (n_damped_groups) { // the groups with a damped member (mh_bank_render_damped_groups): the entries with step 4g, one workgroup per group
+            ensure(ctx, B.junction_gain, size_t(coupled_waves + JUNCTION_WAVES) * max_imp * MODES_PER_WAVE);
+            static PerDeviceOnce attr;
+            attr.run(ctx->device, [] {
+                HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_bank_modes_grouped_damped<Real>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+                HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_bank_modes_grouped_damped_observed<Real>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            });
+            if (grouped_lds<Real>(widest_damped) > 160 * 1024) mh_throw(MH_EINVAL, "a junction group of %u waves", widest_damped); // (none is kept)
+            const DampedGroupArgs<Real> da{{{B.defl_gain, A.d<GroupDev<Real>>(o_groups) + n_groups + n_mixed, A.d<float>(o_approach), A.hd<Real>(o_junction_force), A.hd<double>(o_compliance), A.hd<uint32_t>(o_status)}, A.hd<uint32_t>(o_unconverged)},
+                                           A.d<Real>(o_damping), A.d<Real>(o_carry_in), A.hd<Real>(o_carry_out)};
+            TimedLaunch timed(ctx, MH_KERNEL_JUNCTION, double(damped_members) * double(frames));
+            if (n_taps) {
+                ensure(ctx, B.tap_states, size_t(n_taps) * frames * TAP_FRAME);
+                const ObservedArgs<Real, DampedGroupArgs<Real>> oa{da, A.d<uint32_t>(o_tap_of), B.tap_states};
+                launch_modes(k_bank_modes_grouped_damped_observed<Real>, n_damped_groups, widest_damped * WAVE, grouped_lds<Real>(widest_damped), B.junction_gain, oa);
+            } else {
+                launch_modes(k_bank_modes_grouped_damped<Real>, n_damped_groups, widest_damped * WAVE, grouped_lds<Real>(widest_damped), B.junction_gain, da);
             }
         }
         if (n_taps) { // the tapped waves' partial rows, in k_bank_modes_read's order; they join read_rows ahead of k_bank_read_rows
@@ -2174,7 +2447,7 @@ static int render_junctions(mh_bank *bank, uint32_t frames, float click_gain, ui
                             void *out, double *object_energy, uint32_t *object_live, uint8_t *object_silenced, double *object_modal_energy, uint32_t n_drives,
                             const mh_drive *drives, const float *signals, uint32_t n_pickups, const mh_pickup *pickups, void *pickup_out, uint8_t *pickup_read,
                             uint32_t n_junctions, const mh_junction *junctions, const float *approach, void *force_out, double *compliance_out, uint8_t *status_out,
-                            const float *damping, void *carry, bool observe = false, uint32_t *unconverged_out = nullptr) {
+                            const float *damping, void *carry, bool observe = false, uint32_t *unconverged_out = nullptr, bool damped_in_groups = false) {
     if (!bank || !out || (n_impacts && !impacts) || (n_renderers && !deal_offset) || !out_gain || !listener_gain || (n_drives && (!drives || !signals))) return MH_EINVAL;
     if (n_pickups && (!pickups || !pickup_out || !pickup_read)) return MH_EINVAL;
     if (n_junctions && (!junctions || !approach || !force_out || !compliance_out || !status_out)) return MH_EINVAL;
@@ -2186,7 +2459,7 @@ static int render_junctions(mh_bank *bank, uint32_t frames, float click_gain, ui
         auto go = [&](auto &B) {
             render_impl(B, frames, click_gain, n_impacts, impacts, n_renderers, deal_offset, deal_objects, render_count, tuned_count, out_gain, listener_gain, out, object_energy,
                         object_live, object_silenced, object_modal_energy, n_drives, drives, signals, n_pickups, pickups, pickup_out, pickup_read, n_junctions, junctions, approach,
-                        force_out, compliance_out, status_out, damping, carry, observe, unconverged_out);
+                        force_out, compliance_out, status_out, damping, carry, observe, unconverged_out, damped_in_groups);
         };
         if (bank->dbl) go(*bank->d); else go(*bank->f);
         return MH_OK;
@@ -2238,6 +2511,20 @@ int mh_bank_render_mixed(mh_bank *bank, uint32_t frames, float click_gain, uint3
     return render_junctions(bank, frames, click_gain, n_impacts, impacts, n_renderers, deal_offset, deal_objects, render_count, tuned_count, out_gain, listener_gain, out, object_energy,
                             object_live, object_silenced, object_modal_energy, n_drives, drives, signals, n_pickups, pickups, pickup_out, pickup_read, n_junctions, junctions, approach,
                             force_out, compliance_out, status_out, damping ? damping : &no_damping, carry, true, unconverged_out ? unconverged_out : &no_count);
+}
+int mh_bank_render_damped_groups(mh_bank *bank, uint32_t frames, float click_gain, uint32_t n_impacts, mh_impact *impacts, uint32_t n_renderers, const uint32_t *deal_offset,
+                                 const uint32_t *deal_objects, const uint32_t *render_count, const uint32_t *tuned_count, const float *out_gain, const float *listener_gain,
+                                 void *out, double *object_energy, uint32_t *object_live, uint8_t *object_silenced, double *object_modal_energy, uint32_t n_drives,
+                                 const mh_drive *drives, const float *signals, uint32_t n_pickups, const mh_pickup *pickups, void *pickup_out, uint8_t *pickup_read,
+                                 uint32_t n_junctions, const mh_junction *junctions, const float *approach, void *force_out, double *compliance_out, uint8_t *status_out,
+                                 const float *damping, void *carry, uint32_t *unconverged_out) {
+    if (n_junctions && (!damping || !carry || !unconverged_out)) return MH_EINVAL;
+    static const float no_damping = 0; // (as in mh_bank_render_mixed)
+    static uint32_t no_count = 0;
+    if (unconverged_out) std::fill(unconverged_out, unconverged_out + n_junctions, 0u);
+    return render_junctions(bank, frames, click_gain, n_impacts, impacts, n_renderers, deal_offset, deal_objects, render_count, tuned_count, out_gain, listener_gain, out, object_energy,
+                            object_live, object_silenced, object_modal_energy, n_drives, drives, signals, n_pickups, pickups, pickup_out, pickup_read, n_junctions, junctions, approach,
+                            force_out, compliance_out, status_out, damping ? damping : &no_damping, carry, true, unconverged_out ? unconverged_out : &no_count, true);
 }
 int mh_bank_render_read(mh_bank *bank, uint32_t frames, float click_gain, uint32_t n_impacts, mh_impact *impacts, uint32_t n_renderers, const uint32_t *deal_offset,
                         const uint32_t *deal_objects, const uint32_t *render_count, const uint32_t *tuned_count, const float *out_gain, const float *listener_gain,

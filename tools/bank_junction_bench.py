@@ -72,17 +72,19 @@ def sides_of(j, sides):
     return (j,) if sides == 1 else (2 * j, 2 * j + 1)
 
 
-def measure(tree, entry, junctions, sides, objects, blocks, renderers, forces_path, save_forces, law="linear", members=0, ungrouped=False, pickups=None, mixed=False, double=False):
+def measure(tree, entry, junctions, sides, objects, blocks, renderers, forces_path, save_forces, law="linear", members=0, ungrouped=False, pickups=None, mixed=False, double=False, damped_groups=False):
     """members >= 2: the junctions are groups of `members` exciter junctions, junction q at point q % members of object q // members with
     the shared flag -- or, ungrouped, of object q without it.  pickups = P (not None): the call goes through Scene.render_observed with P
     pickups on every junction object.  mixed: with members and law = "hertz", the groups' members are Hertz junctions and the call goes through
-    Scene.render_mixed (law = "linear": the same groups with linear members through the same entry)."""
+    Scene.render_mixed (law = "linear": the same groups with linear members through the same entry).  damped_groups: the call goes through
+    Scene.render_damped_groups with the carry passed from block to block; law = "hertz-damped": every member a damped Hertz junction
+    (l x0 = 1), "hertz": the same groups with plain Hertz members through the same entry."""
     sys.path.insert(0, tree)
     from mesheditor_amd import bank as hipbank
     from tools import bank_bench
     assert junctions * sides <= objects
     if members:
-        assert entry == "coupled" and sides == 1 and (law == "linear" or (mixed and law == "hertz")) and 2 <= members <= POINTS and junctions % members == 0
+        assert entry == "coupled" and sides == 1 and (law == "linear" or (mixed and law == "hertz") or (damped_groups and law in ("hertz", "hertz-damped"))) and 2 <= members <= POINTS and junctions % members == 0
     where = lambda q: (q, 1) if not members else ((q, q % members) if ungrouped else (q // members, q % members))  # (object, point) of junction q's side a
     sc = bank_bench.build(objects, MODES, renderers) if not double else build_double(hipbank, bank_bench, objects, renderers)  # double: the fp64 bank
     out = np.zeros(BLOCK, sc.dtype)
@@ -97,6 +99,8 @@ def measure(tree, entry, junctions, sides, objects, blocks, renderers, forces_pa
             flag["damped"] = True
         if members and not ungrouped:
             flag = {"shared": True, "hertz": True} if mixed and law == "hertz" else {"shared": True}
+            if damped_groups:
+                flag = {"shared": True, "hertz": True, "damped": True} if law == "hertz-damped" else {"shared": True, "hertz": True}
         first = lambda j: side(where(j)[0], 1.0, where(j)[1]) if members else side(sides_of(j, sides)[0], 1.0)
         make = lambda k: (hipbank.Junction * max(junctions, 1))(*[hipbank.Junction.of(first(j), side(sides_of(j, sides)[1], -1.0) if sides == 2 else None, k[j], **flag)
                                                                     for j in range(junctions)])
@@ -105,7 +109,7 @@ def measure(tree, entry, junctions, sides, objects, blocks, renderers, forces_pa
         # the compliances and the size of the free deflection, from two blocks with K = 0
         comp = np.ones(junctions)
         if junctions:
-            _, _, _, comp, status = (sc.render_mixed if mixed else sc.render_coupled)(out, rows, signals, [], make([0.0] * junctions), none)[:5]
+            _, _, _, comp, status = (sc.render_damped_groups if damped_groups else sc.render_mixed if mixed else sc.render_coupled)(out, rows, signals, [], make([0.0] * junctions), none)[:5]
             assert (status == 1).all() and (comp > 0).all()
             picks = (hipbank.Pickup * junctions)(*[hipbank.Pickup.of(where(j)[0] if members else sides_of(j, sides)[0], where(j)[1], (1.0, 0.0, 0.0), NORMAL, 2.0, 1) for j in range(junctions)])
             reads, _ = sc.render_read(out, rows, signals, picks)
@@ -123,7 +127,10 @@ def measure(tree, entry, junctions, sides, objects, blocks, renderers, forces_pa
         peak_read = [0.0]
 
         def block():
-            if mixed:
+            if damped_groups:
+                _, _, forces, _, status, carry[0], unconverged = sc.render_damped_groups(out, rows, signals, [], contacts, u, damping, carry[0])
+                assert not unconverged.any()
+            elif mixed:
                 _, _, forces, _, status, _, unconverged = sc.render_mixed(out, rows, signals, [], contacts, u)
                 assert not unconverged.any()
             elif pickups is not None:
@@ -172,7 +179,7 @@ def measure(tree, entry, junctions, sides, objects, blocks, renderers, forces_pa
     sc.close()
     t = np.array(times)
     coupled_us = 1e3 * kj["total_ms"] / max(1, kj["launches"])
-    return {"precision": "fp64" if double else "fp32", "entry": "mixed" if mixed else entry if pickups is None else "observed", "pickups_per_object": pickups, "junction_kernels_us_per_block": 1e3 * kj["total_ms"] / max(1, blocks), "law": law, "junctions": junctions, "sides": sides, "members": members, "grouped": bool(members) and not ungrouped, "objects": objects, "modes_per_object": MODES, "blocks": blocks, "ms_per_block": 1e3 * float(t.mean()),
+    return {"precision": "fp64" if double else "fp32", "entry": "damped_groups" if damped_groups else "mixed" if mixed else entry if pickups is None else "observed", "pickups_per_object": pickups, "junction_kernels_us_per_block": 1e3 * kj["total_ms"] / max(1, blocks), "law": law, "junctions": junctions, "sides": sides, "members": members, "grouped": bool(members) and not ungrouped, "objects": objects, "modes_per_object": MODES, "blocks": blocks, "ms_per_block": 1e3 * float(t.mean()),
             "ms_per_block_median": 1e3 * float(np.median(t)), "ms_per_block_p99": 1e3 * float(np.quantile(t, 0.99)), "kernel_us_per_block": 1e3 * k["total_ms"] / max(1, k["launches"]),
             "coupled_kernel_us_per_block": coupled_us, "coupled_us_per_frame": coupled_us / BLOCK, "coupled_cycles_per_frame": coupled_us / BLOCK * ENGINE_MHZ,
             "real_time_ms_per_block": 1e3 * BLOCK / SR}
@@ -506,6 +513,67 @@ def compare_mixed(parent, runs, objects, blocks, renderers, out_path, all_live):
     print(json.dumps(result["summary"]))
 
 
+def compare_damped_groups(parent, runs, objects, blocks, renderers, out_path, all_live):
+    """This tree's groups of n = 2, 3, 4 damped Hertz members through Scene.render_damped_groups beside the same groups with plain Hertz
+    members through the same entry, fp32 (G = 1, 16, 64) and fp64 (G = 16); then the unchanged calls of the parent and of this tree,
+    interleaved in fresh processes -- J = 0, ungrouped J = 1, 16, 64, linear and Hertz groups through render_mixed, and tools/bank_bench.py
+    all-live: the new figures have to land within the parent's own spread.  The file is written after every row."""
+    me = os.path.abspath(__file__)
+    common = ["--objects", str(objects), "--blocks", str(blocks), "--renderers", str(renderers)]
+    result = {"workload": f"{objects} objects x {MODES} modes @48k, {BLOCK}-frame blocks, {renderers} renderers, one drive on every object in every block; G groups of n exciter "
+                          "junctions on one object each (Hertz: K C sqrt(x0) = 10; damped: l x0 = 1), or J ungrouped one-sided junctions (K C = 10)", "runs_each": runs,
+              "damped_groups": {}, "damped_groups_fp64": {}, "all_live": {"parent": [], "new": []}, "j0": {"parent": [], "new": []}, "ungrouped": {}, "linear_groups": {}, "hertz_groups": {}}
+
+    def save():
+        os.makedirs(os.path.dirname(out_path), exist_ok=True)
+        with open(out_path, "w") as f:
+            json.dump(result, f, indent=1)
+    q = subprocess.run(["timeout", "-k", "10", "300", sys.executable, "-c", "import torch; p = torch.cuda.get_device_properties(0); print(p.name, p.gcnArchName, '%d CUs' % p.multi_processor_count, '|', torch.version.hip)"], capture_output=True, text=True)
+    if q.returncode != 0:
+        raise SystemExit("no GPU to measure on: " + q.stderr[-2000:])
+    result["device"], result["hip"] = (v.strip() for v in q.stdout.strip().splitlines()[-1].split("|"))
+    med = lambda rows, key: float(np.median([r[key] for r in rows])) if rows else None
+    spread = lambda rows, key: (max(r[key] for r in rows) / min(r[key] for r in rows)) if rows else None
+    pair = lambda old, new: {"parent_ms_per_block": [r["ms_per_block"] for r in old], "new_ms_per_block": [r["ms_per_block"] for r in new], "parent_spread_max_over_min": spread(old, "ms_per_block"),
+                             "new_median_over_parent_median": (med(new, "ms_per_block") / med(old, "ms_per_block")) if old and new else None}
+    both = lambda row: {"damped_ms_per_block": med(row["damped"], "ms_per_block"), "hertz_ms_per_block": med(row["hertz"], "ms_per_block"),
+                        "damped_kernel_us_per_block": med(row["damped"], "coupled_kernel_us_per_block"), "hertz_kernel_us_per_block": med(row["hertz"], "coupled_kernel_us_per_block"),
+                        "damped_cycles_per_frame": med(row["damped"], "coupled_cycles_per_frame"), "hertz_cycles_per_frame": med(row["hertz"], "coupled_cycles_per_frame")}
+
+    def summarise():
+        result["summary"] = {"real_time_ms_per_block": 1e3 * BLOCK / SR, "damped_groups": {name: both(row) for name, row in result["damped_groups"].items()},
+                             "damped_groups_fp64": {name: both(row) for name, row in result["damped_groups_fp64"].items()},
+                             "all_live": pair(result["all_live"]["parent"], result["all_live"]["new"]), "j0": pair(result["j0"]["parent"], result["j0"]["new"]),
+                             "ungrouped": {name: pair(row["parent"], row["new"]) for name, row in result["ungrouped"].items()},
+                             "linear_groups": {name: pair(row["parent"], row["new"]) for name, row in result["linear_groups"].items()},
+                             "hertz_groups": {name: pair(row["parent"], row["new"]) for name, row in result["hertz_groups"].items()}}
+        save()
+    for _ in range(runs):
+        for double, key, groups in ((False, "damped_groups", (1, 16, 64)), (True, "damped_groups_fp64", (16,))):
+            for n in (2, 3, 4):
+                for g in groups:
+                    row = result[key].setdefault("G = %d, n = %d" % (g, n), {"damped": [], "hertz": []})
+                    extra = ["--double"] if double else []
+                    row["damped"].append(child([me, "--damped-groups", "--law", "hertz-damped", "--members", str(n), "--junctions", str(g * n)] + extra + common))
+                    row["hertz"].append(child([me, "--damped-groups", "--law", "hertz", "--members", str(n), "--junctions", str(g * n)] + extra + common))
+                    summarise()
+    for _ in range(runs):
+        for name, tree in (("parent", parent), ("new", HERE)):  # (the parent's copy of this tool measures the parent's library)
+            tool = os.path.join(tree, "tools", "bank_junction_bench.py")
+            result["j0"][name].append(child([tool, "--entry", "coupled", "--junctions", "0"] + common))
+            for j in JUNCTIONS[1:]:
+                result["ungrouped"].setdefault("J = %d" % j, {"parent": [], "new": []})[name].append(child([tool, "--junctions", str(j)] + common))
+            for n in (2, 4):
+                result["linear_groups"].setdefault("G = 16, n = %d" % n, {"parent": [], "new": []})[name].append(child([tool, "--mixed", "--members", str(n), "--junctions", str(16 * n)] + common))
+                result["hertz_groups"].setdefault("G = 16, n = %d" % n, {"parent": [], "new": []})[name].append(child([tool, "--mixed", "--law", "hertz", "--members", str(n), "--junctions", str(16 * n)] + common))
+            summarise()
+        for name, tree in (("parent", parent), ("new", HERE)) if all_live else ():
+            r = child([os.path.join(tree, "tools", "bank_bench.py")], 600)
+            result["all_live"][name].append({"ms_per_block": r["all_live"]["ms_per_block"], "kernel_us_per_block": r["all_live"]["kernel_us_per_block"]})
+            summarise()
+    print(json.dumps(result["summary"]))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--entry", choices=["coupled", "replay"], default="coupled")
@@ -527,7 +595,8 @@ def main():
     ap.add_argument("--pickups", type=int, default=None, help="coupled: through Scene.render_observed with this many pickups on every junction object (0 ... 8)")
     ap.add_argument("--observed-against", help="built checkout of the parent commit: this tree's render_observed with P pickups per junction object, and the unchanged paths of both trees -> profiles/bank_observed.json")
     ap.add_argument("--mixed", action="store_true", help="with --members: through Scene.render_mixed (--law hertz: Hertz members); with --against: the unchanged calls of both trees and this tree's groups with Hertz members -> profiles/bank_mixed.json")
-    ap.add_argument("--double", action="store_true", help="the fp64 bank (with --mixed)")
+    ap.add_argument("--double", action="store_true", help="the fp64 bank (with --mixed or --damped-groups)")
+    ap.add_argument("--damped-groups", action="store_true", help="with --members: through Scene.render_damped_groups (--law hertz-damped: damped Hertz members; --law hertz: plain ones); with --against: this tree's groups with damped members and the unchanged calls of both trees -> profiles/bank_damped_groups.json")
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--no-all-live", action="store_true", help="skip tools/bank_bench.py of both trees")
     ap.add_argument("--out", default=os.path.join(HERE, "profiles", "bank_junctions.json"))
@@ -541,6 +610,9 @@ def main():
     elif a.laws_against:
         out = a.out if a.out != ap.get_default("out") else os.path.join(HERE, "profiles", "bank_hertz.json")
         compare_laws(os.path.abspath(a.laws_against), a.runs, a.objects, a.blocks, a.renderers, out)
+    elif a.against and a.damped_groups:
+        out = a.out if a.out != ap.get_default("out") else os.path.join(HERE, "profiles", "bank_damped_groups.json")
+        compare_damped_groups(os.path.abspath(a.against), a.runs, a.objects if a.objects != ap.get_default("objects") else 256, a.blocks, a.renderers, out, not a.no_all_live)
     elif a.against and a.mixed:
         out = a.out if a.out != ap.get_default("out") else os.path.join(HERE, "profiles", "bank_mixed.json")
         compare_mixed(os.path.abspath(a.against), a.runs, a.objects if a.objects != ap.get_default("objects") else 256, a.blocks, a.renderers, out, not a.no_all_live)
@@ -550,7 +622,7 @@ def main():
     elif a.against:
         compare(os.path.abspath(a.against), a.runs, a.objects, a.blocks, a.renderers, a.out, not a.no_all_live)
     else:
-        print(json.dumps(measure(os.path.abspath(a.tree), a.entry, a.junctions, a.sides, a.objects, a.blocks, a.renderers, a.forces, a.save_forces, a.law, a.members, a.ungrouped, a.pickups, a.mixed, a.double)))
+        print(json.dumps(measure(os.path.abspath(a.tree), a.entry, a.junctions, a.sides, a.objects, a.blocks, a.renderers, a.forces, a.save_forces, a.law, a.members, a.ungrouped, a.pickups, a.mixed, a.double, a.damped_groups)))
 
 
 if __name__ == "__main__":
