@@ -81,6 +81,9 @@ def lib():
     L = C.CDLL(SO_PATH)
     vp, u32, i32, f64 = C.c_void_p, C.c_uint32, C.c_int, C.c_double
     pp = C.POINTER(vp)
+    # the bank's render entries: what every one takes (bank, frames, click gain, impacts, renderers and the deal, gains, out, the per-object results), then what each adds
+    block, drives, pickups, junctions = [vp, u32, C.c_float, u32, vp, u32] + [vp] * 11, [u32, vp, vp], [u32, vp, vp, vp], [u32, vp, vp, vp, vp, vp]
+    damping_and_carry, counts = [vp, vp], [vp]
     sig = {
         "mh_context_create": (i32, [i32, pp]), "mh_context_destroy": (None, [vp]), "mh_last_error": (C.c_char_p, [vp]),
         "mh_context_synchronize": (i32, [vp]), "mh_context_time_kernels": (i32, [vp, i32]),
@@ -104,18 +107,14 @@ def lib():
         "mh_bank_create": (i32, [vp, i32, u32, u32, u32, vp, vp, vp, vp, vp, vp, pp]), "mh_bank_destroy": (None, [vp]),
         "mh_bank_set_coefficients": (i32, [vp, u32, u32, vp, vp, vp, vp, vp]), "mh_bank_set_shapes": (i32, [vp, u32, u32, vp, vp, vp]),
         "mh_bank_zero_state": (i32, [vp, u32, u32]),
-        "mh_bank_render": (i32, [vp, u32, C.c_float, u32, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
-        "mh_bank_render_driven": (i32, [vp, u32, C.c_float, u32, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp, vp]),
-        "mh_drive_struct_size": (u32, []),
+        "mh_bank_render": (i32, block), "mh_bank_render_driven": (i32, block + drives), "mh_bank_render_read": (i32, block + drives + pickups),
+        "mh_drive_struct_size": (u32, []), "mh_pickup_struct_size": (u32, []), "mh_junction_struct_size": (u32, []),
         "mh_bank_set_deflection_gain": (i32, [vp, u32, u32, vp]),
-        "mh_bank_render_read": (i32, [vp, u32, C.c_float, u32, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp]),
-        "mh_pickup_struct_size": (u32, []),
-        "mh_bank_render_coupled": (i32, [vp, u32, C.c_float, u32, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp, u32, vp, vp, vp, vp, vp]),
-        "mh_junction_struct_size": (u32, []),
-        "mh_bank_render_damped": (i32, [vp, u32, C.c_float, u32, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp]),
-        "mh_bank_render_observed": (i32, [vp, u32, C.c_float, u32, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp]),
-        "mh_bank_render_mixed": (i32, [vp, u32, C.c_float, u32, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp]),
-        "mh_bank_render_damped_groups": (i32, [vp, u32, C.c_float, u32, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp, vp, u32, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "mh_bank_render_coupled": (i32, block + drives + pickups + junctions),
+        "mh_bank_render_damped": (i32, block + drives + pickups + junctions + damping_and_carry),
+        "mh_bank_render_observed": (i32, block + drives + pickups + junctions + damping_and_carry),
+        "mh_bank_render_mixed": (i32, block + drives + pickups + junctions + damping_and_carry + counts),
+        "mh_bank_render_damped_groups": (i32, block + drives + pickups + junctions + damping_and_carry + counts),
         "mh_bank_read_state": (i32, [vp, u32, u32, vp, vp]),
     }
     for name, (res, args) in sig.items():

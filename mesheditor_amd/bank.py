@@ -172,51 +172,62 @@ class Scene:
         if self.L.mhx_render_driven(self.h, _p(out), len(out), len(drives), C.cast(rows, C.c_void_p), _p(sig)):
             raise RuntimeError(self.L.mhx_last_error().decode())
 
+    def _render(self, entry, out, drives, signals, pickups, junctions=None, approach=None, damping=None, carry=None, counted=False):
+        """One block through `entry` of the C wrapper, with what the entry takes beyond render_read's arguments: junctions and approach
+        (render_coupled), damping and carry (render_damped), counted (render_mixed).  Returns the tuple of the widest of them the entry
+        reaches: (reads, read_flags, forces, compliances, statuses, carry, unconverged)."""
+        assert out.dtype == self.dtype and out.flags["C_CONTIGUOUS"]
+        frames = len(out)
+        rows = drives if isinstance(drives, C.Array) else (Drive * max(len(drives), 1))(*[v if isinstance(v, Drive) else Drive(*v) for v in drives])
+        sig = np.ascontiguousarray(signals, np.float32).reshape(len(drives), frames)
+        probes = pickups if isinstance(pickups, C.Array) else (Pickup * max(len(pickups), 1))(*pickups)
+        reads, flags = np.zeros((len(pickups), frames), self.dtype), np.zeros(len(pickups), np.uint8)
+        args, result = [len(drives), C.cast(rows, C.c_void_p), _p(sig), len(pickups), C.cast(probes, C.c_void_p), _p(reads), _p(flags)], (reads, flags)
+        if junctions is not None:
+            n = len(junctions)
+            contacts = junctions if isinstance(junctions, C.Array) else (Junction * max(n, 1))(*junctions)
+            u = np.ascontiguousarray(approach, np.float32).reshape(n, frames)
+            forces, compliances, statuses = np.zeros((n, frames), self.dtype), np.zeros(n), np.zeros(n, np.uint8)
+            args += [n, C.cast(contacts, C.c_void_p), _p(u), _p(forces), _p(compliances), _p(statuses)]
+            result += (forces, compliances, statuses)
+        if damping is not None:
+            rates = np.ascontiguousarray(damping, np.float32).reshape(n)
+            state = np.full(n, np.nan, self.dtype) if carry is None else np.array(carry, self.dtype).reshape(n)
+            args += [_p(rates), _p(state)]
+            result += (state,)
+        if counted:
+            counts = np.zeros(n, np.uint32)
+            args += [_p(counts)]
+            result += (counts,)
+        if entry(self.h, _p(out), frames, *args):
+            raise RuntimeError(self.L.mhx_last_error().decode())
+        return result
+
     def render_read(self, out, drives, signals, pickups):
         """RenderModalRead: render_driven plus deflection pickups (a ctypes array or a sequence of Pickup records).  Returns (reads,
         read_flags): reads[q] is pickup q's row of len(out) values in the scene's precision, read_flags[q] is 1 when it was read and 0
         when it was left out (its row is zeros then)."""
-        assert out.dtype == self.dtype and out.flags["C_CONTIGUOUS"]
-        rows = drives if isinstance(drives, C.Array) else (Drive * max(len(drives), 1))(*[v if isinstance(v, Drive) else Drive(*v) for v in drives])
-        sig = np.ascontiguousarray(signals, np.float32).reshape(len(drives), len(out))
-        probes = pickups if isinstance(pickups, C.Array) else (Pickup * max(len(pickups), 1))(*pickups)
-        reads, flags = np.zeros((len(pickups), len(out)), self.dtype), np.zeros(len(pickups), np.uint8)
-        if self.L.mhx_render_read(self.h, _p(out), len(out), len(drives), C.cast(rows, C.c_void_p), _p(sig), len(pickups), C.cast(probes, C.c_void_p), _p(reads), _p(flags)):
-            raise RuntimeError(self.L.mhx_last_error().decode())
-        return reads, flags
+        return self._render(self.L.mhx_render_read, out, drives, signals, pickups)
 
     def render_coupled(self, out, drives, signals, pickups, junctions, approach):
         """RenderModalCoupled: render_read plus contact junctions (a ctypes array or a sequence of Junction records) and their approach
         signals, float32 [len(junctions)][len(out)].  Returns (reads, read_flags, forces, compliances, statuses): forces[j] is junction
         j's contact force row in the scene's precision, compliances[j] its compliance C, statuses[j] 0 = left out (a zero row), 1 =
         solved, 2 = refused (1 + K C not a finite number above 0: a zero row)."""
-        assert out.dtype == self.dtype and out.flags["C_CONTIGUOUS"]
-        rows = drives if isinstance(drives, C.Array) else (Drive * max(len(drives), 1))(*[v if isinstance(v, Drive) else Drive(*v) for v in drives])
-        sig = np.ascontiguousarray(signals, np.float32).reshape(len(drives), len(out))
-        probes = pickups if isinstance(pickups, C.Array) else (Pickup * max(len(pickups), 1))(*pickups)
-        contacts = junctions if isinstance(junctions, C.Array) else (Junction * max(len(junctions), 1))(*junctions)
-        u = np.ascontiguousarray(approach, np.float32).reshape(len(junctions), len(out))
-        reads, flags = np.zeros((len(pickups), len(out)), self.dtype), np.zeros(len(pickups), np.uint8)
-        forces, compliances, statuses = np.zeros((len(junctions), len(out)), self.dtype), np.zeros(len(junctions)), np.zeros(len(junctions), np.uint8)
-        if self.L.mhx_render_coupled(self.h, _p(out), len(out), len(drives), C.cast(rows, C.c_void_p), _p(sig), len(pickups), C.cast(probes, C.c_void_p), _p(reads), _p(flags),
-                                     len(junctions), C.cast(contacts, C.c_void_p), _p(u), _p(forces), _p(compliances), _p(statuses)):
-            raise RuntimeError(self.L.mhx_last_error().decode())
-        return reads, flags, forces, compliances, statuses
+        return self._render(self.L.mhx_render_coupled, out, drives, signals, pickups, junctions, approach)
 
     def render_observed(self, out, drives, signals, pickups, junctions, approach, damping=None, carry=None):
         """RenderModalObserved: render_damped that also reads the pickups on objects of kept junctions (render_coupled and render_damped leave
         those out).  damping=None: zeros (no junction with damped=True is expected).  Returns render_damped's tuple."""
         rates = np.zeros(len(junctions), np.float32) if damping is None else damping
-        return self.render_damped(out, drives, signals, pickups, junctions, approach, rates, carry, entry=self.L.mhx_render_observed)
+        return self._render(self.L.mhx_render_observed, out, drives, signals, pickups, junctions, approach, rates, carry)
 
     def render_mixed(self, out, drives, signals, pickups, junctions, approach, damping=None, carry=None):
         """RenderModalMixed: render_observed in which a junction with shared=True and hertz=True may be a member of a group (the older entries
         leave it out).  Returns render_observed's tuple plus `unconverged`: per junction, for a member of a group with a Hertz member, the
         frames of the block in which the group's residual test failed (0 on valid input); 0 for every other junction."""
         rates = np.zeros(len(junctions), np.float32) if damping is None else damping
-        counts = np.zeros(len(junctions), np.uint32)
-        entry = lambda *args: self.L.mhx_render_mixed(*args, _p(counts))
-        return self.render_damped(out, drives, signals, pickups, junctions, approach, rates, carry, entry=entry) + (counts,)
+        return self._render(self.L.mhx_render_mixed, out, drives, signals, pickups, junctions, approach, rates, carry, counted=True)
 
     def render_damped_groups(self, out, drives, signals, pickups, junctions, approach, damping=None, carry=None):
         """RenderModalDampedGroups: render_mixed in which a junction with shared=True and damped=True, linear or Hertz, may be a member of a
@@ -224,30 +235,14 @@ class Scene:
         group, the compression its last frame's solve left (pass it to the next block), and `unconverged` counts the members of a group
         with a Hertz or a damped member."""
         rates = np.zeros(len(junctions), np.float32) if damping is None else damping
-        counts = np.zeros(len(junctions), np.uint32)
-        entry = lambda *args: self.L.mhx_render_damped_groups(*args, _p(counts))
-        return self.render_damped(out, drives, signals, pickups, junctions, approach, rates, carry, entry=entry) + (counts,)
+        return self._render(self.L.mhx_render_damped_groups, out, drives, signals, pickups, junctions, approach, rates, carry, counted=True)
 
     def render_damped(self, out, drives, signals, pickups, junctions, approach, damping, carry=None, entry=None):
         """RenderModalDamped: render_coupled with contact damping.  damping: one D in s/m per junction (float32; read for junctions with
         damped=True, l = D * sample rate per frame); carry: one value per junction in the scene's precision -- the compression the last
         frame of the previous block left, as this call returned it then; None or a value that is not finite: no history.  Returns
         render_coupled's tuple plus the new carry (NaN for every junction that is not a solved damped one)."""
-        assert out.dtype == self.dtype and out.flags["C_CONTIGUOUS"]
-        rows = drives if isinstance(drives, C.Array) else (Drive * max(len(drives), 1))(*[v if isinstance(v, Drive) else Drive(*v) for v in drives])
-        sig = np.ascontiguousarray(signals, np.float32).reshape(len(drives), len(out))
-        probes = pickups if isinstance(pickups, C.Array) else (Pickup * max(len(pickups), 1))(*pickups)
-        contacts = junctions if isinstance(junctions, C.Array) else (Junction * max(len(junctions), 1))(*junctions)
-        n = len(junctions)
-        u = np.ascontiguousarray(approach, np.float32).reshape(n, len(out))
-        rates = np.ascontiguousarray(damping, np.float32).reshape(n)
-        state = np.full(n, np.nan, self.dtype) if carry is None else np.array(carry, self.dtype).reshape(n)
-        reads, flags = np.zeros((len(pickups), len(out)), self.dtype), np.zeros(len(pickups), np.uint8)
-        forces, compliances, statuses = np.zeros((n, len(out)), self.dtype), np.zeros(n), np.zeros(n, np.uint8)
-        if (entry or self.L.mhx_render_damped)(self.h, _p(out), len(out), len(drives), C.cast(rows, C.c_void_p), _p(sig), len(pickups), C.cast(probes, C.c_void_p), _p(reads), _p(flags),
-                                    n, C.cast(contacts, C.c_void_p), _p(u), _p(forces), _p(compliances), _p(statuses), _p(rates), _p(state)):
-            raise RuntimeError(self.L.mhx_last_error().decode())
-        return reads, flags, forces, compliances, statuses, state
+        return self._render(entry or self.L.mhx_render_damped, out, drives, signals, pickups, junctions, approach, damping, carry)
 
     def time_kernels(self, enable=True):
         """HIP-event timing of the bank's kernels on its device context (measurement aid)."""

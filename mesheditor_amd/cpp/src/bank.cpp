@@ -498,23 +498,39 @@ template<typename Real> bool HasExcitationPosition(const ModalBankColumns<Real> 
     return uint64_t(ex_pos) * b.ModeCount[object] + b.ModeCount[object] <= uint64_t(last - first);
 }
 
-// What a junction hands back to the caller of RenderModalCoupled.
+// The junction entries are a ladder: each admits what the one before it admits, plus one thing (RenderModal, -Driven and -Read are the
+// coupled one without junctions).
+enum class JunctionEntry {
+    Coupled, // RenderModalCoupled: ModalJunctionDamped is ignored
+    Damped, // RenderModalDamped: + D in s/m per junction, and the carry (in and out)
+    Observed, // RenderModalObserved: + the pickups on junction objects are read
+    Mixed, // RenderModalMixed: + a Hertz junction may join a group; per junction, its frames that failed the residual test
+    DampedGroups, // RenderModalDampedGroups: + a damped junction may join a group as well
+};
+constexpr const char *JunctionEntryName[] = {"RenderModalCoupled", "RenderModalDamped", "RenderModalObserved", "RenderModalMixed", "RenderModalDampedGroups"};
+
+// What a junction entry takes and hands back; an entry leaves what it does not take empty.
 template<typename Real> struct JunctionResults {
+    JunctionEntry Entry{JunctionEntry::Coupled};
     std::span<const ModalJunction> Junctions;
     const float *Approach{nullptr};
     Real *Forces{nullptr};
     double *Compliances{nullptr};
     uint8_t *Statuses{nullptr};
-    const float *Damping{nullptr}; // RenderModalDamped: D in s/m per junction, and the carry (in and out); null: ModalJunctionDamped is ignored
-    Real *Carry{nullptr};
-    bool Observed{false}; // RenderModalObserved: the damped entry that also reads the pickups on junction objects
-    uint32_t *Unconverged{nullptr}; // RenderModalMixed: the observed entry in which a Hertz junction may join a group; per junction, its frames that failed the residual test
-    bool DampedInGroups{false}; // RenderModalDampedGroups: the mixed entry in which a damped junction may join a group as well
+    std::span<const float> Damping{};
+    std::span<Real> Carry{};
+    std::span<uint32_t> Unconverged{};
 };
 
 template<typename Audio, typename Real>
 void RenderBlock(Audio &m, std::span<const ModalDrive> drives, const float *signals, Real *out, uint32_t frames, std::span<const ModalPickup> pickups = {}, Real *reads = nullptr,
                  uint8_t *read_flags = nullptr, const JunctionResults<Real> &coupled = {}) {
+    const auto admits = [&](JunctionEntry e) { return coupled.Entry >= e; };
+    const size_t per_junction = coupled.Junctions.size();
+    if (admits(JunctionEntry::Mixed) && (coupled.Damping.size() < per_junction || coupled.Carry.size() < per_junction || coupled.Unconverged.size() < per_junction))
+        throw std::invalid_argument(std::string(JunctionEntryName[int(coupled.Entry)]) + ": a damping, a carry and a count per junction");
+    if (admits(JunctionEntry::Damped) && (coupled.Damping.size() < per_junction || coupled.Carry.size() < per_junction))
+        throw std::invalid_argument(std::string(JunctionEntryName[int(coupled.Entry)]) + ": a damping and a carry per junction");
     if (frames == 0) return;
     const auto started = std::chrono::steady_clock::now();
     const ReaderScope reading(m.ReaderSeq);
@@ -583,7 +599,7 @@ void RenderBlock(Audio &m, std::span<const ModalDrive> drives, const float *sign
     // (one junction per object, unless both carry ModalJunctionShared: then they form a group -- the decision of modalhip_groups.hpp, which
     // the device entry takes again)
     MhJunctionGroups grouping(n_objects);
-    const uint32_t flag_mask = coupled.Damping ? ~0u : ~ModalJunctionDamped;
+    const uint32_t flag_mask = admits(JunctionEntry::Damped) ? ~0u : ~ModalJunctionDamped;
     std::vector<float> damping; // per kept junction: l = D * SampleRate per frame, rounded once in float
     std::vector<Real> carry;
     for (size_t j = 0; j < junctions.size(); ++j) {
@@ -594,12 +610,12 @@ void RenderBlock(Audio &m, std::span<const ModalDrive> drives, const float *sign
         if (!std::isfinite(v.Stiffness) || v.Stiffness < 0 || !side_ok(v.A) || (two_sided && (v.A.Object == v.B.Object || !side_ok(v.B)))) continue;
         if ((v.Flags & ModalJunctionHertz) && (v.Flags & ModalJunctionBilateral)) continue; // the Hertz law is unilateral
         if ((flags & ModalJunctionDamped) && ((flags & ModalJunctionBilateral) || !std::isfinite(per_frame) || per_frame < 0)) continue; // so is the damped one
-        if (grouping.add(uint32_t(j), flags, v.A.Object, side_waves(v.A), two_sided ? v.B.Object : MH_NO_OBJECT, two_sided ? side_waves(v.B) : 0u, coupled.Unconverged != nullptr, coupled.DampedInGroups) < 0) continue;
+        if (grouping.add(uint32_t(j), flags, v.A.Object, side_waves(v.A), two_sided ? v.B.Object : MH_NO_OBJECT, two_sided ? side_waves(v.B) : 0u, admits(JunctionEntry::Mixed), admits(JunctionEntry::DampedGroups)) < 0) continue;
         mh_junction_side none{};
         none.object = MH_NO_OBJECT;
         d.Junctions.push_back({side_record(v.A), two_sided ? side_record(v.B) : none, v.Stiffness, flags});
         d.JunctionFrom.push_back(uint32_t(j));
-        if (coupled.Damping) {
+        if (admits(JunctionEntry::Damped)) {
             damping.push_back(per_frame);
             carry.push_back(coupled.Carry[j]);
         }
@@ -655,27 +671,23 @@ void RenderBlock(Audio &m, std::span<const ModalDrive> drives, const float *sign
         narrow_listener.assign(b.ListenerGain.begin(), b.ListenerGain.end());
         out_gain = narrow_out.data(), listener_gain = narrow_listener.data();
     }
-    std::vector<uint32_t> unconverged; // RenderModalMixed only: the older entries allocate what they did
-    if (coupled.Unconverged) {
-        unconverged.assign(kept_junctions + 1, 0u);
-        damping.push_back(0.f), carry.push_back(Real(0)); // (never read: the entry wants pointers)
-        if ((coupled.DampedInGroups ? mh_bank_render_damped_groups : mh_bank_render_mixed)(d.Bank, frames, m.ClickGain.load(std::memory_order_relaxed), n_impacts, d.Impacts.data(), renderers, d.DealOffset.data(), d.DealObjects.data(),
-                                 d.RenderCount.data(), d.Tuned.data(), out_gain, listener_gain, out, d.Energy.data(), d.Live.data(), d.Silenced.data(), d.ModalEnergy.data(),
-                                 uint32_t(d.Drives.size()), d.Drives.data(), drive_signals, uint32_t(d.Pickups.size()), d.Pickups.data(), reads, d.PickupRead.data(), kept_junctions, d.Junctions.data(), d.Approach.data(),
-                                 junction_forces.data(), d.JunctionCompliance.data(), d.JunctionStatus.data(), damping.data(), carry.data(), unconverged.data()) != MH_OK)
-            Fail(d);
-    } else if (coupled.Damping) {
-        damping.push_back(0.f), carry.push_back(Real(0)); // (never read: the entry wants pointers)
-        if ((coupled.Observed ? mh_bank_render_observed : mh_bank_render_damped)(d.Bank, frames, m.ClickGain.load(std::memory_order_relaxed), n_impacts, d.Impacts.data(), renderers, d.DealOffset.data(), d.DealObjects.data(),
-                                  d.RenderCount.data(), d.Tuned.data(), out_gain, listener_gain, out, d.Energy.data(), d.Live.data(), d.Silenced.data(), d.ModalEnergy.data(),
-                                  uint32_t(d.Drives.size()), d.Drives.data(), drive_signals, uint32_t(d.Pickups.size()), d.Pickups.data(), reads, d.PickupRead.data(), kept_junctions, d.Junctions.data(), d.Approach.data(),
-                                  junction_forces.data(), d.JunctionCompliance.data(), d.JunctionStatus.data(), damping.data(), carry.data()) != MH_OK)
-            Fail(d);
-    } else if (mh_bank_render_coupled(d.Bank, frames, m.ClickGain.load(std::memory_order_relaxed), n_impacts, d.Impacts.data(), renderers, d.DealOffset.data(), d.DealObjects.data(),
-                              d.RenderCount.data(), d.Tuned.data(), out_gain, listener_gain, out, d.Energy.data(), d.Live.data(), d.Silenced.data(), d.ModalEnergy.data(),
-                              uint32_t(d.Drives.size()), d.Drives.data(), drive_signals, uint32_t(d.Pickups.size()), d.Pickups.data(), reads, d.PickupRead.data(), kept_junctions, d.Junctions.data(), d.Approach.data(),
-                               junction_forces.data(), d.JunctionCompliance.data(), d.JunctionStatus.data()) != MH_OK)
-        Fail(d);
+    std::vector<uint32_t> unconverged(admits(JunctionEntry::Mixed) ? kept_junctions : 0, 0u);
+    // the device entry of the level: what all take, then what the level adds
+    auto call = [&](auto entry, auto... more) {
+        return entry(d.Bank, frames, m.ClickGain.load(std::memory_order_relaxed), n_impacts, d.Impacts.data(), renderers, d.DealOffset.data(), d.DealObjects.data(), d.RenderCount.data(),
+                     d.Tuned.data(), out_gain, listener_gain, out, d.Energy.data(), d.Live.data(), d.Silenced.data(), d.ModalEnergy.data(), uint32_t(d.Drives.size()), d.Drives.data(),
+                     drive_signals, uint32_t(d.Pickups.size()), d.Pickups.data(), reads, d.PickupRead.data(), kept_junctions, d.Junctions.data(), d.Approach.data(), junction_forces.data(),
+                     d.JunctionCompliance.data(), d.JunctionStatus.data(), more...);
+    };
+    int status = MH_OK;
+    switch (coupled.Entry) {
+    case JunctionEntry::Coupled: status = call(mh_bank_render_coupled); break;
+    case JunctionEntry::Damped: status = call(mh_bank_render_damped, damping.data(), carry.data()); break;
+    case JunctionEntry::Observed: status = call(mh_bank_render_observed, damping.data(), carry.data()); break;
+    case JunctionEntry::Mixed: status = call(mh_bank_render_mixed, damping.data(), carry.data(), unconverged.data()); break;
+    case JunctionEntry::DampedGroups: status = call(mh_bank_render_damped_groups, damping.data(), carry.data(), unconverged.data()); break;
+    }
+    if (status != MH_OK) Fail(d);
     if (read_flags) std::copy(d.PickupRead.begin(), d.PickupRead.end(), read_flags);
     if (!junctions.empty()) { // every caller's junction gets its row: zeros and status 0 for the ones left out
         std::fill(coupled.Forces, coupled.Forces + junctions.size() * frames, Real(0));
@@ -687,12 +699,12 @@ void RenderBlock(Audio &m, std::span<const ModalDrive> drives, const float *sign
             if (coupled.Compliances) coupled.Compliances[j] = d.JunctionCompliance[c];
             if (coupled.Statuses) coupled.Statuses[j] = d.JunctionStatus[c];
         }
-        if (coupled.Unconverged) { // 0 for the ones left out
-            std::fill(coupled.Unconverged, coupled.Unconverged + junctions.size(), 0u);
+        if (admits(JunctionEntry::Mixed)) { // 0 for the ones left out
+            std::fill_n(coupled.Unconverged.begin(), junctions.size(), 0u);
             for (uint32_t c = 0; c < kept_junctions; ++c) coupled.Unconverged[d.JunctionFrom[c]] = unconverged[c];
         }
-        if (coupled.Carry) { // a quiet NaN for the ones left out; a kept one's as the entry returned it (NaN unless damped and solved)
-            std::fill(coupled.Carry, coupled.Carry + junctions.size(), std::numeric_limits<Real>::quiet_NaN());
+        if (admits(JunctionEntry::Damped)) { // a quiet NaN for the ones left out; a kept one's as the entry returned it (NaN unless damped and solved)
+            std::fill_n(coupled.Carry.begin(), junctions.size(), std::numeric_limits<Real>::quiet_NaN());
             for (uint32_t c = 0; c < kept_junctions; ++c) coupled.Carry[d.JunctionFrom[c]] = carry[c];
         }
     }
@@ -783,72 +795,52 @@ void RenderModalRead(ModalAudio64 &m, std::span<const ModalDrive> drives, const 
 void RenderModalCoupled(ModalAudio &m, std::span<const ModalDrive> drives, const float *signals, std::span<const ModalPickup> pickups, float *reads,
                         std::span<const ModalJunction> junctions, const float *approach, float *forces, float *out, uint32_t frame_count, uint8_t *read_flags, double *compliances,
                         uint8_t *statuses) {
-    RenderBlock<ModalAudio, float>(m, drives, signals, out, frame_count, pickups, reads, read_flags, {junctions, approach, forces, compliances, statuses});
+    RenderBlock<ModalAudio, float>(m, drives, signals, out, frame_count, pickups, reads, read_flags, {JunctionEntry::Coupled, junctions, approach, forces, compliances, statuses});
 }
 void RenderModalCoupled(ModalAudio64 &m, std::span<const ModalDrive> drives, const float *signals, std::span<const ModalPickup> pickups, double *reads,
                         std::span<const ModalJunction> junctions, const float *approach, double *forces, double *out, uint32_t frame_count, uint8_t *read_flags, double *compliances,
                         uint8_t *statuses) {
-    RenderBlock<ModalAudio64, double>(m, drives, signals, out, frame_count, pickups, reads, read_flags, {junctions, approach, forces, compliances, statuses});
+    RenderBlock<ModalAudio64, double>(m, drives, signals, out, frame_count, pickups, reads, read_flags, {JunctionEntry::Coupled, junctions, approach, forces, compliances, statuses});
 }
 void RenderModalDamped(ModalAudio &m, std::span<const ModalDrive> drives, const float *signals, std::span<const ModalPickup> pickups, float *reads,
                        std::span<const ModalJunction> junctions, const float *approach, std::span<const float> damping, std::span<float> carry, float *forces, float *out,
                        uint32_t frame_count, uint8_t *read_flags, double *compliances, uint8_t *statuses) {
-    if (damping.size() < junctions.size() || carry.size() < junctions.size()) throw std::invalid_argument("RenderModalDamped: a damping and a carry per junction");
-    static const float none = 0; // (no junctions: a pointer that says which entry this is)
-    RenderBlock<ModalAudio, float>(m, drives, signals, out, frame_count, pickups, reads, read_flags, {junctions, approach, forces, compliances, statuses, junctions.empty() ? &none : damping.data(), carry.data()});
+    RenderBlock<ModalAudio, float>(m, drives, signals, out, frame_count, pickups, reads, read_flags, {JunctionEntry::Damped, junctions, approach, forces, compliances, statuses, damping, carry});
 }
 void RenderModalDamped(ModalAudio64 &m, std::span<const ModalDrive> drives, const float *signals, std::span<const ModalPickup> pickups, double *reads,
                        std::span<const ModalJunction> junctions, const float *approach, std::span<const float> damping, std::span<double> carry, double *forces, double *out,
                        uint32_t frame_count, uint8_t *read_flags, double *compliances, uint8_t *statuses) {
-    if (damping.size() < junctions.size() || carry.size() < junctions.size()) throw std::invalid_argument("RenderModalDamped: a damping and a carry per junction");
-    static const float none = 0;
-    RenderBlock<ModalAudio64, double>(m, drives, signals, out, frame_count, pickups, reads, read_flags, {junctions, approach, forces, compliances, statuses, junctions.empty() ? &none : damping.data(), carry.data()});
+    RenderBlock<ModalAudio64, double>(m, drives, signals, out, frame_count, pickups, reads, read_flags, {JunctionEntry::Damped, junctions, approach, forces, compliances, statuses, damping, carry});
 }
 void RenderModalObserved(ModalAudio &m, std::span<const ModalDrive> drives, const float *signals, std::span<const ModalPickup> pickups, float *reads,
                          std::span<const ModalJunction> junctions, const float *approach, std::span<const float> damping, std::span<float> carry, float *forces, float *out,
                          uint32_t frame_count, uint8_t *read_flags, double *compliances, uint8_t *statuses) {
-    if (damping.size() < junctions.size() || carry.size() < junctions.size()) throw std::invalid_argument("RenderModalObserved: a damping and a carry per junction");
-    static const float none = 0; // (no junctions: a pointer that says which entry this is)
-    RenderBlock<ModalAudio, float>(m, drives, signals, out, frame_count, pickups, reads, read_flags, {junctions, approach, forces, compliances, statuses, junctions.empty() ? &none : damping.data(), carry.data(), true});
+    RenderBlock<ModalAudio, float>(m, drives, signals, out, frame_count, pickups, reads, read_flags, {JunctionEntry::Observed, junctions, approach, forces, compliances, statuses, damping, carry});
 }
 void RenderModalObserved(ModalAudio64 &m, std::span<const ModalDrive> drives, const float *signals, std::span<const ModalPickup> pickups, double *reads,
                          std::span<const ModalJunction> junctions, const float *approach, std::span<const float> damping, std::span<double> carry, double *forces, double *out,
                          uint32_t frame_count, uint8_t *read_flags, double *compliances, uint8_t *statuses) {
-    if (damping.size() < junctions.size() || carry.size() < junctions.size()) throw std::invalid_argument("RenderModalObserved: a damping and a carry per junction");
-    static const float none = 0;
-    RenderBlock<ModalAudio64, double>(m, drives, signals, out, frame_count, pickups, reads, read_flags, {junctions, approach, forces, compliances, statuses, junctions.empty() ? &none : damping.data(), carry.data(), true});
+    RenderBlock<ModalAudio64, double>(m, drives, signals, out, frame_count, pickups, reads, read_flags, {JunctionEntry::Observed, junctions, approach, forces, compliances, statuses, damping, carry});
 }
 void RenderModalMixed(ModalAudio &m, std::span<const ModalDrive> drives, const float *signals, std::span<const ModalPickup> pickups, float *reads,
                       std::span<const ModalJunction> junctions, const float *approach, std::span<const float> damping, std::span<float> carry, float *forces, float *out,
                       uint32_t frame_count, std::span<uint32_t> unconverged, uint8_t *read_flags, double *compliances, uint8_t *statuses) {
-    if (damping.size() < junctions.size() || carry.size() < junctions.size() || unconverged.size() < junctions.size()) throw std::invalid_argument("RenderModalMixed: a damping, a carry and a count per junction");
-    static const float none = 0; // (no junctions: pointers that say which entry this is)
-    static uint32_t no_count = 0;
-    RenderBlock<ModalAudio, float>(m, drives, signals, out, frame_count, pickups, reads, read_flags, {junctions, approach, forces, compliances, statuses, junctions.empty() ? &none : damping.data(), carry.data(), true, junctions.empty() ? &no_count : unconverged.data()});
+    RenderBlock<ModalAudio, float>(m, drives, signals, out, frame_count, pickups, reads, read_flags, {JunctionEntry::Mixed, junctions, approach, forces, compliances, statuses, damping, carry, unconverged});
 }
 void RenderModalMixed(ModalAudio64 &m, std::span<const ModalDrive> drives, const float *signals, std::span<const ModalPickup> pickups, double *reads,
                       std::span<const ModalJunction> junctions, const float *approach, std::span<const float> damping, std::span<double> carry, double *forces, double *out,
                       uint32_t frame_count, std::span<uint32_t> unconverged, uint8_t *read_flags, double *compliances, uint8_t *statuses) {
-    if (damping.size() < junctions.size() || carry.size() < junctions.size() || unconverged.size() < junctions.size()) throw std::invalid_argument("RenderModalMixed: a damping, a carry and a count per junction");
-    static const float none = 0;
-    static uint32_t no_count = 0;
-    RenderBlock<ModalAudio64, double>(m, drives, signals, out, frame_count, pickups, reads, read_flags, {junctions, approach, forces, compliances, statuses, junctions.empty() ? &none : damping.data(), carry.data(), true, junctions.empty() ? &no_count : unconverged.data()});
+    RenderBlock<ModalAudio64, double>(m, drives, signals, out, frame_count, pickups, reads, read_flags, {JunctionEntry::Mixed, junctions, approach, forces, compliances, statuses, damping, carry, unconverged});
 }
 void RenderModalDampedGroups(ModalAudio &m, std::span<const ModalDrive> drives, const float *signals, std::span<const ModalPickup> pickups, float *reads,
                              std::span<const ModalJunction> junctions, const float *approach, std::span<const float> damping, std::span<float> carry, float *forces, float *out,
                              uint32_t frame_count, std::span<uint32_t> unconverged, uint8_t *read_flags, double *compliances, uint8_t *statuses) {
-    if (damping.size() < junctions.size() || carry.size() < junctions.size() || unconverged.size() < junctions.size()) throw std::invalid_argument("RenderModalDampedGroups: a damping, a carry and a count per junction");
-    static const float none = 0; // (no junctions: pointers that say which entry this is)
-    static uint32_t no_count = 0;
-    RenderBlock<ModalAudio, float>(m, drives, signals, out, frame_count, pickups, reads, read_flags, {junctions, approach, forces, compliances, statuses, junctions.empty() ? &none : damping.data(), carry.data(), true, junctions.empty() ? &no_count : unconverged.data(), true});
+    RenderBlock<ModalAudio, float>(m, drives, signals, out, frame_count, pickups, reads, read_flags, {JunctionEntry::DampedGroups, junctions, approach, forces, compliances, statuses, damping, carry, unconverged});
 }
 void RenderModalDampedGroups(ModalAudio64 &m, std::span<const ModalDrive> drives, const float *signals, std::span<const ModalPickup> pickups, double *reads,
                              std::span<const ModalJunction> junctions, const float *approach, std::span<const float> damping, std::span<double> carry, double *forces, double *out,
                              uint32_t frame_count, std::span<uint32_t> unconverged, uint8_t *read_flags, double *compliances, uint8_t *statuses) {
-    if (damping.size() < junctions.size() || carry.size() < junctions.size() || unconverged.size() < junctions.size()) throw std::invalid_argument("RenderModalDampedGroups: a damping, a carry and a count per junction");
-    static const float none = 0;
-    static uint32_t no_count = 0;
-    RenderBlock<ModalAudio64, double>(m, drives, signals, out, frame_count, pickups, reads, read_flags, {junctions, approach, forces, compliances, statuses, junctions.empty() ? &none : damping.data(), carry.data(), true, junctions.empty() ? &no_count : unconverged.data(), true});
+    RenderBlock<ModalAudio64, double>(m, drives, signals, out, frame_count, pickups, reads, read_flags, {JunctionEntry::DampedGroups, junctions, approach, forces, compliances, statuses, damping, carry, unconverged});
 }
 mh_context *ModalDeviceContext(ModalAudio &m) { return NeedContext(m), m.Dev->Context; }
 mh_context *ModalDeviceContext(ModalAudio64 &m) { return NeedContext(m), m.Dev->Context; }

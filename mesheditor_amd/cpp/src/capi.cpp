@@ -43,6 +43,43 @@ namespace {
 // f(audio, bank under construction) in the scene's precision
 template<typename F> auto Dispatch(mhx_scene *s, F &&f) { return s->dbl ? f(s->audio64, s->next64) : f(s->audio, s->next); }
 template<typename Audio, typename Bank> Bank &Pick(Audio &a, Bank &next, int live) { return live ? static_cast<Bank &>(LiveBank(a)) : next; }
+
+// What the widest junction entry (mhx_render_damped_groups) takes after the scene, in its order; an entry leaves what it does not take at null.
+struct JunctionBlock {
+    void *Out;
+    uint32_t Frames, DriveCount;
+    const ModalDrive *Drives;
+    const float *Signals;
+    uint32_t PickupCount; const ModalPickup *Pickups; void *Reads; uint8_t *ReadFlags;
+    uint32_t JunctionCount; const ModalJunction *Junctions; const float *Approach; void *Forces; double *Compliances; uint8_t *Statuses;
+    const float *Damping{nullptr}; void *Carry{nullptr};
+    uint32_t *Unconverged{nullptr};
+};
+enum JunctionCall { Coupled, Damped, Observed, Mixed, DampedGroups };
+// One block through the RenderModal* of `call`: the spans and the pointers in the scene's precision.
+int RenderJunctions(mhx_scene *s, JunctionCall call, const JunctionBlock &b) {
+    try {
+        Dispatch(s, [&](auto &a, auto &) {
+            using Real = typename std::remove_reference_t<decltype(a)>::Scalar;
+            const std::span<const ModalDrive> drives(b.Drives, b.DriveCount);
+            const std::span<const ModalPickup> pickups(b.Pickups, b.PickupCount);
+            const std::span<const ModalJunction> junctions(b.Junctions, b.JunctionCount);
+            const std::span<const float> damping(b.Damping, b.JunctionCount);
+            const std::span<Real> carry(static_cast<Real *>(b.Carry), b.JunctionCount);
+            const std::span<uint32_t> counts(b.Unconverged, b.JunctionCount);
+            Real *reads = static_cast<Real *>(b.Reads), *forces = static_cast<Real *>(b.Forces), *out = static_cast<Real *>(b.Out);
+            switch (call) {
+            case Coupled: RenderModalCoupled(a, drives, b.Signals, pickups, reads, junctions, b.Approach, forces, out, b.Frames, b.ReadFlags, b.Compliances, b.Statuses); break;
+            case Damped: RenderModalDamped(a, drives, b.Signals, pickups, reads, junctions, b.Approach, damping, carry, forces, out, b.Frames, b.ReadFlags, b.Compliances, b.Statuses); break;
+            case Observed: RenderModalObserved(a, drives, b.Signals, pickups, reads, junctions, b.Approach, damping, carry, forces, out, b.Frames, b.ReadFlags, b.Compliances, b.Statuses); break;
+            case Mixed: RenderModalMixed(a, drives, b.Signals, pickups, reads, junctions, b.Approach, damping, carry, forces, out, b.Frames, counts, b.ReadFlags, b.Compliances, b.Statuses); break;
+            case DampedGroups: RenderModalDampedGroups(a, drives, b.Signals, pickups, reads, junctions, b.Approach, damping, carry, forces, out, b.Frames, counts, b.ReadFlags, b.Compliances, b.Statuses); break;
+            }
+            return 0;
+        });
+        return 0;
+    } catch (const std::exception &e) { g_error = e.what(); return 1; }
+}
 } // namespace
 
 extern "C" {
@@ -134,93 +171,32 @@ int mhx_render_read(mhx_scene *s, void *out, uint32_t frames, uint32_t n_drives,
 int mhx_render_coupled(mhx_scene *s, void *out, uint32_t frames, uint32_t n_drives, const ModalDrive *drives, const float *signals, uint32_t n_pickups,
                        const ModalPickup *pickups, void *reads, uint8_t *read_flags, uint32_t n_junctions, const ModalJunction *junctions, const float *approach,
                        void *forces, double *compliances, uint8_t *statuses) {
-    try {
-        const std::span<const ModalDrive> list(drives, n_drives);
-        const std::span<const ModalPickup> probes(pickups, n_pickups);
-        const std::span<const ModalJunction> contacts(junctions, n_junctions);
-        if (s->dbl)
-            RenderModalCoupled(s->audio64, list, signals, probes, static_cast<double *>(reads), contacts, approach, static_cast<double *>(forces), static_cast<double *>(out), frames,
-                               read_flags, compliances, statuses);
-        else
-            RenderModalCoupled(s->audio, list, signals, probes, static_cast<float *>(reads), contacts, approach, static_cast<float *>(forces), static_cast<float *>(out), frames,
-                               read_flags, compliances, statuses);
-        return 0;
-    } catch (const std::exception &e) { g_error = e.what(); return 1; }
+    return RenderJunctions(s, Coupled, {out, frames, n_drives, drives, signals, n_pickups, pickups, reads, read_flags, n_junctions, junctions, approach, forces, compliances, statuses});
 }
 // RenderModalDamped: mhx_render_coupled plus `damping` (one D in s/m per junction) and `carry` (one value per junction in the scene's
 // precision, in and out)
 int mhx_render_damped(mhx_scene *s, void *out, uint32_t frames, uint32_t n_drives, const ModalDrive *drives, const float *signals, uint32_t n_pickups,
                       const ModalPickup *pickups, void *reads, uint8_t *read_flags, uint32_t n_junctions, const ModalJunction *junctions, const float *approach,
                       void *forces, double *compliances, uint8_t *statuses, const float *damping, void *carry) {
-    try {
-        const std::span<const ModalDrive> list(drives, n_drives);
-        const std::span<const ModalPickup> probes(pickups, n_pickups);
-        const std::span<const ModalJunction> contacts(junctions, n_junctions);
-        const std::span<const float> rates(damping, n_junctions);
-        if (s->dbl)
-            RenderModalDamped(s->audio64, list, signals, probes, static_cast<double *>(reads), contacts, approach, rates, std::span<double>(static_cast<double *>(carry), n_junctions),
-                              static_cast<double *>(forces), static_cast<double *>(out), frames, read_flags, compliances, statuses);
-        else
-            RenderModalDamped(s->audio, list, signals, probes, static_cast<float *>(reads), contacts, approach, rates, std::span<float>(static_cast<float *>(carry), n_junctions),
-                              static_cast<float *>(forces), static_cast<float *>(out), frames, read_flags, compliances, statuses);
-        return 0;
-    } catch (const std::exception &e) { g_error = e.what(); return 1; }
+    return RenderJunctions(s, Damped, {out, frames, n_drives, drives, signals, n_pickups, pickups, reads, read_flags, n_junctions, junctions, approach, forces, compliances, statuses, damping, carry});
 }
 // RenderModalObserved: mhx_render_damped's parameters; the pickups on junction objects are read
 int mhx_render_observed(mhx_scene *s, void *out, uint32_t frames, uint32_t n_drives, const ModalDrive *drives, const float *signals, uint32_t n_pickups,
                         const ModalPickup *pickups, void *reads, uint8_t *read_flags, uint32_t n_junctions, const ModalJunction *junctions, const float *approach,
                         void *forces, double *compliances, uint8_t *statuses, const float *damping, void *carry) {
-    try {
-        const std::span<const ModalDrive> list(drives, n_drives);
-        const std::span<const ModalPickup> probes(pickups, n_pickups);
-        const std::span<const ModalJunction> contacts(junctions, n_junctions);
-        const std::span<const float> rates(damping, n_junctions);
-        if (s->dbl)
-            RenderModalObserved(s->audio64, list, signals, probes, static_cast<double *>(reads), contacts, approach, rates, std::span<double>(static_cast<double *>(carry), n_junctions),
-                                static_cast<double *>(forces), static_cast<double *>(out), frames, read_flags, compliances, statuses);
-        else
-            RenderModalObserved(s->audio, list, signals, probes, static_cast<float *>(reads), contacts, approach, rates, std::span<float>(static_cast<float *>(carry), n_junctions),
-                                static_cast<float *>(forces), static_cast<float *>(out), frames, read_flags, compliances, statuses);
-        return 0;
-    } catch (const std::exception &e) { g_error = e.what(); return 1; }
+    return RenderJunctions(s, Observed, {out, frames, n_drives, drives, signals, n_pickups, pickups, reads, read_flags, n_junctions, junctions, approach, forces, compliances, statuses, damping, carry});
 }
 // RenderModalMixed: mhx_render_observed's parameters, then the per-junction counts of frames that failed the residual test
 int mhx_render_mixed(mhx_scene *s, void *out, uint32_t frames, uint32_t n_drives, const ModalDrive *drives, const float *signals, uint32_t n_pickups,
                      const ModalPickup *pickups, void *reads, uint8_t *read_flags, uint32_t n_junctions, const ModalJunction *junctions, const float *approach,
                      void *forces, double *compliances, uint8_t *statuses, const float *damping, void *carry, uint32_t *unconverged) {
-    try {
-        const std::span<const ModalDrive> list(drives, n_drives);
-        const std::span<const ModalPickup> probes(pickups, n_pickups);
-        const std::span<const ModalJunction> contacts(junctions, n_junctions);
-        const std::span<const float> rates(damping, n_junctions);
-        const std::span<uint32_t> counts(unconverged, n_junctions);
-        if (s->dbl)
-            RenderModalMixed(s->audio64, list, signals, probes, static_cast<double *>(reads), contacts, approach, rates, std::span<double>(static_cast<double *>(carry), n_junctions),
-                             static_cast<double *>(forces), static_cast<double *>(out), frames, counts, read_flags, compliances, statuses);
-        else
-            RenderModalMixed(s->audio, list, signals, probes, static_cast<float *>(reads), contacts, approach, rates, std::span<float>(static_cast<float *>(carry), n_junctions),
-                             static_cast<float *>(forces), static_cast<float *>(out), frames, counts, read_flags, compliances, statuses);
-        return 0;
-    } catch (const std::exception &e) { g_error = e.what(); return 1; }
+    return RenderJunctions(s, Mixed, {out, frames, n_drives, drives, signals, n_pickups, pickups, reads, read_flags, n_junctions, junctions, approach, forces, compliances, statuses, damping, carry, unconverged});
 }
 // RenderModalDampedGroups: mhx_render_mixed's parameters
 int mhx_render_damped_groups(mhx_scene *s, void *out, uint32_t frames, uint32_t n_drives, const ModalDrive *drives, const float *signals, uint32_t n_pickups,
                              const ModalPickup *pickups, void *reads, uint8_t *read_flags, uint32_t n_junctions, const ModalJunction *junctions, const float *approach,
                              void *forces, double *compliances, uint8_t *statuses, const float *damping, void *carry, uint32_t *unconverged) {
-    try {
-        const std::span<const ModalDrive> list(drives, n_drives);
-        const std::span<const ModalPickup> probes(pickups, n_pickups);
-        const std::span<const ModalJunction> contacts(junctions, n_junctions);
-        const std::span<const float> rates(damping, n_junctions);
-        const std::span<uint32_t> counts(unconverged, n_junctions);
-        if (s->dbl)
-            RenderModalDampedGroups(s->audio64, list, signals, probes, static_cast<double *>(reads), contacts, approach, rates, std::span<double>(static_cast<double *>(carry), n_junctions),
-                                    static_cast<double *>(forces), static_cast<double *>(out), frames, counts, read_flags, compliances, statuses);
-        else
-            RenderModalDampedGroups(s->audio, list, signals, probes, static_cast<float *>(reads), contacts, approach, rates, std::span<float>(static_cast<float *>(carry), n_junctions),
-                                    static_cast<float *>(forces), static_cast<float *>(out), frames, counts, read_flags, compliances, statuses);
-        return 0;
-    } catch (const std::exception &e) { g_error = e.what(); return 1; }
+    return RenderJunctions(s, DampedGroups, {out, frames, n_drives, drives, signals, n_pickups, pickups, reads, read_flags, n_junctions, junctions, approach, forces, compliances, statuses, damping, carry, unconverged});
 }
 // Kernel timing of the scene's device context: enable / read one class (modalhip.h MH_KERNEL_*)
 int mhx_time_kernels(mhx_scene *s, int enable) {

@@ -1766,7 +1766,49 @@ struct Arena {
     ~Arena() { release(); }
 };
 
+// The junction groups of a call by what step 4 solves: linear members only (k_bank_modes_grouped), a Hertz member (mh_bank_render_mixed,
+// step 4m), a damped member (mh_bank_render_damped_groups, step 4g).  Each class has a launch of its own, and the device's list holds the
+// classes in this order.
+enum { LINEAR_GROUPS, HERTZ_GROUPS, DAMPED_GROUPS, GROUP_CLASSES };
+template<typename Real> struct GroupClass {
+    std::vector<GroupDev<Real>> groups; // in call order, until they take their place in the device's list
+    uint32_t widest{0}, members{0}; // the waves of the widest group; the junctions of all of them
+    uint32_t count() const { return uint32_t(groups.size()); }
+};
+
+// The render entries are a ladder: each admits what the one before it admits, plus one thing.  mh_bank_render, _driven and _read are the
+// coupled entry without junctions (and without pickups, without drives).
+enum class Entry {
+    Coupled, // junctions; MH_JUNCTION_DAMPED is ignored
+    Damped, // + damping and the carry
+    Observed, // + a pickup on a kept junction's object is read
+    Mixed, // + a Hertz junction may join a group (step 4m), unconverged_out
+    DampedGroups, // + a damped junction may join a group as well (step 4g)
+};
+// What the widest entry takes, in the order the entries name it; an entry leaves what it does not take at zero.
+struct RenderRequest {
+    Entry entry;
+    uint32_t frames;
+    float click_gain;
+    uint32_t n_impacts;
+    mh_impact *impacts;
+    uint32_t n_renderers;
+    const uint32_t *deal_offset, *deal_objects, *render_count, *tuned_count;
+    const float *out_gain, *listener_gain;
+    void *out;
+    double *object_energy;
+    uint32_t *object_live;
+    uint8_t *object_silenced;
+    double *object_modal_energy;
+    uint32_t n_drives{0}; const mh_drive *drives{nullptr}; const float *signals{nullptr};
+    uint32_t n_pickups{0}; const mh_pickup *pickups{nullptr}; void *pickup_out{nullptr}; uint8_t *pickup_read{nullptr};
+    uint32_t n_junctions{0}; const mh_junction *junctions{nullptr}; const float *approach{nullptr}; void *force_out{nullptr}; double *compliance_out{nullptr}; uint8_t *status_out{nullptr};
+    const float *damping{nullptr}; void *carry{nullptr};
+    uint32_t *unconverged_out{nullptr};
+};
+
 template<typename Real> struct BankImpl {
+    using Scalar = Real;
     mh_context *ctx;
     uint32_t n_objects, n_modes, n_shapes;
     DevArray<Real> coeff_re, coeff_im, state_re, state_im, rad_gain, phase_im, phase_re, shape_x, shape_y, shape_z;
@@ -1778,9 +1820,8 @@ template<typename Real> struct BankImpl {
     DevArray<Real> tap_states; // mh_bank_render_observed: what the tapped waves store, [tapped wave][frame][Im z | Re z][128]
     std::vector<uint8_t> on_junction; // per object: on a side of a junction of this call that was not left out
     std::vector<uint32_t> kept_rows; // the caller's indices of those junctions
-    std::vector<uint32_t> mixed_rows; // mh_bank_render_mixed: those of them that are members of a group with a Hertz member
-    std::vector<GroupDev<Real>> mixed_groups; // and those groups, until they take their place behind the other groups
-    std::vector<GroupDev<Real>> damped_groups; // mh_bank_render_damped_groups: the groups with a damped member, which follow those (their members are in mixed_rows too)
+    std::vector<uint32_t> mixed_rows; // mh_bank_render_mixed: those of them that are members of a group with a Hertz or a damped member
+    GroupClass<Real> group_class[GROUP_CLASSES]; // the call's groups by class
     // per-block scratch
     Arena arena;
     DevArray<Real> force, click, partial, chunk_energy, gain_scratch, rout;
@@ -1808,6 +1849,21 @@ template<typename T> void ensure(mh_context *ctx, DevArray<T> &a, size_t n) {
     if (a.count < n) a.reset(ctx, n + n / 4 + 16);
 }
 
+// A kernel's limit of dynamic LDS raised to the 160 KiB, once per (kernel, device): function attributes are per device, and the first
+// blocks of two banks may race.  (A table, not a PerDeviceOnce per call site: which kernel a junction launch takes is decided at run time.)
+void raise_lds_limit(int device, const void *kernel) {
+    constexpr int MaxKernels = 32; // the junction kernels: 12 per precision
+    static std::mutex guard;
+    static const void *raised[PerDeviceOnce::MaxDevices][MaxKernels];
+    const std::lock_guard<std::mutex> lock(guard);
+    const void **row = raised[device >= 0 && device < PerDeviceOnce::MaxDevices ? device : 0];
+    int n = 0;
+    while (n < MaxKernels && row[n] && row[n] != kernel) ++n;
+    if (n < MaxKernels && row[n] == kernel) return;
+    HIP_CHECK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    if (n < MaxKernels) row[n] = kernel; // (a full table would only set the attribute again)
+}
+
 template<typename Real, typename Src>
 void upload_converted(mh_context *ctx, DevArray<Real> &dst, size_t offset, const Src *src, size_t n) {
     if (!n) return;
@@ -1817,22 +1873,15 @@ void upload_converted(mh_context *ctx, DevArray<Real> &dst, size_t offset, const
 }
 
 template<typename Real>
-void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t n_impacts, mh_impact *impacts, uint32_t n_renderers, const uint32_t *deal_offset,
-                 const uint32_t *deal_objects, const uint32_t *render_count, const uint32_t *tuned_count, const float *out_gain, const float *listener_gain,
-                 void *out_v, double *object_energy, uint32_t *object_live, uint8_t *object_silenced, double *object_modal_energy, uint32_t n_drives,
-                 const mh_drive *drives, const float *signals, uint32_t n_pickups, const mh_pickup *pickups, void *pickup_out_v, uint8_t *pickup_read,
-                 uint32_t n_junctions, const mh_junction *junctions, const float *approach, void *force_out_v, double *compliance_out, uint8_t *status_out,
-                 const float *damping, void *carry_v, bool observe, uint32_t *unconverged_out, bool damped_in_groups) { // damping, carry_v: mh_bank_render_damped's; both null in every other entry (MH_JUNCTION_DAMPED is ignored then)
-    // observe: mh_bank_render_observed -- a pickup on a kept junction's object is read
-    // unconverged_out: mh_bank_render_mixed -- a Hertz junction may join a group (step 4m); null in every other entry
-    // damped_in_groups: mh_bank_render_damped_groups -- the mixed entry in which a damped junction may join a group as well (step 4g)
-    const bool mixed = unconverged_out != nullptr;
+void render_impl(BankImpl<Real> &B, const RenderRequest &r) {
+    const auto admits = [&](Entry e) { return r.entry >= e; }; // what the call's entry takes beyond the coupled one's (Entry)
+    const uint32_t frames = r.frames, n_impacts = r.n_impacts, n_renderers = r.n_renderers, n_drives = r.n_drives, n_pickups = r.n_pickups, n_junctions = r.n_junctions;
     mh_context *ctx = B.ctx;
     hipStream_t st = ctx->stream;
-    Real *out = static_cast<Real *>(out_v);
-    const uint32_t n_dealt = n_renderers ? deal_offset[n_renderers] : 0;
+    Real *out = static_cast<Real *>(r.out);
+    const uint32_t n_dealt = n_renderers ? r.deal_offset[n_renderers] : 0;
     uint32_t n_waves = 0;
-    for (uint32_t d = 0; d < n_dealt; ++d) n_waves += waves_of(render_count[d]);
+    for (uint32_t d = 0; d < n_dealt; ++d) n_waves += waves_of(r.render_count[d]);
     // ---- arena layout: [upload only | both ways | download only] ----
     Arena &A = B.arena;
     A.used = 0;
@@ -1847,8 +1896,8 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
     const size_t o_pick_ptr = A.take((n_dealt + 2) * 4), o_pick_dev = A.take((n_pickups + 1) * sizeof(PickupDev<Real>)), o_pick_rows = A.take((n_pickups + 1) * sizeof(PickupRows));
     const size_t o_excited = A.take((n_dealt + 1) * 4), o_junctions = A.take((n_junctions + 1) * sizeof(JunctionDev<Real>)), o_approach = A.take(size_t(n_junctions) * frames * sizeof(float));
     const size_t o_groups = A.take((n_junctions / 2 + 1) * sizeof(GroupDev<Real>));
-    const size_t o_damping = A.take(damping ? (n_junctions + 1) * sizeof(Real) : 0), o_carry_in = A.take(damping ? (n_junctions + 1) * sizeof(Real) : 0);
-    const size_t o_taps = A.take(observe ? (n_waves + 1) * sizeof(WaveDesc) : 0), o_tap_of = A.take(observe ? (n_waves + JUNCTION_WAVES + 1) * 4 : 0);
+    const size_t o_damping = A.take(admits(Entry::Damped) ? (n_junctions + 1) * sizeof(Real) : 0), o_carry_in = A.take(admits(Entry::Damped) ? (n_junctions + 1) * sizeof(Real) : 0);
+    const size_t o_taps = A.take(admits(Entry::Observed) ? (n_waves + 1) * sizeof(WaveDesc) : 0), o_tap_of = A.take(admits(Entry::Observed) ? (n_waves + JUNCTION_WAVES + 1) * 4 : 0);
     const size_t both_end = A.used;
     // (written by the kernels straight into the pinned arena -- no copy back: the host sees them once the block's last kernel has
     // raised the sequence number)
@@ -1856,8 +1905,8 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
     const size_t o_back = A.take((n_impacts + 1) * sizeof(ImpactBack<Real>));
     const size_t o_pick_out = A.take(size_t(n_pickups) * frames * sizeof(Real));
     const size_t o_junction_force = A.take(size_t(n_junctions) * frames * sizeof(Real)), o_compliance = A.take((n_junctions + 1) * 8), o_status = A.take((n_junctions + 1) * 4);
-    const size_t o_carry_out = A.take(damping ? (n_junctions + 1) * sizeof(Real) : 0);
-    const size_t o_unconverged = A.take(mixed ? (n_junctions + 1) * 4 : 0);
+    const size_t o_carry_out = A.take(admits(Entry::Damped) ? (n_junctions + 1) * sizeof(Real) : 0);
+    const size_t o_unconverged = A.take(admits(Entry::Mixed) ? (n_junctions + 1) * 4 : 0);
     const size_t total = A.used;
     if (total > A.cap) {
         HIP_CHECK(hipStreamSynchronize(st));
@@ -1868,52 +1917,49 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
     uint32_t *chunk_base = A.h<uint32_t>(o_chunk_base), *imp_ptr = A.h<uint32_t>(o_imp_ptr), *imp_idx = A.h<uint32_t>(o_imp_idx), *rcp = A.h<uint32_t>(o_rcp);
     B.dealt_of_object.assign(B.n_objects, -1);
     for (uint32_t d = 0; d < n_dealt; ++d)
-        if (deal_objects[d] < B.n_objects) B.dealt_of_object[deal_objects[d]] = int32_t(d);
+        if (r.deal_objects[d] < B.n_objects) B.dealt_of_object[r.deal_objects[d]] = int32_t(d);
     // ---- junctions: the ones the coupled kernel may follow, one workgroup each; everything else is left out with a zero row ----
     uint32_t n_coupled = 0, coupled_waves = 0, widest_junction = 0;
-    uint32_t n_groups = 0, widest_group = 0, grouped_members = 0; // components of two or more junctions: k_bank_modes_grouped, one workgroup each
-    uint32_t n_mixed = 0, widest_mixed = 0, mixed_members = 0; // those of them with a Hertz member (mh_bank_render_mixed): the entries with step 4m; they follow the others in the list
-    uint32_t n_damped_groups = 0, widest_damped = 0, damped_members = 0; // and those with a damped member (mh_bank_render_damped_groups): the entries with step 4g; they come last
+    uint32_t n_grouped = 0; // components of two or more junctions: k_bank_modes_grouped, one workgroup each, by class (GroupClass)
     B.mixed_rows.clear();
-    B.mixed_groups.clear();
-    B.damped_groups.clear();
+    for (auto &c : B.group_class) c.groups.clear(), c.widest = c.members = 0;
     bool any_hertz = false; // a kept junction with MH_JUNCTION_HERTZ: the call takes the entry that has the solve
     bool any_damped = false; // a kept junction with MH_JUNCTION_DAMPED: the entry that has both solves and the carry
-    const uint32_t flag_mask = damping ? ~0u : ~uint32_t(MH_JUNCTION_DAMPED);
+    const uint32_t flag_mask = admits(Entry::Damped) ? ~0u : ~uint32_t(MH_JUNCTION_DAMPED);
     B.kept_rows.clear();
     if (n_junctions) {
         JunctionDev<Real> *jd = A.h<JunctionDev<Real>>(o_junctions);
         GroupDev<Real> *gd = A.h<GroupDev<Real>>(o_groups);
         B.on_junction.assign(B.n_objects, 0);
         auto side_ok = [&](const mh_junction_side &sd) {
-            if (sd.object >= B.n_objects || B.h_mode_count[sd.object] == 0 || B.dealt_of_object[sd.object] < 0 || render_count[B.dealt_of_object[sd.object]] == 0) return false;
+            if (sd.object >= B.n_objects || B.h_mode_count[sd.object] == 0 || B.dealt_of_object[sd.object] < 0 || r.render_count[B.dealt_of_object[sd.object]] == 0) return false;
             return B.blend_ok(sd);
         };
-        auto side_waves = [&](const mh_junction_side &sd) { return waves_of(render_count[B.dealt_of_object[sd.object]]); };
+        auto side_waves = [&](const mh_junction_side &sd) { return waves_of(r.render_count[B.dealt_of_object[sd.object]]); };
         auto side_dev = [&](const mh_junction_side &sd) {
             const uint32_t d = uint32_t(B.dealt_of_object[sd.object]);
-            return JunctionSideDev<Real>{d, waves_of(render_count[d]), blend_dev<Real>(sd)};
+            return JunctionSideDev<Real>{d, waves_of(r.render_count[d]), blend_dev<Real>(sd)};
         };
         // which junctions are kept, and which share objects (modalhip_groups.hpp: one junction per object unless both carry MH_JUNCTION_SHARED)
         MhJunctionGroups grouping(B.n_objects);
         for (uint32_t j = 0; j < n_junctions; ++j) {
-            const mh_junction &m = junctions[j];
-            status_out[j] = MH_JUNCTION_LEFT_OUT;
-            compliance_out[j] = 0;
+            const mh_junction &m = r.junctions[j];
+            r.status_out[j] = MH_JUNCTION_LEFT_OUT;
+            r.compliance_out[j] = 0;
             const bool two_sided = m.b.object != MH_NO_OBJECT;
             if (!std::isfinite(m.stiffness) || m.stiffness < 0 || !side_ok(m.a) || (two_sided && (m.a.object == m.b.object || !side_ok(m.b)))) continue;
             if ((m.flags & MH_JUNCTION_HERTZ) && (m.flags & MH_JUNCTION_BILATERAL)) continue; // the Hertz law is unilateral
             if (m.flags & flag_mask & MH_JUNCTION_DAMPED) { // the damped law is unilateral too, and its l a finite number from 0 up
-                if ((m.flags & MH_JUNCTION_BILATERAL) || !std::isfinite(damping[j]) || damping[j] < 0) continue;
+                if ((m.flags & MH_JUNCTION_BILATERAL) || !std::isfinite(r.damping[j]) || r.damping[j] < 0) continue;
             }
-            if (grouping.add(j, m.flags & flag_mask, m.a.object, side_waves(m.a), m.b.object, two_sided ? side_waves(m.b) : 0u, mixed, damped_in_groups) < 0) continue;
+            if (grouping.add(j, m.flags & flag_mask, m.a.object, side_waves(m.a), m.b.object, two_sided ? side_waves(m.b) : 0u, admits(Entry::Mixed), admits(Entry::DampedGroups)) < 0) continue;
             B.on_junction[m.a.object] = 1;
             if (two_sided) B.on_junction[m.b.object] = 1;
             B.kept_rows.push_back(j);
         }
         // a component of one junction is an ordinary junction: the coupled kernel, one workgroup each, in call order
         for (const uint32_t j : B.kept_rows) {
-            const mh_junction &m = junctions[j];
+            const mh_junction &m = r.junctions[j];
             if (grouping.components[grouping.of_object[m.a.object]].members.size() != 1) continue;
             const bool two_sided = m.b.object != MH_NO_OBJECT;
             JunctionDev<Real> dev{{side_dev(m.a), two_sided ? side_dev(m.b) : JunctionSideDev<Real>{}}, Real(m.stiffness), m.flags & flag_mask, j, coupled_waves};
@@ -1937,12 +1983,12 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
                 if (g.n_objects == JUNCTION_WAVES) mh_throw(MH_EINVAL, "a junction group of more than %u objects", JUNCTION_WAVES); // (the grouping admits none)
                 const uint32_t s = g.n_objects++, d = uint32_t(B.dealt_of_object[sd.object]);
                 object_of_slot[s] = sd.object;
-                g.dealt[s] = d, g.wave0[s] = g.n_waves, g.waves[s] = waves_of(render_count[d]);
+                g.dealt[s] = d, g.wave0[s] = g.n_waves, g.waves[s] = waves_of(r.render_count[d]);
                 g.n_waves += g.waves[s];
                 return s;
             };
             for (uint32_t i = 0; i < g.n; ++i) {
-                const mh_junction &m = junctions[comp.members[i]];
+                const mh_junction &m = r.junctions[comp.members[i]];
                 const bool two_sided = m.b.object != MH_NO_OBJECT;
                 GroupMemberDev<Real> &dev = g.member[i];
                 dev.k = Real(m.stiffness), dev.flags = m.flags, dev.row = comp.members[i];
@@ -1952,36 +1998,26 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
             }
             if (g.n_waves > JUNCTION_WAVES) mh_throw(MH_EINVAL, "a junction group of %u waves", g.n_waves); // (the grouping admits none)
             coupled_waves += g.n_waves;
-            if (comp.damped) { // (a group has a damped member through mh_bank_render_damped_groups only)
-                B.damped_groups.push_back(g);
-                ++n_damped_groups;
-                damped_members += g.n;
-                widest_damped = std::max(widest_damped, g.n_waves);
-                B.mixed_rows.insert(B.mixed_rows.end(), comp.members.begin(), comp.members.end());
-                continue;
-            }
-            if (comp.hertz) { // parked until the others are known
-                B.mixed_groups.push_back(g);
-                ++n_mixed;
-                mixed_members += g.n;
-                widest_mixed = std::max(widest_mixed, g.n_waves);
-                B.mixed_rows.insert(B.mixed_rows.end(), comp.members.begin(), comp.members.end());
-                continue;
-            }
-            gd[n_groups++] = g;
-            grouped_members += g.n;
-            widest_group = std::max(widest_group, g.n_waves);
+            // (a group has a Hertz member through mh_bank_render_mixed and later only, a damped one through mh_bank_render_damped_groups only)
+            const int cls = comp.damped ? DAMPED_GROUPS : comp.hertz ? HERTZ_GROUPS : LINEAR_GROUPS;
+            GroupClass<Real> &c = B.group_class[cls];
+            c.groups.push_back(g);
+            c.members += g.n;
+            c.widest = std::max(c.widest, g.n_waves);
+            if (cls != LINEAR_GROUPS) B.mixed_rows.insert(B.mixed_rows.end(), comp.members.begin(), comp.members.end());
         }
-        std::copy(B.mixed_groups.begin(), B.mixed_groups.end(), gd + n_groups);
-        std::copy(B.damped_groups.begin(), B.damped_groups.end(), gd + n_groups + n_mixed);
+        for (const auto &c : B.group_class) { // the device's list: class after class
+            std::copy(c.groups.begin(), c.groups.end(), gd + n_grouped);
+            n_grouped += c.count();
+        }
     }
-    const bool any_junction = n_coupled || n_groups || n_mixed || n_damped_groups;
+    const bool any_junction = n_coupled || n_grouped;
     chunk_base[0] = 0;
     uint32_t main_waves = 0; // the main launch's waves: every dealt object that is not on a junction's side
     for (uint32_t d = 0; d < n_dealt; ++d) {
-        const uint32_t count = render_count[d];
+        const uint32_t count = r.render_count[d];
         chunk_base[d + 1] = chunk_base[d] + (count + LANES - 1) / LANES;
-        if (!(any_junction && deal_objects[d] < B.n_objects && B.on_junction[deal_objects[d]]))
+        if (!(any_junction && r.deal_objects[d] < B.n_objects && B.on_junction[r.deal_objects[d]]))
             for (uint32_t k = 0; k < count; k += MODES_PER_WAVE) waves[main_waves++] = {d, k};
         imp_ptr[d + 1] = 0;
     }
@@ -1989,16 +2025,16 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
     uint32_t max_imp = 1, driven_rows = 0;
     if (n_dealt) {
         for (uint32_t i = 0; i < n_impacts; ++i) {
-            const int32_t d = impacts[i].object < B.n_objects ? B.dealt_of_object[impacts[i].object] : -1;
+            const int32_t d = r.impacts[i].object < B.n_objects ? B.dealt_of_object[r.impacts[i].object] : -1;
             if (d >= 0) ++imp_ptr[d + 1];
         }
         // a drive the kernel must not follow is left out here: no such object, an object that was not dealt or has no modes, or an
         // excitation position beyond the object's shape columns (the read would leave the shape buffer)
         B.drive_dealt.assign(n_drives, -1);
         for (uint32_t j = 0; j < n_drives; ++j) {
-            const uint32_t o = drives[j].object;
+            const uint32_t o = r.drives[j].object;
             if (o >= B.n_objects || B.dealt_of_object[o] < 0 || B.h_mode_count[o] == 0) continue;
-            if ((uint64_t(drives[j].ex_pos) + 1) * B.h_mode_count[o] > B.shapes_held(o)) continue;
+            if ((uint64_t(r.drives[j].ex_pos) + 1) * B.h_mode_count[o] > B.shapes_held(o)) continue;
             B.drive_dealt[j] = B.dealt_of_object[o];
             ++imp_ptr[B.drive_dealt[j] + 1];
             ++driven_rows;
@@ -2009,7 +2045,7 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
         }
         B.imp_fill.assign(imp_ptr, imp_ptr + n_dealt);
         for (uint32_t i = 0; i < n_impacts; ++i) {
-            const int32_t d = impacts[i].object < B.n_objects ? B.dealt_of_object[impacts[i].object] : -1;
+            const int32_t d = r.impacts[i].object < B.n_objects ? B.dealt_of_object[r.impacts[i].object] : -1;
             if (d >= 0) imp_idx[B.imp_fill[d]++] = i;
         }
         for (uint32_t j = 0; j < n_drives; ++j) // behind the object's impacts, in the caller's order
@@ -2021,7 +2057,7 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
         uint32_t *excited = A.h<uint32_t>(o_excited);
         excited[0] = 0;
         for (uint32_t d = 0; d < n_dealt; ++d)
-            excited[d + 1] = excited[d] + (imp_ptr[d + 1] - imp_ptr[d]) + (deal_objects[d] < B.n_objects && B.on_junction[deal_objects[d]] ? 1u : 0u);
+            excited[d + 1] = excited[d] + (imp_ptr[d + 1] - imp_ptr[d]) + (r.deal_objects[d] < B.n_objects && B.on_junction[r.deal_objects[d]] ? 1u : 0u);
     }
     // ---- pickups: the ones the kernel may follow, grouped by dealt object in the caller's order; everything else gets a zero row ----
     uint32_t read_row_count = 0, picks_dealt = 0, picks_main = 0; // pickups with rows; those of them whose object the main launch renders
@@ -2035,17 +2071,17 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
         B.picks_on.assign(B.n_objects, 0);
         B.pick_dealt.assign(n_pickups, -1);
         for (uint32_t q = 0; q < n_pickups; ++q) {
-            const mh_pickup &m = pickups[q];
-            pickup_read[q] = 0;
+            const mh_pickup &m = r.pickups[q];
+            r.pickup_read[q] = 0;
             pick_rows[q] = {0, 0};
             if (m.object >= B.n_objects || B.h_mode_count[m.object] == 0 || m.advance > 2) continue;
             const bool junction_object = any_junction && B.on_junction[m.object];
-            if (junction_object && !observe) continue; // its waves are the coupled kernel's, which reads for no pickup except in mh_bank_render_observed
+            if (junction_object && !admits(Entry::Observed)) continue; // its waves are the coupled kernel's, which reads for no pickup except in mh_bank_render_observed
             if (!B.blend_ok(m) || B.picks_on[m.object] >= MH_PICKUPS_PER_OBJECT) continue;
             ++B.picks_on[m.object];
-            pickup_read[q] = 1;
+            r.pickup_read[q] = 1;
             const int32_t d = B.dealt_of_object[m.object];
-            if (d < 0 || render_count[d] == 0) continue; // at rest: read, and all zeros
+            if (d < 0 || r.render_count[d] == 0) continue; // at rest: read, and all zeros
             B.pick_dealt[q] = d;
             ++pick_ptr[d + 1];
             ++picks_dealt;
@@ -2056,15 +2092,15 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
         for (uint32_t q = 0; q < n_pickups; ++q) {
             const int32_t d = B.pick_dealt[q];
             if (d < 0) continue;
-            const mh_pickup &m = pickups[q];
-            pick_rows[q] = {read_row_count, 2 * waves_of(render_count[d])}; // a row per (wave, half) of the object
+            const mh_pickup &m = r.pickups[q];
+            pick_rows[q] = {read_row_count, 2 * waves_of(r.render_count[d])}; // a row per (wave, half) of the object
             pick_dev[B.pick_fill[d]++] = {blend_dev<Real>(m), m.advance, read_row_count};
             read_row_count += pick_rows[q].n_rows;
-            picked_modes += render_count[d];
+            picked_modes += r.render_count[d];
         }
         // the waves of the junction launches that store their states: every wave of a junction object that carries a pickup, by its index
         // among those launches' waves
-        if (observe && picks_dealt > picks_main) {
+        if (admits(Entry::Observed) && picks_dealt > picks_main) {
             WaveDesc *taps = A.h<WaveDesc>(o_taps);
             uint32_t *tap_of = A.h<uint32_t>(o_tap_of);
             std::fill(tap_of, tap_of + n_waves + JUNCTION_WAVES + 1, NO_TAP);
@@ -2081,36 +2117,36 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
                 if (jd[j].side[1].waves) tap_object(jd[j].side[1].dealt, jd[j].first_wave + jd[j].side[0].waves, jd[j].side[1].waves);
             }
             const GroupDev<Real> *gd = A.h<GroupDev<Real>>(o_groups);
-            for (uint32_t g = 0; g < n_groups + n_mixed + n_damped_groups; ++g)
+            for (uint32_t g = 0; g < n_grouped; ++g)
                 for (uint32_t o = 0; o < gd[g].n_objects; ++o) tap_object(gd[g].dealt[o], gd[g].first_wave + gd[g].wave0[o], gd[g].waves[o]);
         }
     }
     for (uint32_t q = 0; q <= n_renderers; ++q) {
-        const uint32_t d0 = q < n_renderers ? deal_offset[q] : n_dealt;
+        const uint32_t d0 = q < n_renderers ? r.deal_offset[q] : n_dealt;
         rcp[q] = chunk_base[std::min(d0, n_dealt)];
     }
     const uint32_t n_chunks = chunk_base[n_dealt];
-    std::copy(out_gain, out_gain + B.n_objects, A.h<Real>(o_out_gain));
-    std::copy(listener_gain, listener_gain + B.n_objects, A.h<Real>(o_listener));
-    std::copy(deal_objects, deal_objects + n_dealt, A.h<uint32_t>(o_deal));
-    std::copy(render_count, render_count + n_dealt, A.h<uint32_t>(o_count));
-    std::copy(tuned_count, tuned_count + n_dealt, A.h<uint32_t>(o_tuned));
+    std::copy(r.out_gain, r.out_gain + B.n_objects, A.h<Real>(o_out_gain));
+    std::copy(r.listener_gain, r.listener_gain + B.n_objects, A.h<Real>(o_listener));
+    std::copy(r.deal_objects, r.deal_objects + n_dealt, A.h<uint32_t>(o_deal));
+    std::copy(r.render_count, r.render_count + n_dealt, A.h<uint32_t>(o_count));
+    std::copy(r.tuned_count, r.tuned_count + n_dealt, A.h<uint32_t>(o_tuned));
     std::copy(out, out + frames, A.h<Real>(o_out));
     ImpactDev<Real> *himp = A.h<ImpactDev<Real>>(o_impacts);
     for (uint32_t i = 0; i < n_impacts; ++i) {
-        const mh_impact &m = impacts[i];
+        const mh_impact &m = r.impacts[i];
         himp[i] = {m.object, m.ex_pos, m.samples_left, 0, Real(m.jx), Real(m.jy), Real(m.jz), Real(m.phase_re), Real(m.phase_im), Real(m.rot_re), Real(m.rot_im),
                    Real(m.gamma), Real(m.accel_amp), Real(m.click_b0), Real(m.click_a1), Real(m.click_a2), Real(m.click_z1), Real(m.click_z2)};
     }
     for (uint32_t j = 0; j < n_drives; ++j) { // only object, ex_pos and the direction are read of a drive's entry
-        const mh_drive &m = drives[j];
+        const mh_drive &m = r.drives[j];
         himp[n_impacts + j] = {m.object, m.ex_pos, 0, 0, Real(m.jx), Real(m.jy), Real(m.jz), 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     }
-    if (n_drives) std::copy(signals, signals + size_t(n_drives) * frames, A.h<float>(o_signals));
-    if (any_junction) std::copy(approach, approach + size_t(n_junctions) * frames, A.h<float>(o_approach));
-    if (any_damped || n_damped_groups) {
-        std::copy(damping, damping + n_junctions, A.h<Real>(o_damping));
-        std::copy(static_cast<const Real *>(carry_v), static_cast<const Real *>(carry_v) + n_junctions, A.h<Real>(o_carry_in));
+    if (n_drives) std::copy(r.signals, r.signals + size_t(n_drives) * frames, A.h<float>(o_signals));
+    if (any_junction) std::copy(r.approach, r.approach + size_t(n_junctions) * frames, A.h<float>(o_approach));
+    if (any_damped || B.group_class[DAMPED_GROUPS].count()) {
+        std::copy(r.damping, r.damping + n_junctions, A.h<Real>(o_damping));
+        std::copy(static_cast<const Real *>(r.carry), static_cast<const Real *>(r.carry) + n_junctions, A.h<Real>(o_carry_in));
     }
     HIP_CHECK(hipMemcpyAsync(A.dev, A.host, both_end, hipMemcpyHostToDevice, st));
     // ---- device passes ----
@@ -2119,7 +2155,7 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
     ensure(ctx, B.force, size_t(std::max<uint32_t>(n_rows, 1)) * frames);
     ensure(ctx, B.click, size_t(std::max<uint32_t>(n_impacts, 1)) * frames);
     if (n_impacts) {
-        k_bank_forces<Real><<<div_up(n_impacts, 64), 64, 0, st>>>(d_impacts, n_impacts, d_listener, Real(click_gain), frames, B.force, B.click, A.hd<ImpactBack<Real>>(o_back));
+        k_bank_forces<Real><<<div_up(n_impacts, 64), 64, 0, st>>>(d_impacts, n_impacts, d_listener, Real(r.click_gain), frames, B.force, B.click, A.hd<ImpactBack<Real>>(o_back));
         KERNEL_CHECK();
     }
     if (n_drives) {
@@ -2138,95 +2174,40 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
                                              A.d<uint32_t>(o_imp_idx), d_impacts, B.force, d_out_gain, d_listener, frames, B.partial, B.chunk_energy, scratch, max_imp, more...);
             KERNEL_CHECK();
         };
-        if (n_coupled) { // the junctions' objects: a launch of their own, one workgroup per junction
+        // A launch of junction objects, one workgroup per junction or per group: the scratch gain rows, the kernel's LDS limit, the bound on
+        // the widest workgroup, and the kernel -- when some junction object carries a pickup, the one that also stores the tapped waves' states.
+        // solved: the junctions the launch solves per frame (MH_KERNEL_JUNCTION's work).
+        static_assert(coupled_lds<Real>(JUNCTION_WAVES) <= 160 * 1024 && grouped_lds<Real>(JUNCTION_WAVES) <= 160 * 1024, "the junction kernels' LDS within the 160 KiB");
+        auto launch_junctions = [&](auto *plain, auto *observed, const auto &args, uint32_t workgroups, uint32_t widest, size_t lds, uint32_t solved) {
+            if (!workgroups) return;
+            if (lds > 160 * 1024) mh_throw(MH_EINVAL, "a junction workgroup of %u waves", widest); // (none is kept)
             ensure(ctx, B.junction_gain, size_t(coupled_waves + JUNCTION_WAVES) * max_imp * MODES_PER_WAVE);
-            static PerDeviceOnce attr;
-            attr.run(ctx->device, [] {
-                HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_bank_modes_coupled<Real>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_bank_modes_coupled_hertz<Real>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_bank_modes_coupled_damped<Real>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            });
-            const CoupledArgs<Real> ca{B.defl_gain, A.d<JunctionDev<Real>>(o_junctions), A.d<float>(o_approach), A.hd<Real>(o_junction_force), A.hd<double>(o_compliance), A.hd<uint32_t>(o_status)};
-            TimedLaunch timed(ctx, MH_KERNEL_JUNCTION, double(n_coupled) * double(frames));
-            if (n_taps) { // some junction object carries a pickup: the entries that also store the tapped waves' states
-                static_assert(coupled_lds<double>(JUNCTION_WAVES) <= 160 * 1024 && coupled_lds<float>(JUNCTION_WAVES) <= 160 * 1024, "the coupled entries' LDS within the 160 KiB");
-                if (coupled_lds<Real>(widest_junction) > 160 * 1024) mh_throw(MH_EINVAL, "a junction of %u waves", widest_junction); // (none is kept)
-                static PerDeviceOnce observed_attr;
-                observed_attr.run(ctx->device, [] {
-                    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_bank_modes_coupled_observed<Real>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_bank_modes_coupled_hertz_observed<Real>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                    HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_bank_modes_coupled_damped_observed<Real>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                });
-                ensure(ctx, B.tap_states, size_t(n_taps) * frames * TAP_FRAME);
-                if (any_damped) {
-                    const ObservedArgs<Real, DampedArgs<Real>> oa{{ca, A.d<Real>(o_damping), A.d<Real>(o_carry_in), A.hd<Real>(o_carry_out)}, A.d<uint32_t>(o_tap_of), B.tap_states};
-                    launch_modes(k_bank_modes_coupled_damped_observed<Real>, n_coupled, widest_junction * WAVE, coupled_lds<Real>(widest_junction), B.junction_gain, oa);
-                } else {
-                    const ObservedArgs<Real, CoupledArgs<Real>> oa{ca, A.d<uint32_t>(o_tap_of), B.tap_states};
-                    launch_modes(any_hertz ? k_bank_modes_coupled_hertz_observed<Real> : k_bank_modes_coupled_observed<Real>, n_coupled, widest_junction * WAVE, coupled_lds<Real>(widest_junction), B.junction_gain, oa);
-                }
-            } else if (any_damped) {
-                const DampedArgs<Real> da{ca, A.d<Real>(o_damping), A.d<Real>(o_carry_in), A.hd<Real>(o_carry_out)};
-                launch_modes(k_bank_modes_coupled_damped<Real>, n_coupled, widest_junction * WAVE, coupled_lds<Real>(widest_junction), B.junction_gain, da);
-            } else {
-                launch_modes(any_hertz ? k_bank_modes_coupled_hertz<Real> : &k_bank_modes_coupled<Real>, n_coupled, widest_junction * WAVE, coupled_lds<Real>(widest_junction), B.junction_gain, ca);
-            }
-        }
-        if (n_groups) { // the groups' objects: a launch of their own, one workgroup per group
-            ensure(ctx, B.junction_gain, size_t(coupled_waves + JUNCTION_WAVES) * max_imp * MODES_PER_WAVE);
-            static PerDeviceOnce attr;
-            attr.run(ctx->device, [] { HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_bank_modes_grouped<Real>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); });
-            const GroupedArgs<Real> ga{B.defl_gain, A.d<GroupDev<Real>>(o_groups), A.d<float>(o_approach), A.hd<Real>(o_junction_force), A.hd<double>(o_compliance), A.hd<uint32_t>(o_status)};
-            TimedLaunch timed(ctx, MH_KERNEL_JUNCTION, double(grouped_members) * double(frames));
-            if (n_taps) {
-                static_assert(grouped_lds<double>(JUNCTION_WAVES) <= 160 * 1024 && grouped_lds<float>(JUNCTION_WAVES) <= 160 * 1024, "the grouped entries' LDS within the 160 KiB");
-                if (grouped_lds<Real>(widest_group) > 160 * 1024) mh_throw(MH_EINVAL, "a junction group of %u waves", widest_group); // (none is kept)
-                static PerDeviceOnce observed_attr;
-                observed_attr.run(ctx->device, [] { HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_bank_modes_grouped_observed<Real>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); });
-                ensure(ctx, B.tap_states, size_t(n_taps) * frames * TAP_FRAME);
-                const ObservedArgs<Real, GroupedArgs<Real>> oa{ga, A.d<uint32_t>(o_tap_of), B.tap_states};
-                launch_modes(k_bank_modes_grouped_observed<Real>, n_groups, widest_group * WAVE, grouped_lds<Real>(widest_group), B.junction_gain, oa);
-            } else {
-                launch_modes(&k_bank_modes_grouped<Real>, n_groups, widest_group * WAVE, grouped_lds<Real>(widest_group), B.junction_gain, ga);
-            }
-        }
-        if (n_mixed) { // the groups with a Hertz member (mh_bank_render_mixed): the entries with step 4m, one workgroup per group
-            ensure(ctx, B.junction_gain, size_t(coupled_waves + JUNCTION_WAVES) * max_imp * MODES_PER_WAVE);
-            static PerDeviceOnce attr;
-            attr.run(ctx->device, [] {
-                HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_bank_modes_grouped_mixed<Real>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_bank_modes_grouped_mixed_observed<Real>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            });
-            if (grouped_lds<Real>(widest_mixed) > 160 * 1024) mh_throw(MH_EINVAL, "a junction group of %u waves", widest_mixed); // (none is kept)
-            const MixedArgs<Real> ma{{B.defl_gain, A.d<GroupDev<Real>>(o_groups) + n_groups, A.d<float>(o_approach), A.hd<Real>(o_junction_force), A.hd<double>(o_compliance), A.hd<uint32_t>(o_status)}, A.hd<uint32_t>(o_unconverged)};
-            TimedLaunch timed(ctx, MH_KERNEL_JUNCTION, double(mixed_members) * double(frames));
-            if (n_taps) {
-                ensure(ctx, B.tap_states, size_t(n_taps) * frames * TAP_FRAME);
-                const ObservedArgs<Real, MixedArgs<Real>> oa{ma, A.d<uint32_t>(o_tap_of), B.tap_states};
-                launch_modes(k_bank_modes_grouped_mixed_observed<Real>, n_mixed, widest_mixed * WAVE, grouped_lds<Real>(widest_mixed), B.junction_gain, oa);
-            } else {
-                launch_modes(k_bank_modes_grouped_mixed<Real>, n_mixed, widest_mixed * WAVE, grouped_lds<Real>(widest_mixed), B.junction_gain, ma);
-            }
-        }
-        if (n_damped_groups) { // the groups with a damped member (mh_bank_render_damped_groups): the entries with step 4g, one workgroup per group
-            ensure(ctx, B.junction_gain, size_t(coupled_waves + JUNCTION_WAVES) * max_imp * MODES_PER_WAVE);
-            static PerDeviceOnce attr;
-            attr.run(ctx->device, [] {
-                HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_bank_modes_grouped_damped<Real>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(k_bank_modes_grouped_damped_observed<Real>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            });
-            if (grouped_lds<Real>(widest_damped) > 160 * 1024) mh_throw(MH_EINVAL, "a junction group of %u waves", widest_damped); // (none is kept)
-            const DampedGroupArgs<Real> da{{{B.defl_gain, A.d<GroupDev<Real>>(o_groups) + n_groups + n_mixed, A.d<float>(o_approach), A.hd<Real>(o_junction_force), A.hd<double>(o_compliance), A.hd<uint32_t>(o_status)}, A.hd<uint32_t>(o_unconverged)},
-                                           A.d<Real>(o_damping), A.d<Real>(o_carry_in), A.hd<Real>(o_carry_out)};
-            TimedLaunch timed(ctx, MH_KERNEL_JUNCTION, double(damped_members) * double(frames));
-            if (n_taps) {
-                ensure(ctx, B.tap_states, size_t(n_taps) * frames * TAP_FRAME);
-                const ObservedArgs<Real, DampedGroupArgs<Real>> oa{da, A.d<uint32_t>(o_tap_of), B.tap_states};
-                launch_modes(k_bank_modes_grouped_damped_observed<Real>, n_damped_groups, widest_damped * WAVE, grouped_lds<Real>(widest_damped), B.junction_gain, oa);
-            } else {
-                launch_modes(k_bank_modes_grouped_damped<Real>, n_damped_groups, widest_damped * WAVE, grouped_lds<Real>(widest_damped), B.junction_gain, da);
-            }
-        }
+            if (n_taps) ensure(ctx, B.tap_states, size_t(n_taps) * frames * TAP_FRAME);
+            raise_lds_limit(ctx->device, n_taps ? reinterpret_cast<const void *>(observed) : reinterpret_cast<const void *>(plain));
+            TimedLaunch timed(ctx, MH_KERNEL_JUNCTION, double(solved) * double(frames));
+            if (n_taps) launch_modes(observed, workgroups, widest * WAVE, lds, B.junction_gain, ObservedArgs<Real, std::decay_t<decltype(args)>>{args, A.d<uint32_t>(o_tap_of), B.tap_states});
+            else launch_modes(plain, workgroups, widest * WAVE, lds, B.junction_gain, args);
+        };
+        Real *d_damping = A.d<Real>(o_damping), *d_carry_in = A.d<Real>(o_carry_in), *carry_out = A.hd<Real>(o_carry_out);
+        // lone junctions: the kernel with the laws the kept ones need
+        const CoupledArgs<Real> ca{B.defl_gain, A.d<JunctionDev<Real>>(o_junctions), A.d<float>(o_approach), A.hd<Real>(o_junction_force), A.hd<double>(o_compliance), A.hd<uint32_t>(o_status)};
+        if (any_damped)
+            launch_junctions(k_bank_modes_coupled_damped<Real>, k_bank_modes_coupled_damped_observed<Real>, DampedArgs<Real>{ca, d_damping, d_carry_in, carry_out}, n_coupled, widest_junction,
+                             coupled_lds<Real>(widest_junction), n_coupled);
+        else
+            launch_junctions(any_hertz ? k_bank_modes_coupled_hertz<Real> : &k_bank_modes_coupled<Real>, any_hertz ? k_bank_modes_coupled_hertz_observed<Real> : k_bank_modes_coupled_observed<Real>, ca,
+                             n_coupled, widest_junction, coupled_lds<Real>(widest_junction), n_coupled);
+        // groups, class after class: each class's entries of the device's list follow those of the class before
+        const GroupClass<Real> &linear = B.group_class[LINEAR_GROUPS], &hertz = B.group_class[HERTZ_GROUPS], &damped = B.group_class[DAMPED_GROUPS];
+        auto groups_from = [&](uint32_t first) {
+            return GroupedArgs<Real>{B.defl_gain, A.d<GroupDev<Real>>(o_groups) + first, A.d<float>(o_approach), A.hd<Real>(o_junction_force), A.hd<double>(o_compliance), A.hd<uint32_t>(o_status)};
+        };
+        launch_junctions(&k_bank_modes_grouped<Real>, k_bank_modes_grouped_observed<Real>, groups_from(0), linear.count(), linear.widest, grouped_lds<Real>(linear.widest), linear.members);
+        launch_junctions(k_bank_modes_grouped_mixed<Real>, k_bank_modes_grouped_mixed_observed<Real>, MixedArgs<Real>{groups_from(linear.count()), A.hd<uint32_t>(o_unconverged)}, hertz.count(), hertz.widest,
+                         grouped_lds<Real>(hertz.widest), hertz.members);
+        launch_junctions(k_bank_modes_grouped_damped<Real>, k_bank_modes_grouped_damped_observed<Real>,
+                         DampedGroupArgs<Real>{{groups_from(linear.count() + hertz.count()), A.hd<uint32_t>(o_unconverged)}, d_damping, d_carry_in, carry_out}, damped.count(), damped.widest,
+                         grouped_lds<Real>(damped.widest), damped.members);
         if (n_taps) { // the tapped waves' partial rows, in k_bank_modes_read's order; they join read_rows ahead of k_bank_read_rows
             ensure(ctx, B.read_rows, size_t(read_row_count + 1) * frames);
             const ReadArgs<Real> rd{B.defl_gain, A.d<uint32_t>(o_pick_ptr), A.d<PickupDev<Real>>(o_pick_dev), B.read_rows, 0u};
@@ -2237,10 +2218,10 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
         }
         if (main_waves) {
             uint64_t rendered_modes = 0;
-            for (uint32_t d = 0; d < n_dealt; ++d) rendered_modes += render_count[d];
+            for (uint32_t d = 0; d < n_dealt; ++d) rendered_modes += r.render_count[d];
             uint64_t driven_modes = 0; // a drive row adds a multiply and an add per mode-sample of its object
             for (uint32_t j = 0; j < n_drives; ++j)
-                if (B.drive_dealt[j] >= 0) driven_modes += render_count[B.drive_dealt[j]];
+                if (B.drive_dealt[j] >= 0) driven_modes += r.render_count[B.drive_dealt[j]];
             TimedLaunch timed(ctx, MH_KERNEL_BANK, (11.0 * double(rendered_modes) + 2.0 * double(driven_modes) + 4.0 * double(picked_modes)) * double(frames)); // ~11 flop per mode-sample
             // a block without drives launches what it always did; one with drives takes the launch with the many-row loop (and its
             // LDS) only when some object has more rows than the register path holds
@@ -2282,38 +2263,38 @@ void render_impl(BankImpl<Real> &B, uint32_t frames, float click_gain, uint32_t 
     A.template mix_and_wait<Real>(st, B.click, clicks_in_mix, B.rout, n_renderers, frames, o_out);
     std::copy(A.h<Real>(o_out), A.h<Real>(o_out) + frames, out);
     if (n_dealt) {
-        std::copy(A.h<double>(o_energy), A.h<double>(o_energy) + n_dealt, object_energy);
-        std::copy(A.h<uint32_t>(o_live), A.h<uint32_t>(o_live) + n_dealt, object_live);
-        std::copy(A.h<uint8_t>(o_silenced), A.h<uint8_t>(o_silenced) + n_dealt, object_silenced);
-        if (object_modal_energy) std::copy(A.h<double>(o_modal), A.h<double>(o_modal) + n_dealt, object_modal_energy);
+        std::copy(A.h<double>(o_energy), A.h<double>(o_energy) + n_dealt, r.object_energy);
+        std::copy(A.h<uint32_t>(o_live), A.h<uint32_t>(o_live) + n_dealt, r.object_live);
+        std::copy(A.h<uint8_t>(o_silenced), A.h<uint8_t>(o_silenced) + n_dealt, r.object_silenced);
+        if (r.object_modal_energy) std::copy(A.h<double>(o_modal), A.h<double>(o_modal) + n_dealt, r.object_modal_energy);
     }
     if (n_pickups) {
-        Real *pickup_out = static_cast<Real *>(pickup_out_v);
+        Real *pickup_out = static_cast<Real *>(r.pickup_out);
         if (picks_dealt) std::copy(A.h<Real>(o_pick_out), A.h<Real>(o_pick_out) + size_t(n_pickups) * frames, pickup_out);
         else std::fill(pickup_out, pickup_out + size_t(n_pickups) * frames, Real(0));
     }
     if (n_junctions) { // rows, compliances and statuses of the solved ones; a junction that was left out keeps its zero row
-        Real *force_out = static_cast<Real *>(force_out_v);
+        Real *force_out = static_cast<Real *>(r.force_out);
         std::fill(force_out, force_out + size_t(n_junctions) * frames, Real(0));
         for (const uint32_t j : B.kept_rows) {
             std::copy(A.h<Real>(o_junction_force) + size_t(j) * frames, A.h<Real>(o_junction_force) + size_t(j + 1) * frames, force_out + size_t(j) * frames);
-            compliance_out[j] = A.h<double>(o_compliance)[j];
-            status_out[j] = uint8_t(A.h<uint32_t>(o_status)[j]);
+            r.compliance_out[j] = A.h<double>(o_compliance)[j];
+            r.status_out[j] = uint8_t(A.h<uint32_t>(o_status)[j]);
         }
-        if (mixed) { // a member of a group with a Hertz member: its frames that failed the residual test; 0 for every other junction
-            std::fill(unconverged_out, unconverged_out + n_junctions, 0u);
-            for (const uint32_t j : B.mixed_rows) unconverged_out[j] = A.h<uint32_t>(o_unconverged)[j];
+        if (admits(Entry::Mixed)) { // a member of a group with a Hertz or a damped member: its frames that failed the residual test; 0 for every other junction
+            std::fill(r.unconverged_out, r.unconverged_out + n_junctions, 0u);
+            for (const uint32_t j : B.mixed_rows) r.unconverged_out[j] = A.h<uint32_t>(o_unconverged)[j];
         }
-        if (carry_v) { // the carry of a damped junction that was solved; a quiet NaN for every other junction
-            Real *carry = static_cast<Real *>(carry_v);
+        if (admits(Entry::Damped)) { // the carry of a damped junction that was solved; a quiet NaN for every other junction
+            Real *carry = static_cast<Real *>(r.carry);
             std::fill(carry, carry + n_junctions, std::numeric_limits<Real>::quiet_NaN());
             for (const uint32_t j : B.kept_rows)
-                if ((junctions[j].flags & MH_JUNCTION_DAMPED) && status_out[j] == MH_JUNCTION_SOLVED) carry[j] = A.h<Real>(o_carry_out)[j];
+                if ((r.junctions[j].flags & MH_JUNCTION_DAMPED) && r.status_out[j] == MH_JUNCTION_SOLVED) carry[j] = A.h<Real>(o_carry_out)[j];
         }
     }
     const ImpactBack<Real> *back = A.h<ImpactBack<Real>>(o_back);
     for (uint32_t i = 0; i < n_impacts; ++i) {
-        mh_impact &m = impacts[i];
+        mh_impact &m = r.impacts[i];
         m.samples_left = back[i].samples_left;
         m.phase_re = double(back[i].phase_re);
         m.phase_im = double(back[i].phase_im);
@@ -2329,6 +2310,11 @@ struct mh_bank {
     std::unique_ptr<BankImpl<float>> f;
     std::unique_ptr<BankImpl<double>> d;
 };
+// f(the bank's implementation), in the bank's precision
+template<typename Bank, typename F> static void in_precision(Bank *bank, F &&f) {
+    if (bank->dbl) f(*bank->d);
+    else f(*bank->f);
+}
 
 template<typename Real>
 static std::unique_ptr<BankImpl<Real>> make_bank(mh_context *ctx, uint32_t n_objects, uint32_t n_modes, uint32_t n_shapes, const uint32_t *mode_offset,
@@ -2385,8 +2371,8 @@ int mh_bank_set_coefficients(mh_bank *bank, uint32_t first, uint32_t count, cons
     if (!bank || (count && (!coeff_re || !coeff_im || !radiation_gain || !out_phase_im || !out_phase_re))) return MH_EINVAL;
     try {
         HIP_CHECK(hipSetDevice(bank->ctx->device));
-        auto go = [&](auto &B, auto tag) {
-            using Real = decltype(tag);
+        auto go = [&](auto &B) {
+            using Real = typename std::decay_t<decltype(B)>::Scalar;
             if (size_t(first) + count > B.n_modes) mh_throw(MH_EINVAL, "mode range [%u, %u) outside the bank's %u modes", first, first + count, B.n_modes);
             upload_converted(bank->ctx, B.coeff_re, first, static_cast<const Real *>(coeff_re), count);
             upload_converted(bank->ctx, B.coeff_im, first, static_cast<const Real *>(coeff_im), count);
@@ -2394,7 +2380,7 @@ int mh_bank_set_coefficients(mh_bank *bank, uint32_t first, uint32_t count, cons
             upload_converted(bank->ctx, B.phase_im, first, static_cast<const Real *>(out_phase_im), count);
             upload_converted(bank->ctx, B.phase_re, first, static_cast<const Real *>(out_phase_re), count);
         };
-        if (bank->dbl) go(*bank->d, double{}); else go(*bank->f, float{});
+        in_precision(bank, go);
         return MH_OK;
     } catch (const std::exception &e) { return mh_guard(bank->ctx, e); }
 }
@@ -2408,7 +2394,7 @@ int mh_bank_set_shapes(mh_bank *bank, uint32_t first, uint32_t count, const floa
             upload_converted(bank->ctx, B.shape_y, first, y, count);
             upload_converted(bank->ctx, B.shape_z, first, z, count);
         };
-        if (bank->dbl) go(*bank->d); else go(*bank->f);
+        in_precision(bank, go);
         return MH_OK;
     } catch (const std::exception &e) { return mh_guard(bank->ctx, e); }
 }
@@ -2417,14 +2403,14 @@ int mh_bank_zero_state(mh_bank *bank, uint32_t first, uint32_t count) {
     try {
         HIP_CHECK(hipSetDevice(bank->ctx->device));
         auto go = [&](auto &B) {
-            using Real = std::remove_pointer_t<decltype(B.state_re.get())>;
+            using Real = typename std::decay_t<decltype(B)>::Scalar;
             if (size_t(first) + count > B.n_modes) mh_throw(MH_EINVAL, "mode range outside the bank");
             if (!count) return;
             HIP_CHECK(hipMemsetAsync(B.state_re.get() + first, 0, count * sizeof(Real), bank->ctx->stream));
             HIP_CHECK(hipMemsetAsync(B.state_im.get() + first, 0, count * sizeof(Real), bank->ctx->stream));
             HIP_CHECK(hipStreamSynchronize(bank->ctx->stream));
         };
-        if (bank->dbl) go(*bank->d); else go(*bank->f);
+        in_precision(bank, go);
         return MH_OK;
     } catch (const std::exception &e) { return mh_guard(bank->ctx, e); }
 }
@@ -2432,47 +2418,60 @@ int mh_bank_set_deflection_gain(mh_bank *bank, uint32_t first, uint32_t count, c
     if (!bank || (count && !deflection_gain)) return MH_EINVAL;
     try {
         HIP_CHECK(hipSetDevice(bank->ctx->device));
-        auto go = [&](auto &B, auto tag) {
-            using Real = decltype(tag);
+        auto go = [&](auto &B) {
+            using Real = typename std::decay_t<decltype(B)>::Scalar;
             if (size_t(first) + count > B.n_modes) mh_throw(MH_EINVAL, "mode range [%u, %u) outside the bank's %u modes", first, first + count, B.n_modes);
             upload_converted(bank->ctx, B.defl_gain, first, static_cast<const Real *>(deflection_gain), count);
         };
-        if (bank->dbl) go(*bank->d, double{}); else go(*bank->f, float{});
+        in_precision(bank, go);
         return MH_OK;
     } catch (const std::exception &e) { return mh_guard(bank->ctx, e); }
 }
-// mh_bank_render_coupled (damping = carry = null: MH_JUNCTION_DAMPED is ignored), mh_bank_render_damped and mh_bank_render_observed (observe)
-static int render_junctions(mh_bank *bank, uint32_t frames, float click_gain, uint32_t n_impacts, mh_impact *impacts, uint32_t n_renderers, const uint32_t *deal_offset,
-                            const uint32_t *deal_objects, const uint32_t *render_count, const uint32_t *tuned_count, const float *out_gain, const float *listener_gain,
-                            void *out, double *object_energy, uint32_t *object_live, uint8_t *object_silenced, double *object_modal_energy, uint32_t n_drives,
-                            const mh_drive *drives, const float *signals, uint32_t n_pickups, const mh_pickup *pickups, void *pickup_out, uint8_t *pickup_read,
-                            uint32_t n_junctions, const mh_junction *junctions, const float *approach, void *force_out, double *compliance_out, uint8_t *status_out,
-                            const float *damping, void *carry, bool observe = false, uint32_t *unconverged_out = nullptr, bool damped_in_groups = false) {
-    if (!bank || !out || (n_impacts && !impacts) || (n_renderers && !deal_offset) || !out_gain || !listener_gain || (n_drives && (!drives || !signals))) return MH_EINVAL;
-    if (n_pickups && (!pickups || !pickup_out || !pickup_read)) return MH_EINVAL;
-    if (n_junctions && (!junctions || !approach || !force_out || !compliance_out || !status_out)) return MH_EINVAL;
-    if (n_renderers && deal_offset[n_renderers] && (!deal_objects || !render_count || !tuned_count || !object_energy || !object_live || !object_silenced)) return MH_EINVAL;
-    if (frames == 0) return MH_OK;
+// The render entries fill the request; the checks -- of what an entry's level takes first, then of what all share -- and the call are here.
+static int render(mh_bank *bank, const RenderRequest &r) {
+    if (r.entry >= Entry::Damped && r.n_junctions && (!r.damping || !r.carry)) return MH_EINVAL;
+    if (r.entry >= Entry::Mixed && r.n_junctions && !r.unconverged_out) return MH_EINVAL;
+    if (r.unconverged_out) std::fill(r.unconverged_out, r.unconverged_out + r.n_junctions, 0u); // (0 whatever becomes of the call)
+    if (!bank || !r.out || (r.n_impacts && !r.impacts) || (r.n_renderers && !r.deal_offset) || !r.out_gain || !r.listener_gain || (r.n_drives && (!r.drives || !r.signals))) return MH_EINVAL;
+    if (r.n_pickups && (!r.pickups || !r.pickup_out || !r.pickup_read)) return MH_EINVAL;
+    if (r.n_junctions && (!r.junctions || !r.approach || !r.force_out || !r.compliance_out || !r.status_out)) return MH_EINVAL;
+    if (r.n_renderers && r.deal_offset[r.n_renderers] && (!r.deal_objects || !r.render_count || !r.tuned_count || !r.object_energy || !r.object_live || !r.object_silenced)) return MH_EINVAL;
+    if (r.frames == 0) return MH_OK;
     try {
         MhSharedPhase not_during_a_factorisation(bank->ctx->device); // a solve's dense coarse factorisation runs alone on the device (mh_eigs.hip)
         HIP_CHECK(hipSetDevice(bank->ctx->device));
-        auto go = [&](auto &B) {
-            render_impl(B, frames, click_gain, n_impacts, impacts, n_renderers, deal_offset, deal_objects, render_count, tuned_count, out_gain, listener_gain, out, object_energy,
-                        object_live, object_silenced, object_modal_energy, n_drives, drives, signals, n_pickups, pickups, pickup_out, pickup_read, n_junctions, junctions, approach,
-                        force_out, compliance_out, status_out, damping, carry, observe, unconverged_out, damped_in_groups);
-        };
-        if (bank->dbl) go(*bank->d); else go(*bank->f);
+        in_precision(bank, [&](auto &B) { render_impl(B, r); });
         return MH_OK;
     } catch (const std::exception &e) { return mh_guard(bank->ctx, e); }
+}
+int mh_bank_render(mh_bank *bank, uint32_t frames, float click_gain, uint32_t n_impacts, mh_impact *impacts, uint32_t n_renderers, const uint32_t *deal_offset,
+                   const uint32_t *deal_objects, const uint32_t *render_count, const uint32_t *tuned_count, const float *out_gain, const float *listener_gain,
+                   void *out, double *object_energy, uint32_t *object_live, uint8_t *object_silenced, double *object_modal_energy) {
+    return render(bank, {Entry::Coupled, frames, click_gain, n_impacts, impacts, n_renderers, deal_offset, deal_objects, render_count, tuned_count, out_gain, listener_gain, out, object_energy,
+                         object_live, object_silenced, object_modal_energy});
+}
+int mh_bank_render_driven(mh_bank *bank, uint32_t frames, float click_gain, uint32_t n_impacts, mh_impact *impacts, uint32_t n_renderers, const uint32_t *deal_offset,
+                          const uint32_t *deal_objects, const uint32_t *render_count, const uint32_t *tuned_count, const float *out_gain, const float *listener_gain,
+                          void *out, double *object_energy, uint32_t *object_live, uint8_t *object_silenced, double *object_modal_energy, uint32_t n_drives,
+                          const mh_drive *drives, const float *signals) {
+    return render(bank, {Entry::Coupled, frames, click_gain, n_impacts, impacts, n_renderers, deal_offset, deal_objects, render_count, tuned_count, out_gain, listener_gain, out, object_energy,
+                         object_live, object_silenced, object_modal_energy, n_drives, drives, signals});
+}
+int mh_bank_render_read(mh_bank *bank, uint32_t frames, float click_gain, uint32_t n_impacts, mh_impact *impacts, uint32_t n_renderers, const uint32_t *deal_offset,
+                        const uint32_t *deal_objects, const uint32_t *render_count, const uint32_t *tuned_count, const float *out_gain, const float *listener_gain,
+                        void *out, double *object_energy, uint32_t *object_live, uint8_t *object_silenced, double *object_modal_energy, uint32_t n_drives,
+                        const mh_drive *drives, const float *signals, uint32_t n_pickups, const mh_pickup *pickups, void *pickup_out, uint8_t *pickup_read) {
+    return render(bank, {Entry::Coupled, frames, click_gain, n_impacts, impacts, n_renderers, deal_offset, deal_objects, render_count, tuned_count, out_gain, listener_gain, out, object_energy,
+                         object_live, object_silenced, object_modal_energy, n_drives, drives, signals, n_pickups, pickups, pickup_out, pickup_read});
 }
 int mh_bank_render_coupled(mh_bank *bank, uint32_t frames, float click_gain, uint32_t n_impacts, mh_impact *impacts, uint32_t n_renderers, const uint32_t *deal_offset,
                            const uint32_t *deal_objects, const uint32_t *render_count, const uint32_t *tuned_count, const float *out_gain, const float *listener_gain,
                            void *out, double *object_energy, uint32_t *object_live, uint8_t *object_silenced, double *object_modal_energy, uint32_t n_drives,
                            const mh_drive *drives, const float *signals, uint32_t n_pickups, const mh_pickup *pickups, void *pickup_out, uint8_t *pickup_read,
                            uint32_t n_junctions, const mh_junction *junctions, const float *approach, void *force_out, double *compliance_out, uint8_t *status_out) {
-    return render_junctions(bank, frames, click_gain, n_impacts, impacts, n_renderers, deal_offset, deal_objects, render_count, tuned_count, out_gain, listener_gain, out, object_energy,
-                            object_live, object_silenced, object_modal_energy, n_drives, drives, signals, n_pickups, pickups, pickup_out, pickup_read, n_junctions, junctions, approach,
-                            force_out, compliance_out, status_out, nullptr, nullptr);
+    return render(bank, {Entry::Coupled, frames, click_gain, n_impacts, impacts, n_renderers, deal_offset, deal_objects, render_count, tuned_count, out_gain, listener_gain, out, object_energy,
+                         object_live, object_silenced, object_modal_energy, n_drives, drives, signals, n_pickups, pickups, pickup_out, pickup_read, n_junctions, junctions, approach, force_out,
+                         compliance_out, status_out});
 }
 int mh_bank_render_damped(mh_bank *bank, uint32_t frames, float click_gain, uint32_t n_impacts, mh_impact *impacts, uint32_t n_renderers, const uint32_t *deal_offset,
                           const uint32_t *deal_objects, const uint32_t *render_count, const uint32_t *tuned_count, const float *out_gain, const float *listener_gain,
@@ -2480,11 +2479,9 @@ int mh_bank_render_damped(mh_bank *bank, uint32_t frames, float click_gain, uint
                           const mh_drive *drives, const float *signals, uint32_t n_pickups, const mh_pickup *pickups, void *pickup_out, uint8_t *pickup_read,
                           uint32_t n_junctions, const mh_junction *junctions, const float *approach, void *force_out, double *compliance_out, uint8_t *status_out,
                           const float *damping, void *carry) {
-    if (n_junctions && (!damping || !carry)) return MH_EINVAL;
-    static const float no_damping = 0; // (n_junctions = 0: render_impl tells the entries apart by the pointer)
-    return render_junctions(bank, frames, click_gain, n_impacts, impacts, n_renderers, deal_offset, deal_objects, render_count, tuned_count, out_gain, listener_gain, out, object_energy,
-                            object_live, object_silenced, object_modal_energy, n_drives, drives, signals, n_pickups, pickups, pickup_out, pickup_read, n_junctions, junctions, approach,
-                            force_out, compliance_out, status_out, damping ? damping : &no_damping, carry);
+    return render(bank, {Entry::Damped, frames, click_gain, n_impacts, impacts, n_renderers, deal_offset, deal_objects, render_count, tuned_count, out_gain, listener_gain, out, object_energy,
+                         object_live, object_silenced, object_modal_energy, n_drives, drives, signals, n_pickups, pickups, pickup_out, pickup_read, n_junctions, junctions, approach, force_out,
+                         compliance_out, status_out, damping, carry});
 }
 int mh_bank_render_observed(mh_bank *bank, uint32_t frames, float click_gain, uint32_t n_impacts, mh_impact *impacts, uint32_t n_renderers, const uint32_t *deal_offset,
                             const uint32_t *deal_objects, const uint32_t *render_count, const uint32_t *tuned_count, const float *out_gain, const float *listener_gain,
@@ -2492,11 +2489,9 @@ int mh_bank_render_observed(mh_bank *bank, uint32_t frames, float click_gain, ui
                             const mh_drive *drives, const float *signals, uint32_t n_pickups, const mh_pickup *pickups, void *pickup_out, uint8_t *pickup_read,
                             uint32_t n_junctions, const mh_junction *junctions, const float *approach, void *force_out, double *compliance_out, uint8_t *status_out,
                             const float *damping, void *carry) {
-    if (n_junctions && (!damping || !carry)) return MH_EINVAL;
-    static const float no_damping = 0; // (as in mh_bank_render_damped)
-    return render_junctions(bank, frames, click_gain, n_impacts, impacts, n_renderers, deal_offset, deal_objects, render_count, tuned_count, out_gain, listener_gain, out, object_energy,
-                            object_live, object_silenced, object_modal_energy, n_drives, drives, signals, n_pickups, pickups, pickup_out, pickup_read, n_junctions, junctions, approach,
-                            force_out, compliance_out, status_out, damping ? damping : &no_damping, carry, true);
+    return render(bank, {Entry::Observed, frames, click_gain, n_impacts, impacts, n_renderers, deal_offset, deal_objects, render_count, tuned_count, out_gain, listener_gain, out, object_energy,
+                         object_live, object_silenced, object_modal_energy, n_drives, drives, signals, n_pickups, pickups, pickup_out, pickup_read, n_junctions, junctions, approach, force_out,
+                         compliance_out, status_out, damping, carry});
 }
 int mh_bank_render_mixed(mh_bank *bank, uint32_t frames, float click_gain, uint32_t n_impacts, mh_impact *impacts, uint32_t n_renderers, const uint32_t *deal_offset,
                          const uint32_t *deal_objects, const uint32_t *render_count, const uint32_t *tuned_count, const float *out_gain, const float *listener_gain,
@@ -2504,13 +2499,9 @@ int mh_bank_render_mixed(mh_bank *bank, uint32_t frames, float click_gain, uint3
                          const mh_drive *drives, const float *signals, uint32_t n_pickups, const mh_pickup *pickups, void *pickup_out, uint8_t *pickup_read,
                          uint32_t n_junctions, const mh_junction *junctions, const float *approach, void *force_out, double *compliance_out, uint8_t *status_out,
                          const float *damping, void *carry, uint32_t *unconverged_out) {
-    if (n_junctions && (!damping || !carry || !unconverged_out)) return MH_EINVAL;
-    static const float no_damping = 0; // (as in mh_bank_render_damped)
-    static uint32_t no_count = 0; // (n_junctions = 0: render_impl tells the entries apart by the pointer; nothing is written through it)
-    if (unconverged_out) std::fill(unconverged_out, unconverged_out + n_junctions, 0u);
-    return render_junctions(bank, frames, click_gain, n_impacts, impacts, n_renderers, deal_offset, deal_objects, render_count, tuned_count, out_gain, listener_gain, out, object_energy,
-                            object_live, object_silenced, object_modal_energy, n_drives, drives, signals, n_pickups, pickups, pickup_out, pickup_read, n_junctions, junctions, approach,
-                            force_out, compliance_out, status_out, damping ? damping : &no_damping, carry, true, unconverged_out ? unconverged_out : &no_count);
+    return render(bank, {Entry::Mixed, frames, click_gain, n_impacts, impacts, n_renderers, deal_offset, deal_objects, render_count, tuned_count, out_gain, listener_gain, out, object_energy,
+                         object_live, object_silenced, object_modal_energy, n_drives, drives, signals, n_pickups, pickups, pickup_out, pickup_read, n_junctions, junctions, approach, force_out,
+                         compliance_out, status_out, damping, carry, unconverged_out});
 }
 int mh_bank_render_damped_groups(mh_bank *bank, uint32_t frames, float click_gain, uint32_t n_impacts, mh_impact *impacts, uint32_t n_renderers, const uint32_t *deal_offset,
                                  const uint32_t *deal_objects, const uint32_t *render_count, const uint32_t *tuned_count, const float *out_gain, const float *listener_gain,
@@ -2518,34 +2509,9 @@ int mh_bank_render_damped_groups(mh_bank *bank, uint32_t frames, float click_gai
                                  const mh_drive *drives, const float *signals, uint32_t n_pickups, const mh_pickup *pickups, void *pickup_out, uint8_t *pickup_read,
                                  uint32_t n_junctions, const mh_junction *junctions, const float *approach, void *force_out, double *compliance_out, uint8_t *status_out,
                                  const float *damping, void *carry, uint32_t *unconverged_out) {
-    if (n_junctions && (!damping || !carry || !unconverged_out)) return MH_EINVAL;
-    static const float no_damping = 0; // (as in mh_bank_render_mixed)
-    static uint32_t no_count = 0;
-    if (unconverged_out) std::fill(unconverged_out, unconverged_out + n_junctions, 0u);
-    return render_junctions(bank, frames, click_gain, n_impacts, impacts, n_renderers, deal_offset, deal_objects, render_count, tuned_count, out_gain, listener_gain, out, object_energy,
-                            object_live, object_silenced, object_modal_energy, n_drives, drives, signals, n_pickups, pickups, pickup_out, pickup_read, n_junctions, junctions, approach,
-                            force_out, compliance_out, status_out, damping ? damping : &no_damping, carry, true, unconverged_out ? unconverged_out : &no_count, true);
-}
-int mh_bank_render_read(mh_bank *bank, uint32_t frames, float click_gain, uint32_t n_impacts, mh_impact *impacts, uint32_t n_renderers, const uint32_t *deal_offset,
-                        const uint32_t *deal_objects, const uint32_t *render_count, const uint32_t *tuned_count, const float *out_gain, const float *listener_gain,
-                        void *out, double *object_energy, uint32_t *object_live, uint8_t *object_silenced, double *object_modal_energy, uint32_t n_drives,
-                        const mh_drive *drives, const float *signals, uint32_t n_pickups, const mh_pickup *pickups, void *pickup_out, uint8_t *pickup_read) {
-    return mh_bank_render_coupled(bank, frames, click_gain, n_impacts, impacts, n_renderers, deal_offset, deal_objects, render_count, tuned_count, out_gain, listener_gain, out,
-                                  object_energy, object_live, object_silenced, object_modal_energy, n_drives, drives, signals, n_pickups, pickups, pickup_out, pickup_read, 0, nullptr,
-                                  nullptr, nullptr, nullptr, nullptr);
-}
-int mh_bank_render_driven(mh_bank *bank, uint32_t frames, float click_gain, uint32_t n_impacts, mh_impact *impacts, uint32_t n_renderers, const uint32_t *deal_offset,
-                          const uint32_t *deal_objects, const uint32_t *render_count, const uint32_t *tuned_count, const float *out_gain, const float *listener_gain,
-                          void *out, double *object_energy, uint32_t *object_live, uint8_t *object_silenced, double *object_modal_energy, uint32_t n_drives,
-                          const mh_drive *drives, const float *signals) {
-    return mh_bank_render_read(bank, frames, click_gain, n_impacts, impacts, n_renderers, deal_offset, deal_objects, render_count, tuned_count, out_gain, listener_gain, out,
-                               object_energy, object_live, object_silenced, object_modal_energy, n_drives, drives, signals, 0, nullptr, nullptr, nullptr);
-}
-int mh_bank_render(mh_bank *bank, uint32_t frames, float click_gain, uint32_t n_impacts, mh_impact *impacts, uint32_t n_renderers, const uint32_t *deal_offset,
-                   const uint32_t *deal_objects, const uint32_t *render_count, const uint32_t *tuned_count, const float *out_gain, const float *listener_gain,
-                   void *out, double *object_energy, uint32_t *object_live, uint8_t *object_silenced, double *object_modal_energy) {
-    return mh_bank_render_driven(bank, frames, click_gain, n_impacts, impacts, n_renderers, deal_offset, deal_objects, render_count, tuned_count, out_gain, listener_gain, out,
-                                 object_energy, object_live, object_silenced, object_modal_energy, 0, nullptr, nullptr);
+    return render(bank, {Entry::DampedGroups, frames, click_gain, n_impacts, impacts, n_renderers, deal_offset, deal_objects, render_count, tuned_count, out_gain, listener_gain, out, object_energy,
+                         object_live, object_silenced, object_modal_energy, n_drives, drives, signals, n_pickups, pickups, pickup_out, pickup_read, n_junctions, junctions, approach, force_out,
+                         compliance_out, status_out, damping, carry, unconverged_out});
 }
 uint32_t mh_drive_struct_size(void) { return uint32_t(sizeof(mh_drive)); }
 uint32_t mh_pickup_struct_size(void) { return uint32_t(sizeof(mh_pickup)); }
@@ -2555,7 +2521,7 @@ int mh_bank_read_state(const mh_bank *bank, uint32_t first, uint32_t count, doub
     try {
         HIP_CHECK(hipSetDevice(bank->ctx->device));
         auto go = [&](auto &B) {
-            using Real = std::remove_pointer_t<decltype(B.state_re.get())>;
+            using Real = typename std::decay_t<decltype(B)>::Scalar;
             if (size_t(first) + count > B.n_modes) mh_throw(MH_EINVAL, "mode range outside the bank");
             std::vector<Real> re(count), im(count);
             if (!count) return;
@@ -2564,7 +2530,7 @@ int mh_bank_read_state(const mh_bank *bank, uint32_t first, uint32_t count, doub
             HIP_CHECK(hipStreamSynchronize(bank->ctx->stream));
             for (uint32_t i = 0; i < count; ++i) { state_re[i] = double(re[i]); state_im[i] = double(im[i]); }
         };
-        if (bank->dbl) go(*bank->d); else go(*bank->f);
+        in_precision(bank, go);
         return MH_OK;
     } catch (const std::exception &e) { return mh_guard(bank->ctx, e); }
 }

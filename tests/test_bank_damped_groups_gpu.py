@@ -15,7 +15,9 @@ members Hertz, odd ones linear), or mixed: member 0 damped Hertz, 1 plain Hertz,
 6. Bit-exact: a second run, 1 against 4 renderers, bystanders, one block against two halves with the carry passed (128 = 64 + 64 and
    231 = 3 x 77), a dead group against silent members, gating.
 7. Replay: the returned rows as drives on a twin move an object that carries one replayed row bit for bit in fp32.
-8. The kinds still left out have the bits of the call without them; a refused group has the bits of K = 0 and NaN carries."""
+8. The kinds still left out have the bits of the call without them; a refused group has the bits of K = 0 and NaN carries.
+9. Every junction launch in one call -- lone, linear group, Hertz-member group, damped-member group, tapped waves, the main launch -- has
+   the bits of four calls with one kind each."""
 import numpy as np
 import pytest
 
@@ -498,3 +500,43 @@ def test_a_refused_group_has_the_bits_of_k_0_and_nan_carries(use_double):
     else:
         dead = _run(use_double, _specs("chain", [0.0, 0.0], False), u, rates)
         assert list(huge[3]) == [2, 2] and not huge[0].any() and all(np.isnan(c).all() for c in huge[5]) and _same(huge[6], dead[6])
+
+
+# ---- 9. every junction launch in one call ----
+@PRECISIONS
+@pytest.mark.parametrize("renderers", [1, 4])
+def test_every_junction_launch_in_one_call_is_the_four_calls_with_one_kind_each(use_double, renderers):
+    """One render_damped_groups call with a lone damped Hertz junction (the first 64-mode object), a linear group of two (the 32-mode
+    object), a group of two with a Hertz member (the 130-mode hub: two waves) and a group of two with a damped member (the 256-mode
+    object), all exciter junctions, named in an order that interleaves the kinds; an advance-1 pickup on the object of each, and one on
+    the second 64-mode object, which no junction names; noise drives on all five.  Two blocks of 40 frames with the carry passed on: 40
+    frames are one full and one partial turn-around tile in fp32 (32 samples), two full and one partial in fp64 (16).
+    Four further calls on fresh scenes hold one kind each, with its pickup and the same drives: every junction's force row, compliance,
+    status, carry and unconverged count, and every junction-object pickup row, equal theirs bit for bit -- a launch's place behind the
+    others (its groups' offset in the list, first_wave, its gain rows, the taps' indices) changes nothing."""
+    frames, blocks = 40, 2
+    modes = MODES + [64, 64]
+    comp = _comp("four", use_double)
+    four = _shape("four", [10.0 / c for c in comp])
+    kinds = {"lone": [dg.spec(gh.side(3, 2, direction=(0.0, 1.0, 0.25)), None, 2e9, hertz=True, damped=True)],
+             "linear": [four[0] + (False,), four[1] + (False,)],
+             "hertz": [dg.spec(gh.side(1, 1, direction=groups_suite.NORMAL), None, 2e9, hertz=True), dg.spec(gh.side(1, 3, direction=(0.5, 0.5, -1.0)), None, 1e5)],
+             "damped": [dg.spec(gh.side(2, 1, direction=(1.0, 0.0, 0.5)), None, 2e9, hertz=True, damped=True), dg.spec(gh.side(2, 3, direction=(0.0, 1.0, 0.25)), None, 1e5)]}
+    order = [("damped", 0), ("linear", 0), ("lone", 0), ("hertz", 0), ("linear", 1), ("damped", 1), ("hertz", 1)]
+    specs = [kinds[k][i] for k, i in order]
+    u = _approach(len(specs), frames, blocks) + np.float32(4 * FREE)  # (raised: every member is compressed in most frames)
+    rates = np.full(len(specs), _rate(1.0 / FREE)[0], np.float32)
+    picked = ["damped", "linear", "lone", "hertz"]
+    pickups = [oh.side_pickup(kinds[k][0][0]) for k in picked]
+    off = ph.spec(4, 1, direction=(0.0, 1.0, 0.5), advance=1)
+    every = _run(use_double, specs, u, rates, renderers, blocks=blocks, frames=frames, pickups=pickups + [off], modes=modes)
+    assert list(every[3]) == [1] * len(specs) and (np.abs(every[0]).max(axis=1) > 0).all()
+    assert (np.abs(every[1]).max(axis=1) > 0).all()
+    is_damped = np.array([bool(s[6]) for s in specs])
+    assert all(np.isfinite(c[is_damped]).all() and np.isnan(c[~is_damped]).all() for c in every[5])
+    for kind in kinds:
+        at = [j for j, (k, _) in enumerate(order) if k == kind]
+        one = _run(use_double, [specs[j] for j in at], u[at], rates[at], renderers, blocks=blocks, frames=frames, pickups=[pickups[picked.index(kind)]], modes=modes)
+        assert np.array_equal(every[0][at], one[0]) and np.array_equal(every[2][at], one[2]) and np.array_equal(every[3][at], one[3]), kind
+        assert np.array_equal(every[4][at], one[4]) and all(np.array_equal(a[at], b, equal_nan=True) for a, b in zip(every[5], one[5])), kind
+        assert np.array_equal(every[1][picked.index(kind)], one[1][0]), kind
