@@ -651,6 +651,21 @@ template<typename Real> __device__ __forceinline__ void tap_store(Real *tap_row,
     *reinterpret_cast<PairOf<Real> *>(at) = z_im;
     *reinterpret_cast<PairOf<Real> *>(at + MODES_PER_WAVE) = z_re;
 }
+// Number checks on what a junction's block keeps; a NaN fails each of them.  (Where a kernel still spells one out, the named form changed the
+// instructions of an entry that has none of the group solves in it: profiles/bank_junction_steps.txt.)
+template<typename Real> __device__ __forceinline__ bool within_bound(Real v, Real bound) { return v >= -bound && v <= bound; }
+template<typename Real> __device__ __forceinline__ bool is_finite(Real v) { return within_bound(v, std::numeric_limits<Real>::max()); }
+template<typename Real> __device__ __forceinline__ bool finite_from_zero(Real v) { return v >= Real(0) && v <= std::numeric_limits<Real>::max(); } // finite and not below 0
+template<typename Real> __device__ __forceinline__ bool finite_above_zero(Real v) { return v > Real(0) && v <= std::numeric_limits<Real>::max(); }
+// The turn-around of bank_modes at the end of a junction kernel's tile: every chunk's 8 terms added in mode order.  Two barriers, taken by
+// every wave of the workgroup.
+template<uint32_t TS, typename Real>
+__device__ __forceinline__ void junction_turn_around(const Real *s_term, const WaveLane<Real> &w, uint32_t lane, uint32_t s0, uint32_t sn, Real *partial, uint32_t frames) {
+    mh_lds_writes_landed();
+    __syncthreads();
+    chunk_sums<TS>(s_term, w, lane, s0, sn, partial, frames);
+    __syncthreads();
+}
 // HERTZ = false (k_bank_modes_coupled<Real>): every junction is a linear spring -- the entry of a call without a Hertz junction, instruction
 // for instruction what it was before the parameter.  HERTZ = true: a junction with MH_JUNCTION_HERTZ takes hertz_force, a linear one the
 // same expression as in the other entry through one workgroup-uniform branch.  DAMPED = true (with HERTZ: k_bank_modes_coupled_damped<Real>):
@@ -710,7 +725,7 @@ template<typename Real, bool HERTZ = false, bool DAMPED = false, bool OBSERVE = 
     const Real zero = 0;
     const Real compliance = junction_sum(fma_real(g_re.y, a.y, fma_real(g_re.x, a.x, zero)), 1);
     const Real denom_k = Real(1) + J.k * compliance;
-    bool solved = denom_k > Real(0) && denom_k <= std::numeric_limits<Real>::max(); // a finite number above 0 (a NaN fails both)
+    bool solved = finite_above_zero(denom_k);
     bool hertz = false; // workgroup-uniform
     Real kc = 0, kc15 = 0; // Hertz: c = K C and 1.5 c, once per block
     if constexpr (HERTZ) {
@@ -782,11 +797,7 @@ template<typename Real, bool HERTZ = false, bool DAMPED = false, bool OBSERVE = 
             if (lane == ds) f_tile = f;
         }
         if (wave == 0 && lane < sn) f_row[s0 + lane] = f_tile;
-        // the turn-around of bank_modes: every chunk's 8 terms added in mode order
-        mh_lds_writes_landed();
-        __syncthreads();
-        chunk_sums<TS>(s_term, w, lane, s0, sn, partial, frames);
-        __syncthreads();
+        junction_turn_around<TS>(s_term, w, lane, s0, sn, partial, frames);
     }
     if constexpr (DAMPED)
         if (damped && threadIdx.x == 0) ca.carry_out[J.row] = y_prev; // (the host hands it on only for a solved junction)
@@ -933,6 +944,81 @@ __device__ __forceinline__ double wave_uniform(double v) {
     const uint32_t lo = __builtin_amdgcn_readfirstlane(uint32_t(bits)), hi = __builtin_amdgcn_readfirstlane(uint32_t(bits >> 32));
     return __builtin_bit_cast(double, uint64_t(hi) << 32 | lo);
 }
+// What steps 4m and 4g share of a group's Newton iteration, one definition each.  c: the matrix C; y, f, kd: the iterate, its forces and
+// df / dy; x: the frame's reaches.
+// F_i = (y_i + sum_j C_ij f_j) - x_i; twice: the sum carried in twice the working precision.  UNIFORM: step 4g's placement -- F goes through
+// wave_uniform (the iterate lives in scalar registers between the steps); step 4m leaves it where the compiler puts it.
+template<bool UNIFORM, typename Real>
+__device__ __forceinline__ void group_residual(const Real (&c)[GROUP][GROUP], const Real (&y)[GROUP], const Real (&f)[GROUP], const Real (&x)[GROUP], bool twice, Real (&F)[GROUP]) {
+#pragma unroll
+    for (uint32_t i = 0; i < GROUP; ++i) {
+        Real Fi;
+        if (!twice) {
+            Real acc = 0;
+#pragma unroll
+            for (uint32_t j = 0; j < GROUP; ++j) acc = acc + c[i][j] * f[j];
+            Fi = (y[i] + acc) - x[i];
+        } else {
+            Real sum = y[i], low = 0, r, e;
+#pragma unroll
+            for (uint32_t j = 0; j < GROUP; ++j) {
+                const Real p = two_product(c[i][j], f[j], e);
+                sum = two_sum(sum, p, r);
+                low = low + (r + e);
+            }
+            sum = two_sum(sum, -x[i], r);
+            low = low + r;
+            Fi = sum + low;
+        }
+        if constexpr (UNIFORM) F[i] = wave_uniform(Fi);
+        else F[i] = Fi;
+    }
+}
+// The Newton direction d of J d = F, J = I + C diag(kd): J eliminated without pivoting in ascending order, back substitution in descending order.
+template<typename Real> __device__ __forceinline__ void newton_direction(const Real (&c)[GROUP][GROUP], const Real (&kd)[GROUP], const Real (&F)[GROUP], Real (&d)[GROUP]) {
+    Real Jm[GROUP][GROUP], r[GROUP];
+#pragma unroll
+    for (uint32_t i = 0; i < GROUP; ++i) {
+#pragma unroll
+        for (uint32_t j = 0; j < GROUP; ++j) Jm[i][j] = i == j ? Real(1) + c[i][j] * kd[j] : c[i][j] * kd[j];
+        r[i] = F[i];
+    }
+#pragma unroll
+    for (uint32_t p = 0; p < GROUP; ++p) {
+        const Real inv = Real(1) / Jm[p][p];
+#pragma unroll
+        for (uint32_t j = p + 1; j < GROUP; ++j) Jm[p][j] = Jm[p][j] * inv;
+        r[p] = r[p] * inv;
+#pragma unroll
+        for (uint32_t i = p + 1; i < GROUP; ++i) {
+            const Real t = Jm[i][p];
+#pragma unroll
+            for (uint32_t j = p + 1; j < GROUP; ++j) Jm[i][j] = Jm[i][j] - t * Jm[p][j];
+            r[i] = r[i] - t * r[p];
+        }
+    }
+#pragma unroll
+    for (int p = int(GROUP) - 1; p >= 0; --p) {
+        Real acc = r[p];
+#pragma unroll
+        for (int j = p + 1; j < int(GROUP); ++j) acc = acc - Jm[p][j] * d[j];
+        d[p] = acc;
+    }
+}
+// The residual test: |F_i| against `units` u (|y_i| + sum_j |C_ij| size_j + |x_i|), size_j the magnitude member j's force is formed from.
+template<typename Real>
+__device__ __forceinline__ bool residual_met(const Real (&c)[GROUP][GROUP], const Real (&y)[GROUP], const Real (&size)[GROUP], const Real (&x)[GROUP], const Real (&F)[GROUP], Real units) {
+    bool met = true;
+#pragma unroll
+    for (uint32_t i = 0; i < GROUP; ++i) {
+        Real acc = 0;
+#pragma unroll
+        for (uint32_t j = 0; j < GROUP; ++j) acc = acc + __builtin_fabs(c[i][j]) * size[j];
+        const Real mag = (__builtin_fabs(y[i]) + acc) + __builtin_fabs(x[i]);
+        met = met && __builtin_fabs(F[i]) <= (units * (std::numeric_limits<Real>::epsilon() * Real(0.5))) * mag;
+    }
+    return met;
+}
 // Step 4g (modalhip.h, mh_bank_render_damped_groups): what a group with a damped member keeps for the block, all of it wave-uniform.
 template<typename Real> struct DampedGroup {
     Real c[GROUP][GROUP], k[GROUP], ck[GROUP], ck15[GROUP], lam[GROUP]; // C, K, ck_jj = C_jj K_j, 1.5 ck_jj, l (0 on a member that is not damped)
@@ -980,61 +1066,11 @@ template<typename Real> __device__ __forceinline__ bool damped_group_solve(const
             __builtin_amdgcn_sched_barrier(0); // one member's tree at a time: their temporaries are not to be live side by side
         }
     }
-    // F_i = (y_i + sum_j C_ij f_j) - x_i; twice: the sum carried in twice the working precision (step 4m's)
-    auto residual = [&](bool twice) {
-#pragma unroll
-        for (uint32_t i = 0; i < GROUP; ++i) {
-            if (!twice) {
-                Real acc = 0;
-#pragma unroll
-                for (uint32_t j = 0; j < GROUP; ++j) acc = acc + g.c[i][j] * f[j];
-                F[i] = wave_uniform((y[i] + acc) - x[i]);
-            } else {
-                Real sum = y[i], low = 0, r, e;
-#pragma unroll
-                for (uint32_t j = 0; j < GROUP; ++j) {
-                    const Real p = two_product(g.c[i][j], f[j], e);
-                    sum = two_sum(sum, p, r);
-                    low = low + (r + e);
-                }
-                sum = two_sum(sum, -x[i], r);
-                low = low + r;
-                F[i] = wave_uniform(sum + low);
-            }
-        }
-    };
-    residual(DAMPED_STEPS <= DAMPED_REFINED);
+    group_residual<true>(g.c, y, f, x, DAMPED_STEPS <= DAMPED_REFINED, F);
 #pragma unroll 1
     for (int step = 0; step < DAMPED_STEPS; ++step) {
-        // J = I + C diag(kd), eliminated without pivoting in ascending order; back substitution in descending order (step 4m's)
-        Real Jm[GROUP][GROUP], r[GROUP], d[GROUP];
-#pragma unroll
-        for (uint32_t i = 0; i < GROUP; ++i) {
-#pragma unroll
-            for (uint32_t j = 0; j < GROUP; ++j) Jm[i][j] = i == j ? Real(1) + g.c[i][j] * kd[j] : g.c[i][j] * kd[j];
-            r[i] = F[i];
-        }
-#pragma unroll
-        for (uint32_t p = 0; p < GROUP; ++p) {
-            const Real inv = Real(1) / Jm[p][p];
-#pragma unroll
-            for (uint32_t j = p + 1; j < GROUP; ++j) Jm[p][j] = Jm[p][j] * inv;
-            r[p] = r[p] * inv;
-#pragma unroll
-            for (uint32_t i = p + 1; i < GROUP; ++i) {
-                const Real t = Jm[i][p];
-#pragma unroll
-                for (uint32_t j = p + 1; j < GROUP; ++j) Jm[i][j] = Jm[i][j] - t * Jm[p][j];
-                r[i] = r[i] - t * r[p];
-            }
-        }
-#pragma unroll
-        for (int p = int(GROUP) - 1; p >= 0; --p) {
-            Real acc = r[p];
-#pragma unroll
-            for (int j = p + 1; j < int(GROUP); ++j) acc = acc - Jm[p][j] * d[j];
-            d[p] = acc;
-        }
+        Real d[GROUP];
+        newton_direction(g.c, kd, F, d);
         // a unilateral member that was open or clamped (kd = 0), or whose step more than doubles y, takes its own tree at its row's
         // linearised right-hand side instead: from below the root Newton's iteration on a convex law lands far above it and creeps
         // back.  Not in the refined steps.
@@ -1047,7 +1083,7 @@ template<typename Real> __device__ __forceinline__ bool damped_group_solve(const
             law(j);
             __builtin_amdgcn_sched_barrier(0);
         }
-        residual(step + 1 >= DAMPED_STEPS - DAMPED_REFINED);
+        group_residual<true>(g.c, y, f, x, step + 1 >= DAMPED_STEPS - DAMPED_REFINED, F);
     }
     // the residual test: |F_i| against 32 u (|y_i| + sum_j |C_ij| s_j + |x_i|), s_j = K phi(y) (1 + l (|y| + |y_p|)) on a damped member, |f_j| on every other
     Real size[GROUP];
@@ -1060,15 +1096,7 @@ template<typename Real> __device__ __forceinline__ bool damped_group_solve(const
             size[j] = (g.k[j] * phi) * (Real(1) + l_now[j] * (__builtin_fabs(y[j]) + __builtin_fabs(y_prev[j])));
         }
     }
-    bool met = true;
-#pragma unroll
-    for (uint32_t i = 0; i < GROUP; ++i) {
-        Real acc = 0;
-#pragma unroll
-        for (uint32_t j = 0; j < GROUP; ++j) acc = acc + __builtin_fabs(g.c[i][j]) * size[j];
-        const Real mag = (__builtin_fabs(y[i]) + acc) + __builtin_fabs(x[i]);
-        met = met && __builtin_fabs(F[i]) <= (Real(32) * (std::numeric_limits<Real>::epsilon() * Real(0.5))) * mag;
-    }
+    const bool met = residual_met(g.c, y, size, x, F, Real(32));
 #pragma unroll
     for (uint32_t j = 0; j < GROUP; ++j)
         if (g.damped >> j & 1u) y_prev[j] = wave_uniform(y[j]);
@@ -1119,8 +1147,8 @@ template<typename Real, bool OBSERVE = false, bool MIXED = false, bool DAMPED = 
             if (M->flags & MH_JUNCTION_DAMPED) {
                 damped |= 1u << i;
                 lam[i] = wave_uniform(ga.damping[M->row]);
-                const Real came = wave_uniform(ga.carry_in[M->row]), top = std::numeric_limits<Real>::max();
-                if (came >= -top && came <= top) y_prev[i] = came, known |= 1u << i; // a finite carry: there is a history
+                const Real came = wave_uniform(ga.carry_in[M->row]);
+                if (is_finite(came)) y_prev[i] = came, known |= 1u << i; // a finite carry: there is a history
             }
         if (!active || (sa != slot && sb != slot)) continue;
         const uint32_t sd = sa == slot ? 0u : 1u;
@@ -1199,10 +1227,10 @@ template<typename Real, bool OBSERVE = false, bool MIXED = false, bool DAMPED = 
                 W[i][j] = col[i]; // step 4m keeps C alone
                 if constexpr (DAMPED) W[i][j] = wave_uniform(col[i]); // (step 4g keeps it in scalar registers from here on)
                 const Real range = sqrt_real(most); // and J multiplies two entries: |C_ij K_j| within the square root of the largest number
-                if (i < n && j < n) numbers_ok = numbers_ok && kc >= -range && kc <= range;
+                if (i < n && j < n) numbers_ok = numbers_ok && within_bound(kc, range);
                 if constexpr (DAMPED) { // and kd_j = K_j (phi' m + phi l_j): |C_ij K_j l_j| within it as well
                     const Real kcl = kc * lam[j];
-                    if (i < n && j < n && (damped >> j & 1u)) numbers_ok = numbers_ok && kcl >= -range && kcl <= range;
+                    if (i < n && j < n && (damped >> j & 1u)) numbers_ok = numbers_ok && within_bound(kcl, range);
                 }
             }
             if constexpr (!MIXED) W[i][j] = (mask >> i & 1u) ? ((mask >> j & 1u) ? (i == j ? Real(1) + kc : kc) : zero) : col[i];
@@ -1219,10 +1247,10 @@ template<typename Real, bool OBSERVE = false, bool MIXED = false, bool DAMPED = 
             ck15[i] = Real(1.5) * ckd[i];
             if constexpr (DAMPED) ckd[i] = wave_uniform(ckd[i]), ck15[i] = wave_uniform(ck15[i]);
             const Real denom = Real(1) + ckd[i];
-            if (i < n) pivots_ok = pivots_ok && ((hertz >> i & 1u) ? (W[i][i] >= Real(0) && ckd[i] >= Real(0)) : (denom > Real(0) && denom <= most));
+            if (i < n) pivots_ok = pivots_ok && ((hertz >> i & 1u) ? (W[i][i] >= Real(0) && ckd[i] >= Real(0)) : finite_above_zero(denom));
             if constexpr (DAMPED) { // a damped member: C_ii, C_ii K_i and C_ii K_i l_i not below 0, as in step 4d
                 const Real cl = ckd[i] * lam[i];
-                if (i < n && (damped >> i & 1u)) pivots_ok = pivots_ok && W[i][i] >= Real(0) && ckd[i] >= Real(0) && cl >= Real(0) && cl <= most;
+                if (i < n && (damped >> i & 1u)) pivots_ok = pivots_ok && W[i][i] >= Real(0) && ckd[i] >= Real(0) && finite_from_zero(cl);
             }
         }
     }
@@ -1332,78 +1360,23 @@ template<typename Real, bool OBSERVE = false, bool MIXED = false, bool DAMPED = 
                         law(j);
                     }
                 }
-                // F_i = (y_i + sum_j C_ij f_j) - x_i; twice: the sum carried in twice the working precision
-                auto residual = [&](bool twice) {
-#pragma unroll
-                    for (uint32_t i = 0; i < GROUP; ++i) {
-                        if (!twice) {
-                            Real acc = 0;
-#pragma unroll
-                            for (uint32_t j = 0; j < GROUP; ++j) acc = acc + W[i][j] * f[j];
-                            F[i] = (y[i] + acc) - x[i];
-                        } else {
-                            Real sum = y[i], low = 0, r, e;
-#pragma unroll
-                            for (uint32_t j = 0; j < GROUP; ++j) {
-                                const Real p = two_product(W[i][j], f[j], e);
-                                sum = two_sum(sum, p, r);
-                                low = low + (r + e);
-                            }
-                            sum = two_sum(sum, -x[i], r);
-                            low = low + r;
-                            F[i] = sum + low;
-                        }
-                    }
-                };
-                residual(MIXED_STEPS <= MIXED_REFINED);
+                group_residual<false>(W, y, f, x, MIXED_STEPS <= MIXED_REFINED, F);
 #pragma unroll 1
                 for (int step = 0; step < MIXED_STEPS; ++step) {
-                    // J = I + C diag(K phi'), eliminated without pivoting in ascending order; back substitution in descending order
-                    Real Jm[GROUP][GROUP], r[GROUP], d[GROUP];
-#pragma unroll
-                    for (uint32_t i = 0; i < GROUP; ++i) {
-#pragma unroll
-                        for (uint32_t j = 0; j < GROUP; ++j) Jm[i][j] = i == j ? Real(1) + W[i][j] * kd[j] : W[i][j] * kd[j];
-                        r[i] = F[i];
-                    }
-#pragma unroll
-                    for (uint32_t p = 0; p < GROUP; ++p) {
-                        const Real inv = Real(1) / Jm[p][p];
-#pragma unroll
-                        for (uint32_t j = p + 1; j < GROUP; ++j) Jm[p][j] = Jm[p][j] * inv;
-                        r[p] = r[p] * inv;
-#pragma unroll
-                        for (uint32_t i = p + 1; i < GROUP; ++i) {
-                            const Real t = Jm[i][p];
-#pragma unroll
-                            for (uint32_t j = p + 1; j < GROUP; ++j) Jm[i][j] = Jm[i][j] - t * Jm[p][j];
-                            r[i] = r[i] - t * r[p];
-                        }
-                    }
-#pragma unroll
-                    for (int p = int(GROUP) - 1; p >= 0; --p) {
-                        Real acc = r[p];
-#pragma unroll
-                        for (int j = p + 1; j < int(GROUP); ++j) acc = acc - Jm[p][j] * d[j];
-                        d[p] = acc;
-                    }
+                    Real d[GROUP];
+                    newton_direction(W, kd, F, d);
 #pragma unroll
                     for (uint32_t j = 0; j < GROUP; ++j) {
                         y[j] = y[j] - d[j];
                         law(j);
                     }
-                    residual(step + 1 >= MIXED_STEPS - MIXED_REFINED);
+                    group_residual<false>(W, y, f, x, step + 1 >= MIXED_STEPS - MIXED_REFINED, F);
                 }
                 // the residual test: |F_i| against 16 u (|y_i| + sum_j |C_ij f_j| + |x_i|)
-                bool met = true;
+                Real size[GROUP];
 #pragma unroll
-                for (uint32_t i = 0; i < GROUP; ++i) {
-                    Real acc = 0;
-#pragma unroll
-                    for (uint32_t j = 0; j < GROUP; ++j) acc = acc + __builtin_fabs(W[i][j]) * __builtin_fabs(f[j]);
-                    const Real mag = (__builtin_fabs(y[i]) + acc) + __builtin_fabs(x[i]);
-                    met = met && __builtin_fabs(F[i]) <= (Real(16) * (std::numeric_limits<Real>::epsilon() * Real(0.5))) * mag;
-                }
+                for (uint32_t j = 0; j < GROUP; ++j) size[j] = __builtin_fabs(f[j]);
+                const bool met = residual_met(W, y, size, x, F, Real(16));
                 if (solved && !met) ++unconverged;
 #pragma unroll
                 for (uint32_t i = 0; i < GROUP; ++i) f_now[i] = solved ? f[i] : zero;
@@ -1470,11 +1443,7 @@ template<typename Real, bool OBSERVE = false, bool MIXED = false, bool DAMPED = 
 #pragma unroll
         for (uint32_t i = 0; i < GROUP; ++i)
             if (i < n && wave == i % block_waves && lane < sn) ga.force_out[size_t(G->member[i].row) * frames + s0 + lane] = f_tile[i];
-        // the turn-around of bank_modes: every chunk's 8 terms added in mode order
-        mh_lds_writes_landed();
-        __syncthreads();
-        chunk_sums<TS>(s_term, w, lane, s0, sn, partial, frames);
-        __syncthreads();
+        junction_turn_around<TS>(s_term, w, lane, s0, sn, partial, frames);
     }
     if constexpr (MIXED)
         if (threadIdx.x == 0)

@@ -220,6 +220,43 @@ def test_a_dead_group_is_an_observer(use_double, renderers, frames):
             assert _same(ref_states[b], states[b]), (variant, b)
 
 
+@PRECISIONS
+def test_a_dead_group_on_objects_with_three_force_rows_is_an_observer(use_double):
+    """The pair on two objects of 100 and 128 modes with three force rows each -- one more than the group kernel keeps in registers, so the
+    third row's gains go through the wave's scratch row -- two blocks of 40 frames (a whole tile and a partial one at either tile size).
+    K = 0 under a lively u, and stiff members whose exciters are far away, give zero rows, status 1, and the bits of the run with a
+    zero-signal drive at every side in the group's place."""
+    modes, frames, blocks = [100, 128], 40, 2
+    directions = ((1.0, 0.5, -0.25), NORMAL, (0.5, 0.5, -1.0))
+
+    def run(variant):
+        sc, _ = dh.device_scene(modes, T60, 1, use_double)
+        specs = _shape("pair", [0.0 if variant == "k0" else 1e6] * 2)
+        sig, states = np.zeros(blocks * frames, sc.dtype), []
+        for b in range(blocks):
+            rows = [(o, p, directions[p], _signal("noise", 3 * o + p, blocks * frames)[b * frames:(b + 1) * frames]) for o in range(len(modes)) for p in range(3)]
+            drives, signals = _drive_args(rows, frames)
+            out = sig[b * frames:(b + 1) * frames]
+            if variant == "drive":
+                places = [(sd[0], sd[1][0]) + tuple(sd[3]) for s in specs for sd in (s[0], s[1])]
+                sc.render_driven(out, drives + places, np.concatenate([signals, np.zeros((len(places), frames), np.float32)]))
+            else:
+                u = np.array([_signal("noise", 40 + j, blocks * frames)[b * frames:(b + 1) * frames] for j in range(2)], np.float32) if variant == "k0" else np.full((2, frames), -1e30, np.float32)
+                _, _, forces, comp, status = sc.render_coupled(out, drives, signals, [], gh.records(specs), u)
+                assert list(status) == [1, 1] and not forces.any() and (comp > 0).all(), (variant, b)
+            states.append([a.copy() for a in sc.object_state()] + _states(sc))
+        sc.close()
+        return sig, states
+
+    ref, ref_states = run("drive")
+    assert np.abs(ref).max() > 0 and np.isfinite(ref).all()
+    for variant in ("k0", "open"):
+        got, states = run(variant)
+        assert np.array_equal(ref, got), variant
+        for b in range(blocks):
+            assert _same(ref_states[b], states[b]), (variant, b)
+
+
 # ---- 5. members gated apart ----
 _GATED = {}
 GATED_BLOCKS = 6
