@@ -226,11 +226,85 @@ int mhl_system_bench_elementwise(mh_system *s, uint32_t width, uint32_t reps, do
     } catch (const std::exception &e) { return mh_guard(ctx, e); }
 }
 
+} // extern "C"
+
+namespace {
+// Kinds 2 and 3 of mhl_context_bench_dense: the eigensolver's basis update with column maps, as update_basis calls it, in its two
+// forms on the same inputs -- [X[:, map] | W | P] Ct with X n x b, wa active columns (map[k] = k, or k + k / 2: gaps), W and P n x wb,
+// wa + wb output columns of which the first wa are the new Ritz vectors.  Form 0 stores them to the compact panel alone (pitch = wa
+// rounded up to even), form 1 to the compact panel and to the mapped columns of X.  Returns the number of entries in which a result is
+// not what form 0's compact panel, scattered here on the host, says it must be: X after form 1 (columns outside the map unchanged),
+// the compact panel of form 1, its other wb output columns, X after form 0 (only read) -- and in which form 0 itself misses the
+// product formed on the host by more than the rounding of a sum of m products.  With more rows than 64 x the workgroups the device
+// holds, workgroups take several row tiles each: the persistent loop the in-place argument of k_combine is about.
+double lab_mapped_update_mismatches(mh_context *ctx, bool gaps, size_t n, uint32_t wa, uint32_t wb) {
+    const uint32_t b = (wa + wa / 2 + 3u) & ~1u, pitch = (wa + 1u) & ~1u, m = wa + 2 * wb, nc = wa + wb;
+    std::vector<uint32_t> map(wa);
+    for (uint32_t k = 0; k < wa; ++k) map[k] = gaps ? k + k / 2 : k;
+    auto fill = [](std::vector<double> &v, size_t salt) {
+        for (size_t i = 0; i < v.size(); ++i) v[i] = double(((i + salt) * 2654435761u) % 1000) * 1e-3 - 0.5;
+    };
+    std::vector<double> hx(n * b), hw(n * wb), hp(n * wb), hc(size_t(m) * nc);
+    fill(hx, 0), fill(hw, 7919), fill(hp, 104729), fill(hc, 1299709);
+    struct Out { std::vector<double> xn, x, p; };
+    auto run = [&](int form) {
+        DevArray<double> dx(ctx, n * b), dw(ctx, n * wb), dp(ctx, n * wb), dc(ctx, size_t(m) * nc), dxn(ctx, n * pitch), dpo(ctx, n * wb);
+        DevArray<uint32_t> dmap(ctx, wa);
+        dx.upload(hx.data(), hx.size());
+        dw.upload(hw.data(), hw.size());
+        dp.upload(hp.data(), hp.size());
+        dc.upload(hc.data(), hc.size());
+        dmap.upload(map.data(), wa);
+        dxn.zero();
+        if (form == 0) mh_combine(ctx, n, dx, wa, dw, wb, dp, wb, dc, nc, dxn, wa, dpo, false, b, dmap, pitch);
+        else mh_combine(ctx, n, dx, wa, dw, wb, dp, wb, dc, nc, dxn, wa, dpo, false, b, dmap, pitch, nullptr, 0, 0, dx, b, dmap);
+        Out o{std::vector<double>(n * pitch), std::vector<double>(n * b), std::vector<double>(n * wb)};
+        dxn.download(o.xn.data(), o.xn.size());
+        dx.download(o.x.data(), o.x.size());
+        dpo.download(o.p.data(), o.p.size());
+        return o;
+    };
+    const Out one = run(0), two = run(1);
+    auto differing = [](const std::vector<double> &a, const std::vector<double> &c) {
+        size_t d = 0;
+        for (size_t i = 0; i < a.size(); ++i) d += !(a[i] == c[i]);
+        return d;
+    };
+    size_t bad = differing(one.x, hx);
+    for (size_t r = 0; r < n; ++r) // form 0 against the product on the host
+        for (uint32_t c = 0; c < nc; ++c) {
+            double ref = 0, mag = 0;
+            for (uint32_t k = 0; k < m; ++k) {
+                const double s = k < wa ? hx[r * b + map[k]] : k < wa + wb ? hw[r * wb + (k - wa)] : hp[r * wb + (k - wa - wb)];
+                ref += s * hc[size_t(k) * nc + c];
+                mag += std::abs(s * hc[size_t(k) * nc + c]);
+            }
+            const double got = c < wa ? one.xn[r * pitch + c] : one.p[r * wb + (c - wa)];
+            bad += !(std::abs(got - ref) <= 2.0 * m * 2.3e-16 * mag);
+        }
+    std::vector<double> want = hx; // form 0's compact panel scattered on the host
+    size_t written = 0;
+    for (size_t r = 0; r < n; ++r)
+        for (uint32_t k = 0; k < wa; ++k) {
+            want[r * b + map[k]] = one.xn[r * pitch + k];
+            written += want[r * b + map[k]] != hx[r * b + map[k]];
+        }
+    if (written < n * wa / 2) mh_throw(MH_EHIP, "mapped update check: the update left %zu of %zu entries as they were", n * wa - written, n * size_t(wa));
+    bad += differing(two.xn, one.xn) + differing(two.x, want) + differing(two.p, one.p);
+    return double(bad);
+}
+} // namespace
+
+extern "C" {
 int mhl_context_bench_dense(mh_context *ctx, int kind, uint64_t n, uint32_t wa, uint32_t wb, uint32_t reps, double *avg_ms) {
-    if (!ctx || !avg_ms || n == 0 || wa == 0 || wb == 0 || reps == 0 || kind < 0 || kind > 1) return MH_EINVAL;
+    if (!ctx || !avg_ms || n == 0 || wa == 0 || wb == 0 || reps == 0 || kind < 0 || kind > 3) return MH_EINVAL;
     try {
         HIP_CHECK(hipSetDevice(ctx->device));
         std::lock_guard<std::mutex> lock(mh_solve_mutex());
+        if (kind >= 2) { // (a check, not a timing: the count of wrong entries leaves in *avg_ms)
+            *avg_ms = lab_mapped_update_mismatches(ctx, kind == 3, n, wa, wb);
+            return MH_OK;
+        }
         DevArray<double> x(ctx, n * wa), y(ctx, n * wb), g(ctx, size_t(wa + wb) * (wa + wb)), z(ctx, n * wa);
         std::vector<double> h(n * std::max(wa, wb));
         for (size_t i = 0; i < h.size(); ++i) h[i] = double((i * 2654435761u) % 1000) * 1e-3 - 0.5;

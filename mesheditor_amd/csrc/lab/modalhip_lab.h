@@ -13,7 +13,10 @@ int mhl_system_elementwise_matvec(mh_system *, const double *x, double *y, uint3
 int mhl_system_bench_elementwise(mh_system *, uint32_t width, uint32_t reps, double *avg_ms);
 /* The fp32 smoother's fused product-and-Chebyshev step on level 2 / 1 over an n x width panel cut into `slabs` contiguous panels. */
 int mhl_system_bench_cheb_step(mh_system *, int level, uint32_t width, uint32_t slabs, uint32_t reps, double *avg_ms);
-/* kind 0 = Gram G = X^T Y (X n x wa, Y n x wb), kind 1 = basis update Z = [X | W] C: average device time of `reps` launches. */
+/* kind 0 = Gram G = X^T Y (X n x wa, Y n x wb), kind 1 = basis update Z = [X | W] C: average device time of `reps` launches;
+ * kinds 2, 3 = a check, not a timing: the eigensolver's column-mapped basis update [X[:, map] | W | P] C (wa active columns of X through the
+ * identity map / a map with gaps, W and P n x wb) in its one-destination and two-destination forms on the same inputs; *avg_ms
+ * receives the number of entries that are not what the one-destination form's compact panel, scattered on the host, requires (0 = all equal). */
 int mhl_context_bench_dense(mh_context *, int kind, uint64_t n, uint32_t wa, uint32_t wb, uint32_t reps, double *avg_ms);
 /* The Rayleigh-Ritz step's Householder tridiagonalisation called directly: a (m x m, symmetric, both triangles, m <= 256) ->
  * d[m], e[m - 1]; variant 0 = one workgroup, 1 = several workgroups exchanging tagged values. */

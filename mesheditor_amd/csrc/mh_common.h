@@ -627,8 +627,10 @@ void mh_gram(mh_context *ctx, size_t n, const double *x, uint32_t wa, const doub
 // [X | W | P] * Ct -> out1 (first n1 columns), out2 (the rest); Ct row-major m x nc.  mh_dense.hip
 void mh_combine(mh_context *ctx, size_t n, const double *x, uint32_t wx, const double *w, uint32_t ww, const double *p, uint32_t wp, const double *ct, uint32_t nc,
                 double *out1, uint32_t n1, double *out2, bool accumulate = false, uint32_t ldx = 0, const uint32_t *xmap = nullptr, uint32_t ld1 = 0,
-                const uint32_t *omap = nullptr, uint32_t col_begin = 0, uint32_t col_count = 0); // optional column maps on X (read) and out1 (write), pitches
+                const uint32_t *omap = nullptr, uint32_t col_begin = 0, uint32_t col_count = 0, // optional column maps on X (read) and out1 (write), pitches
                                                                                                 // ldx / ld1; col_count > 0: only columns [col_begin, +col_count) of Ct
+                double *out1_also = nullptr, uint32_t ld1_also = 0, const uint32_t *omap_also = nullptr); // (with xmap, one launch:) out1's columns are stored a second time,
+                                                                                                         // column c to column omap_also[c] of a panel of pitch ld1_also (may be X: see k_combine)
 bool mh_tridiag_lowest_wide(mh_context *ctx, const double *d, const double *e, uint32_t m, uint32_t k, double *w, double *z, uint32_t ldz, double *work, int *info2,
                             double *quality_host); // orders 257 .. 768 (mh_dense.hip)
 void mh_apply_q(mh_context *ctx, const double *a, const double *tau, uint32_t m, double *z, uint32_t ldz, uint32_t ncols); // mh_dense.hip: Z <- Q Z after mh_sytrd_small / mh_sytrd_wide (order <= 768)

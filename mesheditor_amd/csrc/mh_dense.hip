@@ -221,14 +221,23 @@ constexpr int CK = 16; // K chunk (32 measured slower: 475 vs 427 us at 75 + 75 
 // scalar bases with constant per-thread offsets (coefficients, outputs), and from compile-time LDS offsets (the chunk loop is
 // unrolled over its two stage buffers).  Workgroups are persistent (row tiles dealt round-robin), so the table and the launch
 // are paid once.
-template<int NT, bool ACCUMULATE, bool MAPPED> // 16-column output tiles per wave (nc <= 16 * NT); ACCUMULATE: out += instead of out =; MAPPED: column maps on X / out1
+template<int NT, bool ACCUMULATE, bool MAPPED, bool ALSO = false> // 16-column output tiles per wave (nc <= 16 * NT); ACCUMULATE: out += instead of out =; MAPPED: column maps on X / out1; ALSO: out1 stored twice
 __global__ void __launch_bounds__(256) k_combine(const double *__restrict__ X, int wx, int ldx, const uint32_t *__restrict__ xmap, const double *__restrict__ W, int ww,
                                                 const double *__restrict__ P, int wp,
                                                 const double *__restrict__ Ct, int ldc, int c0, int nc, size_t n, double *__restrict__ out1, int n1,
-                                                double *__restrict__ out2, size_t split_stride, int ld1, const uint32_t *__restrict__ omap) {
+                                                double *__restrict__ out2, size_t split_stride, int ld1, const uint32_t *__restrict__ omap,
+                                                double *out1_also = nullptr, int ld1_also = 0, const uint32_t *__restrict__ omap_also = nullptr) {
     // X's logical column k lives at physical column xmap[k] of a panel of pitch ldx (xmap null: identity); out1's logical
-    // column c goes to physical column omap[c] of a panel of pitch ld1 (in place over X is safe: a workgroup reads all of a
-    // tile's 64 rows before it writes them)
+    // column c goes to physical column omap[c] of a panel of pitch ld1.  ALSO: and a second time to column omap_also[c] of
+    // out1_also (pitch ld1_also) -- the compact panel the image product loads in 16-byte pairs and the basis' own columns leave
+    // in one pass, from the same accumulators.
+    // In place over X (out1 is X: chol_orthonormalise; out1_also is X, through the map X is read by: update_basis) is safe, and this is
+    // where it holds (X and out1 carry __restrict__ all the same: the basis is only ever read through the integer address table
+    // below, not through X, and every such read is consumed into LDS before the barrier that precedes the stores): rows belong
+    // to one workgroup (a tile's 64, dealt whole; the clamped loads of a short last tile stay inside it); a tile's stores
+    // come after its chunk loop, whose last chunk fetches nothing and ends with a barrier, so every wave has committed every
+    // K-chunk of the tile's rows to LDS before any wave stores; and the next tile's first fetch comes after the stores, at
+    // the top of the tile loop -- nothing of a later tile is prefetched.  One K slice only (gridDim.y == 1: mh_combine).
     // this launch owns output columns c0 .. c0 + nc of the ldc the coefficient matrix has; with gridDim.y > 1 the K range
     // is cut into gridDim.y slices and slice s writes its partial product to out1 + s * split_stride
     extern __shared__ __attribute__((aligned(16))) double smem[];
@@ -274,9 +283,15 @@ __global__ void __launch_bounds__(256) k_combine(const double *__restrict__ X, i
     const int col_l = lane & 15, row_l = lane >> 4;
     const int pitch2 = ldc - n1;
     uint32_t ocol[MAPPED ? NT : 1]; // MAPPED: out1 columns through the map
+    uint32_t ocol_also[ALSO ? NT : 1];
     if (MAPPED) {
 #pragma unroll
         for (int t = 0; t < NT; ++t) ocol[t] = omap[min(c0 + 16 * t + col_l, max(n1, 1) - 1)] * 8u;
+    }
+    if (ALSO) {
+        static_assert(!ALSO || (MAPPED && !ACCUMULATE), "the second store goes with the mapped, overwriting form");
+#pragma unroll
+        for (int t = 0; t < NT; ++t) ocol_also[t] = omap_also[min(c0 + 16 * t + col_l, max(n1, 1) - 1)] * 8u;
     }
     double ps[SJ], pc[NT];
     const size_t tiles = (n + 63) / 64;
@@ -345,10 +360,12 @@ __global__ void __launch_bounds__(256) k_combine(const double *__restrict__ X, i
             if (r >= n) continue;
             char *row1 = reinterpret_cast<char *>(out1 + r * size_t(ld1)) + (MAPPED ? 0 : (c0 + col_l) * 8);
             char *row2 = reinterpret_cast<char *>(out2 + r * size_t(pitch2)) + (c0 + col_l - n1) * 8;
+            char *row1_also = ALSO ? reinterpret_cast<char *>(out1_also + r * size_t(ld1_also)) : nullptr;
 #pragma unroll
             for (int t = 0; t < NT; ++t) {
                 if (t >= NT - 2 && t * 16 + col_l >= nc) continue; // only the last two strips can pass nc
                 const int s0 = c0 + 16 * t; // first column of the strip (uniform)
+                if (ALSO && s0 + col_l < n1) *reinterpret_cast<double *>(row1_also + size_t(ocol_also[t])) = acc[t][reg];
                 double *dst;
                 if (s0 + 16 <= n1) dst = reinterpret_cast<double *>(row1 + (MAPPED ? size_t(ocol[t]) : size_t(128 * t)));
                 else if (s0 >= n1) dst = reinterpret_cast<double *>(row2 + 128 * t);
@@ -493,16 +510,16 @@ __global__ void k_iota(uint32_t *p, uint32_t n) {
 namespace {
 // Workgroups of an instantiation that fit a CU with `lds` bytes of dynamic LDS each (its two stage buffers may exceed the 64 KB
 // a launch may ask for by default: the limit is raised once per device); asked once per (device, 4 KB LDS class).
-template<int NT, bool ACCUMULATE, bool MAPPED> int combine_residency(mh_context *ctx, size_t lds) {
+template<int NT, bool ACCUMULATE, bool MAPPED, bool ALSO = false> int combine_residency(mh_context *ctx, size_t lds) {
     static PerDeviceOnce attr;
-    attr.run(ctx->device, [] { HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_combine<NT, ACCUMULATE, MAPPED>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); });
+    attr.run(ctx->device, [] { HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_combine<NT, ACCUMULATE, MAPPED, ALSO>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); });
     static std::mutex guard;
     static std::map<std::pair<int, size_t>, int> known;
     std::lock_guard<std::mutex> lock(guard);
     auto [it, fresh] = known.try_emplace({ctx->device, lds >> 12}, 1);
     if (fresh) {
         int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void *>(&k_combine<NT, ACCUMULATE, MAPPED>), 256, ((lds >> 12) + 1) << 12) == hipSuccess && nb > 0) it->second = std::min(nb, 8);
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void *>(&k_combine<NT, ACCUMULATE, MAPPED, ALSO>), 256, ((lds >> 12) + 1) << 12) == hipSuccess && nb > 0) it->second = std::min(nb, 8);
     }
     return it->second;
 }
@@ -520,10 +537,12 @@ const uint32_t *mh_identity_map(mh_context *ctx) {
 
 void mh_combine(mh_context *ctx, size_t n, const double *x, uint32_t wx, const double *w, uint32_t ww, const double *p, uint32_t wp, const double *ct, uint32_t nc,
                 double *out1, uint32_t n1, double *out2, bool accumulate, uint32_t ldx, const uint32_t *xmap, uint32_t ld1, const uint32_t *omap, uint32_t col_begin,
-                uint32_t col_count) {
+                uint32_t col_count, double *out1_also, uint32_t ld1_also, const uint32_t *omap_also) {
     if (!nc) return;
     if (!col_count) { col_begin = 0; col_count = nc; }
-    const bool caller_omap = omap != nullptr;
+    const bool caller_omap = omap != nullptr || out1_also != nullptr;
+    // (a second destination of out1: the mapped kernel's, in one launch -- several launches over the same basis may not write what they read)
+    if (out1_also && (!xmap || !omap_also || !ld1_also || accumulate || col_count > 256)) mh_throw(MH_EINVAL, "combine: a second destination needs column maps and one launch (%u columns)", col_count);
     if (col_begin + col_count > nc) mh_throw(MH_EINVAL, "combine: columns %u + %u exceed %u", col_begin, col_count, nc);
     const bool mapped = xmap != nullptr;
     if (mapped && accumulate) mh_throw(MH_EINVAL, "combine: column maps are not supported with accumulate");
@@ -581,10 +600,11 @@ void mh_combine(mh_context *ctx, size_t n, const double *x, uint32_t wx, const d
             constexpr int CP = (NT * 16) % 32 == 16 ? NT * 16 : NT * 16 + 16;
             const size_t lds = 2 * (size_t(64) * (CK + 2) + size_t(CK) * CP) * sizeof(double) + size_t(m_total + CK) * 12;
             const size_t lds_m = lds;
-            const int per_cu = accumulate ? combine_residency<NT, true, false>(ctx, lds) : mapped ? combine_residency<NT, false, true>(ctx, lds) : combine_residency<NT, false, false>(ctx, lds);
+            const int per_cu = accumulate ? combine_residency<NT, true, false>(ctx, lds) : out1_also ? combine_residency<NT, false, true, true>(ctx, lds) : mapped ? combine_residency<NT, false, true>(ctx, lds) : combine_residency<NT, false, false>(ctx, lds);
             const unsigned grid = unsigned(std::min<size_t>(div_up(n, 64), size_t(per_cu) * ctx->cu_count));
 #define MH_COMBINE_ARGS x, int(wx), int(ldx ? ldx : wx), xmap, w, int(ww), p, int(wp), ct, int(nc), int(c0), int(ncc), n, out1, int(n1), out2, 0, int(ld1 ? ld1 : n1), omap
             if (accumulate) k_combine<NT, true, false><<<grid, 256, lds, ctx->stream>>>(MH_COMBINE_ARGS);
+            else if (out1_also) k_combine<NT, false, true, true><<<grid, 256, lds_m, ctx->stream>>>(MH_COMBINE_ARGS, out1_also, int(ld1_also), omap_also);
             else if (mapped) k_combine<NT, false, true><<<grid, 256, lds_m, ctx->stream>>>(MH_COMBINE_ARGS);
             else k_combine<NT, false, false><<<grid, 256, lds, ctx->stream>>>(MH_COMBINE_ARGS);
 #undef MH_COMBINE_ARGS

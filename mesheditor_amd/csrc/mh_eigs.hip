@@ -21,7 +21,7 @@
 #include <optional>
 #include <type_traits>
 
-__global__ void k_shift_values(const double *kval, const double *mval, size_t nblocks, double sigma, double *aval);
+__global__ void k_shift_values(const double *kval, const double *mval, size_t nblocks, double sigma, double *aval, float *aval32);
 __global__ void k_diag_inverse(const uint32_t *row_ptr, const uint32_t *col, const double *aval, uint32_t nnodes, double *dinv);
 __global__ void k_coarse_matrix(const uint32_t *row_ptr, const uint32_t *col, const double *aval, const double *tmat, const uint32_t *agg_of, const uint32_t *agg_ptr,
                                 const uint32_t *agg_nodes, uint32_t nagg, double *a0);
@@ -61,7 +61,7 @@ std::mutex g_solve_mutex;
 //   MH_CYCLE=d2,d1,g,ratio[,ratio1]  shape of the preconditioner cycle: Chebyshev degrees of the P2 and P1 smoothers, P1 cycles per
 //                           application, spectrum ratio lmax / lmin the smoothers target; 0 or missing keeps a built-in value
 //   MH_TEST=...             test hooks, comma separated (what each forces: beside its member): sytrd_giveup, no_tridiag_wide, last_resort,
-//                           coarse_pivot, selfcheck_fail, lmax_low, potrf_chain, no_poly_start, fresh_structure
+//                           coarse_pivot, selfcheck_fail, lmax_low, potrf_chain, no_poly_start, fresh_structure, copy_passes
 // Read elsewhere: MH_AGG, MH_PATCH_Q, MH_CLUSTERS, MH_CLUSTER_CAP, MH_POOL_CAP_MB; MH_TEST's poison, redzone and farzone (mh_common.h),
 // sytrd_multi, sytrd_fused and own_gemm (mh_dense.hip).
 struct Switches {
@@ -78,6 +78,7 @@ struct Switches {
     bool potrf_chain = getenv("MH_TEST") && strstr(getenv("MH_TEST"), "potrf_chain"); // the Gram blocks' Cholesky factorisations as the chain of launches they were before round 5
     bool no_poly_start = getenv("MH_TEST") && strstr(getenv("MH_TEST"), "no_poly_start"); // (A/B hook of round 5: the cold start block as rounds 1-4 had it)
     bool fresh_structure = getenv("MH_TEST") && strstr(getenv("MH_TEST"), "fresh_structure"); // (A/B hook: every mh_assemble builds the mesh's structure anew -- mh_pipeline.hip reads it too -- and the start block's box comes from k_bbox, as before the structure was kept)
+    bool copy_passes = getenv("MH_TEST") && strstr(getenv("MH_TEST"), "copy_passes"); // (A/B hook: the tall copy passes that moved a panel, or computed what the next launch overwrote, run again -- the scatter after the basis update, the gather before the preconditioner, the start block's copy, image transform and full random fill, the conversion of aval -- every returned number is the same bit for bit)
     Switches() {
         if (const char *c = getenv("MH_CYCLE")) {
             double v[5] = {0, 0, 0, 0, 0};
@@ -180,9 +181,12 @@ struct Timer {
 };
 
 // ---- elementwise panel kernels (n x w row-major, flat index) ------------------------------------------------
-__global__ void k_random_panel(double *__restrict__ x, size_t count, uint64_t seed) {
-    const size_t i = size_t(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (i >= count) return;
+// Gaussian noise in columns col0 .. w - 1 of a rows x w panel; an entry's value depends on the seed and on its flat index alone
+__global__ void k_random_panel(double *__restrict__ x, size_t rows, uint32_t w, uint32_t col0, uint64_t seed) {
+    const size_t j = size_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    const uint32_t wf = w - col0;
+    if (j >= rows * wf) return;
+    const size_t i = (j / wf) * w + col0 + j % wf;
     auto mix = [](uint64_t z) {
         z += 0x9e3779b97f4a7c15ull;
         z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
@@ -240,14 +244,21 @@ __global__ void k_prolong_p1_v4(const f4_t *__restrict__ x1, const uint32_t *__r
     x2[i] += a == bb ? va : 0.5f * (va + x1[(size_t(3) * bb + comp) * w4 + c]);
 }
 // The same with zero initial iterate, reading the double-precision right-hand side at its own pitch ws and leaving its
-// single-precision copy b32 (pitch w, zero padded) for the later steps: conversion and first step in one pass.
-__global__ void k_cheb_init_convert(const double *__restrict__ src, uint32_t ws, const float *__restrict__ dinv, float inv_theta, float *__restrict__ b32,
+// single-precision copy b32 (pitch w, zero padded) for the later steps: conversion and first step in one pass.  The source is a
+// PanelColumns: its ws columns may be any columns of a wider panel, so the caller's residuals need no compact copy first.
+struct PanelColumns {
+    uint32_t pitch;      // row pitch of the panel
+    uint32_t count;      // logical columns; columns at or past it read as zero
+    const uint32_t *map; // logical column c lives at physical column map[c]; null: at c
+    __device__ __forceinline__ size_t at(size_t row, uint32_t c) const { return row * pitch + (map ? map[c] : c); }
+};
+__global__ void k_cheb_init_convert(const double *__restrict__ src, PanelColumns sc, const float *__restrict__ dinv, float inv_theta, float *__restrict__ b32,
                                     float *__restrict__ r, float *__restrict__ d, float *__restrict__ x, size_t rows, uint32_t w) {
     const size_t i = size_t(blockIdx.x) * blockDim.x + threadIdx.x;
     if (i >= rows * w) return;
     const size_t row = i / w;
     const uint32_t c = uint32_t(i % w);
-    const float rv = c < ws ? float(src[row * ws + c]) : 0.f;
+    const float rv = c < sc.count ? float(src[sc.at(row, c)]) : 0.f;
     const float dv = dinv[row] * rv * inv_theta;
     b32[i] = rv;
     r[i] = rv;
@@ -293,15 +304,15 @@ template<typename S, typename D> __global__ void k_convert_pitch(const S *__rest
 // r1 = P^T (b - t): corner value plus half of every incident edge's midside value.
 template<typename T>
 __global__ void k_restrict_p1(const T *__restrict__ b, const T *__restrict__ t, const uint32_t *__restrict__ p1_corner, const uint32_t *__restrict__ eptr,
-                              const uint32_t *__restrict__ emid, T *__restrict__ r1, uint32_t npts, uint32_t w, uint32_t wb = 0) {
-    // wb: pitch of b when it differs from the pitch w of t and r1 (columns >= wb of b read as zero)
+                              const uint32_t *__restrict__ emid, T *__restrict__ r1, uint32_t npts, uint32_t w, PanelColumns bc = PanelColumns{0, 0, nullptr}) {
+    // bc: where the columns of b live when it is not a panel of the pitch w of t and r1 (columns >= bc.count of b read as zero)
     const size_t i = size_t(blockIdx.x) * blockDim.x + threadIdx.x;
     if (i >= size_t(npts) * 3 * w) return;
     const uint32_t c = uint32_t(i % w), comp = uint32_t((i / w) % 3), p = uint32_t(i / (size_t(3) * w));
-    const uint32_t pb = wb ? wb : w;
+    if (!bc.pitch) bc.pitch = bc.count = w;
     auto res = [&](uint32_t node) {
         const size_t row = size_t(3) * node + comp;
-        return (c < pb ? b[row * pb + c] : T(0)) - t[row * w + c];
+        return (c < bc.count ? b[bc.at(row, c)] : T(0)) - t[row * w + c];
     };
     T s = res(p1_corner[p]);
     T h = 0;
@@ -993,7 +1004,7 @@ template<typename T> struct Precond {
     const PatchSet &patches_of(const BsrLevel &lvl) const { return lvl.id == 2 ? sys->patches2 : sys->patches1; }
     // deg Chebyshev-Jacobi steps on lvl; when z_out is given the last step writes the iterate there (in double)
     void cheb(const BsrLevel &lvl, int deg, const T *b, T *x, bool zero_init, T *r, T *d, T *t, uint32_t w, double *z_out = nullptr, uint32_t w_out = 0,
-              const double *b_src = nullptr, uint32_t w_src = 0, T *b_copy = nullptr) { // b_src: (single-precision cycle) convert the right-hand side on the way
+              const double *b_src = nullptr, PanelColumns b_cols = PanelColumns{0, 0, nullptr}, T *b_copy = nullptr) { // b_src: (single-precision cycle) convert the right-hand side on the way
         const size_t rows = size_t(3) * lvl.n_nodes;
         const double lmax = lvl.lmax, lmin = lvl.lmax / (lvl.id == 1 && ratio1 > 0 ? ratio1 : ratio);
         const double theta = 0.5 * (lmax + lmin), delta = 0.5 * (lmax - lmin), sig = theta / delta;
@@ -1001,7 +1012,7 @@ template<typename T> struct Precond {
         const T *dinv = dinv_of(lvl);
         if (!zero_init) spmm(lvl, x, t, w);
         if constexpr (!kDouble) {
-            if (b_src && zero_init) k_cheb_init_convert<<<grid1(rows * w), TB, 0, ctx->stream>>>(b_src, w_src, dinv, float(1.0 / theta), b_copy, r, d, x, rows, w);
+            if (b_src && zero_init) k_cheb_init_convert<<<grid1(rows * w), TB, 0, ctx->stream>>>(b_src, b_cols, dinv, float(1.0 / theta), b_copy, r, d, x, rows, w);
             else k_cheb_init_v4<<<grid1(rows * (w / 4)), TB, 0, ctx->stream>>>(reinterpret_cast<const f4_t *>(b), zero_init ? nullptr : reinterpret_cast<const f4_t *>(t), dinv,
                                                                                float(1.0 / theta), reinterpret_cast<f4_t *>(r), reinterpret_cast<f4_t *>(d),
                                                                                reinterpret_cast<f4_t *>(x), zero_init ? 0 : 1, rows, w / 4);
@@ -1047,9 +1058,13 @@ template<typename T> struct Precond {
             KERNEL_CHECK();
         }
     }
-    // z = B r for an n2 x w panel
-    void apply(const double *r_in, double *z_out, uint32_t w_in) {
+    // z = B r for an n2 x w panel.  The single-precision cycle reads r_in in two kernels only (the first smoothing step, which leaves
+    // its float copy, and the restriction of the double residual), both element by element: there r_in may be w_in columns of a
+    // wider panel -- row pitch r_pitch (0: w_in), column c at r_map[c] (null: at c) -- and the caller gathers nothing.
+    void apply(const double *r_in, double *z_out, uint32_t w_in, uint32_t r_pitch = 0, const uint32_t *r_map = nullptr) {
         mh_finish_hierarchy(sys);
+        if (kDouble && (r_map || (r_pitch && r_pitch != w_in))) mh_throw(MH_EINVAL, "the double-precision cycle takes a compact right-hand side");
+        const PanelColumns r_cols{r_pitch ? r_pitch : w_in, w_in, r_map};
         const uint32_t w = pitch(w_in);
         const uint32_t nn = sys->n_nodes, np = sys->n_points, na = sys->n_agg;
         const size_t n2 = size_t(3) * nn, n1 = size_t(3) * np, n0 = size_t(6) * na;
@@ -1058,7 +1073,7 @@ template<typename T> struct Precond {
         else r = rin.get(); // filled by the first smoothing step below
         T *z = z2.get();
         if constexpr (kDouble) cheb(sys->L2, deg2, r, z, true, r2, d2, t2, w);
-        else cheb(sys->L2, deg2, r, z, true, r2, d2, t2, w, nullptr, 0, r_in, w_in, rin.get());
+        else cheb(sys->L2, deg2, r, z, true, r2, d2, t2, w, nullptr, 0, r_in, r_cols, rin.get());
         // Residual for the next level.  With single-precision smoothers it is formed in double (double A, double r,
         // the float iterate): a float residual carries an error of 6e-8 ||A|| ||z|| that the coarse solves amplify by
         // the condition number, which stalls the lowest modes of thin, ill-conditioned bodies at ~1e-4.
@@ -1068,7 +1083,7 @@ template<typename T> struct Precond {
             KERNEL_CHECK();
         } else {
             mh_spmm_mixed(ctx, sys->L2, z, t2d, w);
-            k_restrict_p1<double><<<grid1(n1 * w), TB, 0, ctx->stream>>>(r_in, t2d.get(), sys->p1_corner, sys->p1_edge_ptr, sys->p1_edge_mid, r1d.get(), np, w, w_in); // r_in at its own pitch
+            k_restrict_p1<double><<<grid1(n1 * w), TB, 0, ctx->stream>>>(r_in, t2d.get(), sys->p1_corner, sys->p1_edge_ptr, sys->p1_edge_mid, r1d.get(), np, w, r_cols); // r_in at its own pitch, through its own map
             KERNEL_CHECK();
             k_convert<double, T><<<grid1(n1 * w), TB, 0, ctx->stream>>>(r1d.get(), r1.get(), n1 * w);
             KERNEL_CHECK();
@@ -1100,7 +1115,7 @@ double estimate_lmax(mh_context *ctx, BsrLevel &lvl, const PatchSet &ps) {
     const uint32_t w = 8;
     const size_t rows = size_t(3) * lvl.n_nodes;
     DevArray<double> v(ctx, rows * w), t(ctx, rows * w), nrm(ctx, w), scratch, py(ctx, ps.scratch_rows() * w);
-    k_random_panel<<<grid1(rows * w), TB, 0, ctx->stream>>>(v, rows * w, 0x5eedull);
+    k_random_panel<<<grid1(rows * w), TB, 0, ctx->stream>>>(v, rows, w, 0, 0x5eedull);
     KERNEL_CHECK();
     colsumsq(ctx, v, rows, w, nrm, scratch);
     k_scale_cols_inv_sqrt<<<grid1(rows * w), TB, 0, ctx->stream>>>(v, nrm, rows, w);
@@ -1212,7 +1227,11 @@ void mh_build_hierarchy(mh_system *sys, double sigma, bool defer) {
     for (BsrLevel *lvl : {&sys->L2, &sys->L1}) {
         lvl->aval.reset(ctx, lvl->n_blocks * 9);
         lvl->dinv.reset(ctx, size_t(3) * lvl->n_nodes);
-        k_shift_values<<<grid1(lvl->n_blocks * 9), TB, 0, ctx->stream>>>(lvl->kval, lvl->mval, lvl->n_blocks, sigma, lvl->aval);
+        // (the smoothers' single-precision copy of the operator leaves with it: the values are in registers here, and a conversion of its
+        // own read them back once per level; MH_TEST=copy_passes: that conversion, below.  Unconditional, as the conversion was: the
+        // hierarchy is built before a solve chooses the precision of its smoothers)
+        lvl->aval32.reset(ctx, lvl->n_blocks * 9);
+        k_shift_values<<<grid1(lvl->n_blocks * 9), TB, 0, ctx->stream>>>(lvl->kval, lvl->mval, lvl->n_blocks, sigma, lvl->aval, switches().copy_passes ? nullptr : lvl->aval32.get());
         KERNEL_CHECK();
         k_diag_inverse<<<grid1(lvl->n_nodes), TB, 0, ctx->stream>>>(lvl->row_ptr, lvl->col, lvl->aval, lvl->n_nodes, lvl->dinv);
         KERNEL_CHECK();
@@ -1237,10 +1256,11 @@ void mh_build_hierarchy(mh_system *sys, double sigma, bool defer) {
         for (BsrLevel *lvl : {&sys->L2, &sys->L1}) {
             lvl->lmax = estimate_lmax(ctx, *lvl, lvl->id == 2 ? sys->patches2 : sys->patches1);
             if (sys->lmax_widened) lvl->lmax *= 1.25; // (an earlier solve of this system needed the wider bound: eigs_impl)
-            lvl->aval32.reset(ctx, lvl->n_blocks * 9);
             lvl->dinv32.reset(ctx, size_t(3) * lvl->n_nodes);
-            k_convert<double, float><<<grid1(lvl->n_blocks * 9), TB, 0, ctx->stream>>>(lvl->aval.get(), lvl->aval32.get(), lvl->n_blocks * 9);
-            KERNEL_CHECK();
+            if (switches().copy_passes) {
+                k_convert<double, float><<<grid1(lvl->n_blocks * 9), TB, 0, ctx->stream>>>(lvl->aval.get(), lvl->aval32.get(), lvl->n_blocks * 9);
+                KERNEL_CHECK();
+            }
             k_convert<double, float><<<grid1(size_t(3) * lvl->n_nodes), TB, 0, ctx->stream>>>(lvl->dinv.get(), lvl->dinv32.get(), size_t(3) * lvl->n_nodes);
             KERNEL_CHECK();
         }
@@ -1372,7 +1392,7 @@ void dense_eigs(mh_system *sys, uint32_t nev, double sigma, double *eigenvalues,
     a.zero();
     m.zero();
     lvl.aval.reset(ctx, lvl.n_blocks * 9);
-    k_shift_values<<<grid1(lvl.n_blocks * 9), TB, 0, ctx->stream>>>(lvl.kval, lvl.mval, lvl.n_blocks, sigma, lvl.aval);
+    k_shift_values<<<grid1(lvl.n_blocks * 9), TB, 0, ctx->stream>>>(lvl.kval, lvl.mval, lvl.n_blocks, sigma, lvl.aval, nullptr);
     KERNEL_CHECK();
     k_bsr_to_dense<<<grid1(lvl.n_nodes), TB, 0, ctx->stream>>>(lvl.row_ptr, lvl.col, lvl.aval, lvl.mval, lvl.n_nodes, a, m);
     KERNEL_CHECK();
@@ -1650,8 +1670,8 @@ struct BlockLobpcg {
         }
         if (w > 256) {
             panel_trsm(ctx, n, V, w, Gs, w);
-            if (MV) panel_trsm(ctx, n, MV, w, Gs, w);
-            if (AV) panel_trsm(ctx, n, AV, w, Gs, w);
+            if (MV && transform_images) panel_trsm(ctx, n, MV, w, Gs, w);
+            if (AV && transform_images) panel_trsm(ctx, n, AV, w, Gs, w);
         } else {
             // V <- V L^-T through the explicit small inverse and the MFMA basis-update kernel (in place: a workgroup
             // reads its rows before it writes them): L^-1 column-major IS the k-major coefficient matrix of V L^-T
@@ -1668,22 +1688,37 @@ struct BlockLobpcg {
     }
 
     // z = B r for w columns (in column slabs above kPrecondColumns: precondition_in_slabs)
-    void precondition(const double *r, double *z, uint32_t w) {
+    // r_pitch, r_map: r as w columns of a wider panel (Precond::apply) -- only where precondition_reads_columns(w) says so
+    void precondition(const double *r, double *z, uint32_t w, uint32_t r_pitch = 0, const uint32_t *r_map = nullptr) {
+        if ((r_pitch || r_map) && !precondition_reads_columns(w)) mh_throw(MH_EINVAL, "this preconditioner path takes a compact right-hand side");
         precondition_in_slabs(ctx, n, r, z, w, [&](const double *rp, double *zp, uint32_t wc) {
             if (panel_cg) panel_cg->solve(*prec64, rp, zp, wc, inner_cg);
-            else if (prec32) prec32->apply(rp, zp, wc);
+            else if (prec32) prec32->apply(rp, zp, wc, r_pitch, r_map);
             else prec64->apply(rp, zp, wc);
         });
     }
+    // The single-precision cycle on one slab reads its right-hand side in two element-wise kernels: it takes the columns where they
+    // lie.  The double-precision cycle, the inner conjugate gradients and the slabs hand r to many kernels: they keep a compact copy.
+    bool precondition_reads_columns(uint32_t w) const { return prec32 && !panel_cg && w <= kPrecondColumns && !switches().copy_passes; }
 
     // The initial block: seed columns (warm start), then Gaussian noise, the exact rigid-body modes, one smoothing pass;
     // M-orthonormalised and rotated into its Ritz vectors.
     void start() {
         redos_at_start = ctx->sytrd_redos;
         if (ctx->rr_check) HIP_CHECK(hipMemsetAsync(ctx->rr_check, 0, sizeof(unsigned long long), st));
-        k_random_panel<<<grid1(n * b), TB, 0, st>>>(X, n * b, 20260710ull);
-        KERNEL_CHECK();
+        // Gaussian noise in every column -- except, on a cold start with the polynomial block, in the columns that the rigid-body modes
+        // and the polynomial fields overwrite below: three quarters of the panel; the noise there is filled after the decision, with
+        // the same generator on the same indices (MH_TEST=copy_passes: everywhere, first, as it was)
+        const bool fill_late = !switches().copy_passes;
+        if (!fill_late) {
+            k_random_panel<<<grid1(n * b), TB, 0, st>>>(X, n, b, 0, 20260710ull);
+            KERNEL_CHECK();
+        }
         warm = seed_basis && seed_rows == n && seed_cols >= nev;
+        if (warm && fill_late) { // (the seed's columns and the rigid-body modes go over a full fill)
+            k_random_panel<<<grid1(n * b), TB, 0, st>>>(X, n, b, 0, 20260710ull);
+            KERNEL_CHECK();
+        }
         if (warm) {
             const uint32_t ncols = std::min(seed_cols, b);
             DevArray<float> seed(ctx, n * ncols);
@@ -1704,7 +1739,6 @@ struct BlockLobpcg {
             k_inject_rbm<<<grid1(sys->n_nodes), TB, 0, st>>>(sys->node_xyz, sys->node_component, sys->component_centroid, sys->n_components, sys->n_nodes, X, b, 0);
             KERNEL_CHECK();
         };
-        if (seed_rigid) inject_rigid_modes();
         // Smooth start (round 5): behind the rigid-body modes a cold block begins from low-degree polynomial displacement fields
         // (k_inject_poly: uniform strains, then every Legendre product of total degree 2, 3, ... while whole degrees fit) instead of noise
         // in three quarters of its columns; the last quarter stays random (what the polynomials cannot represent still has to be found).
@@ -1745,11 +1779,21 @@ struct BlockLobpcg {
                 DevArray<uint32_t> tri_d(ctx, std::max<size_t>(1, triples.size()));
                 box_d.upload(box, 6);
                 if (!triples.empty()) tri_d.upload(triples.data(), triples.size());
+                const uint32_t first_random = n_rigid + 6 + 3 * uint32_t(triples.size()); // (k_inject_rbm and k_inject_poly write every row of the columns before it)
+                if (fill_late && first_random < b) {
+                    k_random_panel<<<grid1(n * (b - first_random)), TB, 0, st>>>(X, n, b, first_random, 20260710ull);
+                    KERNEL_CHECK();
+                }
                 k_inject_poly<<<grid1(sys->n_nodes), TB, 0, st>>>(sys->node_xyz, box_d, sys->n_nodes, tri_d, uint32_t(triples.size()), X, b, n_rigid);
                 KERNEL_CHECK();
                 HIP_CHECK(hipStreamSynchronize(st)); // (the small arrays return to the pool; the uploads read stack memory)
             }
         }
+        if (fill_late && !warm && !with_poly) { // no polynomial block (thin body, several bodies, a rank-deficient first try): noise everywhere
+            k_random_panel<<<grid1(n * b), TB, 0, st>>>(X, n, b, 0, 20260710ull);
+            KERNEL_CHECK();
+        }
+        if (seed_rigid) inject_rigid_modes(); // (after the fill: the noise leaves their columns alone only beside the polynomial block)
         // A cold start begins from B M x for Gaussian noise x (one preconditioner application: the high-frequency content
         // of the noise is damped before the first Rayleigh-Ritz step), with the exact rigid-body modes put back: one
         // iteration fewer on every workload measured (18 -> 17 at S100k, 40 -> 39 on the ball, 17 -> 16 at S30k).
@@ -1760,12 +1804,16 @@ struct BlockLobpcg {
                 precondition(MX, Xn, b);
                 precond_seconds += tp.stop();
                 prof.op_applications += b;
-                HIP_CHECK(hipMemcpyAsync(X, Xn.get(), n * b * sizeof(double), hipMemcpyDeviceToDevice, st));
+                // (the smoothed block becomes X by name; MH_TEST=copy_passes: by a copy of the panel, as it was)
+                if (switches().copy_passes) HIP_CHECK(hipMemcpyAsync(X, Xn.get(), n * b * sizeof(double), hipMemcpyDeviceToDevice, st));
+                else std::swap(X, Xn);
             }
             if (seed_rigid) inject_rigid_modes();
         }
         mh_spmm(ctx, sys->L2, nullptr, X, nullptr, sys->L2.mval, MX, b);
-        if (!chol_orthonormalise(X, MX, nullptr, b)) {
+        // (M X is only read here, for the Gram matrix: the fused product below forms both images of the orthonormalised block, so M X L^-T
+        // would be overwritten unread; MH_TEST=copy_passes forms it)
+        if (!chol_orthonormalise(X, MX, nullptr, b, switches().copy_passes)) {
             if (with_poly) { // a body the polynomial fields are dependent on (too few node layers along an axis): the random block instead
                 if (verbose) fprintf(stderr, "[lobpcg] polynomial start block rank deficient: random block instead\n");
                 poly_allowed = false;
@@ -1923,6 +1971,11 @@ struct BlockLobpcg {
         w = uint32_t(act.size());
         idx_d.upload(act.data(), w);
         const double *residuals = Rw.get();
+        // Rw exists only to hand the active residual columns to the preconditioner.  Where that reads its right-hand side column by
+        // column (precondition_reads_columns), it takes them from Rr or R through the map and neither gather below is launched.
+        const bool in_place = precondition_reads_columns(w);
+        uint32_t r_pitch = 0;
+        const uint32_t *r_map = nullptr;
         if (rw_from_rr) { // the epilogue's compact panel holds the previous active set; today's is a subset of it
             if (act == res_act && res_pitch == w) {
                 residuals = Rr.get(); // nothing was locked and the pitch is the count: the panel is the input as it stands
@@ -1936,9 +1989,15 @@ struct BlockLobpcg {
                     pos[k] = uint32_t(q);
                 }
                 pos_d.upload(pos.data(), w);
-                k_gather_cols<<<grid1(n * w), TB, 0, st>>>(Rr, pos_d, Rw, n, res_pitch, w);
-                KERNEL_CHECK();
+                if (in_place) {
+                    residuals = Rr.get(), r_pitch = res_pitch, r_map = pos_d;
+                } else {
+                    k_gather_cols<<<grid1(n * w), TB, 0, st>>>(Rr, pos_d, Rw, n, res_pitch, w);
+                    KERNEL_CHECK();
+                }
             }
+        } else if (in_place) {
+            residuals = R.get(), r_pitch = b, r_map = idx_d;
         } else {
             k_gather_cols<<<grid1(n * w), TB, 0, st>>>(R, idx_d, Rw, n, b, w);
             KERNEL_CHECK();
@@ -1949,7 +2008,7 @@ struct BlockLobpcg {
         theta_act_d.upload(theta_act.data(), w);
         {
             Timer tp(ctx);
-            precondition(residuals, W, w);
+            precondition(residuals, W, w, r_pitch, r_map);
             precond_seconds += tp.stop();
             prof.op_applications += w;
         }
@@ -2162,14 +2221,24 @@ struct BlockLobpcg {
                 ROCBLAS_CHECK(rocblas_dgemm(ctx->blas, rocblas_operation_none, rocblas_operation_transpose, pitchc, rocblas_int(wp), rocblas_int(w), &minus, rows_w, pitchc, Hp,
                                             rocblas_int(wp), &plus, rows_p, pitchc));
             }
-            mh_combine(ctx, n, X, wa, W, w, P, wp, Ct, wa + wp_new, Xn, wa, Pn, false, b, idx_d, pitch);
+            // Where the new Ritz vectors go.  Blocks of up to 128 columns (one update launch, always our kernel): the update stores each
+            // tile twice, into the compact panel Xn the image product below loads in 16-byte pairs and into the active columns of X
+            // (k_combine says why writing X in the launch that reads it is safe).  Wider blocks, whose update takes several launches
+            // over the same inputs, and MH_TEST=copy_passes: Xn, then a scatter into X.  (An update in place, with the product reading
+            // X at its own pitch, would serve only while the active columns are the leading ones: a free body's exact rigid-body
+            // columns lock at the first test, so that never happens -- profiles/copy_passes_ab.txt -- and the form is not built.)
+            const bool one_launch = b <= 128 && !switches().copy_passes;
+            if (one_launch) mh_combine(ctx, n, X, wa, W, w, P, wp, Ct, wa + wp_new, Xn, wa, Pn, false, b, idx_d, pitch, nullptr, 0, 0, X, b, idx_d);
+            else mh_combine(ctx, n, X, wa, W, w, P, wp, Ct, wa + wp_new, Xn, wa, Pn, false, b, idx_d, pitch);
             // M P_new (kept for blocks wider than 128 columns: the next projection needs it) from P_new itself: one pass over M.  Until
             // round 4 it was recombined from [M X, M W, M P] with the coefficients of P_new -- three tall panels read for one written:
             // 215-pair solves 1.7 ... 2.8 % slower, 129-pair solves 1 ... 1.5 % (and the image carried the recombination's rounding).
             if (wp_new && !pproj_ok) mh_spmm(ctx, sys->L2, nullptr, Pn, nullptr, sys->L2.mval, MPn, wp_new);
-            if (pitch == wa) k_scatter_cols<<<grid1(n * wa), TB, 0, st>>>(Xn.get(), idx_d, X.get(), n, b, wa);
-            else k_scatter_cols_pitch<<<grid1(n * wa), TB, 0, st>>>(Xn.get(), pitch, idx_d, X.get(), n, b, wa);
-            KERNEL_CHECK();
+            if (!one_launch) {
+                if (pitch == wa) k_scatter_cols<<<grid1(n * wa), TB, 0, st>>>(Xn.get(), idx_d, X.get(), n, b, wa);
+                else k_scatter_cols_pitch<<<grid1(n * wa), TB, 0, st>>>(Xn.get(), pitch, idx_d, X.get(), n, b, wa);
+                KERNEL_CHECK();
+            }
             if (Rr.count) {
                 // the new Ritz values sit in `evals` in the active slots' order: the residuals and their norms leave with the images
                 mh_spmm_mapped(ctx, sys->L2, sys->L2.aval, Xn, AX, sys->L2.mval, MX, pitch, b, wa, idx_d, evals, Rr, res_partial, scaled_norms ? sys->L2.dinv.get() : nullptr);

@@ -624,12 +624,16 @@ uint32_t mh_graph_aggregates(const std::vector<uint32_t> &row_ptr, const std::ve
     return graph_aggregates(row_ptr, col, n, target, max_order, agg_of);
 }
 
-__global__ void k_shift_values(const double *__restrict__ kval, const double *__restrict__ mval, size_t nblocks, double sigma, double *__restrict__ aval) {
+// aval = K - sigma M; aval32 (optional): the single-precision copy the smoothers read, rounded from the double that is stored
+__global__ void k_shift_values(const double *__restrict__ kval, const double *__restrict__ mval, size_t nblocks, double sigma, double *__restrict__ aval,
+                               float *__restrict__ aval32) {
     const size_t i = size_t(blockIdx.x) * blockDim.x + threadIdx.x;
     if (i >= nblocks * 9) return;
     const size_t b = i / 9;
     const int e = int(i % 9);
-    aval[i] = kval[i] - ((e == 0 || e == 4 || e == 8) ? sigma * mval[b] : 0.0);
+    const double v = kval[i] - ((e == 0 || e == 4 || e == 8) ? sigma * mval[b] : 0.0);
+    aval[i] = v;
+    if (aval32) aval32[i] = float(v);
 }
 
 __global__ void k_diag_inverse(const uint32_t *__restrict__ row_ptr, const uint32_t *__restrict__ col, const double *__restrict__ aval, uint32_t nnodes, double *__restrict__ dinv) {

@@ -138,6 +138,14 @@ def gram(ctx, x, y):
     return g.T.copy()
 
 
+def mapped_update_mismatches(ctx, n, wa, wb, gaps):
+    """The eigensolver's column-mapped basis update in its two forms (compact panel; compact panel and the mapped columns of X) on the same
+    inputs: the number of entries in which the second differs from the first one's result scattered on the host (0 = equal)."""
+    bad = C.c_double(-1)
+    ctx.check(lib().mhl_context_bench_dense(ctx.h, 3 if gaps else 2, n, wa, wb, 1, C.byref(bad)))
+    return int(bad.value)
+
+
 def bench_stream(ctx, nbytes=4 << 30, reps=10):
     """(copy GB/s counting read + written bytes, read GB/s) of streaming kernels over `nbytes`: the device's measured HBM ceilings."""
     c, r = C.c_double(0), C.c_double(0)
