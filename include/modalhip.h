@@ -342,7 +342,7 @@ int mh_bank_render_read(mh_bank *, uint32_t frames, float click_gain, uint32_t n
  * Status of a Hertz junction: MH_JUNCTION_REFUSED when C < 0, or C or K*C is not finite (1 + K*C plays no part); C = 0 is solved, f = K*x^1.5.
  * A refused junction gives a zero row and its objects render as with K = 0, as above.
  * MH_JUNCTION_HERTZ | MH_JUNCTION_BILATERAL is left out (status 0, a zero row, C = 0): the law has no tension branch.  Every other
- * left-out kind is as above.  Not in this version: a hysteretic law, friction, roughness, other exponents (the damped -- Hunt-Crossley --
+ * left-out kind is as above.  Not in this version: a hysteretic law, roughness, other exponents (friction: "Friction" below; the damped -- Hunt-Crossley --
  * law and its state between blocks: "Contact damping" below).
  *
  * Groups, flags & MH_JUNCTION_SHARED: several junctions on one object (a bowl on three points, a table under several objects, a bar on two
@@ -386,7 +386,7 @@ int mh_bank_render_read(mh_bank *, uint32_t frames, float click_gain, uint32_t n
  * this version); a flagged junction on an object of a kept unflagged one.  Two junctions between the same pair of objects, at different
  * points, are a legal group.  Pickups on a junction's object stay left out (mh_bank_render_observed reads them).  MH_JUNCTION_GROUP = 4 is what a wave's registers hold: one
  * gain triple per member per lane, 195 VGPRs in fp64 (118 in fp32), nothing in scratch.  (Hertz in groups: mh_bank_render_mixed; damping in groups:
- * mh_bank_render_damped_groups.)  Not in this version, as above: friction, roughness.
+ * mh_bank_render_damped_groups.)  Not in this version, as above: friction inside groups, roughness.
  *
  * Contact damping, flags & MH_JUNCTION_DAMPED (mh_bank_render_damped only: mh_bank_render_coupled ignores the bit): the Hunt-Crossley
  * term of the reference's surface renderer (DampingFactor = 1.5 (1 - e) ContactDamping, src/audio/surface/).  The junction obeys
@@ -431,7 +431,7 @@ int mh_bank_render_read(mh_bank *, uint32_t frames, float click_gain, uint32_t n
  * that holds a damped one (decided with the groups, modalhip_groups.hpp).  A lone damped junction with MH_JUNCTION_SHARED is an ordinary
  * damped junction.  Every junction without the bit keeps its bits beside a damped one, and a call in which no kept junction has the bit
  * launches what mh_bank_render_coupled launches.
- * Not in this version: a bilateral damped law (damping in groups: mh_bank_render_damped_groups, below), hysteretic laws, friction and roughness, pickups on junction objects
+ * Not in this version: a bilateral damped law (damping in groups: mh_bank_render_damped_groups, below), hysteretic laws, friction on a damped junction, roughness, pickups on junction objects
  * (in this entry: mh_bank_render_observed reads them, "Pickups on junction objects" below).
  *
  * Pickups on junction objects, mh_bank_render_observed: mh_bank_render_damped -- its parameters in its order, nothing more -- except that a
@@ -458,7 +458,7 @@ int mh_bank_render_read(mh_bank *, uint32_t frames, float click_gain, uint32_t n
  * With frames = 0 nothing is read and the carry comes back unchanged.  A call without a pickup on a kept junction's object launches
  * exactly what mh_bank_render_damped launches.  mh_bank_render_coupled and mh_bank_render_damped keep leaving such pickups out.
  * Not in this version: a bilateral damped law (Hertz inside groups: mh_bank_render_mixed, damping inside groups:
- * mh_bank_render_damped_groups, below), friction,
+ * mh_bank_render_damped_groups, below; friction: mh_bank_render_friction, "Friction" below),
  * roughness, contact forces acting inside a pickup's look-ahead.
  *
  * Hertz junctions in groups, mh_bank_render_mixed: mh_bank_render_observed -- its parameters in its order -- followed by one output,
@@ -512,7 +512,7 @@ int mh_bank_render_read(mh_bank *, uint32_t frames, float click_gain, uint32_t n
  * member, or 1 + C_ii K_i is not a finite number above 0 on a linear one; solved otherwise.  compliance_out[i] = C_ii in both cases.
  * k_bank_modes_grouped<Real, OBSERVE, true>: the same solve in every lane of every wave; 230 / 246 VGPRs (fp32 / fp64), nothing in scratch;
  * 512-frame blocks on an MI355X, n = 2 ... 4: fp32 20 600 - 27 100 cycles per frame, 4.6 - 6.1 ms; fp64 24 600 - 31 200 cycles, 5.4 - 6.9 ms.
- * Not in this version: a bilateral Hertz or damped law, more than four members, friction, roughness (damping inside groups:
+ * Not in this version: a bilateral Hertz or damped law, more than four members, friction inside groups, roughness (damping inside groups:
  * mh_bank_render_damped_groups, next).
  *
  * Damped junctions in groups, mh_bank_render_damped_groups: mh_bank_render_mixed -- its parameters in its order and nothing more.  One
@@ -574,8 +574,70 @@ int mh_bank_render_read(mh_bank *, uint32_t frames, float click_gain, uint32_t n
  * frame, no barrier, LDS slot or global access per frame beyond step 4m's; the carries are written once after the loop.  Resources:
  * profiles/bank_damped_groups_resources.txt.  512-frame blocks on an MI355X, n = 2 ... 4: fp32 35 500 - 45 200 cycles per frame, 7.8 - 10.0 ms;
  * fp64 47 600 - 58 900 cycles, 10.4 - 12.8 ms: beyond the 10.67 ms of real time for n = 3 and 4.
- * Not in this version: a bilateral damped or Hertz law, more than four members, friction, roughness, hysteretic laws, a warm start of the
- * Newton iteration from the previous frame (the bits would depend on the block length). */
+ * Not in this version: a bilateral damped or Hertz law, more than four members, friction inside groups, roughness, hysteretic laws, a warm start of the
+ * Newton iteration from the previous frame (the bits would depend on the block length).
+ *
+ * Friction, flags & MH_JUNCTION_FRICTION (mh_bank_render_friction only: every older entry ignores the bit): Coulomb friction with stiction
+ * on a lone junction -- the tangential channel of the reference's surface contact (SolveVoiceFriction, src/audio/surface/).  Beside its
+ * normal law (linear or Hertz, unilateral) the junction carries one slider behind one stick spring.  friction[j] (mh_friction) holds a
+ * tangent per side (ta, tb: a positive f_t pushes side a's modes along ta and side b's along tb, exactly as f does along n; a two-sided
+ * caller passes tb = -ta, as it passes opposite normals), the Coulomb coefficient mu and the stick spring's stiffness kt in N/m.  Per mode of
+ * a side, in the bank's precision, with the side's blended shape:  a_t = RadiationGain*(shape . t),  read_t = scale*(shape . t)*
+ * DeflectionGain,  gt_im = read_t*c_re,  gt_re = read_t*c_im  -- the gains of the normal channel with t in the place of n.
+ * A second signal per junction comes beside `approach`: `travel`, [n_junctions][frames] float, w: the rigid tangential offset of the two
+ * surfaces -- a position, as u is; a sample that is not finite counts as 0.  State: one value per junction, `anchor` ([n_junctions], the
+ * bank's precision, in and out), q: where the slider stands.  A value that is not finite means "no history": the frame takes q = x_t (on
+ * entry: frame 0).  On return: q after the last frame for a frictional junction that was solved, a quiet NaN for every other junction;
+ * frames = 0 leaves it alone.  The solve keeps no other state: one block of N frames and two of N / 2 with the anchor passed on are the
+ * same bits.
+ * The law: f_t = kt*(e - q) while |f_t| <= mu*f_n (stick: q stays); otherwise |f_t| = mu*f_n and the slider moves in the direction of the
+ * force, to q = e - f_t/kt (slip).  An open contact carries no shear and the slider follows it (q = x_t).  e is the tangential relative
+ * displacement of the contact points in frame s + 1 and y the compression of frame s + 1: as with every law here, the forces of frame s
+ * meet the law at the displacements of frame s + 1.
+ *   1, 2. as in mh_bank_render_coupled, bit for bit, for d_n; a second sum d_t = sum_sides sum_k gt_im[k]*Im z~[k] + gt_re[k]*Re z~[k] with the
+ *       same lane part, the same tree and the same order.
+ *   3.  four compliances, constant over the block, each with step 3's summation order:  C_nn = sum g_re*a (the bits of step 3's C, and
+ *       what compliance_out returns),  C_nt = sum g_re*a_t,  C_tn = sum gt_re*a,  C_tt = sum gt_re*a_t.  C_nt and C_tn are equal in exact
+ *       arithmetic; each is used where it arises, C_nt in the normal row and C_tn in the tangential one.  Also once per block, nothing
+ *       contracted:  den = 1 + kt*C_tt;  beta = (kt*C_tn)/den;  C_S = C_nn - C_nt*beta;  C_P = C_nn + mu*C_nt;  C_M = C_nn - mu*C_nt;  and for
+ *       each C_b of the three:  K*C_b,  1.5*(K*C_b),  1 + K*C_b.
+ *   4t. x_n = u[s] - d_n,  x_t = w[s] - d_t.  If q is not finite: q = x_t.  N(x, C_b) is the scalar solve of the junction's normal law:
+ *       linear (K*max(x, 0)) / (1 + K*C_b), step 4's expression; Hertz step 4h's tree with c = K*C_b.
+ *       If x_n > 0 fails (a NaN included): f_n = f_t = +0, q = x_t (branch O).  Otherwise r = x_t - q, alpha = (kt*r)/den, and three
+ *       candidates:
+ *         S (stick):   x_S = x_n - C_nt*alpha;  f_n = N(x_S, C_S);  f_t = alpha - beta*f_n;  q' = q;
+ *                      consistent when |f_t| <= mu*f_n;  miss |f_t| - mu*f_n.
+ *         P (slip +):  f_n = N(x_n, C_P);  f_t = mu*f_n;  e = (x_t - C_tn*f_n) - C_tt*f_t;  q' = e - f_t/kt;
+ *                      consistent when q' >= q;  miss kt*(q - q').
+ *         M (slip -):  f_n = N(x_n, C_M);  f_t = -(mu*f_n);  e and q' as in P;  consistent when q' <= q;  miss kt*(q' - q).
+ *       Taken: the first consistent candidate in the order S, P, M; where rounding on a boundary leaves none, the one with the least miss,
+ *       the earlier one on a tie (the rule of "Groups").  q becomes the taken candidate's q'.
+ *       The stick candidate's elimination is exact: f_t*(1 + kt*C_tt) = kt*(x_t - q - C_tn*f_n) put into y = x_n - C_nn*f_n - C_nt*f_t leaves
+ *       the normal law alone on (x_S, C_S); C_S is a Schur complement of a Gram matrix, so it is not below 0.  Nothing is iterated that
+ *       the bank does not already iterate, no trip count depends on data, and there is no state but q.
+ *   5.  Re z[k] = Re z~[k] + (a[k]*f_n + a_t[k]*f_t) on every side, the inner sum formed first -- the association in which two drives with
+ *       the signals f_n and f_t excite the object --; the frame's output term is formed from that state.
+ * Returned besides force_out (f_n), compliance_out (C_nn) and status_out: tangent_out, [n_junctions][frames] in the bank's precision, the f_t
+ * rows, WRITTEN; the new anchor; friction_counts_out, [n_junctions][3]: the frames taken on S, the frames taken on P or M, and the frames
+ * on which no candidate was consistent (they are counted under the candidate taken as well).  Zeros for every junction that is not a
+ * solved frictional one.  On valid input the third count is small: a diagnostic in the sense of unconverged_out, not an error.
+ * Status: MH_JUNCTION_REFUSED (zero rows, a NaN anchor, the objects render as with K = 0) on the normal law's own conditions, and when
+ * C_tt, C_nt or C_tn is not finite, C_tt < 0, den is not a finite number above 0, C_P or C_M is not a finite number from 0 up -- that is
+ * mu*|C_nt| <= C_nn, the condition under which exactly one candidate is consistent (tests/test_bank_friction_cpu.py counts them) --, or a
+ * K*C_b is not finite.
+ * Left out (status 0, zero rows, C = 0, a NaN anchor, the bits of the call without the junction): the flag together with
+ * MH_JUNCTION_BILATERAL, MH_JUNCTION_DAMPED or MH_JUNCTION_SHARED; a tangent component, mu or kt that is not finite; mu < 0 or kt < 0; every
+ * left-out kind of mh_bank_render_coupled.
+ * Dead: kt = 0, mu = 0, or zero tangents leave f_n, `out` and every state equal to those of the same junction without the flag: C_S, C_P
+ * and C_M are then the bits of C_nn, and N keeps step 4's and step 4h's trees.  (f_t is 0 for kt = 0 and for mu = 0; with zero tangents it
+ * is the rigid slider's force under w, and it moves nothing.)
+ * Every junction without the bit keeps its bits beside a frictional one, and a call without a kept frictional junction launches exactly
+ * what mh_bank_render_damped_groups launches.  Pickups on a frictional junction's objects are read as in mh_bank_render_observed.
+ * k_bank_modes_coupled_friction<Real>: the three candidates one per lane, a ballot and a lane read; resources:
+ * profiles/bank_friction_resources.txt.  512-frame blocks on an MI355X, J = 1 ... 64: fp32 1 750 - 2 340 cycles per frame (linear - Hertz), 0.56 - 0.75 ms;
+ * fp64 2 220 - 2 750 cycles, 0.69 - 0.80 ms (profiles/bank_friction.json).
+ * Not in this version: friction inside groups, with damping or on a bilateral junction, a transverse second axis, Dahl micro-slip,
+ * roughness. */
 typedef struct {
     uint32_t object;
     uint32_t points[3];
@@ -593,11 +655,20 @@ typedef struct {
 #define MH_JUNCTION_HERTZ 2u
 #define MH_JUNCTION_SHARED 4u
 #define MH_JUNCTION_DAMPED 8u
+#define MH_JUNCTION_FRICTION 16u
 #define MH_JUNCTION_MODES 1024
 #define MH_JUNCTION_GROUP 4 /* the most junctions one group may hold */
 enum { MH_JUNCTION_LEFT_OUT = 0, MH_JUNCTION_SOLVED = 1, MH_JUNCTION_REFUSED = 2 };
 /* sizeof(mh_junction) as this library was built */
 uint32_t mh_junction_struct_size(void);
+/* What a junction with MH_JUNCTION_FRICTION carries beside its record ("Friction" above), by the junction's index in the call. */
+typedef struct {
+    float ta[3], tb[3]; /* the tangent of side a and of side b */
+    float mu; /* the Coulomb coefficient */
+    float stiffness; /* kt: the stick spring of the contact patch, N/m */
+} mh_friction;
+/* sizeof(mh_friction) as this library was built */
+uint32_t mh_friction_struct_size(void);
 /* mh_bank_render_read with junctions.  Every object that is not on a solved or refused junction's side goes through the kernels it would
  * have gone through without junctions; `out`, the per-object results and the impacts come back as from mh_bank_render_read.  With
  * n_junctions = 0 this is mh_bank_render_read. */
@@ -642,6 +713,17 @@ int mh_bank_render_damped_groups(mh_bank *, uint32_t frames, float click_gain, u
                                  const mh_drive *drives, const float *signals, uint32_t n_pickups, const mh_pickup *pickups, void *pickup_out,
                                  uint8_t *pickup_read, uint32_t n_junctions, const mh_junction *junctions, const float *approach, void *force_out,
                                  double *compliance_out, uint8_t *status_out, const float *damping, void *carry, uint32_t *unconverged_out);
+/* mh_bank_render_damped_groups with Coulomb friction on lone junctions: "Friction" above.  friction: [n_junctions] records and travel:
+ * [n_junctions][frames], both read for flagged junctions only; tangent_out: [n_junctions][frames] and anchor: [n_junctions], in the bank's
+ * precision; friction_counts_out: [n_junctions][3].  With no flagged junction this is mh_bank_render_damped_groups, launch for launch. */
+int mh_bank_render_friction(mh_bank *, uint32_t frames, float click_gain, uint32_t n_impacts, mh_impact *impacts,
+                            uint32_t n_renderers, const uint32_t *deal_offset, const uint32_t *deal_objects, const uint32_t *render_count,
+                            const uint32_t *tuned_count, const float *out_gain, const float *listener_gain, void *out, double *object_energy,
+                            uint32_t *object_live, uint8_t *object_silenced, double *object_modal_energy, uint32_t n_drives,
+                            const mh_drive *drives, const float *signals, uint32_t n_pickups, const mh_pickup *pickups, void *pickup_out,
+                            uint8_t *pickup_read, uint32_t n_junctions, const mh_junction *junctions, const float *approach, void *force_out,
+                            double *compliance_out, uint8_t *status_out, const float *damping, void *carry, uint32_t *unconverged_out,
+                            const mh_friction *friction, const float *travel, void *tangent_out, void *anchor, uint32_t *friction_counts_out);
 /* Read back state columns (for parity tests and the modal-energy diagnostic, ModalAudio.cpp:564-577). */
 int mh_bank_read_state(const mh_bank *, uint32_t first, uint32_t count, double *state_re, double *state_im);
 

@@ -60,6 +60,11 @@ NO_OBJECT, JUNCTION_BILATERAL, JUNCTION_MODES = 0xffffffff, 1, 1024  # MH_NO_OBJ
 JUNCTION_HERTZ = 2  # MH_JUNCTION_HERTZ
 JUNCTION_SHARED, JUNCTION_GROUP = 4, 4  # MH_JUNCTION_SHARED, MH_JUNCTION_GROUP
 JUNCTION_DAMPED = 8  # MH_JUNCTION_DAMPED
+JUNCTION_FRICTION = 16  # MH_JUNCTION_FRICTION
+
+
+class Friction(C.Structure):  # mh_friction
+    _fields_ = [("ta", C.c_float * 3), ("tb", C.c_float * 3), ("mu", C.c_float), ("stiffness", C.c_float)]
 
 
 def build(force=False):
@@ -84,6 +89,7 @@ def lib():
     # the bank's render entries: what every one takes (bank, frames, click gain, impacts, renderers and the deal, gains, out, the per-object results), then what each adds
     block, drives, pickups, junctions = [vp, u32, C.c_float, u32, vp, u32] + [vp] * 11, [u32, vp, vp], [u32, vp, vp, vp], [u32, vp, vp, vp, vp, vp]
     damping_and_carry, counts = [vp, vp], [vp]
+    friction = [vp, vp, vp, vp, vp]  # the records, the travel rows, the f_t rows, the anchor, the three counts per junction
     sig = {
         "mh_context_create": (i32, [i32, pp]), "mh_context_destroy": (None, [vp]), "mh_last_error": (C.c_char_p, [vp]),
         "mh_context_synchronize": (i32, [vp]), "mh_context_time_kernels": (i32, [vp, i32]),
@@ -115,6 +121,7 @@ def lib():
         "mh_bank_render_observed": (i32, block + drives + pickups + junctions + damping_and_carry),
         "mh_bank_render_mixed": (i32, block + drives + pickups + junctions + damping_and_carry + counts),
         "mh_bank_render_damped_groups": (i32, block + drives + pickups + junctions + damping_and_carry + counts),
+        "mh_bank_render_friction": (i32, block + drives + pickups + junctions + damping_and_carry + counts + friction), "mh_friction_struct_size": (u32, []),
         "mh_bank_read_state": (i32, [vp, u32, u32, vp, vp]),
     }
     for name, (res, args) in sig.items():

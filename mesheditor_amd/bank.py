@@ -48,23 +48,36 @@ class JunctionSide(C.Structure):  # ModalJunctionSide, modal/bank.hpp (mh_juncti
 
 NO_OBJECT, JUNCTION_BILATERAL, JUNCTION_HERTZ, JUNCTION_SHARED = 0xffffffff, 1, 2, 4  # NoModalObject, ModalJunctionBilateral, ModalJunctionHertz, ModalJunctionShared
 JUNCTION_DAMPED = 8  # ModalJunctionDamped
+JUNCTION_FRICTION = 16  # ModalJunctionFriction
+
+
+class Friction(C.Structure):  # ModalFriction, modal/bank.hpp (mh_friction of modalhip.h field for field)
+    _fields_ = [("ta", C.c_float * 3), ("tb", C.c_float * 3), ("mu", C.c_float), ("stiffness", C.c_float)]
+
+    @classmethod
+    def of(cls, ta=(0.0, 0.0, 0.0), tb=(0.0, 0.0, 0.0), mu=0.0, stiffness=0.0):
+        """ta, tb: the tangent of side a and of side b (a two-sided junction passes tb = -ta); mu: the Coulomb coefficient; stiffness: the
+        stick spring kt of the contact patch in N/m."""
+        return cls((C.c_float * 3)(*ta), (C.c_float * 3)(*tb), mu, stiffness)
 
 
 class Junction(C.Structure):  # ModalJunction, modal/bank.hpp (mh_junction of modalhip.h field for field)
     _fields_ = [("a", JunctionSide), ("b", JunctionSide), ("stiffness", C.c_float), ("flags", C.c_uint32)]
 
     @classmethod
-    def of(cls, a, b=None, stiffness=0.0, bilateral=False, hertz=False, shared=False, damped=False):
+    def of(cls, a, b=None, stiffness=0.0, bilateral=False, hertz=False, shared=False, damped=False, friction=False):
         """a, b: JunctionSide records or the arguments of JunctionSide.of as tuples; b = None: one-sided (an exciter the caller moves).
         hertz: f = K delta^1.5 with `stiffness` in N/m^1.5 instead of the linear spring (unilateral only: with bilateral it is left out).
         shared: the junction may name an object that an earlier kept junction with shared=True names; up to four linear junctions that
         share objects in this way are one group, solved together in every frame (modalhip.h, MH_JUNCTION_SHARED).
         damped: Hunt-Crossley contact damping on the linear or the Hertz law (Scene.render_damped only; unilateral, and alone on its objects:
-        with bilateral, or where it would share an object, it is left out)."""
+        with bilateral, or where it would share an object, it is left out).
+        friction: Coulomb friction with stiction beside the normal law (Scene.render_friction only, which takes a Friction record and a travel
+        row per junction; unilateral, undamped and without shared: otherwise it is left out)."""
         side = lambda v: v if isinstance(v, JunctionSide) else JunctionSide.of(*v)
         none = JunctionSide(NO_OBJECT, (C.c_uint32 * 3)(0, 0, 0), (C.c_float * 3)(1, 0, 0), 0.0, 0.0, 0.0, 1.0)
         return cls(side(a), side(b) if b is not None else none, stiffness, (JUNCTION_BILATERAL if bilateral else 0) | (JUNCTION_HERTZ if hertz else 0) | (JUNCTION_SHARED if shared else 0) |
-                   (JUNCTION_DAMPED if damped else 0))
+                   (JUNCTION_DAMPED if damped else 0) | (JUNCTION_FRICTION if friction else 0))
 
 
 def lib():
@@ -89,6 +102,7 @@ def lib():
         "mhx_render_observed": (i32, [vp, vp, u32, u32, vp, vp, u32, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp]),
         "mhx_render_mixed": (i32, [vp, vp, u32, u32, vp, vp, u32, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp]),
         "mhx_render_damped_groups": (i32, [vp, vp, u32, u32, vp, vp, u32, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "mhx_render_friction": (i32, [vp, vp, u32, u32, vp, vp, u32, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "mhx_active_impacts": (u32, [vp]), "mhx_modal_energy": (f64, [vp]), "mhx_render_share": (f32, [vp]), "mhx_find_object": (i32, [vp, u32]),
         "mhx_time_kernels": (i32, [vp, i32]), "mhx_kernel_class_stats": (i32, [vp, i32, C.POINTER(C.c_uint64), C.POINTER(f64), C.POINTER(f64)]),
         "mhx_column": (u32, [vp, i32, i32, vp]), "mhx_object_state": (None, [vp, vp, vp, vp]),
@@ -172,10 +186,11 @@ class Scene:
         if self.L.mhx_render_driven(self.h, _p(out), len(out), len(drives), C.cast(rows, C.c_void_p), _p(sig)):
             raise RuntimeError(self.L.mhx_last_error().decode())
 
-    def _render(self, entry, out, drives, signals, pickups, junctions=None, approach=None, damping=None, carry=None, counted=False):
+    def _render(self, entry, out, drives, signals, pickups, junctions=None, approach=None, damping=None, carry=None, counted=False, friction=None, travel=None, anchor=None):
         """One block through `entry` of the C wrapper, with what the entry takes beyond render_read's arguments: junctions and approach
-        (render_coupled), damping and carry (render_damped), counted (render_mixed).  Returns the tuple of the widest of them the entry
-        reaches: (reads, read_flags, forces, compliances, statuses, carry, unconverged)."""
+        (render_coupled), damping and carry (render_damped), counted (render_mixed), friction, travel and anchor (render_friction).  Returns
+        the tuple of the widest of them the entry reaches: (reads, read_flags, forces, compliances, statuses, carry, unconverged, tangent,
+        anchor, friction_counts)."""
         assert out.dtype == self.dtype and out.flags["C_CONTIGUOUS"]
         frames = len(out)
         rows = drives if isinstance(drives, C.Array) else (Drive * max(len(drives), 1))(*[v if isinstance(v, Drive) else Drive(*v) for v in drives])
@@ -199,6 +214,12 @@ class Scene:
             counts = np.zeros(n, np.uint32)
             args += [_p(counts)]
             result += (counts,)
+        if friction is not None:
+            slides = friction if isinstance(friction, C.Array) else (Friction * max(n, 1))(*friction)
+            w = np.ascontiguousarray(travel, np.float32).reshape(n, frames)
+            tangent, stands, taken = np.zeros((n, frames), self.dtype), np.full(n, np.nan, self.dtype) if anchor is None else np.array(anchor, self.dtype).reshape(n), np.zeros((n, 3), np.uint32)
+            args += [C.cast(slides, C.c_void_p), _p(w), _p(tangent), _p(stands), _p(taken)]
+            result += (tangent, stands, taken)
         if entry(self.h, _p(out), frames, *args):
             raise RuntimeError(self.L.mhx_last_error().decode())
         return result
@@ -236,6 +257,17 @@ class Scene:
         with a Hertz or a damped member."""
         rates = np.zeros(len(junctions), np.float32) if damping is None else damping
         return self._render(self.L.mhx_render_damped_groups, out, drives, signals, pickups, junctions, approach, rates, carry, counted=True)
+
+    def render_friction(self, out, drives, signals, pickups, junctions, approach, friction, travel, damping=None, carry=None, anchor=None):
+        """RenderModalFriction: render_damped_groups in which a lone junction with friction=True also solves a tangential force per frame --
+        stick inside the Coulomb cone, slide at its edge (modalhip.h, "Friction").  friction: one Friction record per junction (a ctypes
+        array or a sequence) and travel: float32 [len(junctions)][len(out)], the rigid tangential offset of the two surfaces, both read for
+        flagged junctions only; anchor: one value per junction in the scene's precision -- where the slider stood after the previous block,
+        as this call returned it then; None or a value that is not finite: no history.  Returns render_damped_groups' tuple plus (tangent,
+        anchor, counts): tangent[j] is junction j's row of f_t, anchor the new anchors (NaN for every junction that is not a solved
+        frictional one), counts[j] the frames taken on stick, on slip, and those without a consistent candidate."""
+        rates = np.zeros(len(junctions), np.float32) if damping is None else damping
+        return self._render(self.L.mhx_render_friction, out, drives, signals, pickups, junctions, approach, rates, carry, counted=True, friction=friction, travel=travel, anchor=anchor)
 
     def render_damped(self, out, drives, signals, pickups, junctions, approach, damping, carry=None, entry=None):
         """RenderModalDamped: render_coupled with contact damping.  damping: one D in s/m per junction (float32; read for junctions with

@@ -80,6 +80,10 @@ constexpr uint32_t ModalJunctionBilateral{1};
 constexpr uint32_t ModalJunctionHertz{2};
 constexpr uint32_t ModalJunctionShared{4};
 constexpr uint32_t ModalJunctionDamped{8};
+// Flags bit 4, ModalJunctionFriction (RenderModalFriction only; every older entry ignores it): Coulomb friction with stiction on a lone
+// junction -- one slider behind one stick spring beside the normal law, solved in the same frame (modalhip.h, "Friction").  Unilateral,
+// undamped and alone on its objects: with ModalJunctionBilateral, ModalJunctionDamped or ModalJunctionShared it is left out.
+constexpr uint32_t ModalJunctionFriction{16};
 struct ModalJunctionSide {
     uint32_t Object{NoModalObject};
     uint32_t Points[3]{0, 0, 0};
@@ -91,6 +95,14 @@ struct ModalJunction {
     ModalJunctionSide A, B;
     float Stiffness{0};
     uint32_t Flags{0};
+};
+// What a junction with ModalJunctionFriction carries beside its record (mh_friction of modalhip.h field for field): a tangent per side -- a
+// positive tangential force pushes side A along Ta and side B along Tb, so a two-sided caller passes Tb = -Ta --, the Coulomb coefficient
+// and the stick stiffness of the contact patch in N/m (TangentialStiffness of modal/contact.hpp gives it).
+struct ModalFriction {
+    float Ta[3]{0, 0, 0}, Tb[3]{0, 0, 0};
+    float Mu{0};
+    float Stiffness{0};
 };
 
 constexpr float AirDensity{1.204f}, SpeedOfSound{343.f}, ListenerDistance{1.f};
@@ -331,6 +343,27 @@ void RenderModalDampedGroups(ModalAudio &, std::span<const ModalDrive> drives, c
 void RenderModalDampedGroups(ModalAudio64 &, std::span<const ModalDrive> drives, const float *signals, std::span<const ModalPickup> pickups, double *reads,
                              std::span<const ModalJunction> junctions, const float *approach, std::span<const float> damping, std::span<double> carry, double *forces, double *out,
                              uint32_t frame_count, std::span<uint32_t> unconverged, uint8_t *read_flags = nullptr, double *compliances = nullptr, uint8_t *statuses = nullptr);
+// Friction (modalhip.h, mh_bank_render_friction): RenderModalDampedGroups -- its parameters in its order up to
+// `unconverged` -- followed by what the tangential channel takes and returns.  A kept lone junction with ModalJunctionFriction also solves,
+// in every frame, a tangential force f_t: stick inside the Coulomb cone (f_t = kt (e - q), the slider q stays), slide at its edge
+// (|f_t| = Mu f_n, the slider follows).  friction: one record per junction and travel: one row of frame_count samples per junction (the
+// rigid tangential offset of the two surfaces, a position; a sample that is not finite counts as 0), both read for flagged junctions only.
+// tangents receives one row of f_t per junction (written).  anchor: one value per junction in the bank's precision, in and out: where the
+// slider stands.  A value that is not finite on entry means "no history" (frame 0 takes it from the contact itself); on return a solved
+// frictional junction has its anchor, every other junction a quiet NaN; with frame_count = 0 it comes back unchanged.  friction_counts: three
+// per junction -- the frames taken on stick, on slip, and those on which rounding left no candidate consistent (small on valid input).
+// Left out beyond RenderModalDampedGroups' kinds: the flag with ModalJunctionBilateral, ModalJunctionDamped or ModalJunctionShared; a
+// tangent component, Mu or Stiffness that is not finite; Mu < 0 or Stiffness < 0.  Refused (status 2) beyond the normal law's conditions:
+// the cone condition Mu |C_nt| <= C_nn fails, or a compliance is not finite.  Stiffness = 0, Mu = 0 or zero tangents leave the normal force,
+// `out` and the bank as without the flag.  Without a flagged junction this is RenderModalDampedGroups.
+void RenderModalFriction(ModalAudio &, std::span<const ModalDrive> drives, const float *signals, std::span<const ModalPickup> pickups, float *reads,
+                         std::span<const ModalJunction> junctions, const float *approach, std::span<const float> damping, std::span<float> carry, float *forces, float *out,
+                         uint32_t frame_count, std::span<uint32_t> unconverged, std::span<const ModalFriction> friction, const float *travel, float *tangents,
+                         std::span<float> anchor, std::span<uint32_t> friction_counts, uint8_t *read_flags = nullptr, double *compliances = nullptr, uint8_t *statuses = nullptr);
+void RenderModalFriction(ModalAudio64 &, std::span<const ModalDrive> drives, const float *signals, std::span<const ModalPickup> pickups, double *reads,
+                         std::span<const ModalJunction> junctions, const float *approach, std::span<const float> damping, std::span<double> carry, double *forces, double *out,
+                         uint32_t frame_count, std::span<uint32_t> unconverged, std::span<const ModalFriction> friction, const float *travel, double *tangents,
+                         std::span<double> anchor, std::span<uint32_t> friction_counts, uint8_t *read_flags = nullptr, double *compliances = nullptr, uint8_t *statuses = nullptr);
 // Not in the reference: the libmodalhip context the bank's device mirror lives on (created on demand), for callers that
 // time its kernels (mh_context_time_kernels / mh_context_kernel_class_stats).
 mh_context *ModalDeviceContext(ModalAudio &);

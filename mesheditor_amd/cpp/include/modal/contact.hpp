@@ -35,4 +35,8 @@ double EstimateContactTime(const ContactDynamics &, uint32_t excitable_index, ve
 // D = 1.5 max(1 - e, 0) / v -- Hunt and Crossley's relation as the reference's surface renderer sizes its damping term (DampingFactor =
 // 1.5 (1 - e) ContactDamping, src/audio/surface/SurfaceAudio.cpp).  What RenderModalDamped takes per junction (modal/bank.hpp).
 inline double ContactDamping(double restitution, double approach_speed) { return 1.5 * (1.0 - restitution > 0.0 ? 1.0 - restitution : 0.0) / approach_speed; }
+// Not in the reference's ContactModel.h: the stick stiffness kt in N/m of a circular contact patch of radius a between bodies with the
+// combined shear modulus G* (1 / G* = (2 - nu_1) / G_1 + (2 - nu_2) / G_2), kt = 8 G* a -- Mindlin's tangential compliance of a Hertz
+// contact without slip.  What ModalFriction::Stiffness takes (modal/bank.hpp).
+inline double TangentialStiffness(double combined_shear_modulus, double patch_radius) { return 8.0 * combined_shear_modulus * patch_radius; }
 inline constexpr double MinContactTime = 2e-5, MaxContactTime = 5e-2;

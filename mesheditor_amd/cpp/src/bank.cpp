@@ -506,8 +506,9 @@ enum class JunctionEntry {
     Observed, // RenderModalObserved: + the pickups on junction objects are read
     Mixed, // RenderModalMixed: + a Hertz junction may join a group; per junction, its frames that failed the residual test
     DampedGroups, // RenderModalDampedGroups: + a damped junction may join a group as well
+    Friction, // RenderModalFriction: + ModalJunctionFriction on a lone junction; the travel rows, the f_t rows, the anchor (in and out), the counts
 };
-constexpr const char *JunctionEntryName[] = {"RenderModalCoupled", "RenderModalDamped", "RenderModalObserved", "RenderModalMixed", "RenderModalDampedGroups"};
+constexpr const char *JunctionEntryName[] = {"RenderModalCoupled", "RenderModalDamped", "RenderModalObserved", "RenderModalMixed", "RenderModalDampedGroups", "RenderModalFriction"};
 
 // What a junction entry takes and hands back; an entry leaves what it does not take empty.
 template<typename Real> struct JunctionResults {
@@ -520,6 +521,11 @@ template<typename Real> struct JunctionResults {
     std::span<const float> Damping{};
     std::span<Real> Carry{};
     std::span<uint32_t> Unconverged{};
+    std::span<const ModalFriction> Friction{};
+    const float *Travel{nullptr};
+    Real *Tangents{nullptr};
+    std::span<Real> Anchor{};
+    std::span<uint32_t> FrictionCounts{};
 };
 
 template<typename Audio, typename Real>
@@ -527,6 +533,9 @@ void RenderBlock(Audio &m, std::span<const ModalDrive> drives, const float *sign
                  uint8_t *read_flags = nullptr, const JunctionResults<Real> &coupled = {}) {
     const auto admits = [&](JunctionEntry e) { return coupled.Entry >= e; };
     const size_t per_junction = coupled.Junctions.size();
+    if (admits(JunctionEntry::Friction) && per_junction &&
+        (coupled.Friction.size() < per_junction || !coupled.Travel || !coupled.Tangents || coupled.Anchor.size() < per_junction || coupled.FrictionCounts.size() < 3 * per_junction))
+        throw std::invalid_argument(std::string(JunctionEntryName[int(coupled.Entry)]) + ": a friction record, a travel row, a tangent row, an anchor and three counts per junction");
     if (admits(JunctionEntry::Mixed) && (coupled.Damping.size() < per_junction || coupled.Carry.size() < per_junction || coupled.Unconverged.size() < per_junction))
         throw std::invalid_argument(std::string(JunctionEntryName[int(coupled.Entry)]) + ": a damping, a carry and a count per junction");
     if (admits(JunctionEntry::Damped) && (coupled.Damping.size() < per_junction || coupled.Carry.size() < per_junction))
@@ -599,9 +608,12 @@ void RenderBlock(Audio &m, std::span<const ModalDrive> drives, const float *sign
     // (one junction per object, unless both carry ModalJunctionShared: then they form a group -- the decision of modalhip_groups.hpp, which
     // the device entry takes again)
     MhJunctionGroups grouping(n_objects);
-    const uint32_t flag_mask = admits(JunctionEntry::Damped) ? ~0u : ~ModalJunctionDamped;
+    const uint32_t flag_mask = (admits(JunctionEntry::Damped) ? ~0u : ~ModalJunctionDamped) & (admits(JunctionEntry::Friction) ? ~0u : ~ModalJunctionFriction);
     std::vector<float> damping; // per kept junction: l = D * SampleRate per frame, rounded once in float
     std::vector<Real> carry;
+    std::vector<mh_friction> friction; // per kept junction: its friction record, its travel row and its anchor (RenderModalFriction)
+    std::vector<float> travel;
+    std::vector<Real> anchor;
     for (size_t j = 0; j < junctions.size(); ++j) {
         const ModalJunction &v = junctions[j];
         const bool two_sided = v.B.Object != NoModalObject;
@@ -610,6 +622,13 @@ void RenderBlock(Audio &m, std::span<const ModalDrive> drives, const float *sign
         if (!std::isfinite(v.Stiffness) || v.Stiffness < 0 || !side_ok(v.A) || (two_sided && (v.A.Object == v.B.Object || !side_ok(v.B)))) continue;
         if ((v.Flags & ModalJunctionHertz) && (v.Flags & ModalJunctionBilateral)) continue; // the Hertz law is unilateral
         if ((flags & ModalJunctionDamped) && ((flags & ModalJunctionBilateral) || !std::isfinite(per_frame) || per_frame < 0)) continue; // so is the damped one
+        if (flags & ModalJunctionFriction) { // friction goes with a lone unilateral undamped junction, and its numbers are finite and not below 0
+            if (flags & (ModalJunctionBilateral | ModalJunctionDamped | ModalJunctionShared)) continue;
+            const ModalFriction &t = coupled.Friction[j];
+            bool ok = std::isfinite(t.Mu) && std::isfinite(t.Stiffness) && t.Mu >= 0 && t.Stiffness >= 0;
+            for (int c = 0; c < 3; ++c) ok = ok && std::isfinite(t.Ta[c]) && std::isfinite(t.Tb[c]);
+            if (!ok) continue;
+        }
         if (grouping.add(uint32_t(j), flags, v.A.Object, side_waves(v.A), two_sided ? v.B.Object : MH_NO_OBJECT, two_sided ? side_waves(v.B) : 0u, admits(JunctionEntry::Mixed), admits(JunctionEntry::DampedGroups)) < 0) continue;
         mh_junction_side none{};
         none.object = MH_NO_OBJECT;
@@ -618,6 +637,14 @@ void RenderBlock(Audio &m, std::span<const ModalDrive> drives, const float *sign
         if (admits(JunctionEntry::Damped)) {
             damping.push_back(per_frame);
             carry.push_back(coupled.Carry[j]);
+        }
+        if (admits(JunctionEntry::Friction)) { // (read for flagged junctions only: an unflagged one's record and row are zeros)
+            const bool flagged = (flags & ModalJunctionFriction) != 0;
+            const ModalFriction t = flagged ? coupled.Friction[j] : ModalFriction{};
+            friction.push_back({{t.Ta[0], t.Ta[1], t.Ta[2]}, {t.Tb[0], t.Tb[1], t.Tb[2]}, t.Mu, t.Stiffness});
+            if (flagged) travel.insert(travel.end(), coupled.Travel + j * frames, coupled.Travel + (j + 1) * frames);
+            else travel.insert(travel.end(), frames, 0.f);
+            anchor.push_back(coupled.Anchor[j]);
         }
         d.Approach.insert(d.Approach.end(), coupled.Approach + j * frames, coupled.Approach + (j + 1) * frames);
         auto excite = [&](uint32_t o) {
@@ -672,6 +699,8 @@ void RenderBlock(Audio &m, std::span<const ModalDrive> drives, const float *sign
         out_gain = narrow_out.data(), listener_gain = narrow_listener.data();
     }
     std::vector<uint32_t> unconverged(admits(JunctionEntry::Mixed) ? kept_junctions : 0, 0u);
+    std::vector<Real> tangents(admits(JunctionEntry::Friction) ? size_t(kept_junctions) * frames : 0);
+    std::vector<uint32_t> friction_counts(admits(JunctionEntry::Friction) ? 3 * size_t(kept_junctions) : 0, 0u);
     // the device entry of the level: what all take, then what the level adds
     auto call = [&](auto entry, auto... more) {
         return entry(d.Bank, frames, m.ClickGain.load(std::memory_order_relaxed), n_impacts, d.Impacts.data(), renderers, d.DealOffset.data(), d.DealObjects.data(), d.RenderCount.data(),
@@ -686,6 +715,9 @@ void RenderBlock(Audio &m, std::span<const ModalDrive> drives, const float *sign
     case JunctionEntry::Observed: status = call(mh_bank_render_observed, damping.data(), carry.data()); break;
     case JunctionEntry::Mixed: status = call(mh_bank_render_mixed, damping.data(), carry.data(), unconverged.data()); break;
     case JunctionEntry::DampedGroups: status = call(mh_bank_render_damped_groups, damping.data(), carry.data(), unconverged.data()); break;
+    case JunctionEntry::Friction:
+        status = call(mh_bank_render_friction, damping.data(), carry.data(), unconverged.data(), friction.data(), travel.data(), tangents.data(), anchor.data(), friction_counts.data());
+        break;
     }
     if (status != MH_OK) Fail(d);
     if (read_flags) std::copy(d.PickupRead.begin(), d.PickupRead.end(), read_flags);
@@ -706,6 +738,17 @@ void RenderBlock(Audio &m, std::span<const ModalDrive> drives, const float *sign
         if (admits(JunctionEntry::Damped)) { // a quiet NaN for the ones left out; a kept one's as the entry returned it (NaN unless damped and solved)
             std::fill_n(coupled.Carry.begin(), junctions.size(), std::numeric_limits<Real>::quiet_NaN());
             for (uint32_t c = 0; c < kept_junctions; ++c) coupled.Carry[d.JunctionFrom[c]] = carry[c];
+        }
+        if (admits(JunctionEntry::Friction)) { // zero rows, a quiet NaN and zero counts for the ones left out; a kept one's as the entry returned them
+            std::fill(coupled.Tangents, coupled.Tangents + junctions.size() * frames, Real(0));
+            std::fill_n(coupled.Anchor.begin(), junctions.size(), std::numeric_limits<Real>::quiet_NaN());
+            std::fill_n(coupled.FrictionCounts.begin(), 3 * junctions.size(), 0u);
+            for (uint32_t c = 0; c < kept_junctions; ++c) {
+                const size_t j = d.JunctionFrom[c];
+                std::copy(tangents.begin() + size_t(c) * frames, tangents.begin() + size_t(c + 1) * frames, coupled.Tangents + j * frames);
+                coupled.Anchor[j] = anchor[c];
+                std::copy(friction_counts.begin() + 3 * size_t(c), friction_counts.begin() + 3 * size_t(c + 1), coupled.FrictionCounts.begin() + 3 * j);
+            }
         }
     }
 
@@ -841,6 +884,20 @@ void RenderModalDampedGroups(ModalAudio64 &m, std::span<const ModalDrive> drives
                              std::span<const ModalJunction> junctions, const float *approach, std::span<const float> damping, std::span<double> carry, double *forces, double *out,
                              uint32_t frame_count, std::span<uint32_t> unconverged, uint8_t *read_flags, double *compliances, uint8_t *statuses) {
     RenderBlock<ModalAudio64, double>(m, drives, signals, out, frame_count, pickups, reads, read_flags, {JunctionEntry::DampedGroups, junctions, approach, forces, compliances, statuses, damping, carry, unconverged});
+}
+void RenderModalFriction(ModalAudio &m, std::span<const ModalDrive> drives, const float *signals, std::span<const ModalPickup> pickups, float *reads,
+                         std::span<const ModalJunction> junctions, const float *approach, std::span<const float> damping, std::span<float> carry, float *forces, float *out,
+                         uint32_t frame_count, std::span<uint32_t> unconverged, std::span<const ModalFriction> friction, const float *travel, float *tangents, std::span<float> anchor,
+                         std::span<uint32_t> friction_counts, uint8_t *read_flags, double *compliances, uint8_t *statuses) {
+    RenderBlock<ModalAudio, float>(m, drives, signals, out, frame_count, pickups, reads, read_flags,
+                                   {JunctionEntry::Friction, junctions, approach, forces, compliances, statuses, damping, carry, unconverged, friction, travel, tangents, anchor, friction_counts});
+}
+void RenderModalFriction(ModalAudio64 &m, std::span<const ModalDrive> drives, const float *signals, std::span<const ModalPickup> pickups, double *reads,
+                         std::span<const ModalJunction> junctions, const float *approach, std::span<const float> damping, std::span<double> carry, double *forces, double *out,
+                         uint32_t frame_count, std::span<uint32_t> unconverged, std::span<const ModalFriction> friction, const float *travel, double *tangents, std::span<double> anchor,
+                         std::span<uint32_t> friction_counts, uint8_t *read_flags, double *compliances, uint8_t *statuses) {
+    RenderBlock<ModalAudio64, double>(m, drives, signals, out, frame_count, pickups, reads, read_flags,
+                                      {JunctionEntry::Friction, junctions, approach, forces, compliances, statuses, damping, carry, unconverged, friction, travel, tangents, anchor, friction_counts});
 }
 mh_context *ModalDeviceContext(ModalAudio &m) { return NeedContext(m), m.Dev->Context; }
 mh_context *ModalDeviceContext(ModalAudio64 &m) { return NeedContext(m), m.Dev->Context; }

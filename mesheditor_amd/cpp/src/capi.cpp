@@ -44,7 +44,7 @@ namespace {
 template<typename F> auto Dispatch(mhx_scene *s, F &&f) { return s->dbl ? f(s->audio64, s->next64) : f(s->audio, s->next); }
 template<typename Audio, typename Bank> Bank &Pick(Audio &a, Bank &next, int live) { return live ? static_cast<Bank &>(LiveBank(a)) : next; }
 
-// What the widest junction entry (mhx_render_damped_groups) takes after the scene, in its order; an entry leaves what it does not take at null.
+// What the widest junction entry (mhx_render_friction) takes after the scene, in its order; an entry leaves what it does not take at null.
 struct JunctionBlock {
     void *Out;
     uint32_t Frames, DriveCount;
@@ -54,8 +54,9 @@ struct JunctionBlock {
     uint32_t JunctionCount; const ModalJunction *Junctions; const float *Approach; void *Forces; double *Compliances; uint8_t *Statuses;
     const float *Damping{nullptr}; void *Carry{nullptr};
     uint32_t *Unconverged{nullptr};
+    const ModalFriction *Friction{nullptr}; const float *Travel{nullptr}; void *Tangents{nullptr}; void *Anchor{nullptr}; uint32_t *FrictionCounts{nullptr};
 };
-enum JunctionCall { Coupled, Damped, Observed, Mixed, DampedGroups };
+enum JunctionCall { Coupled, Damped, Observed, Mixed, DampedGroups, Friction };
 // One block through the RenderModal* of `call`: the spans and the pointers in the scene's precision.
 int RenderJunctions(mhx_scene *s, JunctionCall call, const JunctionBlock &b) {
     try {
@@ -74,6 +75,11 @@ int RenderJunctions(mhx_scene *s, JunctionCall call, const JunctionBlock &b) {
             case Observed: RenderModalObserved(a, drives, b.Signals, pickups, reads, junctions, b.Approach, damping, carry, forces, out, b.Frames, b.ReadFlags, b.Compliances, b.Statuses); break;
             case Mixed: RenderModalMixed(a, drives, b.Signals, pickups, reads, junctions, b.Approach, damping, carry, forces, out, b.Frames, counts, b.ReadFlags, b.Compliances, b.Statuses); break;
             case DampedGroups: RenderModalDampedGroups(a, drives, b.Signals, pickups, reads, junctions, b.Approach, damping, carry, forces, out, b.Frames, counts, b.ReadFlags, b.Compliances, b.Statuses); break;
+            case Friction:
+                RenderModalFriction(a, drives, b.Signals, pickups, reads, junctions, b.Approach, damping, carry, forces, out, b.Frames, counts, std::span<const ModalFriction>(b.Friction, b.JunctionCount), b.Travel,
+                                    static_cast<Real *>(b.Tangents), std::span<Real>(static_cast<Real *>(b.Anchor), b.JunctionCount), std::span<uint32_t>(b.FrictionCounts, 3 * size_t(b.JunctionCount)), b.ReadFlags,
+                                    b.Compliances, b.Statuses);
+                break;
             }
             return 0;
         });
@@ -197,6 +203,15 @@ int mhx_render_damped_groups(mhx_scene *s, void *out, uint32_t frames, uint32_t 
                              const ModalPickup *pickups, void *reads, uint8_t *read_flags, uint32_t n_junctions, const ModalJunction *junctions, const float *approach,
                              void *forces, double *compliances, uint8_t *statuses, const float *damping, void *carry, uint32_t *unconverged) {
     return RenderJunctions(s, DampedGroups, {out, frames, n_drives, drives, signals, n_pickups, pickups, reads, read_flags, n_junctions, junctions, approach, forces, compliances, statuses, damping, carry, unconverged});
+}
+// RenderModalFriction: mhx_render_damped_groups' parameters, then `friction` (one ModalFriction per junction), `travel` [n_junctions][frames] float,
+// `tangents` [n_junctions][frames] and `anchor` (one value per junction, in and out) in the scene's precision, `friction_counts` [n_junctions][3]
+int mhx_render_friction(mhx_scene *s, void *out, uint32_t frames, uint32_t n_drives, const ModalDrive *drives, const float *signals, uint32_t n_pickups,
+                        const ModalPickup *pickups, void *reads, uint8_t *read_flags, uint32_t n_junctions, const ModalJunction *junctions, const float *approach,
+                        void *forces, double *compliances, uint8_t *statuses, const float *damping, void *carry, uint32_t *unconverged, const ModalFriction *friction,
+                        const float *travel, void *tangents, void *anchor, uint32_t *friction_counts) {
+    return RenderJunctions(s, Friction, {out, frames, n_drives, drives, signals, n_pickups, pickups, reads, read_flags, n_junctions, junctions, approach, forces, compliances, statuses, damping, carry, unconverged,
+                                         friction, travel, tangents, anchor, friction_counts});
 }
 // Kernel timing of the scene's device context: enable / read one class (modalhip.h MH_KERNEL_*)
 int mhx_time_kernels(mhx_scene *s, int enable) {

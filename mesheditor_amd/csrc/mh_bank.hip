@@ -813,6 +813,196 @@ template<typename Real> constexpr auto k_bank_modes_coupled_observed = &k_bank_m
 template<typename Real> constexpr auto k_bank_modes_coupled_hertz_observed = &k_bank_modes_coupled<Real, true, false, true>;
 template<typename Real> constexpr auto k_bank_modes_coupled_damped_observed = &k_bank_modes_coupled<Real, true, true, true>;
 
+// Friction (mh_bank_render_friction; contract in modalhip.h, step 4t).  A lone junction with MH_JUNCTION_FRICTION:
+// the coupled kernel's workgroup -- one wave per 128 modes of each side, the same barriers -- with a second gain triple per lane
+// (a_t, gt_im, gt_re: the side's blend along its tangent), a second sum d_t beside d_n (a second slot per wave, the same barrier), and
+// step 4t in the place of step 4: the candidates S, P, M one per lane (lane & 3; the fourth repeats M and is not asked), each one scalar
+// solve the bank already has, then a ballot over lanes 0 .. 2, its lowest set bit and a lane read per value.  The four compliances take
+// two reductions ahead of the loop (C_nn and C_nt, then C_tn and C_tt).  Slots: [parity][n | t][wave]; the two rounds use the even and
+// the odd buffer, frame 0 the even one again, as in the coupled kernel.  Barriers: 2 + frames + 2 per tile -- a function of `frames` alone.
+// The anchor q sits in a register from frame to frame and is written once after the loop, with the counts, by wave 0.
+// A kernel of its own from the leaf functions the coupled kernel is made of: that one's instantiations keep their resource reports
+// (profiles/bank_friction_resources.txt).
+template<typename Real> struct FrictionJunctionDev {
+    JunctionDev<Real> j; // the normal channel, as the coupled kernel takes it
+    Real t[2][3]; // the sides' tangents
+    Real mu, kt;
+};
+template<typename Real> struct FrictionArgs {
+    const Real *defl_gain;
+    const FrictionJunctionDev<Real> *junctions;
+    const float *approach, *travel; // [caller's junction][frames]
+    Real *force_out, *tangent_out; // [caller's junction][frames], where the host reads them
+    double *compliance_out;
+    uint32_t *status_out;
+    const Real *anchor_in; // by the caller's junction index
+    Real *anchor_out;
+    uint32_t *counts_out; // [caller's junction][3]: frames on S, on P or M, without a consistent candidate
+};
+template<typename Real> constexpr size_t friction_lds(uint32_t waves) {
+    return 4 * JUNCTION_WAVES * sizeof(Real) + size_t(waves) * coupled_tile<Real>() * (MODES_PER_WAVE + 2) * sizeof(Real);
+}
+template<typename Real> struct FrictionSums {
+    Real n, t;
+};
+template<typename Real, bool OBSERVE = false> __global__ void __launch_bounds__(JUNCTION_WAVES *WAVE) k_bank_modes_coupled_friction(BANK_MODES_PARAMS, JunctionArgs<Real, FrictionArgs<Real>, OBSERVE> fa) { // (`waves`: the main launch's, not read here)
+    typedef PairOf<Real> Pair;
+    constexpr uint32_t TS = coupled_tile<Real>();
+    extern __shared__ __attribute__((aligned(16))) unsigned char friction_mem[];
+    Real *s_slot = reinterpret_cast<Real *>(friction_mem); // [2][2][JUNCTION_WAVES]
+    const uint32_t wave = threadIdx.x / WAVE, lane = threadIdx.x % WAVE;
+    Real *s_term = s_slot + 4 * JUNCTION_WAVES + size_t(wave) * TS * PITCH; // this wave's tile, [sample][mode]
+    const FrictionJunctionDev<Real> *__restrict__ F = fa.junctions + blockIdx.x;
+    const JunctionDev<Real> J = F->j;
+    const uint32_t waves_a = J.side[0].waves, n_w = waves_a + J.side[1].waves;
+    const bool active = wave < n_w;
+    const uint32_t sd = active && wave >= waves_a ? 1 : 0;
+    const JunctionSideDev<Real> S = J.side[sd];
+    const uint32_t first_mode = active ? (wave - (wave >= waves_a ? waves_a : 0u)) * MODES_PER_WAVE : 0u;
+    // an idle wave has no live mode: nothing below loads or stores for it
+    WaveLane<Real> w = load_wave(b, deal_objects, chunk_base, out_gain, listener_gain, S.dealt, first_mode, active ? render_count[S.dealt] : 0u, lane);
+    BlendDev<Real> along_t = S.at; // the side's blend with t in the place of n
+    along_t.nx = F->t[sd][0], along_t.ny = F->t[sd][1], along_t.nz = F->t[sd][2];
+    Pair a = {0, 0}, g_im = {0, 0}, g_re = {0, 0}, a_t = {0, 0}, gt_im = {0, 0}, gt_re = {0, 0};
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+        if (w.live[h]) {
+            const BlendRead<Real> point = blend_read(b, w, S.at, fa.defl_gain, h), slide = blend_read(b, w, along_t, fa.defl_gain, h);
+            a[h] = b.rad_gain[w.k0 + w.k + h] * point.along;
+            a_t[h] = b.rad_gain[w.k0 + w.k + h] * slide.along;
+            const ReadGains<Real> g = read_gains(point.read, w.c_re[h], w.c_im[h], 1u), gt = read_gains(slide.read, w.c_re[h], w.c_im[h], 1u);
+            g_im[h] = g.im, g_re[h] = g.re;
+            gt_im[h] = gt.im, gt_re[h] = gt.re;
+        }
+    // the object's force rows, as in the coupled kernel
+    const uint32_t i0 = imp_ptr[S.dealt], n_imp = active ? imp_ptr[S.dealt + 1] - i0 : 0u;
+    Pair g_reg[IMP_REG] = {};
+    Real *g_mem = gain_scratch + size_t(J.first_wave + wave) * max_imp * MODES_PER_WAVE;
+    for (uint32_t t = 0; t < n_imp; ++t) {
+        const Pair g = row_gain(b, w, impacts[imp_idx[i0 + t]]);
+        if (t < IMP_REG) g_reg[t] = g;
+        else *reinterpret_cast<Pair *>(g_mem + size_t(t) * MODES_PER_WAVE + 2 * lane) = g;
+    }
+    // two sums over the junction's modes in one barrier, each as the coupled kernel's one: the lane's part -> the wave (DPP tree) -> the
+    // waves in ascending order from +0; the same bits in every lane of every wave
+    auto junction_sums = [&](Real mine_n, Real mine_t, uint32_t buffer) {
+        const Real wn = mh_wave_sum(mine_n), wt = mh_wave_sum(mine_t);
+        Real *slot = s_slot + buffer * 2 * JUNCTION_WAVES;
+        if (lane == 0) slot[wave] = wn, slot[JUNCTION_WAVES + wave] = wt;
+        mh_lds_writes_landed();
+        __syncthreads();
+        Real vn[JUNCTION_WAVES], vt[JUNCTION_WAVES];
+#pragma unroll
+        for (uint32_t i = 0; i < JUNCTION_WAVES; ++i) vn[i] = slot[i], vt[i] = slot[JUNCTION_WAVES + i];
+        FrictionSums<Real> acc = {0, 0};
+#pragma unroll
+        for (uint32_t i = 0; i < JUNCTION_WAVES; ++i) { // a slot beyond the junction's waves is not added
+            acc.n = i < n_w ? acc.n + vn[i] : acc.n;
+            acc.t = i < n_w ? acc.t + vt[i] : acc.t;
+        }
+        return acc;
+    };
+    const Real zero = 0;
+    // step 3: C_nn (the bits of the coupled kernel's C) and C_nt, then C_tn and C_tt
+    const FrictionSums<Real> from_n = junction_sums(fma_real(g_re.y, a.y, fma_real(g_re.x, a.x, zero)), fma_real(g_re.y, a_t.y, fma_real(g_re.x, a_t.x, zero)), 0);
+    const FrictionSums<Real> from_t = junction_sums(fma_real(gt_re.y, a.y, fma_real(gt_re.x, a.x, zero)), fma_real(gt_re.y, a_t.y, fma_real(gt_re.x, a_t.x, zero)), 1);
+    const Real c_nn = from_n.n, c_nt = from_n.t, c_tn = from_t.n, c_tt = from_t.t;
+    const Real mu = F->mu, kt = F->kt;
+    const bool hertz = (J.flags & MH_JUNCTION_HERTZ) != 0; // workgroup-uniform
+    // once per block: the stick elimination's den and beta, and the compliance each candidate's scalar solve sees
+    const Real den = Real(1) + kt * c_tt, beta = (kt * c_tn) / den;
+    const Real c_stick = c_nn - c_nt * beta, c_plus = c_nn + mu * c_nt, c_minus = c_nn - mu * c_nt;
+    const Real kc_nn = J.k * c_nn, kc_stick = J.k * c_stick, kc_plus = J.k * c_plus, kc_minus = J.k * c_minus;
+    bool solved = hertz ? finite_from_zero(c_nn) && finite_from_zero(kc_nn) : finite_above_zero(Real(1) + kc_nn); // the normal law's own conditions
+    solved = solved && is_finite(c_tt) && is_finite(c_nt) && is_finite(c_tn) && c_tt >= Real(0) && finite_above_zero(den) && finite_from_zero(c_plus) && finite_from_zero(c_minus) &&
+             is_finite(kc_stick) && is_finite(kc_plus) && is_finite(kc_minus);
+    // this lane's candidate: 0 = S, 1 = P, 2 = M (lane 3 of a quad repeats M)
+    const uint32_t cand = min(lane & 3u, 2u);
+    const Real kc = cand == 0 ? kc_stick : cand == 1 ? kc_plus : kc_minus, kc15 = Real(1.5) * kc, denom = Real(1) + kc;
+    if (threadIdx.x == 0) {
+        fa.compliance_out[J.row] = double(c_nn);
+        fa.status_out[J.row] = solved ? MH_JUNCTION_SOLVED : MH_JUNCTION_REFUSED;
+    }
+    Real q = fa.anchor_in[J.row]; // not finite: no history
+    uint32_t n_stick = 0, n_slip = 0, n_none = 0;
+    const float *u_row = fa.approach + size_t(J.row) * frames, *w_row = fa.travel + size_t(J.row) * frames;
+    Real *f_row = fa.force_out + size_t(J.row) * frames, *ft_row = fa.tangent_out + size_t(J.row) * frames;
+    Real *tap_row = nullptr;
+    if constexpr (OBSERVE) tap_row = tap_of<Real>(fa, active, J.first_wave + wave, frames, lane);
+    for (uint32_t s0 = 0; s0 < frames; s0 += TS) {
+        const uint32_t sn = min(TS, frames - s0);
+        // this tile's approach and travel samples, lane = sample (not finite: 0, as a drive's)
+        Real u_tile = 0, w_tile = 0;
+        if (lane < sn) u_tile = finite_or_zero<Real>(u_row[s0 + lane]), w_tile = finite_or_zero<Real>(w_row[s0 + lane]);
+        // the tile's excitation, parked where the output terms will go
+        for (uint32_t ds = 0; ds < sn; ++ds) {
+            Pair excite = {0, 0};
+            for (uint32_t t = 0; t < n_imp; ++t) {
+                const Real f = force[size_t(imp_idx[i0 + t]) * frames + s0 + ds];
+                excite += f * (t < IMP_REG ? g_reg[t] : *reinterpret_cast<const Pair *>(g_mem + size_t(t) * MODES_PER_WAVE + 2 * lane));
+            }
+            *reinterpret_cast<Pair *>(s_term + ds * PITCH + 2 * lane) = excite;
+        }
+        Real f_tile = 0, ft_tile = 0;
+        for (uint32_t ds = 0; ds < sn; ++ds) {
+            const Pair excite = *reinterpret_cast<const Pair *>(s_term + ds * PITCH + 2 * lane); // what this lane parked
+            const Pair re = w.z_re * w.c_re - w.z_im * w.c_im + excite;
+            w.z_im = w.z_re * w.c_im + w.z_im * w.c_re;
+            const Real mine_n = fma_real(g_re.y, re.y, fma_real(g_im.y, w.z_im.y, fma_real(g_re.x, re.x, fma_real(g_im.x, w.z_im.x, zero))));
+            const Real mine_t = fma_real(gt_re.y, re.y, fma_real(gt_im.y, w.z_im.y, fma_real(gt_re.x, re.x, fma_real(gt_im.x, w.z_im.x, zero))));
+            const FrictionSums<Real> d = junction_sums(mine_n, mine_t, (s0 + ds) & 1u);
+            const Real x_n = lane_bcast(u_tile, ds) - d.n, x_t = lane_bcast(w_tile, ds) - d.t;
+            if (!is_finite(q)) q = x_t; // no history: the slider stands where the contact is
+            Real f_n = 0, f_t = 0;
+            if (!(x_n > Real(0))) { // branch O: open, or a NaN -- no shear, and the slider follows
+                q = x_t;
+            } else {
+                // step 4t: this lane's candidate
+                const Real alpha = (kt * (x_t - q)) / den;
+                const Real x_c = cand == 0 ? x_n - c_nt * alpha : x_n;
+                Real fn_c;
+                if (hertz) fn_c = hertz_force(x_c, kc, kc15, J.k);
+                else fn_c = (J.k * (x_c > Real(0) ? x_c : Real(0))) / denom;
+                const Real cone = mu * fn_c;
+                const Real ft_c = cand == 0 ? alpha - beta * fn_c : cand == 1 ? cone : -cone;
+                const Real e = (x_t - c_tn * fn_c) - c_tt * ft_c;
+                const Real q_c = cand == 0 ? q : e - ft_c / kt;
+                const bool consistent = cand == 0 ? __builtin_fabs(ft_c) <= cone : cand == 1 ? q_c >= q : q_c <= q;
+                const Real miss = cand == 0 ? __builtin_fabs(ft_c) - cone : cand == 1 ? kt * (q - q_c) : kt * (q_c - q);
+                const uint32_t found = uint32_t(__builtin_amdgcn_ballot_w64(consistent)) & 7u; // lanes 0 .. 2
+                uint32_t taken;
+                if (found) {
+                    taken = uint32_t(__builtin_ctz(found));
+                } else { // rounding on a boundary left none: the one that misses by least, the earlier one on a tie
+                    const Real m0 = lane_bcast(miss, 0u), m1 = lane_bcast(miss, 1u), m2 = lane_bcast(miss, 2u);
+                    taken = m1 < m0 ? 1u : 0u;
+                    if (m2 < (taken ? m1 : m0)) taken = 2u;
+                    ++n_none;
+                }
+                taken = __builtin_amdgcn_readfirstlane(taken);
+                if (taken == 0) ++n_stick;
+                else ++n_slip;
+                f_n = solved ? lane_bcast(fn_c, taken) : zero;
+                f_t = solved ? lane_bcast(ft_c, taken) : zero;
+                q = lane_bcast(q_c, taken);
+            }
+            w.z_re = re + (a * f_n + a_t * f_t);
+            *reinterpret_cast<Pair *>(s_term + ds * PITCH + 2 * lane) = w.p_im * w.z_im + w.p_re * w.z_re;
+            if constexpr (OBSERVE)
+                if (tap_row) tap_store(tap_row, s0 + ds, w.z_im, w.z_re);
+            if (lane == ds) f_tile = f_n, ft_tile = f_t;
+        }
+        if (wave == 0 && lane < sn) f_row[s0 + lane] = f_tile, ft_row[s0 + lane] = ft_tile;
+        junction_turn_around<TS>(s_term, w, lane, s0, sn, partial, frames);
+    }
+    if (threadIdx.x == 0) { // (the host hands the anchor and the counts on only for a solved junction)
+        fa.anchor_out[J.row] = q;
+        fa.counts_out[3 * J.row] = n_stick, fa.counts_out[3 * J.row + 1] = n_slip, fa.counts_out[3 * J.row + 2] = n_none;
+    }
+    store_wave(b, w, lane, chunk_energy);
+}
+template<typename Real> constexpr auto k_bank_modes_coupled_friction_observed = &k_bank_modes_coupled_friction<Real, true>;
+
 // Groups of junctions that share objects (MH_JUNCTION_SHARED; contract in modalhip.h).  ONE WORKGROUP PER GROUP, one
 // wave per 128 modes of each DISTINCT object of the group (the objects in the order the members name them, side a before side b), modes
 // in registers two per lane; a wave holds one gain triple (a, g_im, g_re) per member that has a side on its object -- up to
@@ -1753,6 +1943,7 @@ enum class Entry {
     Observed, // + a pickup on a kept junction's object is read
     Mixed, // + a Hertz junction may join a group (step 4m), unconverged_out
     DampedGroups, // + a damped junction may join a group as well (step 4g)
+    Friction, // + MH_JUNCTION_FRICTION on a lone junction (step 4t): the tangential channel, the anchor, the counts
 };
 // What the widest entry takes, in the order the entries name it; an entry leaves what it does not take at zero.
 struct RenderRequest {
@@ -1774,6 +1965,7 @@ struct RenderRequest {
     uint32_t n_junctions{0}; const mh_junction *junctions{nullptr}; const float *approach{nullptr}; void *force_out{nullptr}; double *compliance_out{nullptr}; uint8_t *status_out{nullptr};
     const float *damping{nullptr}; void *carry{nullptr};
     uint32_t *unconverged_out{nullptr};
+    const mh_friction *friction{nullptr}; const float *travel{nullptr}; void *tangent_out{nullptr}; void *anchor{nullptr}; uint32_t *friction_counts_out{nullptr};
 };
 
 template<typename Real> struct BankImpl {
@@ -1790,6 +1982,7 @@ template<typename Real> struct BankImpl {
     std::vector<uint8_t> on_junction; // per object: on a side of a junction of this call that was not left out
     std::vector<uint32_t> kept_rows; // the caller's indices of those junctions
     std::vector<uint32_t> mixed_rows; // mh_bank_render_mixed: those of them that are members of a group with a Hertz or a damped member
+    std::vector<uint32_t> friction_rows; // mh_bank_render_friction: those of them with MH_JUNCTION_FRICTION
     GroupClass<Real> group_class[GROUP_CLASSES]; // the call's groups by class
     // per-block scratch
     Arena arena;
@@ -1821,7 +2014,7 @@ template<typename T> void ensure(mh_context *ctx, DevArray<T> &a, size_t n) {
 // A kernel's limit of dynamic LDS raised to the 160 KiB, once per (kernel, device): function attributes are per device, and the first
 // blocks of two banks may race.  (A table, not a PerDeviceOnce per call site: which kernel a junction launch takes is decided at run time.)
 void raise_lds_limit(int device, const void *kernel) {
-    constexpr int MaxKernels = 32; // the junction kernels: 12 per precision
+    constexpr int MaxKernels = 32; // the junction kernels: 14 per precision
     static std::mutex guard;
     static const void *raised[PerDeviceOnce::MaxDevices][MaxKernels];
     const std::lock_guard<std::mutex> lock(guard);
@@ -1867,6 +2060,9 @@ void render_impl(BankImpl<Real> &B, const RenderRequest &r) {
     const size_t o_groups = A.take((n_junctions / 2 + 1) * sizeof(GroupDev<Real>));
     const size_t o_damping = A.take(admits(Entry::Damped) ? (n_junctions + 1) * sizeof(Real) : 0), o_carry_in = A.take(admits(Entry::Damped) ? (n_junctions + 1) * sizeof(Real) : 0);
     const size_t o_taps = A.take(admits(Entry::Observed) ? (n_waves + 1) * sizeof(WaveDesc) : 0), o_tap_of = A.take(admits(Entry::Observed) ? (n_waves + JUNCTION_WAVES + 1) * 4 : 0);
+    const bool with_friction = admits(Entry::Friction) && n_junctions;
+    const size_t o_friction = A.take(with_friction ? (n_junctions + 1) * sizeof(FrictionJunctionDev<Real>) : 0), o_travel = A.take(with_friction ? size_t(n_junctions) * frames * sizeof(float) : 0);
+    const size_t o_anchor_in = A.take(with_friction ? (n_junctions + 1) * sizeof(Real) : 0);
     const size_t both_end = A.used;
     // (written by the kernels straight into the pinned arena -- no copy back: the host sees them once the block's last kernel has
     // raised the sequence number)
@@ -1876,6 +2072,8 @@ void render_impl(BankImpl<Real> &B, const RenderRequest &r) {
     const size_t o_junction_force = A.take(size_t(n_junctions) * frames * sizeof(Real)), o_compliance = A.take((n_junctions + 1) * 8), o_status = A.take((n_junctions + 1) * 4);
     const size_t o_carry_out = A.take(admits(Entry::Damped) ? (n_junctions + 1) * sizeof(Real) : 0);
     const size_t o_unconverged = A.take(admits(Entry::Mixed) ? (n_junctions + 1) * 4 : 0);
+    const size_t o_tangent = A.take(with_friction ? size_t(n_junctions) * frames * sizeof(Real) : 0), o_anchor_out = A.take(with_friction ? (n_junctions + 1) * sizeof(Real) : 0);
+    const size_t o_friction_counts = A.take(with_friction ? (size_t(n_junctions) + 1) * 3 * 4 : 0);
     const size_t total = A.used;
     if (total > A.cap) {
         HIP_CHECK(hipStreamSynchronize(st));
@@ -1890,11 +2088,13 @@ void render_impl(BankImpl<Real> &B, const RenderRequest &r) {
     // ---- junctions: the ones the coupled kernel may follow, one workgroup each; everything else is left out with a zero row ----
     uint32_t n_coupled = 0, coupled_waves = 0, widest_junction = 0;
     uint32_t n_grouped = 0; // components of two or more junctions: k_bank_modes_grouped, one workgroup each, by class (GroupClass)
+    uint32_t n_friction = 0, widest_friction = 0; // lone junctions with MH_JUNCTION_FRICTION: k_bank_modes_coupled_friction, a launch of their own
+    B.friction_rows.clear();
     B.mixed_rows.clear();
     for (auto &c : B.group_class) c.groups.clear(), c.widest = c.members = 0;
     bool any_hertz = false; // a kept junction with MH_JUNCTION_HERTZ: the call takes the entry that has the solve
     bool any_damped = false; // a kept junction with MH_JUNCTION_DAMPED: the entry that has both solves and the carry
-    const uint32_t flag_mask = admits(Entry::Damped) ? ~0u : ~uint32_t(MH_JUNCTION_DAMPED);
+    const uint32_t flag_mask = (admits(Entry::Damped) ? ~0u : ~uint32_t(MH_JUNCTION_DAMPED)) & (admits(Entry::Friction) ? ~0u : ~uint32_t(MH_JUNCTION_FRICTION));
     B.kept_rows.clear();
     if (n_junctions) {
         JunctionDev<Real> *jd = A.h<JunctionDev<Real>>(o_junctions);
@@ -1921,6 +2121,13 @@ void render_impl(BankImpl<Real> &B, const RenderRequest &r) {
             if (m.flags & flag_mask & MH_JUNCTION_DAMPED) { // the damped law is unilateral too, and its l a finite number from 0 up
                 if ((m.flags & MH_JUNCTION_BILATERAL) || !std::isfinite(r.damping[j]) || r.damping[j] < 0) continue;
             }
+            if (m.flags & flag_mask & MH_JUNCTION_FRICTION) { // friction goes with a lone unilateral undamped junction, and its numbers are finite and not below 0
+                if (m.flags & (MH_JUNCTION_BILATERAL | MH_JUNCTION_DAMPED | MH_JUNCTION_SHARED)) continue;
+                const mh_friction &t = r.friction[j];
+                bool ok = std::isfinite(t.mu) && std::isfinite(t.stiffness) && t.mu >= 0 && t.stiffness >= 0;
+                for (int c = 0; c < 3; ++c) ok = ok && std::isfinite(t.ta[c]) && std::isfinite(t.tb[c]);
+                if (!ok) continue;
+            }
             if (grouping.add(j, m.flags & flag_mask, m.a.object, side_waves(m.a), m.b.object, two_sided ? side_waves(m.b) : 0u, admits(Entry::Mixed), admits(Entry::DampedGroups)) < 0) continue;
             B.on_junction[m.a.object] = 1;
             if (two_sided) B.on_junction[m.b.object] = 1;
@@ -1933,6 +2140,14 @@ void render_impl(BankImpl<Real> &B, const RenderRequest &r) {
             const bool two_sided = m.b.object != MH_NO_OBJECT;
             JunctionDev<Real> dev{{side_dev(m.a), two_sided ? side_dev(m.b) : JunctionSideDev<Real>{}}, Real(m.stiffness), m.flags & flag_mask, j, coupled_waves};
             const uint32_t w = dev.side[0].waves + dev.side[1].waves;
+            if (dev.flags & MH_JUNCTION_FRICTION) { // a class of its own
+                const mh_friction &t = r.friction[j];
+                A.h<FrictionJunctionDev<Real>>(o_friction)[n_friction++] = {dev, {{Real(t.ta[0]), Real(t.ta[1]), Real(t.ta[2])}, {Real(t.tb[0]), Real(t.tb[1]), Real(t.tb[2])}}, Real(t.mu), Real(t.stiffness)};
+                B.friction_rows.push_back(j);
+                coupled_waves += w;
+                widest_friction = std::max(widest_friction, w);
+                continue;
+            }
             jd[n_coupled++] = dev;
             any_hertz = any_hertz || (m.flags & MH_JUNCTION_HERTZ) != 0;
             any_damped = any_damped || (dev.flags & MH_JUNCTION_DAMPED) != 0;
@@ -1980,7 +2195,7 @@ void render_impl(BankImpl<Real> &B, const RenderRequest &r) {
             n_grouped += c.count();
         }
     }
-    const bool any_junction = n_coupled || n_grouped;
+    const bool any_junction = n_coupled || n_grouped || n_friction;
     chunk_base[0] = 0;
     uint32_t main_waves = 0; // the main launch's waves: every dealt object that is not on a junction's side
     for (uint32_t d = 0; d < n_dealt; ++d) {
@@ -2081,10 +2296,12 @@ void render_impl(BankImpl<Real> &B, const RenderRequest &r) {
                 }
             };
             const JunctionDev<Real> *jd = A.h<JunctionDev<Real>>(o_junctions);
-            for (uint32_t j = 0; j < n_coupled; ++j) {
-                tap_object(jd[j].side[0].dealt, jd[j].first_wave, jd[j].side[0].waves);
-                if (jd[j].side[1].waves) tap_object(jd[j].side[1].dealt, jd[j].first_wave + jd[j].side[0].waves, jd[j].side[1].waves);
-            }
+            auto tap_junction = [&](const JunctionDev<Real> &j) {
+                tap_object(j.side[0].dealt, j.first_wave, j.side[0].waves);
+                if (j.side[1].waves) tap_object(j.side[1].dealt, j.first_wave + j.side[0].waves, j.side[1].waves);
+            };
+            for (uint32_t j = 0; j < n_coupled; ++j) tap_junction(jd[j]);
+            for (uint32_t j = 0; j < n_friction; ++j) tap_junction(A.h<FrictionJunctionDev<Real>>(o_friction)[j].j);
             const GroupDev<Real> *gd = A.h<GroupDev<Real>>(o_groups);
             for (uint32_t g = 0; g < n_grouped; ++g)
                 for (uint32_t o = 0; o < gd[g].n_objects; ++o) tap_object(gd[g].dealt[o], gd[g].first_wave + gd[g].wave0[o], gd[g].waves[o]);
@@ -2117,6 +2334,10 @@ void render_impl(BankImpl<Real> &B, const RenderRequest &r) {
         std::copy(r.damping, r.damping + n_junctions, A.h<Real>(o_damping));
         std::copy(static_cast<const Real *>(r.carry), static_cast<const Real *>(r.carry) + n_junctions, A.h<Real>(o_carry_in));
     }
+    for (const uint32_t j : B.friction_rows) { // travel and anchor are read for flagged junctions only
+        std::copy(r.travel + size_t(j) * frames, r.travel + size_t(j + 1) * frames, A.h<float>(o_travel) + size_t(j) * frames);
+        A.h<Real>(o_anchor_in)[j] = static_cast<const Real *>(r.anchor)[j];
+    }
     HIP_CHECK(hipMemcpyAsync(A.dev, A.host, both_end, hipMemcpyHostToDevice, st));
     // ---- device passes ----
     Real *d_out_gain = A.d<Real>(o_out_gain), *d_listener = A.d<Real>(o_listener), *d_out = A.d<Real>(o_out);
@@ -2146,7 +2367,7 @@ void render_impl(BankImpl<Real> &B, const RenderRequest &r) {
         // A launch of junction objects, one workgroup per junction or per group: the scratch gain rows, the kernel's LDS limit, the bound on
         // the widest workgroup, and the kernel -- when some junction object carries a pickup, the one that also stores the tapped waves' states.
         // solved: the junctions the launch solves per frame (MH_KERNEL_JUNCTION's work).
-        static_assert(coupled_lds<Real>(JUNCTION_WAVES) <= 160 * 1024 && grouped_lds<Real>(JUNCTION_WAVES) <= 160 * 1024, "the junction kernels' LDS within the 160 KiB");
+        static_assert(coupled_lds<Real>(JUNCTION_WAVES) <= 160 * 1024 && grouped_lds<Real>(JUNCTION_WAVES) <= 160 * 1024 && friction_lds<Real>(JUNCTION_WAVES) <= 160 * 1024, "the junction kernels' LDS within the 160 KiB");
         auto launch_junctions = [&](auto *plain, auto *observed, const auto &args, uint32_t workgroups, uint32_t widest, size_t lds, uint32_t solved) {
             if (!workgroups) return;
             if (lds > 160 * 1024) mh_throw(MH_EINVAL, "a junction workgroup of %u waves", widest); // (none is kept)
@@ -2166,6 +2387,12 @@ void render_impl(BankImpl<Real> &B, const RenderRequest &r) {
         else
             launch_junctions(any_hertz ? k_bank_modes_coupled_hertz<Real> : &k_bank_modes_coupled<Real>, any_hertz ? k_bank_modes_coupled_hertz_observed<Real> : k_bank_modes_coupled_observed<Real>, ca,
                              n_coupled, widest_junction, coupled_lds<Real>(widest_junction), n_coupled);
+        // lone junctions with friction: the kernel with the tangential channel (step 4t)
+        if (n_friction)
+            launch_junctions(&k_bank_modes_coupled_friction<Real>, k_bank_modes_coupled_friction_observed<Real>,
+                             FrictionArgs<Real>{B.defl_gain, A.d<FrictionJunctionDev<Real>>(o_friction), A.d<float>(o_approach), A.d<float>(o_travel), A.hd<Real>(o_junction_force), A.hd<Real>(o_tangent),
+                                                A.hd<double>(o_compliance), A.hd<uint32_t>(o_status), A.d<Real>(o_anchor_in), A.hd<Real>(o_anchor_out), A.hd<uint32_t>(o_friction_counts)},
+                             n_friction, widest_friction, friction_lds<Real>(widest_friction), n_friction);
         // groups, class after class: each class's entries of the device's list follow those of the class before
         const GroupClass<Real> &linear = B.group_class[LINEAR_GROUPS], &hertz = B.group_class[HERTZ_GROUPS], &damped = B.group_class[DAMPED_GROUPS];
         auto groups_from = [&](uint32_t first) {
@@ -2259,6 +2486,18 @@ void render_impl(BankImpl<Real> &B, const RenderRequest &r) {
             std::fill(carry, carry + n_junctions, std::numeric_limits<Real>::quiet_NaN());
             for (const uint32_t j : B.kept_rows)
                 if ((r.junctions[j].flags & MH_JUNCTION_DAMPED) && r.status_out[j] == MH_JUNCTION_SOLVED) carry[j] = A.h<Real>(o_carry_out)[j];
+        }
+        if (admits(Entry::Friction)) { // a solved frictional junction: its f_t row, its anchor and its counts; zeros, a quiet NaN and zeros for every other junction
+            Real *tangent = static_cast<Real *>(r.tangent_out), *anchor = static_cast<Real *>(r.anchor);
+            std::fill(tangent, tangent + size_t(n_junctions) * frames, Real(0));
+            std::fill(anchor, anchor + n_junctions, std::numeric_limits<Real>::quiet_NaN());
+            std::fill(r.friction_counts_out, r.friction_counts_out + size_t(n_junctions) * 3, 0u);
+            for (const uint32_t j : B.friction_rows) {
+                if (r.status_out[j] != MH_JUNCTION_SOLVED) continue;
+                std::copy(A.h<Real>(o_tangent) + size_t(j) * frames, A.h<Real>(o_tangent) + size_t(j + 1) * frames, tangent + size_t(j) * frames);
+                anchor[j] = A.h<Real>(o_anchor_out)[j];
+                std::copy(A.h<uint32_t>(o_friction_counts) + 3 * size_t(j), A.h<uint32_t>(o_friction_counts) + 3 * size_t(j + 1), r.friction_counts_out + 3 * size_t(j));
+            }
         }
     }
     const ImpactBack<Real> *back = A.h<ImpactBack<Real>>(o_back);
@@ -2401,6 +2640,12 @@ static int render(mh_bank *bank, const RenderRequest &r) {
     if (r.entry >= Entry::Damped && r.n_junctions && (!r.damping || !r.carry)) return MH_EINVAL;
     if (r.entry >= Entry::Mixed && r.n_junctions && !r.unconverged_out) return MH_EINVAL;
     if (r.unconverged_out) std::fill(r.unconverged_out, r.unconverged_out + r.n_junctions, 0u); // (0 whatever becomes of the call)
+    if (r.entry >= Entry::Friction && r.n_junctions) {
+        if (!r.junctions || !r.tangent_out || !r.anchor || !r.friction_counts_out) return MH_EINVAL;
+        for (uint32_t j = 0; j < r.n_junctions; ++j) // friction[j] and travel row j are read for flagged junctions only
+            if ((r.junctions[j].flags & MH_JUNCTION_FRICTION) && (!r.friction || !r.travel)) return MH_EINVAL;
+        std::fill(r.friction_counts_out, r.friction_counts_out + size_t(r.n_junctions) * 3, 0u);
+    }
     if (!bank || !r.out || (r.n_impacts && !r.impacts) || (r.n_renderers && !r.deal_offset) || !r.out_gain || !r.listener_gain || (r.n_drives && (!r.drives || !r.signals))) return MH_EINVAL;
     if (r.n_pickups && (!r.pickups || !r.pickup_out || !r.pickup_read)) return MH_EINVAL;
     if (r.n_junctions && (!r.junctions || !r.approach || !r.force_out || !r.compliance_out || !r.status_out)) return MH_EINVAL;
@@ -2482,6 +2727,18 @@ int mh_bank_render_damped_groups(mh_bank *bank, uint32_t frames, float click_gai
                          object_live, object_silenced, object_modal_energy, n_drives, drives, signals, n_pickups, pickups, pickup_out, pickup_read, n_junctions, junctions, approach, force_out,
                          compliance_out, status_out, damping, carry, unconverged_out});
 }
+int mh_bank_render_friction(mh_bank *bank, uint32_t frames, float click_gain, uint32_t n_impacts, mh_impact *impacts, uint32_t n_renderers, const uint32_t *deal_offset,
+                            const uint32_t *deal_objects, const uint32_t *render_count, const uint32_t *tuned_count, const float *out_gain, const float *listener_gain,
+                            void *out, double *object_energy, uint32_t *object_live, uint8_t *object_silenced, double *object_modal_energy, uint32_t n_drives,
+                            const mh_drive *drives, const float *signals, uint32_t n_pickups, const mh_pickup *pickups, void *pickup_out, uint8_t *pickup_read,
+                            uint32_t n_junctions, const mh_junction *junctions, const float *approach, void *force_out, double *compliance_out, uint8_t *status_out,
+                            const float *damping, void *carry, uint32_t *unconverged_out, const mh_friction *friction, const float *travel, void *tangent_out, void *anchor,
+                            uint32_t *friction_counts_out) {
+    return render(bank, {Entry::Friction, frames, click_gain, n_impacts, impacts, n_renderers, deal_offset, deal_objects, render_count, tuned_count, out_gain, listener_gain, out, object_energy,
+                         object_live, object_silenced, object_modal_energy, n_drives, drives, signals, n_pickups, pickups, pickup_out, pickup_read, n_junctions, junctions, approach, force_out,
+                         compliance_out, status_out, damping, carry, unconverged_out, friction, travel, tangent_out, anchor, friction_counts_out});
+}
+uint32_t mh_friction_struct_size(void) { return uint32_t(sizeof(mh_friction)); }
 uint32_t mh_drive_struct_size(void) { return uint32_t(sizeof(mh_drive)); }
 uint32_t mh_pickup_struct_size(void) { return uint32_t(sizeof(mh_pickup)); }
 uint32_t mh_junction_struct_size(void) { return uint32_t(sizeof(mh_junction)); }

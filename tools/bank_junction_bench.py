@@ -40,6 +40,9 @@ the exciter dipping in and out of the surface.
                                                                              unchanged paths -- render_coupled, render_damped and tools/bank_bench.py -- of a
                                                                              built checkout T of the parent commit and of this tree, interleaved in fresh
                                                                              processes -> profiles/bank_observed.json
+    python tools/bank_junction_bench.py --friction --law hertz --junctions 16   one measurement: lone junctions with Coulomb friction through Scene.render_friction
+    python tools/bank_junction_bench.py --friction --against T               this tree's frictional junctions beside the same junctions without the flag, and the
+                                                                             unchanged calls of T and of this tree -> profiles/bank_friction.json
 
 (The coupled kernel and the group kernel are timed under one kernel class, 6: a block that holds lone junctions AND groups makes two
 launches of it, and `coupled_kernel_us_per_block`, the class total over its launch count, is then per launch.  No mode here mixes the two.
@@ -72,13 +75,16 @@ def sides_of(j, sides):
     return (j,) if sides == 1 else (2 * j, 2 * j + 1)
 
 
-def measure(tree, entry, junctions, sides, objects, blocks, renderers, forces_path, save_forces, law="linear", members=0, ungrouped=False, pickups=None, mixed=False, double=False, damped_groups=False):
+def measure(tree, entry, junctions, sides, objects, blocks, renderers, forces_path, save_forces, law="linear", members=0, ungrouped=False, pickups=None, mixed=False, double=False, damped_groups=False,
+            friction=False):
     """members >= 2: the junctions are groups of `members` exciter junctions, junction q at point q % members of object q // members with
     the shared flag -- or, ungrouped, of object q without it.  pickups = P (not None): the call goes through Scene.render_observed with P
     pickups on every junction object.  mixed: with members and law = "hertz", the groups' members are Hertz junctions and the call goes through
     Scene.render_mixed (law = "linear": the same groups with linear members through the same entry).  damped_groups: the call goes through
     Scene.render_damped_groups with the carry passed from block to block; law = "hertz-damped": every member a damped Hertz junction
-    (l x0 = 1), "hertz": the same groups with plain Hertz members through the same entry."""
+    (l x0 = 1), "hertz": the same groups with plain Hertz members through the same entry.  friction: lone junctions (law "linear" or "hertz") with
+    the friction flag through Scene.render_friction -- tangent (1, 0.25, 0) on side a and its opposite on side b, mu = 0.3 (halved until the
+    cone condition admits it), kt = K, a travel of twice the free deflection that swings once per block, the anchor passed from block to block."""
     sys.path.insert(0, tree)
     from mesheditor_amd import bank as hipbank
     from tools import bank_bench
@@ -97,6 +103,9 @@ def measure(tree, entry, junctions, sides, objects, blocks, renderers, forces_pa
         damped = law in ("damped", "hertz-damped")
         if damped:
             flag["damped"] = True
+        if friction:
+            assert not members and law in ("linear", "hertz") and pickups is None
+            flag["friction"] = True
         if members and not ungrouped:
             flag = {"shared": True, "hertz": True} if mixed and law == "hertz" else {"shared": True}
             if damped_groups:
@@ -109,7 +118,9 @@ def measure(tree, entry, junctions, sides, objects, blocks, renderers, forces_pa
         # the compliances and the size of the free deflection, from two blocks with K = 0
         comp = np.ones(junctions)
         if junctions:
-            _, _, _, comp, status = (sc.render_damped_groups if damped_groups else sc.render_mixed if mixed else sc.render_coupled)(out, rows, signals, [], make([0.0] * junctions), none)[:5]
+            dead = (hipbank.Friction * junctions)(*[hipbank.Friction.of() for _ in range(junctions)]) if friction else None
+            probe = (lambda *a: sc.render_friction(*a, dead, none)) if friction else sc.render_damped_groups if damped_groups else sc.render_mixed if mixed else sc.render_coupled
+            _, _, _, comp, status = probe(out, rows, signals, [], make([0.0] * junctions), none)[:5]
             assert (status == 1).all() and (comp > 0).all()
             picks = (hipbank.Pickup * junctions)(*[hipbank.Pickup.of(where(j)[0] if members else sides_of(j, sides)[0], where(j)[1], (1.0, 0.0, 0.0), NORMAL, 2.0, 1) for j in range(junctions)])
             reads, _ = sc.render_read(out, rows, signals, picks)
@@ -121,13 +132,30 @@ def measure(tree, entry, junctions, sides, objects, blocks, renderers, forces_pa
         u = u if junctions else none
         damping = [1.0 / (float(u[j].max()) * SR) for j in range(junctions)]  # damped: D in s/m with l x0 = D SR x0 = 1
         carry = [None]
+        if friction and junctions:
+            stiff = [float(c.stiffness) for c in contacts]
+            travel = np.array([(2.0 * free[j] * np.sin(2 * np.pi * t / 512.0 + 0.5 * j)).astype(np.float32) for j in range(junctions)])
+            tangent = (1.0, 0.25, 0.0)
+            mu, anchor, counts = 0.3, [None], np.zeros(3, np.int64)
+            while True:  # the cone condition mu |C_nt| <= C_nn: a refused junction halves mu
+                slides = (hipbank.Friction * junctions)(*[hipbank.Friction.of(tangent, tuple(-v for v in tangent) if sides == 2 else (0.0, 0.0, 0.0), mu, stiff[j]) for j in range(junctions)])
+                if (sc.render_friction(out, rows, signals, [], contacts, u, slides, travel)[4] == 1).all():
+                    break
+                mu *= 0.5
+                assert mu > 1e-3
         watched = sorted({where(j)[0] for j in range(junctions)} if members else {o for j in range(junctions) for o in sides_of(j, sides)})
         probes = [hipbank.Pickup.of(o, (o + i) % POINTS, (1.0, 0.0, 0.0), NORMAL, 1.0 + 0.5 * i, i % 3) for o in watched for i in range(pickups or 0)]
         probes = (hipbank.Pickup * len(probes))(*probes) if probes else []
         peak_read = [0.0]
 
         def block():
-            if damped_groups:
+            if friction and junctions:
+                got = sc.render_friction(out, rows, signals, [], contacts, u, slides, travel, None, None, anchor[0])
+                forces, status, anchor[0] = got[2], got[4], got[8]
+                counts[:] += got[9].sum(axis=0).astype(np.int64)
+            elif friction:
+                forces, status = sc.render_friction(out, rows, signals, [], contacts, u, [], none)[2:5:2]
+            elif damped_groups:
                 _, _, forces, _, status, carry[0], unconverged = sc.render_damped_groups(out, rows, signals, [], contacts, u, damping, carry[0])
                 assert not unconverged.any()
             elif mixed:
@@ -179,7 +207,8 @@ def measure(tree, entry, junctions, sides, objects, blocks, renderers, forces_pa
     sc.close()
     t = np.array(times)
     coupled_us = 1e3 * kj["total_ms"] / max(1, kj["launches"])
-    return {"precision": "fp64" if double else "fp32", "entry": "damped_groups" if damped_groups else "mixed" if mixed else entry if pickups is None else "observed", "pickups_per_object": pickups, "junction_kernels_us_per_block": 1e3 * kj["total_ms"] / max(1, blocks), "law": law, "junctions": junctions, "sides": sides, "members": members, "grouped": bool(members) and not ungrouped, "objects": objects, "modes_per_object": MODES, "blocks": blocks, "ms_per_block": 1e3 * float(t.mean()),
+    more = {"friction_mu": mu, "friction_frames_stick_slip_none": [int(v) for v in counts]} if friction and junctions else {}
+    return {**more, "precision": "fp64" if double else "fp32", "entry": "friction" if friction else "damped_groups" if damped_groups else "mixed" if mixed else entry if pickups is None else "observed", "pickups_per_object": pickups, "junction_kernels_us_per_block": 1e3 * kj["total_ms"] / max(1, blocks), "law": law, "junctions": junctions, "sides": sides, "members": members, "grouped": bool(members) and not ungrouped, "objects": objects, "modes_per_object": MODES, "blocks": blocks, "ms_per_block": 1e3 * float(t.mean()),
             "ms_per_block_median": 1e3 * float(np.median(t)), "ms_per_block_p99": 1e3 * float(np.quantile(t, 0.99)), "kernel_us_per_block": 1e3 * k["total_ms"] / max(1, k["launches"]),
             "coupled_kernel_us_per_block": coupled_us, "coupled_us_per_frame": coupled_us / BLOCK, "coupled_cycles_per_frame": coupled_us / BLOCK * ENGINE_MHZ,
             "real_time_ms_per_block": 1e3 * BLOCK / SR}
@@ -574,6 +603,65 @@ def compare_damped_groups(parent, runs, objects, blocks, renderers, out_path, al
     print(json.dumps(result["summary"]))
 
 
+def compare_friction(parent, runs, objects, blocks, renderers, out_path, all_live):
+    """This tree's J = 1, 16, 64 lone frictional junctions, linear and Hertz, one- and two-sided (J = 16), through Scene.render_friction beside the
+    same junctions without the flag through the same entry, fp32 and fp64 (J = 16); then the unchanged calls of the parent and of this tree,
+    interleaved in fresh processes -- J = 0, J = 1, 16, 64 linear and Hertz through render_coupled, and tools/bank_bench.py all-live: the new
+    figures have to land within the parent's own spread.  The file is written after every row."""
+    me = os.path.abspath(__file__)
+    common = ["--objects", str(objects), "--blocks", str(blocks), "--renderers", str(renderers)]
+    result = {"workload": f"{objects} objects x {MODES} modes @48k, {BLOCK}-frame blocks, {renderers} renderers, one drive on every object in every block; J lone junctions "
+                          "(linear: K C = 10; Hertz: K C sqrt(x0) = 10), with friction: mu = 0.3, kt = K, a travel of twice the free deflection", "runs_each": runs,
+              "friction": {}, "friction_fp64": {}, "all_live": {"parent": [], "new": []}, "j0": {"parent": [], "new": []}, "linear": {}, "hertz": {}}
+
+    def save():
+        os.makedirs(os.path.dirname(out_path), exist_ok=True)
+        with open(out_path, "w") as f:
+            json.dump(result, f, indent=1)
+    q = subprocess.run(["timeout", "-k", "10", "300", sys.executable, "-c", "import torch; p = torch.cuda.get_device_properties(0); print(p.name, p.gcnArchName, '%d CUs' % p.multi_processor_count, '|', torch.version.hip)"], capture_output=True, text=True)
+    if q.returncode != 0:
+        raise SystemExit("no GPU to measure on: " + q.stderr[-2000:])
+    result["device"], result["hip"] = (v.strip() for v in q.stdout.strip().splitlines()[-1].split("|"))
+    med = lambda rows, key: float(np.median([r[key] for r in rows])) if rows else None
+    spread = lambda rows, key: (max(r[key] for r in rows) / min(r[key] for r in rows)) if rows else None
+    pair = lambda old, new: {"parent_ms_per_block": [r["ms_per_block"] for r in old], "new_ms_per_block": [r["ms_per_block"] for r in new], "parent_spread_max_over_min": spread(old, "ms_per_block"),
+                             "new_median_over_parent_median": (med(new, "ms_per_block") / med(old, "ms_per_block")) if old and new else None}
+    both = lambda row: {"friction_ms_per_block": med(row["friction"], "ms_per_block"), "plain_ms_per_block": med(row["plain"], "ms_per_block"),
+                        "friction_kernel_us_per_block": med(row["friction"], "coupled_kernel_us_per_block"), "plain_kernel_us_per_block": med(row["plain"], "coupled_kernel_us_per_block"),
+                        "friction_cycles_per_frame": med(row["friction"], "coupled_cycles_per_frame"), "plain_cycles_per_frame": med(row["plain"], "coupled_cycles_per_frame"),
+                        "frames_stick_slip_none": row["friction"][-1].get("friction_frames_stick_slip_none") if row["friction"] else None}
+
+    def summarise():
+        result["summary"] = {"real_time_ms_per_block": 1e3 * BLOCK / SR, "friction": {name: both(row) for name, row in result["friction"].items()},
+                             "friction_fp64": {name: both(row) for name, row in result["friction_fp64"].items()},
+                             "all_live": pair(result["all_live"]["parent"], result["all_live"]["new"]), "j0": pair(result["j0"]["parent"], result["j0"]["new"]),
+                             "linear": {name: pair(row["parent"], row["new"]) for name, row in result["linear"].items()},
+                             "hertz": {name: pair(row["parent"], row["new"]) for name, row in result["hertz"].items()}}
+        save()
+    for _ in range(runs):
+        for double, key, counts in ((False, "friction", JUNCTIONS[1:]), (True, "friction_fp64", (16,))):
+            for law in ("linear", "hertz"):
+                for j, sides in [(j, 1) for j in counts] + [(16, 2)]:
+                    row = result[key].setdefault("%s, J = %d x %d-sided" % (law, j, sides), {"friction": [], "plain": []})
+                    extra = (["--double"] if double else []) + ["--law", law, "--junctions", str(j), "--sides", str(sides)]
+                    row["friction"].append(child([me, "--friction"] + extra + common))
+                    row["plain"].append(child([me, "--damped-groups"] + extra + common))
+                    summarise()
+    for _ in range(runs if parent else 0):
+        for name, tree in (("parent", parent), ("new", HERE)):  # (the parent's copy of this tool measures the parent's library)
+            tool = os.path.join(tree, "tools", "bank_junction_bench.py")
+            result["j0"][name].append(child([tool, "--entry", "coupled", "--junctions", "0"] + common))
+            for j in JUNCTIONS[1:]:
+                result["linear"].setdefault("J = %d" % j, {"parent": [], "new": []})[name].append(child([tool, "--junctions", str(j)] + common))
+                result["hertz"].setdefault("J = %d" % j, {"parent": [], "new": []})[name].append(child([tool, "--law", "hertz", "--junctions", str(j)] + common))
+            summarise()
+        for name, tree in (("parent", parent), ("new", HERE)) if all_live else ():
+            r = child([os.path.join(tree, "tools", "bank_bench.py")], 600)
+            result["all_live"][name].append({"ms_per_block": r["all_live"]["ms_per_block"], "kernel_us_per_block": r["all_live"]["kernel_us_per_block"]})
+            summarise()
+    print(json.dumps(result["summary"]))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--entry", choices=["coupled", "replay"], default="coupled")
@@ -597,6 +685,7 @@ def main():
     ap.add_argument("--mixed", action="store_true", help="with --members: through Scene.render_mixed (--law hertz: Hertz members); with --against: the unchanged calls of both trees and this tree's groups with Hertz members -> profiles/bank_mixed.json")
     ap.add_argument("--double", action="store_true", help="the fp64 bank (with --mixed or --damped-groups)")
     ap.add_argument("--damped-groups", action="store_true", help="with --members: through Scene.render_damped_groups (--law hertz-damped: damped Hertz members; --law hertz: plain ones); with --against: this tree's groups with damped members and the unchanged calls of both trees -> profiles/bank_damped_groups.json")
+    ap.add_argument("--friction", action="store_true", help="lone junctions with Coulomb friction through Scene.render_friction (--law linear or hertz); with --against: this tree's frictional junctions beside the same junctions without the flag, and the unchanged calls of both trees -> profiles/bank_friction.json")
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--no-all-live", action="store_true", help="skip tools/bank_bench.py of both trees")
     ap.add_argument("--out", default=os.path.join(HERE, "profiles", "bank_junctions.json"))
@@ -610,6 +699,9 @@ def main():
     elif a.laws_against:
         out = a.out if a.out != ap.get_default("out") else os.path.join(HERE, "profiles", "bank_hertz.json")
         compare_laws(os.path.abspath(a.laws_against), a.runs, a.objects, a.blocks, a.renderers, out)
+    elif a.against and a.friction:
+        out = a.out if a.out != ap.get_default("out") else os.path.join(HERE, "profiles", "bank_friction.json")
+        compare_friction(os.path.abspath(a.against), a.runs, a.objects if a.objects != ap.get_default("objects") else 256, a.blocks, a.renderers, out, not a.no_all_live)
     elif a.against and a.damped_groups:
         out = a.out if a.out != ap.get_default("out") else os.path.join(HERE, "profiles", "bank_damped_groups.json")
         compare_damped_groups(os.path.abspath(a.against), a.runs, a.objects if a.objects != ap.get_default("objects") else 256, a.blocks, a.renderers, out, not a.no_all_live)
@@ -622,7 +714,7 @@ def main():
     elif a.against:
         compare(os.path.abspath(a.against), a.runs, a.objects, a.blocks, a.renderers, a.out, not a.no_all_live)
     else:
-        print(json.dumps(measure(os.path.abspath(a.tree), a.entry, a.junctions, a.sides, a.objects, a.blocks, a.renderers, a.forces, a.save_forces, a.law, a.members, a.ungrouped, a.pickups, a.mixed, a.double, a.damped_groups)))
+        print(json.dumps(measure(os.path.abspath(a.tree), a.entry, a.junctions, a.sides, a.objects, a.blocks, a.renderers, a.forces, a.save_forces, a.law, a.members, a.ungrouped, a.pickups, a.mixed, a.double, a.damped_groups, a.friction)))
 
 
 if __name__ == "__main__":
