@@ -735,3 +735,142 @@ int mhl_context_bench_stream(mh_context *ctx, uint64_t bytes, uint32_t reps, dou
 }
 
 }
+
+// ---- the sparse block product's forms on a caller's matrix (tests/test_spmm_forms_gpu.py) ------------------------------------
+namespace {
+// quiet NaNs with a payload: arithmetic on finite inputs produces the canonical NaN at most, never these
+template<typename T> T lab_sentinel();
+template<> double lab_sentinel<double>() {
+    const uint64_t bits = MHL_SPMM_SENTINEL64;
+    double v;
+    memcpy(&v, &bits, sizeof v);
+    return v;
+}
+template<> float lab_sentinel<float>() {
+    const uint32_t bits = MHL_SPMM_SENTINEL32;
+    float v;
+    memcpy(&v, &bits, sizeof v);
+    return v;
+}
+
+// A device buffer of n entries between two guards of MHL_SPMM_GUARD entries, everything pre-filled with the sentinel (the body with
+// `init` when given); fetch() copies guards and body back.  The guard is a multiple of 16 bytes: the body keeps the pool's alignment.
+template<typename T> struct LabGuarded {
+    DevArray<T> dev;
+    size_t n;
+    LabGuarded(mh_context *ctx, size_t n_, const T *init = nullptr) : n(n_) {
+        std::vector<T> h(n + 2 * MHL_SPMM_GUARD, lab_sentinel<T>());
+        if (init) std::copy(init, init + n, h.begin() + MHL_SPMM_GUARD);
+        dev.reset(ctx, h.size());
+        dev.upload(h.data(), h.size());
+        HIP_CHECK(hipStreamSynchronize(ctx->stream)); // h goes out of scope
+    }
+    T *body() const { return dev.get() + MHL_SPMM_GUARD; }
+    void fetch(void *host) const { dev.download(static_cast<T *>(host), n + 2 * MHL_SPMM_GUARD); }
+};
+
+template<typename T> void lab_upload(mh_context *ctx, DevArray<T> &d, const void *src, size_t n, size_t lead = 0) {
+    d.reset(ctx, n + lead + 2); // (two spare entries: a pointer moved by `lead` stays inside, and no array is empty)
+    if (n) HIP_CHECK(hipMemcpyAsync(d.get() + lead, src, n * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+    HIP_CHECK(hipStreamSynchronize(ctx->stream));
+}
+} // namespace
+
+extern "C" {
+// One form of the BSR 3x3 product (modalhip_lab.h: MHL_SPMM_*) on the caller's matrix and panels, through the product's own dispatchers
+// (mh_spmm, mh_spmm_f32, mh_spmm_mixed, mh_spmm_mapped, mh_spmm_f32_cheb_step): no node permutation, no kernel chosen here.  Every
+// output comes back whole, guards included.  The arguments are checked on the host so that no launch reads or writes outside its arrays.
+int mhl_context_spmm_form(mh_context *ctx, mhl_spmm_request *q) {
+    if (!ctx || !q || !q->row_ptr || !q->col || !q->x || q->n_nodes == 0 || q->w == 0 || q->w > 4096) return MH_EINVAL;
+    const int form = q->form;
+    if (form < MHL_SPMM_F64_A || form > MHL_SPMM_F32_CHEB) return MH_EINVAL;
+    const bool f64_plain = form <= MHL_SPMM_F64_AM, mapped = form == MHL_SPMM_MAPPED || form == MHL_SPMM_MAPPED_RES, cheb = form == MHL_SPMM_F32_CHEB;
+    const bool with_a = form != MHL_SPMM_F64_M, with_m = form == MHL_SPMM_F64_M || form == MHL_SPMM_F64_AM || mapped;
+    const bool vals_f32 = form == MHL_SPMM_F32_A || cheb, x_f32 = vals_f32 || form == MHL_SPMM_MIXED;
+    if ((with_a && (!q->vals9 || (!q->y && !cheb))) || (with_m && (!q->mscal || !q->y2)) || (q->misalign && !f64_plain)) return MH_EINVAL;
+    const uint32_t nn = q->n_nodes, w = q->w;
+    if (q->row_ptr[0] != 0) return MH_EINVAL;
+    for (uint32_t i = 0; i < nn; ++i)
+        if (q->row_ptr[i + 1] < q->row_ptr[i]) return MH_EINVAL;
+    const uint32_t nblocks = q->row_ptr[nn];
+    for (uint32_t p = 0; p < nblocks; ++p)
+        if (q->col[p] >= nn) return MH_EINVAL;
+    if (mapped) {
+        if (!q->omap || q->ldy == 0 || q->wreal == 0 || q->wreal > w) return MH_EINVAL;
+        for (uint32_t c = 0; c < q->wreal; ++c)
+            if (q->omap[c] >= q->ldy) return MH_EINVAL;
+        if (form == MHL_SPMM_MAPPED_RES && (!q->theta || !q->r_out || !q->partial)) return MH_EINVAL;
+    }
+    if (cheb && (!q->dinv32 || !q->r || !q->xs || !q->cheb_r || !q->cheb_d_out || !q->cheb_x || !q->cheb_d_in)) return MH_EINVAL;
+    try {
+        HIP_CHECK(hipSetDevice(ctx->device));
+        MhSharedPhase not_during_a_factorisation(ctx->device);
+        const size_t rows = size_t(3) * nn, panel = rows * w;
+        BsrLevel lvl;
+        lvl.n_nodes = nn;
+        lvl.n_blocks = nblocks;
+        lab_upload(ctx, lvl.row_ptr, q->row_ptr, size_t(nn) + 1);
+        lab_upload(ctx, lvl.col, q->col, nblocks);
+        if (with_a && vals_f32) lab_upload(ctx, lvl.aval32, q->vals9, size_t(9) * nblocks);
+        else if (with_a) lab_upload(ctx, lvl.aval, q->vals9, size_t(9) * nblocks);
+        if (with_m) lab_upload(ctx, lvl.mval, q->mscal, nblocks);
+        q->taken = 1;
+        if (cheb) {
+            DevArray<float> dinv;
+            lab_upload(ctx, dinv, q->dinv32, rows);
+            LabGuarded<float> d_in(ctx, panel, static_cast<const float *>(q->x)), d_out(ctx, panel), r(ctx, panel, q->r), xs(ctx, panel, q->xs);
+            q->taken = mh_spmm_f32_cheb_step(ctx, lvl, d_in.body(), d_out.body(), r.body(), xs.body(), dinv, q->c1, q->c2, w) ? 1 : 0;
+            d_in.fetch(q->cheb_d_in);
+            d_out.fetch(q->cheb_d_out);
+            r.fetch(q->cheb_r);
+            xs.fetch(q->cheb_x);
+            return MH_OK;
+        }
+        const size_t lead = q->misalign ? 1 : 0; // 8 bytes into a larger allocation: launch_spmm_wide's aligned16 test fails
+        DevArray<double> x64;
+        DevArray<float> x32;
+        if (x_f32) lab_upload(ctx, x32, q->x, panel);
+        else lab_upload(ctx, x64, q->x, panel, lead);
+        if (mapped) {
+            const size_t out = rows * q->ldy;
+            LabGuarded<double> y(ctx, out), y2(ctx, out);
+            if (form == MHL_SPMM_MAPPED_RES) {
+                DevArray<uint32_t> omap;
+                DevArray<double> theta, dinv;
+                lab_upload(ctx, omap, q->omap, q->wreal);
+                lab_upload(ctx, theta, q->theta, w);
+                if (q->dinv) lab_upload(ctx, dinv, q->dinv, rows);
+                LabGuarded<double> r_out(ctx, panel), partial(ctx, size_t(2) * nn * w);
+                mh_spmm_mapped(ctx, lvl, lvl.aval, x64, y.body(), lvl.mval, y2.body(), w, q->ldy, q->wreal, omap, theta, r_out.body(), partial.body(), q->dinv ? dinv.get() : nullptr);
+                r_out.fetch(q->r_out);
+                partial.fetch(q->partial);
+            } else {
+                DevArray<uint32_t> omap;
+                lab_upload(ctx, omap, q->omap, q->wreal);
+                mh_spmm_mapped(ctx, lvl, lvl.aval, x64, y.body(), lvl.mval, y2.body(), w, q->ldy, q->wreal, omap);
+                HIP_CHECK(hipStreamSynchronize(ctx->stream)); // omap goes out of scope
+            }
+            y.fetch(q->y);
+            y2.fetch(q->y2);
+            return MH_OK;
+        }
+        if (form == MHL_SPMM_F32_A) {
+            LabGuarded<float> y(ctx, panel);
+            mh_spmm_f32(ctx, lvl, x32, y.body(), w);
+            y.fetch(q->y);
+            return MH_OK;
+        }
+        if (form == MHL_SPMM_MIXED) {
+            LabGuarded<double> y(ctx, panel);
+            mh_spmm_mixed(ctx, lvl, x32, y.body(), w);
+            y.fetch(q->y);
+            return MH_OK;
+        }
+        LabGuarded<double> y(ctx, with_a ? panel : 0), y2(ctx, with_m ? panel : 0);
+        mh_spmm(ctx, lvl, with_a ? lvl.aval.get() : nullptr, x64.get() + lead, with_a ? y.body() : nullptr, with_m ? lvl.mval.get() : nullptr, with_m ? y2.body() : nullptr, w);
+        if (with_a) y.fetch(q->y);
+        if (with_m) y2.fetch(q->y2);
+        return MH_OK;
+    } catch (const std::exception &e) { return mh_guard(ctx, e); }
+}
+}

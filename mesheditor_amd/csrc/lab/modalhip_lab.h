@@ -38,6 +38,42 @@ int mhl_context_small_gemm(mh_context *, int ta, int tb, uint32_t M, uint32_t N,
                            uint32_t ldc, uint32_t reps, double *avg_ms);
 /* G (wa x wb, column-major) = X^T Y for row-major host panels (n x wa), (n x wb): the solver's Gram kernel */
 int mhl_context_gram(mh_context *, uint64_t n, const double *x, uint32_t wa, const double *y, uint32_t wb, double *g);
+/* One form of the BSR 3x3 product (mh_spmm.hip) on the caller's own matrix, through the product's dispatchers: no node permutation, the
+ * launch selection is the solver's.  Panels are row-major, 3 n_nodes rows of pitch w.  Every output is a host array of
+ * MHL_SPMM_GUARD + entries + MHL_SPMM_GUARD values: the device buffer is pre-filled with the sentinel (a quiet NaN with a payload) and
+ * copied back whole, so entries that were never written and entries that should not have been touched both show.  A form the
+ * dispatcher refuses on the host (MH_EINVAL) leaves the outputs as the caller passed them. */
+enum {
+    MHL_SPMM_F64_A = 0,      /* y = A x                                  vals9, x double */
+    MHL_SPMM_F64_M = 1,      /* y2 = M x                                 mscal, x double */
+    MHL_SPMM_F64_AM = 2,     /* y = A x, y2 = M x in one launch */
+    MHL_SPMM_F32_A = 3,      /* y = A x                                  vals9, x, y float */
+    MHL_SPMM_MIXED = 4,      /* y (double) = A x                         vals9 double, x float */
+    MHL_SPMM_MAPPED = 5,     /* columns omap[c], c < wreal, of y, y2 (3 n_nodes x ldy) */
+    MHL_SPMM_MAPPED_RES = 6, /* the same with the residual epilogue: r_out (3 n_nodes x w), partial (n_nodes x 2 x w) */
+    MHL_SPMM_F32_CHEB = 7    /* the fused Chebyshev step: x is d (float); cheb_r, cheb_x start as r, xs; cheb_d_in is d after the launch */
+};
+#define MHL_SPMM_GUARD 64u
+#define MHL_SPMM_SENTINEL64 0x7ff8a5a5a5a5a5a5ull
+#define MHL_SPMM_SENTINEL32 0x7fd5a5a5u
+typedef struct mhl_spmm_request {
+    int32_t form;
+    uint32_t misalign; /* plain fp64 forms: the x panel starts 8 bytes into its allocation (no 16-byte loads: k_spmm serves even widths too) */
+    uint32_t n_nodes, w;
+    uint32_t ldy, wreal; /* mapped forms */
+    float c1, c2;        /* Chebyshev step */
+    const uint32_t *row_ptr, *col, *omap;
+    const void *vals9;   /* 9 per node block, row-major: double, or float for MHL_SPMM_F32_A and MHL_SPMM_F32_CHEB */
+    const double *mscal; /* 1 per node block */
+    const void *x;
+    const double *theta, *dinv;   /* residual epilogue: w values; 3 n_nodes weights or null */
+    const float *dinv32, *r, *xs; /* Chebyshev step: 3 n_nodes; panels */
+    void *y, *y2;
+    double *r_out, *partial;
+    float *cheb_r, *cheb_d_out, *cheb_x, *cheb_d_in;
+    int32_t taken; /* out: 0 when mh_spmm_f32_cheb_step declined the panel */
+} mhl_spmm_request;
+int mhl_context_spmm_form(mh_context *, mhl_spmm_request *);
 /* measured HBM ceilings of the device: a streaming copy (read + written bytes per second) and a streaming read, in GB/s */
 int mhl_context_bench_stream(mh_context *, uint64_t bytes, uint32_t reps, double *copy_gbs, double *read_gbs);
 /* the context's device pool: bytes held from the device, bytes of them idle in the cache, the cap on the idle part */

@@ -39,6 +39,7 @@ def lib():
         L.mhl_system_hierarchy_sizes.restype, L.mhl_system_hierarchy_sizes.argtypes = i32, [vp, C.c_double, i32, vp]
         L.mhl_system_hierarchy_export.restype, L.mhl_system_hierarchy_export.argtypes = i32, [vp, u32, vp, vp, vp, vp, vp, vp, vp]
         L.mhl_system_patch_export.restype, L.mhl_system_patch_export.argtypes = i32, [vp, i32, vp, vp, vp, vp, vp, vp]
+        L.mhl_context_spmm_form.restype, L.mhl_context_spmm_form.argtypes = i32, [vp, C.POINTER(SpmmRequest)]
         _LIB = L
     return _LIB
 
@@ -136,6 +137,76 @@ def gram(ctx, x, y):
     g = np.zeros((wb, wa))  # column-major wa x wb
     ctx.check(lib().mhl_context_gram(ctx.h, n, _p(xc), wa, _p(yc), wb, _p(g)))
     return g.T.copy()
+
+
+SPMM_FORMS = ("f64_a", "f64_m", "f64_am", "f32_a", "mixed", "mapped", "mapped_res", "f32_cheb")  # modalhip_lab.h: MHL_SPMM_*
+SPMM_GUARD = 64
+SPMM_SENTINEL = {np.dtype(np.float64): np.uint64(0x7FF8A5A5A5A5A5A5), np.dtype(np.float32): np.uint32(0x7FD5A5A5)}
+
+
+class SpmmRequest(C.Structure):
+    _fields_ = [("form", C.c_int32), ("misalign", C.c_uint32), ("n_nodes", C.c_uint32), ("w", C.c_uint32), ("ldy", C.c_uint32), ("wreal", C.c_uint32),
+                ("c1", C.c_float), ("c2", C.c_float), ("row_ptr", C.c_void_p), ("col", C.c_void_p), ("omap", C.c_void_p), ("vals9", C.c_void_p),
+                ("mscal", C.c_void_p), ("x", C.c_void_p), ("theta", C.c_void_p), ("dinv", C.c_void_p), ("dinv32", C.c_void_p), ("r", C.c_void_p),
+                ("xs", C.c_void_p), ("y", C.c_void_p), ("y2", C.c_void_p), ("r_out", C.c_void_p), ("partial", C.c_void_p), ("cheb_r", C.c_void_p),
+                ("cheb_d_out", C.c_void_p), ("cheb_x", C.c_void_p), ("cheb_d_in", C.c_void_p), ("taken", C.c_int32)]
+
+
+def spmm_untouched(a):
+    """Boolean array: which entries of an output of spmm_form still hold the sentinel, bit for bit."""
+    return a.view(np.uint64 if a.dtype == np.float64 else np.uint32) == SPMM_SENTINEL[a.dtype]
+
+
+def spmm_form(ctx, form, row_ptr, col, x, vals9=None, mscal=None, misalign=False, ldy=0, wreal=0, omap=None, theta=None, dinv=None, c1=0.0, c2=0.0,
+              r=None, xs=None):
+    """One form (SPMM_FORMS) of the BSR 3x3 product on the caller's matrix through the product's own dispatchers.  x: the row-major panel
+    (3 n_nodes x w; float32 for f32_a, mixed and f32_cheb, where it is d); vals9 (n_blocks x 9) is handed over as float32 for f32_a and
+    f32_cheb and as float64 otherwise, WITHOUT conversion (a wrong dtype is an error).  Returns (rc, taken, out): the entry's status,
+    whether the Chebyshev step took the panel, and per output its (body, guards): the body in its panel shape and the two guard regions
+    joined.  Entries nobody wrote hold the sentinel (spmm_untouched); when the dispatcher refused on the host every entry does."""
+    f = SPMM_FORMS.index(form)
+    f32_vals, f32_x = form in ("f32_a", "f32_cheb"), form in ("f32_a", "mixed", "f32_cheb")
+    keep = []
+
+    def arr(a, dtype):
+        if a is None:
+            return None
+        a = np.asarray(a)
+        assert a.dtype == dtype and a.flags.c_contiguous, (a.dtype, dtype)
+        keep.append(a)
+        return _p(a)
+
+    x = np.asarray(x)
+    n3, w = x.shape
+    nn = len(row_ptr) - 1
+    assert n3 == 3 * nn
+    outs = {}
+
+    def out(name, rows, pitch, dtype):
+        buf = np.empty(rows * pitch + 2 * SPMM_GUARD, dtype)
+        buf.view(np.uint64 if dtype == np.float64 else np.uint32)[:] = SPMM_SENTINEL[np.dtype(dtype)]
+        outs[name] = (buf, rows, pitch)
+        return _p(buf)
+
+    q = SpmmRequest(form=f, misalign=int(misalign), n_nodes=nn, w=w, ldy=ldy, wreal=wreal, c1=c1, c2=c2)
+    q.row_ptr, q.col, q.omap = arr(row_ptr, np.uint32), arr(col, np.uint32), arr(omap, np.uint32)
+    q.vals9, q.mscal = arr(vals9, np.float32 if f32_vals else np.float64), arr(mscal, np.float64)
+    q.x = arr(x, np.float32 if f32_x else np.float64)
+    q.theta, q.dinv = arr(theta, np.float64), arr(dinv, np.float64) if form != "f32_cheb" else None
+    if form == "f32_cheb":
+        q.dinv32, q.r, q.xs = arr(dinv, np.float32), arr(r, np.float32), arr(xs, np.float32)
+        q.cheb_r, q.cheb_d_out, q.cheb_x, q.cheb_d_in = (out(k, n3, w, np.float32) for k in ("r", "d_out", "x", "d_in"))
+    else:
+        pitch = ldy if form.startswith("mapped") else w
+        if form != "f64_m":
+            q.y = out("y", n3, pitch, np.float32 if form == "f32_a" else np.float64)
+        if form in ("f64_m", "f64_am", "mapped", "mapped_res"):
+            q.y2 = out("y2", n3, pitch, np.float64)
+        if form == "mapped_res":
+            q.r_out, q.partial = out("r_out", n3, w, np.float64), out("partial", 2 * nn, w, np.float64)
+    rc = lib().mhl_context_spmm_form(ctx.h, C.byref(q))
+    res = {k: (b[SPMM_GUARD:-SPMM_GUARD].reshape(rows, pitch), np.concatenate([b[:SPMM_GUARD], b[-SPMM_GUARD:]])) for k, (b, rows, pitch) in outs.items()}
+    return rc, bool(q.taken), res
 
 
 def mapped_update_mismatches(ctx, n, wa, wb, gaps):
