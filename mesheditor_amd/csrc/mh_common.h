@@ -12,6 +12,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <iterator>
 #include <limits>
 #include <atomic>
@@ -667,7 +668,8 @@ void mh_spmm_mapped(mh_context *ctx, const BsrLevel &lvl, const double *vals9, c
                     const double *res_dinv = nullptr); // mh_spmm.hip: results into mapped columns of wider panels; optional residual epilogue (w <= 128):
                                                        // res_out (n x w) = A x - theta M x, res_partial (n_nodes x 2 x w) = per-node sums of r^2 and (M x)^2 (weighted by res_dinv)
 bool mh_spmm_f32_cheb_step(mh_context *ctx, const BsrLevel &lvl, const float *d_in, float *d_out, float *r, float *x, const float *dinv, float c1, float c2,
-                           uint32_t w); // mh_spmm.hip: product + Chebyshev step in one launch
+                           uint32_t w, const float *r_in = nullptr, const float *x_in = nullptr); // mh_spmm.hip: product + Chebyshev step in one launch; r_in, x_in: r and x read from elsewhere than they are written; r, d_out null: not stored
+bool mh_cheb_step_fuses(uint32_t w, std::initializer_list<const float *> panels); // mh_spmm.hip: would mh_spmm_f32_cheb_step take these panels
 void mh_spmm_f32(mh_context *ctx, const BsrLevel &lvl, const float *x, float *y, uint32_t w); // mh_spmm.hip
 void mh_spmm_mixed(mh_context *ctx, const BsrLevel &lvl, const float *x, double *y, uint32_t w); // double A x of a float panel
 const uint32_t *mh_identity_map(mh_context *ctx); // 0, 1, 2, ... (1 024 entries) on the device

@@ -61,7 +61,8 @@ std::mutex g_solve_mutex;
 //   MH_CYCLE=d2,d1,g,ratio[,ratio1]  shape of the preconditioner cycle: Chebyshev degrees of the P2 and P1 smoothers, P1 cycles per
 //                           application, spectrum ratio lmax / lmin the smoothers target; 0 or missing keeps a built-in value
 //   MH_TEST=...             test hooks, comma separated (what each forces: beside its member): sytrd_giveup, no_tridiag_wide, last_resort,
-//                           coarse_pivot, selfcheck_fail, lmax_low, potrf_chain, no_poly_start, fresh_structure, copy_passes
+//                           coarse_pivot, selfcheck_fail, lmax_low, potrf_chain, no_poly_start, fresh_structure, copy_passes,
+//                           smoother_stores
 // Read elsewhere: MH_AGG, MH_PATCH_Q, MH_CLUSTERS, MH_CLUSTER_CAP, MH_POOL_CAP_MB; MH_TEST's poison, redzone and farzone (mh_common.h),
 // sytrd_multi, sytrd_fused and own_gemm (mh_dense.hip).
 struct Switches {
@@ -79,6 +80,7 @@ struct Switches {
     bool no_poly_start = getenv("MH_TEST") && strstr(getenv("MH_TEST"), "no_poly_start"); // (A/B hook of round 5: the cold start block as rounds 1-4 had it)
     bool fresh_structure = getenv("MH_TEST") && strstr(getenv("MH_TEST"), "fresh_structure"); // (A/B hook: every mh_assemble builds the mesh's structure anew -- mh_pipeline.hip reads it too -- and the start block's box comes from k_bbox, as before the structure was kept)
     bool copy_passes = getenv("MH_TEST") && strstr(getenv("MH_TEST"), "copy_passes"); // (A/B hook: the tall copy passes that moved a panel, or computed what the next launch overwrote, run again -- the scatter after the basis update, the gather before the preconditioner, the start block's copy, image transform and full random fill, the conversion of aval -- every returned number is the same bit for bit)
+    bool smoother_stores = getenv("MH_TEST") && strstr(getenv("MH_TEST"), "smoother_stores"); // (A/B hook: the single-precision smoothers store every panel again, read or not -- r and x of a zero start, r and d' of a sequence's last step -- and the restricted residual is converted to float by a launch of its own; every returned number is the same bit for bit)
     Switches() {
         if (const char *c = getenv("MH_CYCLE")) {
             double v[5] = {0, 0, 0, 0, 0};
@@ -212,15 +214,17 @@ __global__ void k_cheb_init(const T *__restrict__ b, const T *__restrict__ t, co
 }
 // Single-precision panels have pitches that are multiples of 4: the smoother's elementwise steps move 16 bytes per lane.
 typedef float f4_t __attribute__((ext_vector_type(4)));
+// r, x null (a zero start whose next step is the fused one: Precond::cheb): not stored -- r would be b and x would be d, bit for bit, and
+// that step reads b and d instead.
 __global__ void k_cheb_init_v4(const f4_t *__restrict__ b, const f4_t *__restrict__ t, const float *__restrict__ dinv, float inv_theta, f4_t *__restrict__ r,
                                f4_t *__restrict__ d, f4_t *__restrict__ x, int accumulate, size_t rows, uint32_t w4) {
     const size_t i = size_t(blockIdx.x) * blockDim.x + threadIdx.x;
     if (i >= rows * w4) return;
     const f4_t rv = t ? b[i] - t[i] : b[i];
     const f4_t dv = (dinv[i / w4] * inv_theta) * rv;
-    r[i] = rv;
+    if (r) r[i] = rv;
     d[i] = dv;
-    x[i] = accumulate ? x[i] + dv : dv;
+    if (x) x[i] = accumulate ? x[i] + dv : dv;
 }
 __global__ void k_cheb_last_v4(const f4_t *__restrict__ t, const float *__restrict__ dinv, float c1, float c2, const f4_t *__restrict__ r, const f4_t *__restrict__ d,
                                const f4_t *__restrict__ x, double *__restrict__ z, size_t rows, uint32_t w4, uint32_t wo) {
@@ -261,9 +265,9 @@ __global__ void k_cheb_init_convert(const double *__restrict__ src, PanelColumns
     const float rv = c < sc.count ? float(src[sc.at(row, c)]) : 0.f;
     const float dv = dinv[row] * rv * inv_theta;
     b32[i] = rv;
-    r[i] = rv;
+    if (r) r[i] = rv; // (r, x null: as in k_cheb_init_v4 -- the copies of b32 and d are not stored)
     d[i] = dv;
-    x[i] = dv;
+    if (x) x[i] = dv;
 }
 template<typename T>
 __global__ void k_cheb_step(const T *__restrict__ t, const T *__restrict__ dinv, T c1, T c2, T *__restrict__ r, T *__restrict__ d, T *__restrict__ x, size_t rows,
@@ -304,8 +308,10 @@ template<typename S, typename D> __global__ void k_convert_pitch(const S *__rest
 // r1 = P^T (b - t): corner value plus half of every incident edge's midside value.
 template<typename T>
 __global__ void k_restrict_p1(const T *__restrict__ b, const T *__restrict__ t, const uint32_t *__restrict__ p1_corner, const uint32_t *__restrict__ eptr,
-                              const uint32_t *__restrict__ emid, T *__restrict__ r1, uint32_t npts, uint32_t w, PanelColumns bc = PanelColumns{0, 0, nullptr}) {
+                              const uint32_t *__restrict__ emid, T *__restrict__ r1, uint32_t npts, uint32_t w, PanelColumns bc = PanelColumns{0, 0, nullptr},
+                              float *__restrict__ r1_f32 = nullptr) {
     // bc: where the columns of b live when it is not a panel of the pitch w of t and r1 (columns >= bc.count of b read as zero)
+    // r1_f32 (optional): takes float(r1), the right-hand side of the single-precision P1 smoother, so no conversion pass follows
     const size_t i = size_t(blockIdx.x) * blockDim.x + threadIdx.x;
     if (i >= size_t(npts) * 3 * w) return;
     const uint32_t c = uint32_t(i % w), comp = uint32_t((i / w) % 3), p = uint32_t(i / (size_t(3) * w));
@@ -317,7 +323,9 @@ __global__ void k_restrict_p1(const T *__restrict__ b, const T *__restrict__ t, 
     T s = res(p1_corner[p]);
     T h = 0;
     for (uint32_t e = eptr[p]; e < eptr[p + 1]; ++e) h += res(emid[e]);
-    r1[i] = s + T(0.5) * h;
+    const T v = s + T(0.5) * h;
+    r1[i] = v;
+    if (r1_f32) r1_f32[i] = float(v);
 }
 // x2 += P x1
 template<typename T>
@@ -1002,6 +1010,13 @@ template<typename T> struct Precond {
         else return lvl.dinv32.get();
     }
     const PatchSet &patches_of(const BsrLevel &lvl) const { return lvl.id == 2 ? sys->patches2 : sys->patches1; }
+    // Will step k (1 <= k < deg) of a sequence be the product with the step as its epilogue (mh_spmm_f32_cheb_step)?  Asked by the start
+    // pass, which leaves unstored what that launch reads elsewhere, and by the loop that launches it: one answer for both.
+    static bool step_fuses(int k, int deg, bool hands_on, uint32_t w, std::initializer_list<const T *> panels) {
+        constexpr bool fuse_steps = true; // the smoothing step as the epilogue of the product that forms A d (neutral in time, one panel pass less)
+        if constexpr (kDouble) return false;
+        else return fuse_steps && k >= 1 && k < deg && !(hands_on && k + 1 == deg) && mh_cheb_step_fuses(w, panels);
+    }
     // deg Chebyshev-Jacobi steps on lvl; when z_out is given the last step writes the iterate there (in double)
     void cheb(const BsrLevel &lvl, int deg, const T *b, T *x, bool zero_init, T *r, T *d, T *t, uint32_t w, double *z_out = nullptr, uint32_t w_out = 0,
               const double *b_src = nullptr, PanelColumns b_cols = PanelColumns{0, 0, nullptr}, T *b_copy = nullptr) { // b_src: (single-precision cycle) convert the right-hand side on the way
@@ -1010,28 +1025,39 @@ template<typename T> struct Precond {
         const double theta = 0.5 * (lmax + lmin), delta = 0.5 * (lmax - lmin), sig = theta / delta;
         double rho = 1.0 / sig;
         const T *dinv = dinv_of(lvl);
+        const PatchSet &ps = patches_of(lvl);
+        // Stores nothing reads (single-precision cycle, level without patches: k_patch_gather adds into d and x separately, and the
+        // patch solve reads the stored r).  A zero start leaves r = b and x = d bit for bit: when the fused step follows, the start pass
+        // stores neither and that step reads b and d in their place.  After the last step of a sequence that hands nothing on, the
+        // residual, restriction or prolongation that follows reads x alone and the next sequence starts r, d and t again: that step
+        // stores neither r nor d'.  MH_TEST=smoother_stores: every one of them stored, as it was.
+        const bool lean = !kDouble && !ps.any() && !switches().smoother_stores;
+        const bool start_lean = lean && zero_init && step_fuses(1, deg, z_out != nullptr, w, {b, x, r, d, t});
         if (!zero_init) spmm(lvl, x, t, w);
         if constexpr (!kDouble) {
-            if (b_src && zero_init) k_cheb_init_convert<<<grid1(rows * w), TB, 0, ctx->stream>>>(b_src, b_cols, dinv, float(1.0 / theta), b_copy, r, d, x, rows, w);
+            if (b_src && zero_init) k_cheb_init_convert<<<grid1(rows * w), TB, 0, ctx->stream>>>(b_src, b_cols, dinv, float(1.0 / theta), b_copy, start_lean ? nullptr : r, d, start_lean ? nullptr : x, rows, w);
             else k_cheb_init_v4<<<grid1(rows * (w / 4)), TB, 0, ctx->stream>>>(reinterpret_cast<const f4_t *>(b), zero_init ? nullptr : reinterpret_cast<const f4_t *>(t), dinv,
-                                                                               float(1.0 / theta), reinterpret_cast<f4_t *>(r), reinterpret_cast<f4_t *>(d),
-                                                                               reinterpret_cast<f4_t *>(x), zero_init ? 0 : 1, rows, w / 4);
+                                                                               float(1.0 / theta), reinterpret_cast<f4_t *>(start_lean ? nullptr : r), reinterpret_cast<f4_t *>(d),
+                                                                               reinterpret_cast<f4_t *>(start_lean ? nullptr : x), zero_init ? 0 : 1, rows, w / 4);
         } else {
             k_cheb_init<T><<<grid1(rows * w), TB, 0, ctx->stream>>>(b, zero_init ? nullptr : t, dinv, T(1.0 / theta), r, d, x, zero_init ? 0 : 1, rows, w);
         }
         KERNEL_CHECK();
         // the smoother's scaling is M^-1 = D^-1 + the sliver patches: the kernels above and below apply the D^-1 part, every step is
         // followed by the patch part of the same residual (r holds it; the last step's is r - t, formed on the fly)
-        const PatchSet &ps = patches_of(lvl);
         mh_apply_patches<T>(ctx, ps, r, nullptr, w, T(1.0 / theta), d, x, nullptr, 0, patch_y.get());
-        constexpr bool fuse_steps = true; // the smoothing step as the epilogue of the product that forms A d (neutral in time, one panel pass less)
         T *cur = d, *alt = t; // the direction lives in `cur`; `alt` takes the product, or (fused step) the next direction
         for (int k = 1; k < deg; ++k) {
             const double rho_new = 1.0 / (2 * sig - rho);
             const bool last = z_out && k + 1 == deg;
-            bool fused = false;
+            const bool fused = step_fuses(k, deg, z_out != nullptr, w, {b, x, r, d, t});
             if constexpr (!kDouble) {
-                if (fuse_steps && !last) fused = mh_spmm_f32_cheb_step(ctx, lvl, cur, alt, r, x, dinv, float(rho_new * rho), float(2 * rho_new / delta), w);
+                if (fused) {
+                    const bool first = start_lean && k == 1, closing = lean && k + 1 == deg; // (fused, so z_out is null or more steps follow: a closing step here hands nothing on)
+                    if (!mh_spmm_f32_cheb_step(ctx, lvl, cur, closing ? nullptr : alt, closing ? nullptr : r, x, dinv, float(rho_new * rho), float(2 * rho_new / delta), w,
+                                               first ? (b_src ? b_copy : b) : r, first ? cur : nullptr)) // (r read from r by name: a closing step has nowhere to write it)
+                        mh_throw(MH_EINVAL, "the fused smoothing step declined a panel of pitch %u that it had been asked about", w);
+                }
             }
             if (fused) {
                 std::swap(cur, alt);
@@ -1083,10 +1109,13 @@ template<typename T> struct Precond {
             KERNEL_CHECK();
         } else {
             mh_spmm_mixed(ctx, sys->L2, z, t2d, w);
-            k_restrict_p1<double><<<grid1(n1 * w), TB, 0, ctx->stream>>>(r_in, t2d.get(), sys->p1_corner, sys->p1_edge_ptr, sys->p1_edge_mid, r1d.get(), np, w, r_cols); // r_in at its own pitch, through its own map
+            k_restrict_p1<double><<<grid1(n1 * w), TB, 0, ctx->stream>>>(r_in, t2d.get(), sys->p1_corner, sys->p1_edge_ptr, sys->p1_edge_mid, r1d.get(), np, w, r_cols, // r_in at its own pitch, through its own map
+                                                                        switches().smoother_stores ? nullptr : r1.get()); // and its float copy beside it (MH_TEST=smoother_stores: by the conversion below, as it was)
             KERNEL_CHECK();
-            k_convert<double, T><<<grid1(n1 * w), TB, 0, ctx->stream>>>(r1d.get(), r1.get(), n1 * w);
-            KERNEL_CHECK();
+            if (switches().smoother_stores) {
+                k_convert<double, T><<<grid1(n1 * w), TB, 0, ctx->stream>>>(r1d.get(), r1.get(), n1 * w);
+                KERNEL_CHECK();
+            }
         }
         for (int g = 0; g < gamma; ++g) {
             cheb(sys->L1, deg1, r1, x1, g == 0, rr1, d1, t1, w);

@@ -121,12 +121,17 @@ __global__ void __launch_bounds__(TB) k_spmm(const uint32_t *__restrict__ row_pt
 // A X, M X of the new Ritz vectors written straight into the active columns of the block.
 // EPI = 1: instead of storing t = A d, the Chebyshev step that consumes it runs on the rows while they are in registers:
 // r -= t, d' = c1 d + c2 D^-1 r, x += d'.  d' goes to a second buffer (other rows are still gathering d).  One launch and one
-// pass over t less per smoothing step.
+// pass over t less per smoothing step.  What the step reads and what it stores are named apart: after a zero start r is the right-hand
+// side and x is d, bit for bit, so the first step reads those (r_in, x_in) and the start pass stores neither; after the last step of a
+// sequence that hands nothing on only x is read again, so r and d_out are null there and nothing is stored for them.  All of these are
+// kernel-argument tests, the same in every wave of the launch.
 struct ChebStep {
-    float *r = nullptr;
+    float *r = nullptr;          // r' goes here; null: not stored
+    const float *r_in = nullptr; // r comes from here; null: from r
     const float *dinv = nullptr;
-    float *d_out = nullptr;
-    float *x = nullptr;
+    float *d_out = nullptr;      // d' goes here; null: not stored
+    float *x = nullptr;          // x' goes here, always
+    const float *x_in = nullptr; // x comes from here; null: from x.  The gathered panel itself (x = d): the row loaded for d serves both
     float c1 = 0.f, c2 = 0.f;
 };
 // MAPOUT with a residual epilogue: the rows of A x and M x are in registers when they are stored, and theta is known, so the
@@ -179,11 +184,12 @@ __global__ void __launch_bounds__(TB) MH_SPMM_OCC k_spmm_wide(const uint32_t *__
     if constexpr (EPI == 1 && PRE) {
         if (g == 0 && act) {
             const size_t o = size_t(3) * row * w + coff;
+            const float *rsrc = epi.r_in ? epi.r_in : epi.r, *xsrc = epi.x_in ? epi.x_in : epi.x;
 #pragma unroll
             for (int i = 0; i < 3; ++i) {
-                er[i] = *reinterpret_cast<const Acc *>(epi.r + o + size_t(i) * w);
+                er[i] = *reinterpret_cast<const Acc *>(rsrc + o + size_t(i) * w);
                 ed[i] = __builtin_convertvector(*reinterpret_cast<const Vec *>(x + o + size_t(i) * w), Acc);
-                ex[i] = *reinterpret_cast<const Acc *>(epi.x + o + size_t(i) * w);
+                ex[i] = static_cast<const void *>(xsrc) == static_cast<const void *>(x) ? ed[i] : *reinterpret_cast<const Acc *>(xsrc + o + size_t(i) * w);
                 edinv[i] = epi.dinv[size_t(3) * row + i];
             }
         }
@@ -288,6 +294,8 @@ __global__ void __launch_bounds__(TB) MH_SPMM_OCC k_spmm_wide(const uint32_t *__
     if constexpr (EPI == 1) {
         if (g == 0 && act) {
             const size_t o = size_t(3) * row * w + coff;
+            const float *rsrc = epi.r_in ? epi.r_in : epi.r, *xsrc = epi.x_in ? epi.x_in : epi.x;
+            const bool x_is_d = static_cast<const void *>(xsrc) == static_cast<const void *>(x);
 #pragma unroll
             for (int i = 0; i < 3; ++i) {
                 const size_t oi = o + size_t(i) * w;
@@ -299,12 +307,13 @@ __global__ void __launch_bounds__(TB) MH_SPMM_OCC k_spmm_wide(const uint32_t *__
                 } else {
                     // loaded here rather than up front: nine more vector registers per lane would cost two waves of occupancy,
                     // and occupancy is what hides the gathers of the big level
-                    rv = *reinterpret_cast<const Acc *>(epi.r + oi) - acc[i];
-                    dv = epi.c1 * __builtin_convertvector(*reinterpret_cast<const Vec *>(x + oi), Acc) + (epi.c2 * epi.dinv[size_t(3) * row + i]) * rv;
-                    xn = *reinterpret_cast<const Acc *>(epi.x + oi) + dv;
+                    rv = *reinterpret_cast<const Acc *>(rsrc + oi) - acc[i];
+                    const Acc dold = __builtin_convertvector(*reinterpret_cast<const Vec *>(x + oi), Acc);
+                    dv = epi.c1 * dold + (epi.c2 * epi.dinv[size_t(3) * row + i]) * rv;
+                    xn = (x_is_d ? dold : *reinterpret_cast<const Acc *>(xsrc + oi)) + dv;
                 }
-                *reinterpret_cast<Acc *>(epi.r + oi) = rv;
-                *reinterpret_cast<Acc *>(epi.d_out + oi) = dv;
+                if (epi.r) *reinterpret_cast<Acc *>(epi.r + oi) = rv;
+                if (epi.d_out) *reinterpret_cast<Acc *>(epi.d_out + oi) = dv;
                 *reinterpret_cast<Acc *>(epi.x + oi) = xn;
             }
         }
@@ -497,18 +506,29 @@ void mh_spmm_mapped(mh_context *ctx, const BsrLevel &lvl, const double *vals9, c
     }
 }
 
+// Does the wide-load kernel take panels of this pitch at these addresses (null ones do not count)?  The smoother asks before its start
+// pass decides what to leave unstored, and mh_spmm_f32_cheb_step asks again.
+bool mh_cheb_step_fuses(uint32_t w, std::initializer_list<const float *> panels) {
+    uintptr_t bits = 0;
+    for (const float *p : panels) bits |= reinterpret_cast<uintptr_t>(p);
+    return w % 4 == 0 && w <= 256 && !(bits & 15);
+}
 // One Chebyshev-Jacobi step of the single-precision smoother with the product fused in (see ChebStep): t = A d never reaches
 // memory.  false when the panel does not qualify for the wide-load kernel (the caller then runs product and step apart).
-bool mh_spmm_f32_cheb_step(mh_context *ctx, const BsrLevel &lvl, const float *d_in, float *d_out, float *r, float *x, const float *dinv, float c1, float c2, uint32_t w) {
+// r_in, x_in: where the step reads r and x when that is not where it writes them (null: there); r, d_out null: r', d' are not stored.
+bool mh_spmm_f32_cheb_step(mh_context *ctx, const BsrLevel &lvl, const float *d_in, float *d_out, float *r, float *x, const float *dinv, float c1, float c2, uint32_t w,
+                           const float *r_in, const float *x_in) {
     if (w == 0) return true;
-    const bool aligned16 = !((reinterpret_cast<uintptr_t>(d_in) | reinterpret_cast<uintptr_t>(d_out) | reinterpret_cast<uintptr_t>(r) | reinterpret_cast<uintptr_t>(x)) & 15);
-    if (w % 4 || w > 256 || !aligned16) return false;
-    // algorithmic bytes: the product's (d read, no t written) plus the step's own passes: r and x read and written, d' written
-    TimedLaunch timed(ctx, MH_KERNEL_SPMM, spmm_bytes(lvl, w, 4, 4, 0, true, false) + 5.0 * 4.0 * 3.0 * double(lvl.n_nodes) * w);
+    if (!mh_cheb_step_fuses(w, {d_in, d_out, r, x, r_in, x_in})) return false;
+    if (!x || !(r || r_in)) mh_throw(MH_EINVAL, "Chebyshev step without an iterate or a residual to read");
+    // algorithmic bytes: the product's (d read, no t written) plus the step's own passes: r read, x read (unless it is d, which the product
+    // has counted) and written, and r' and d' written where they are stored
+    const double passes = 1.0 + (x_in && x_in == d_in ? 0.0 : 1.0) + 1.0 + (r ? 1.0 : 0.0) + (d_out ? 1.0 : 0.0);
+    TimedLaunch timed(ctx, MH_KERNEL_SPMM, spmm_bytes(lvl, w, 4, 4, 0, true, false) + passes * 4.0 * 3.0 * double(lvl.n_nodes) * w);
     constexpr int xcd = 1;
     const unsigned grid = (div_up(lvl.n_nodes, TB / 64) + 7) / 8 * 8;
     ChebStep epi;
-    epi.r = r; epi.dinv = dinv; epi.d_out = d_out; epi.x = x; epi.c1 = c1; epi.c2 = c2;
+    epi.r = r; epi.r_in = r_in; epi.dinv = dinv; epi.d_out = d_out; epi.x = x; epi.x_in = x_in; epi.c1 = c1; epi.c2 = c2;
     auto go = [&](auto cl_tag) {
         constexpr int CL = decltype(cl_tag)::value;
         if (latency_bound_level(lvl))
