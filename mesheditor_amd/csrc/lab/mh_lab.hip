@@ -7,6 +7,7 @@
 #include "modalhip_lab.h"
 
 #include <algorithm>
+#include <optional>
 
 void mh_elementwise_apply(mh_context *ctx, const mh_system *sys, double sigma, const double *x, double *y, uint32_t w); // lab/mh_elem.hip
 
@@ -736,37 +737,41 @@ int mhl_context_bench_stream(mh_context *ctx, uint64_t bytes, uint32_t reps, dou
 
 }
 
-// ---- the sparse block product's forms on a caller's matrix (tests/test_spmm_forms_gpu.py) ------------------------------------
+// ---- the sparse block product's forms on a caller's matrix (tests/test_spmm_forms_gpu.py), and the helpers it shares with the dense
+// products' forms at the end of this file ------------------------------------------------------------------------------------------
 namespace {
 // quiet NaNs with a payload: arithmetic on finite inputs produces the canonical NaN at most, never these
 template<typename T> T lab_sentinel();
 template<> double lab_sentinel<double>() {
-    const uint64_t bits = MHL_SPMM_SENTINEL64;
+    const uint64_t bits = MHL_SENTINEL64;
     double v;
     memcpy(&v, &bits, sizeof v);
     return v;
 }
 template<> float lab_sentinel<float>() {
-    const uint32_t bits = MHL_SPMM_SENTINEL32;
+    const uint32_t bits = MHL_SENTINEL32;
     float v;
     memcpy(&v, &bits, sizeof v);
     return v;
 }
 
-// A device buffer of n entries between two guards of MHL_SPMM_GUARD entries, everything pre-filled with the sentinel (the body with
-// `init` when given); fetch() copies guards and body back.  The guard is a multiple of 16 bytes: the body keeps the pool's alignment.
+// A device buffer of n entries between two guards of MHL_GUARD entries, everything pre-filled with the sentinel (the body with
+// `init` when given); fetch() copies guards and body back (nowhere when the caller has no array for it).  The guard is a multiple of
+// 16 bytes: the body keeps the pool's alignment.
 template<typename T> struct LabGuarded {
     DevArray<T> dev;
     size_t n;
     LabGuarded(mh_context *ctx, size_t n_, const T *init = nullptr) : n(n_) {
-        std::vector<T> h(n + 2 * MHL_SPMM_GUARD, lab_sentinel<T>());
-        if (init) std::copy(init, init + n, h.begin() + MHL_SPMM_GUARD);
+        std::vector<T> h(n + 2 * MHL_GUARD, lab_sentinel<T>());
+        if (init) std::copy(init, init + n, h.begin() + MHL_GUARD);
         dev.reset(ctx, h.size());
         dev.upload(h.data(), h.size());
         HIP_CHECK(hipStreamSynchronize(ctx->stream)); // h goes out of scope
     }
-    T *body() const { return dev.get() + MHL_SPMM_GUARD; }
-    void fetch(void *host) const { dev.download(static_cast<T *>(host), n + 2 * MHL_SPMM_GUARD); }
+    T *body() const { return dev.get() + MHL_GUARD; }
+    void fetch(void *host) const {
+        if (host) dev.download(static_cast<T *>(host), n + 2 * MHL_GUARD);
+    }
 };
 
 template<typename T> void lab_upload(mh_context *ctx, DevArray<T> &d, const void *src, size_t n, size_t lead = 0) {
@@ -870,6 +875,133 @@ int mhl_context_spmm_form(mh_context *ctx, mhl_spmm_request *q) {
         mh_spmm(ctx, lvl, with_a ? lvl.aval.get() : nullptr, x64.get() + lead, with_a ? y.body() : nullptr, with_m ? lvl.mval.get() : nullptr, with_m ? y2.body() : nullptr, w);
         if (with_a) y.fetch(q->y);
         if (with_m) y2.fetch(q->y2);
+        return MH_OK;
+    } catch (const std::exception &e) { return mh_guard(ctx, e); }
+}
+}
+
+// ---- the dense tall products' forms on a caller's arrays (tests/test_combine_forms_gpu.py) -----------------------------------------
+namespace {
+bool lab_map_inside(const uint32_t *map, uint32_t count, uint32_t limit) {
+    for (uint32_t c = 0; c < count; ++c)
+        if (map[c] >= limit) return false;
+    return true;
+}
+// The request's coefficient matrix on the device, k-major m x nc: uploaded as it is, or packed there by the solver's packer into a
+// guarded buffer that returns to the caller as ct_out.
+struct LabCoefficients {
+    DevArray<double> plain, c1, c2;
+    std::optional<LabGuarded<double>> packed;
+    const double *ct{nullptr};
+    static bool valid(const mhl_dense_request *q, uint32_t m, uint32_t nc) {
+        if (q->coeff_layout == MHL_COEFF_KMAJOR) return q->ct != nullptr;
+        if ((q->pack_a && !q->c1) || (q->pack_b && !q->c2)) return false;
+        if (q->coeff_layout == MHL_COEFF_BLOCKS) return q->pack_a + q->pack_b == nc && q->pack_ld >= m;
+        return q->coeff_layout == MHL_COEFF_STACKED && q->pack_a + q->pack_b == m;
+    }
+    LabCoefficients(mh_context *ctx, const mhl_dense_request *q, uint32_t m, uint32_t nc) {
+        if (q->coeff_layout == MHL_COEFF_KMAJOR) {
+            lab_upload(ctx, plain, q->ct, size_t(m) * nc);
+            ct = plain.get();
+            return;
+        }
+        packed.emplace(ctx, size_t(m) * nc);
+        const bool blocks = q->coeff_layout == MHL_COEFF_BLOCKS;
+        lab_upload(ctx, c1, q->c1, blocks ? size_t(q->pack_ld) * q->pack_a : size_t(q->pack_a) * nc);
+        lab_upload(ctx, c2, q->c2, blocks ? size_t(q->pack_ld) * q->pack_b : size_t(q->pack_b) * nc);
+        if (blocks) mh_pack_coefficients(ctx, c1, q->pack_a, c2, q->pack_b, m, q->pack_ld, packed->body());
+        else mh_pack_stacked(ctx, c1, q->pack_a, c2, q->pack_b, nc, q->pack_scale, packed->body());
+        ct = packed->body();
+    }
+    void fetch(double *host) const {
+        if (packed) packed->fetch(host);
+    }
+};
+} // namespace
+
+extern "C" {
+// One form of the dense tall products (modalhip_lab.h: MHL_DENSE_*) through the solver's own dispatchers: no kernel and no launch shape is
+// chosen here.  The request is checked on the host for what the dispatchers take on trust -- pointers, maps and pitches that stay inside
+// the arrays -- and for nothing that they check themselves (column ranges, the combinations a second destination allows, the width limits).
+int mhl_context_dense_form(mh_context *ctx, mhl_dense_request *q) {
+    if (!ctx || !q) return MH_EINVAL;
+    q->dispatched = 0;
+    q->cu_count = ctx->cu_count;
+    const int form = q->form;
+    if (form < MHL_DENSE_COMBINE || form > MHL_DENSE_PACK) return MH_EINVAL;
+    const size_t n = q->n;
+    const uint32_t wx = q->wx, ww = q->ww, wp = q->wp, nc = q->nc, n1 = q->n1, ldx = q->ldx ? q->ldx : wx;
+    const uint32_t m = form == MHL_DENSE_GRAM ? 0 : wx + ww + wp;
+    if (form != MHL_DENSE_GRAM && (!m || !nc || nc > 4096 || m > 4096 || !LabCoefficients::valid(q, m, nc))) return MH_EINVAL;
+    if (form != MHL_DENSE_PACK && (!n || (wx && !q->x) || (ww && !q->w) || (wp && !q->p))) return MH_EINVAL;
+    if (q->xmap ? !lab_map_inside(q->xmap, wx, ldx) : ldx < wx) return MH_EINVAL;
+    const uint32_t ld1 = q->ld1 ? q->ld1 : n1, ldy = q->ldy ? q->ldy : ww;
+    if (form == MHL_DENSE_COMBINE) {
+        if (n1 > nc || (nc > n1 && !q->out2) || q->in_place < 0 || q->in_place > 2 || (q->in_place && !q->x)) return MH_EINVAL;
+        if (q->in_place == 1 ? (q->out1 || ld1 != ldx) : !q->out1) return MH_EINVAL;
+        if (q->omap ? !lab_map_inside(q->omap, n1, ld1) : ld1 < n1) return MH_EINVAL;
+        if (q->in_place == 2 ? (q->out1_also || (q->ld1_also && q->ld1_also != ldx)) : (q->out1_also && !q->ld1_also)) return MH_EINVAL;
+        if (q->omap_also && !lab_map_inside(q->omap_also, n1, q->in_place == 2 ? ldx : q->ld1_also)) return MH_EINVAL;
+    } else if (form == MHL_DENSE_SHORT_PRODUCT) {
+        if (ww || wp || ldx != wx || q->xmap || !q->out1 || !q->slices || q->slices > 64 || (q->slices > 1 && !q->partial)) return MH_EINVAL;
+    } else if (form == MHL_DENSE_GRAM) {
+        if (!wx || !ww || ldx != wx || q->xmap || !q->g || q->ld < q->g_row0 + wx || q->g_cols < q->g_col0 + ww) return MH_EINVAL;
+        if (q->ymap ? !lab_map_inside(q->ymap, ww, ldy) : ldy < ww) return MH_EINVAL;
+    }
+    try {
+        HIP_CHECK(hipSetDevice(ctx->device));
+        MhSharedPhase not_during_a_factorisation(ctx->device);
+        if (form == MHL_DENSE_PACK) {
+            q->dispatched = 1;
+            const LabCoefficients coeff(ctx, q, m, nc);
+            coeff.fetch(q->ct_out);
+            return MH_OK;
+        }
+        LabGuarded<double> x(ctx, n * ldx, q->x);
+        DevArray<double> w, p;
+        if (q->w) lab_upload(ctx, w, q->w, n * (form == MHL_DENSE_GRAM ? ldy : ww));
+        if (q->p) lab_upload(ctx, p, q->p, n * wp);
+        if (form == MHL_DENSE_GRAM) {
+            DevArray<uint32_t> ymap;
+            if (q->ymap) lab_upload(ctx, ymap, q->ymap, ww);
+            LabGuarded<double> g(ctx, size_t(q->ld) * q->g_cols);
+            q->dispatched = 1;
+            mh_gram(ctx, n, x.body(), wx, w, ww, g.body() + size_t(q->g_col0) * q->ld + q->g_row0, q->ld, q->ldy, q->ymap ? ymap.get() : nullptr);
+            g.fetch(q->g);
+            x.fetch(q->x_out);
+            return MH_OK;
+        }
+        const LabCoefficients coeff(ctx, q, m, nc);
+        const double *xd = q->x ? x.body() : nullptr;
+        if (form == MHL_DENSE_SHORT_PRODUCT) {
+            LabGuarded<double> out(ctx, n * nc), partial(ctx, q->slices > 1 ? size_t(q->slices) * n * nc : 0);
+            q->dispatched = 1;
+            mh_short_product(ctx, n, xd, wx, coeff.ct, nc, out.body(), q->slices > 1 ? partial.body() : nullptr, q->slices);
+            out.fetch(q->out1);
+            if (q->slices > 1) partial.fetch(q->partial);
+            x.fetch(q->x_out);
+            coeff.fetch(q->ct_out);
+            return MH_OK;
+        }
+        DevArray<uint32_t> xmap, omap, omap_also;
+        if (q->xmap) lab_upload(ctx, xmap, q->xmap, wx);
+        if (q->omap) lab_upload(ctx, omap, q->omap, n1);
+        if (q->omap_also) lab_upload(ctx, omap_also, q->omap_also, n1);
+        const bool old = q->accumulate != 0; // out += : the outputs start as the caller's values
+        LabGuarded<double> out1(ctx, q->in_place == 1 ? 0 : n * ld1, old && q->out1 ? q->out1 + MHL_GUARD : nullptr);
+        LabGuarded<double> out2(ctx, q->out2 ? n * (nc - n1) : 0, old && q->out2 ? q->out2 + MHL_GUARD : nullptr);
+        LabGuarded<double> also(ctx, q->out1_also ? n * q->ld1_also : 0);
+        double *d1 = q->in_place == 1 ? x.body() : out1.body(), *d2 = q->out2 ? out2.body() : nullptr;
+        double *d_also = q->in_place == 2 ? x.body() : q->out1_also ? also.body() : nullptr;
+        q->dispatched = 1;
+        mh_combine(ctx, n, xd, wx, q->w ? w.get() : nullptr, ww, q->p ? p.get() : nullptr, wp, coeff.ct, nc, d1, n1, d2, old, q->ldx, q->xmap ? xmap.get() : nullptr, q->ld1,
+                   q->omap ? omap.get() : nullptr, q->col_begin, q->col_count, d_also, q->ld1_also, q->omap_also ? omap_also.get() : nullptr);
+        HIP_CHECK(hipStreamSynchronize(ctx->stream)); // (before anything is fetched: a launch error surfaces here, with the host arrays as passed)
+        out1.fetch(q->out1);
+        out2.fetch(q->out2);
+        also.fetch(q->out1_also);
+        x.fetch(q->x_out);
+        coeff.fetch(q->ct_out);
         return MH_OK;
     } catch (const std::exception &e) { return mh_guard(ctx, e); }
 }

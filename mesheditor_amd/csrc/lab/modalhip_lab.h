@@ -53,9 +53,13 @@ enum {
     MHL_SPMM_MAPPED_RES = 6, /* the same with the residual epilogue: r_out (3 n_nodes x w), partial (n_nodes x 2 x w) */
     MHL_SPMM_F32_CHEB = 7    /* the fused Chebyshev step: x is d (float); cheb_r, cheb_x start as r, xs; cheb_d_in is d after the launch */
 };
-#define MHL_SPMM_GUARD 64u
-#define MHL_SPMM_SENTINEL64 0x7ff8a5a5a5a5a5a5ull
-#define MHL_SPMM_SENTINEL32 0x7fd5a5a5u
+/* the guard and sentinel conventions of every "form" entry of this header (the sparse product's below, the dense products' further down) */
+#define MHL_GUARD 64u
+#define MHL_SENTINEL64 0x7ff8a5a5a5a5a5a5ull
+#define MHL_SENTINEL32 0x7fd5a5a5u
+#define MHL_SPMM_GUARD MHL_GUARD
+#define MHL_SPMM_SENTINEL64 MHL_SENTINEL64
+#define MHL_SPMM_SENTINEL32 MHL_SENTINEL32
 typedef struct mhl_spmm_request {
     int32_t form;
     uint32_t misalign; /* plain fp64 forms: the x panel starts 8 bytes into its allocation (no 16-byte loads: k_spmm serves even widths too) */
@@ -74,6 +78,44 @@ typedef struct mhl_spmm_request {
     int32_t taken; /* out: 0 when mh_spmm_f32_cheb_step declined the panel */
 } mhl_spmm_request;
 int mhl_context_spmm_form(mh_context *, mhl_spmm_request *);
+/* One form of the dense tall products (mh_dense.hip) on the caller's arrays, through the solver's own dispatchers: mh_combine, mh_short_product,
+ * mh_gram, and the two coefficient packers.  Panels are row-major.  Every output, and X (an output when the call runs in place, bit-unchanged
+ * otherwise), is a host array of MHL_GUARD + entries + MHL_GUARD values: the device buffer is pre-filled with the sentinel -- its body with the
+ * caller's values where the form reads them: X always, out1 / out2 under `accumulate` -- and copied back whole.  A request this entry itself
+ * rejects leaves `dispatched` 0; one the dispatcher refuses on the host (MH_EINVAL) leaves it 1, and the host arrays as the caller passed them. */
+enum {
+    MHL_DENSE_COMBINE = 0,       /* mh_combine with exactly the request's arguments */
+    MHL_DENSE_SHORT_PRODUCT = 1, /* mh_short_product: out1 (n x nc) = x (n x wx) ct, in `slices` K slices through `partial` (slices x n x nc) */
+    MHL_DENSE_GRAM = 2,          /* mh_gram: the wx x ww block at (g_row0, g_col0) of g (ld x g_cols, column-major) = x^T y, y = w (n x ldy, columns through ymap) */
+    MHL_DENSE_PACK = 3           /* the packer of `coeff_layout` alone: ct_out */
+};
+enum {
+    MHL_COEFF_KMAJOR = 0,   /* ct: (wx + ww + wp) x nc, row-major, as the kernel reads it */
+    MHL_COEFF_BLOCKS = 1,   /* mh_pack_coefficients: c1 (m x pack_a), c2 (m x pack_b), column-major at pack_ld, side by side; m = wx + ww + wp, nc = pack_a + pack_b */
+    MHL_COEFF_STACKED = 2   /* mh_pack_stacked: c1 (pack_a x nc), c2 (pack_b x nc), column-major, one above the other, times pack_scale; pack_a + pack_b = wx + ww + wp */
+};
+typedef struct mhl_dense_request {
+    int32_t form;
+    int32_t in_place; /* 0: separate outputs; 1: out1 is the device copy of X (the Cholesky-QR call); 2: out1_also is the device copy of X (the basis update's call) */
+    int32_t accumulate, coeff_layout;
+    uint64_t n;
+    uint32_t wx, ldx, ww, wp; /* ldx 0: wx */
+    uint32_t nc, n1, ld1, ld1_also;
+    uint32_t col_begin, col_count, slices;
+    uint32_t pack_a, pack_b, pack_ld;
+    uint32_t ldy, ld, g_cols, g_row0, g_col0; /* Gram; ldy 0: ww */
+    uint32_t pad_;
+    double pack_scale;
+    const uint32_t *xmap, *omap, *omap_also, *ymap;
+    const double *x, *w, *p; /* host panels: n x (ldx or wx), n x ww (Gram: n x ldy), n x wp; a null panel goes to the dispatcher as null */
+    const double *ct, *c1, *c2;
+    double *x_out;                    /* guarded n x (ldx or wx) */
+    double *out1, *out2, *out1_also;  /* guarded n x (ld1 or n1), n x (nc - n1), n x ld1_also; out1 null with in_place 1, out1_also null with in_place 2 */
+    double *partial, *ct_out, *g;     /* guarded slices x n x nc (slices > 1), m x nc (packed layouts), ld x g_cols */
+    int32_t cu_count;                 /* out: the context's compute units (k_combine's grid is capped at 8 workgroups each) */
+    int32_t dispatched;               /* out */
+} mhl_dense_request;
+int mhl_context_dense_form(mh_context *, mhl_dense_request *);
 /* measured HBM ceilings of the device: a streaming copy (read + written bytes per second) and a streaming read, in GB/s */
 int mhl_context_bench_stream(mh_context *, uint64_t bytes, uint32_t reps, double *copy_gbs, double *read_gbs);
 /* the context's device pool: bytes held from the device, bytes of them idle in the cache, the cap on the idle part */

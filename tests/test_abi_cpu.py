@@ -66,9 +66,10 @@ def _exported_functions(path, prefix):
 
 # The lab library's entry points by name: a header edit that drops, renames or adds one shows here.  (23: the preconditioner's four --
 # mhl_system_precondition and the three calls of the hierarchy export, tests/test_preconditioner_gpu.py -- joined the 19 before them;
-# 24: mhl_context_spmm_form, the sparse block product's forms on a caller's matrix, tests/test_spmm_forms_gpu.py.)
+# 24: mhl_context_spmm_form, the sparse block product's forms on a caller's matrix, tests/test_spmm_forms_gpu.py;
+# 25: mhl_context_dense_form, the dense tall products' forms on a caller's arrays, tests/test_combine_forms_gpu.py.)
 LAB_ENTRY_POINTS = (
-    "mhl_context_bench_dense", "mhl_context_bench_stream", "mhl_context_gram", "mhl_context_pool_stats", "mhl_context_potrf_inverse",
+    "mhl_context_bench_dense", "mhl_context_bench_stream", "mhl_context_dense_form", "mhl_context_gram", "mhl_context_pool_stats", "mhl_context_potrf_inverse",
     "mhl_context_rr_solve", "mhl_context_small_gemm", "mhl_context_spd_inverse", "mhl_context_spmm_form", "mhl_context_tridiag_lowest", "mhl_context_tridiagonalize",
     "mhl_context_tridiagonalize_full", "mhl_graph_aggregates", "mhl_soak_aggressor", "mhl_system_bench_cheb_step", "mhl_system_bench_elementwise",
     "mhl_system_bench_spmm", "mhl_system_elementwise_matvec", "mhl_system_hierarchy_export", "mhl_system_hierarchy_sizes", "mhl_system_patch_export",
@@ -84,7 +85,7 @@ def test_lab_library_exports_exactly_its_named_entry_points(core):
     L = lab.lib()
     header = open(os.path.join(ROOT, "mesheditor_amd", "csrc", "lab", "modalhip_lab.h")).read()
     declared = sorted(set(re.findall(r"\b(mhl_[a-z0-9_]+)\s*\(", header)))
-    assert declared == sorted(LAB_ENTRY_POINTS) and len(declared) == 24 and all(hasattr(L, n) for n in declared)
+    assert declared == sorted(LAB_ENTRY_POINTS) and len(declared) == 25 and all(hasattr(L, n) for n in declared)
     assert _exported_functions(lab.SO_PATH, "mhl_") == set(declared)
     P = core.lib()
     assert not [n for n in declared if hasattr(P, n)] and not hasattr(P, "mh_system_bench_spmm")

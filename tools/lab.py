@@ -40,6 +40,7 @@ def lib():
         L.mhl_system_hierarchy_export.restype, L.mhl_system_hierarchy_export.argtypes = i32, [vp, u32, vp, vp, vp, vp, vp, vp, vp]
         L.mhl_system_patch_export.restype, L.mhl_system_patch_export.argtypes = i32, [vp, i32, vp, vp, vp, vp, vp, vp]
         L.mhl_context_spmm_form.restype, L.mhl_context_spmm_form.argtypes = i32, [vp, C.POINTER(SpmmRequest)]
+        L.mhl_context_dense_form.restype, L.mhl_context_dense_form.argtypes = i32, [vp, C.POINTER(DenseRequest)]
         _LIB = L
     return _LIB
 
@@ -139,9 +140,32 @@ def gram(ctx, x, y):
     return g.T.copy()
 
 
+# The guard and sentinel conventions of the "form" entries (modalhip_lab.h: MHL_GUARD, MHL_SENTINEL*): every output is a host array of
+# GUARD + entries + GUARD values that comes back whole from a device buffer pre-filled with the sentinel.
+GUARD = 64
+SENTINEL = {np.dtype(np.float64): np.uint64(0x7FF8A5A5A5A5A5A5), np.dtype(np.float32): np.uint32(0x7FD5A5A5)}
+
+
+def untouched(a):
+    """Boolean array: which entries of an output of a form entry still hold the sentinel, bit for bit."""
+    return a.view(np.uint64 if a.dtype == np.float64 else np.uint32) == SENTINEL[a.dtype]
+
+
+def _guarded(entries, dtype=np.float64, body=None):
+    """A host output buffer: sentinels, the body `body` when given."""
+    buf = np.empty(entries + 2 * GUARD, dtype)
+    buf.view(np.uint64 if dtype == np.float64 else np.uint32)[:] = SENTINEL[np.dtype(dtype)]
+    if body is not None:
+        buf[GUARD:GUARD + entries] = np.asarray(body, dtype=dtype).reshape(-1)
+    return buf
+
+
+def _body_and_guards(buf, shape):
+    return buf[GUARD:len(buf) - GUARD].reshape(shape), np.concatenate([buf[:GUARD], buf[len(buf) - GUARD:]])
+
+
 SPMM_FORMS = ("f64_a", "f64_m", "f64_am", "f32_a", "mixed", "mapped", "mapped_res", "f32_cheb")  # modalhip_lab.h: MHL_SPMM_*
-SPMM_GUARD = 64
-SPMM_SENTINEL = {np.dtype(np.float64): np.uint64(0x7FF8A5A5A5A5A5A5), np.dtype(np.float32): np.uint32(0x7FD5A5A5)}
+SPMM_GUARD, SPMM_SENTINEL, spmm_untouched = GUARD, SENTINEL, untouched
 
 
 class SpmmRequest(C.Structure):
@@ -150,11 +174,6 @@ class SpmmRequest(C.Structure):
                 ("mscal", C.c_void_p), ("x", C.c_void_p), ("theta", C.c_void_p), ("dinv", C.c_void_p), ("dinv32", C.c_void_p), ("r", C.c_void_p),
                 ("xs", C.c_void_p), ("y", C.c_void_p), ("y2", C.c_void_p), ("r_out", C.c_void_p), ("partial", C.c_void_p), ("cheb_r", C.c_void_p),
                 ("cheb_d_out", C.c_void_p), ("cheb_x", C.c_void_p), ("cheb_d_in", C.c_void_p), ("taken", C.c_int32)]
-
-
-def spmm_untouched(a):
-    """Boolean array: which entries of an output of spmm_form still hold the sentinel, bit for bit."""
-    return a.view(np.uint64 if a.dtype == np.float64 else np.uint32) == SPMM_SENTINEL[a.dtype]
 
 
 def spmm_form(ctx, form, row_ptr, col, x, vals9=None, mscal=None, misalign=False, ldy=0, wreal=0, omap=None, theta=None, dinv=None, c1=0.0, c2=0.0,
@@ -183,8 +202,7 @@ def spmm_form(ctx, form, row_ptr, col, x, vals9=None, mscal=None, misalign=False
     outs = {}
 
     def out(name, rows, pitch, dtype):
-        buf = np.empty(rows * pitch + 2 * SPMM_GUARD, dtype)
-        buf.view(np.uint64 if dtype == np.float64 else np.uint32)[:] = SPMM_SENTINEL[np.dtype(dtype)]
+        buf = _guarded(rows * pitch, dtype)
         outs[name] = (buf, rows, pitch)
         return _p(buf)
 
@@ -205,8 +223,111 @@ def spmm_form(ctx, form, row_ptr, col, x, vals9=None, mscal=None, misalign=False
         if form == "mapped_res":
             q.r_out, q.partial = out("r_out", n3, w, np.float64), out("partial", 2 * nn, w, np.float64)
     rc = lib().mhl_context_spmm_form(ctx.h, C.byref(q))
-    res = {k: (b[SPMM_GUARD:-SPMM_GUARD].reshape(rows, pitch), np.concatenate([b[:SPMM_GUARD], b[-SPMM_GUARD:]])) for k, (b, rows, pitch) in outs.items()}
-    return rc, bool(q.taken), res
+    return rc, bool(q.taken), {k: _body_and_guards(b, (rows, pitch)) for k, (b, rows, pitch) in outs.items()}
+
+
+DENSE_FORMS = ("combine", "short_product", "gram", "pack")  # modalhip_lab.h: MHL_DENSE_*
+
+
+class DenseRequest(C.Structure):
+    _fields_ = [("form", C.c_int32), ("in_place", C.c_int32), ("accumulate", C.c_int32), ("coeff_layout", C.c_int32), ("n", C.c_uint64),
+                ("wx", C.c_uint32), ("ldx", C.c_uint32), ("ww", C.c_uint32), ("wp", C.c_uint32), ("nc", C.c_uint32), ("n1", C.c_uint32), ("ld1", C.c_uint32),
+                ("ld1_also", C.c_uint32), ("col_begin", C.c_uint32), ("col_count", C.c_uint32), ("slices", C.c_uint32), ("pack_a", C.c_uint32),
+                ("pack_b", C.c_uint32), ("pack_ld", C.c_uint32), ("ldy", C.c_uint32), ("ld", C.c_uint32), ("g_cols", C.c_uint32), ("g_row0", C.c_uint32),
+                ("g_col0", C.c_uint32), ("pad_", C.c_uint32), ("pack_scale", C.c_double), ("xmap", C.c_void_p), ("omap", C.c_void_p), ("omap_also", C.c_void_p),
+                ("ymap", C.c_void_p), ("x", C.c_void_p), ("w", C.c_void_p), ("p", C.c_void_p), ("ct", C.c_void_p), ("c1", C.c_void_p), ("c2", C.c_void_p),
+                ("x_out", C.c_void_p), ("out1", C.c_void_p), ("out2", C.c_void_p), ("out1_also", C.c_void_p), ("partial", C.c_void_p), ("ct_out", C.c_void_p),
+                ("g", C.c_void_p), ("cu_count", C.c_int32), ("dispatched", C.c_int32)]
+
+
+class DenseResult:
+    """rc, dispatched (False: the lab entry itself rejected the request, the dispatcher never saw it), cu_count, and per output its
+    (body, guards) in `out`: x (n x pitch), out1, out2, out1_also, partial (slices x n x nc), ct (m x nc), g (ld x g_cols, as a matrix)."""
+
+    def __init__(self, rc, q, out):
+        self.rc, self.dispatched, self.cu_count, self.out = rc, bool(q.dispatched), int(q.cu_count), out
+
+    def body(self, k):
+        return self.out[k][0]
+
+
+def dense_form(ctx, form, n=0, x=None, wx=None, ldx=0, w=None, p=None, nc=0, n1=0, ld1=0, col_begin=0, col_count=0, accumulate=False, slices=1, xmap=None,
+               omap=None, omap_also=None, ld1_also=0, also=False, ct=None, blocks=None, stacked=None, in_place=0, old1=None, old2=None, ymap=None, ww=None,
+               ldy=0, ld=0, g_cols=0, g_row0=0, g_col0=0, m=None):
+    """One form (DENSE_FORMS) of the dense tall products through the solver's own dispatchers (modalhip_lab.h: mhl_dense_request).
+    x, w, p: row-major float64 panels of n rows, or None (an absent part: null pointer, width 0); x has ldx columns when ldx is given, of
+    which wx (default: all, or len(xmap)) are read.  Coefficients: ct (m x nc, k-major), or blocks = (c1, c2) -- matrices of pack_ld rows whose
+    first m rows mh_pack_coefficients sets side by side -- or stacked = (c1, c2, scale) for mh_pack_stacked; None for an absent block.
+    in_place: 1 = out1 is X, 2 = out1_also is X; also = True: a separate second destination of pitch ld1_also.  old1, old2: the start
+    values of out1 (n x pitch), out2 under accumulate.  Gram: y = w with ww logical columns (through ymap) at pitch ldy, g (ld x g_cols)
+    written at (g_row0, g_col0).  `m` is needed by the pack form alone.  Returns a DenseResult."""
+    f = DENSE_FORMS.index(form)
+    keep = []
+
+    def arr(a, dtype=np.float64, order="C"):
+        if a is None:
+            return None
+        a = np.asarray(a)
+        assert a.dtype == dtype and (a.flags.c_contiguous if order == "C" else a.flags.f_contiguous), (a.dtype, dtype, order)
+        keep.append(a)
+        return _p(a)
+
+    if wx is None:
+        wx = 0 if x is None else len(xmap) if xmap is not None else x.shape[1]
+    if ww is None:
+        ww = 0 if w is None else len(ymap) if ymap is not None else w.shape[1]
+    wp = 0 if p is None else p.shape[1]
+    if m is None:
+        m = wx + ww + wp
+    else:
+        wx = m  # (the pack form: no panels)
+    for a, width in ((x, ldx or wx), (w, (ldy or ww) if form == "gram" else ww)):
+        assert a is None or a.shape == (n, width), (a.shape, n, width)
+    q = DenseRequest(form=f, in_place=in_place, accumulate=int(accumulate), n=n, wx=wx, ldx=ldx, ww=ww, wp=wp, nc=nc, n1=n1, ld1=ld1, ld1_also=ld1_also,
+                     col_begin=col_begin, col_count=col_count, slices=slices, ldy=ldy, ld=ld, g_cols=g_cols, g_row0=g_row0, g_col0=g_col0)
+    q.x, q.w, q.p = arr(x), arr(w), arr(p)
+    q.xmap, q.omap, q.omap_also, q.ymap = (arr(a, np.uint32) for a in (xmap, omap, omap_also, ymap))
+    bufs = {}
+
+    def out(name, shape, body=None):
+        bufs[name] = (_guarded(int(np.prod(shape)), body=body), shape)
+        return _p(bufs[name][0])
+
+    if blocks is not None:
+        c1, c2 = blocks
+        q.coeff_layout, q.pack_a, q.pack_b = 1, 0 if c1 is None else c1.shape[1], 0 if c2 is None else c2.shape[1]
+        q.pack_ld = (c1 if c1 is not None else c2).shape[0]
+        q.c1, q.c2 = arr(c1, order="F"), arr(c2, order="F")
+    elif stacked is not None:
+        c1, c2, scale = stacked
+        q.coeff_layout, q.pack_a, q.pack_b, q.pack_scale = 2, 0 if c1 is None else c1.shape[0], 0 if c2 is None else c2.shape[0], scale
+        q.c1, q.c2 = arr(c1, order="F"), arr(c2, order="F")
+    elif form != "gram":
+        assert ct.shape == (m, nc)
+        q.ct = arr(ct)
+    if q.coeff_layout:
+        q.ct_out = out("ct", (m, nc))
+    if form != "pack" and x is not None:
+        q.x_out = out("x", x.shape)
+    if form == "combine":
+        pitch1 = ld1 or n1
+        if in_place != 1:
+            q.out1 = out("out1", (n, pitch1), old1)
+        if nc > n1:
+            q.out2 = out("out2", (n, nc - n1), old2)
+        if also:
+            q.out1_also = out("out1_also", (n, ld1_also))
+    elif form == "short_product":
+        q.out1 = out("out1", (n, nc))
+        if slices > 1:
+            q.partial = out("partial", (slices, n, nc))
+    elif form == "gram":
+        q.g = out("g", (g_cols, ld))
+    rc = lib().mhl_context_dense_form(ctx.h, C.byref(q))
+    res = {k: _body_and_guards(b, shape) for k, (b, shape) in bufs.items()}
+    if "g" in res:
+        res["g"] = (res["g"][0].T, res["g"][1])  # column-major ld x g_cols
+    return DenseResult(rc, q, res)
 
 
 def mapped_update_mismatches(ctx, n, wa, wb, gaps):
