@@ -257,8 +257,9 @@ double lab_mapped_update_mismatches(mh_context *ctx, bool gaps, size_t n, uint32
         dc.upload(hc.data(), hc.size());
         dmap.upload(map.data(), wa);
         dxn.zero();
-        if (form == 0) mh_combine(ctx, n, dx, wa, dw, wb, dp, wb, dc, nc, dxn, wa, dpo, false, b, dmap, pitch);
-        else mh_combine(ctx, n, dx, wa, dw, wb, dp, wb, dc, nc, dxn, wa, dpo, false, b, dmap, pitch, nullptr, 0, 0, dx, b, dmap);
+        MhCombine update{.x = dx, .wx = wa, .ldx = b, .xmap = dmap, .w = dw, .ww = wb, .p = dp, .wp = wb, .ct = dc, .nc = nc, .out1 = dxn, .n1 = wa, .ld1 = pitch, .out2 = dpo};
+        if (form == 1) update.out1_also = dx, update.ld1_also = b, update.omap_also = dmap;
+        mh_combine(ctx, n, update);
         Out o{std::vector<double>(n * pitch), std::vector<double>(n * b), std::vector<double>(n * wb)};
         dxn.download(o.xn.data(), o.xn.size());
         dx.download(o.x.data(), o.x.size());
@@ -315,7 +316,7 @@ int mhl_context_bench_dense(mh_context *ctx, int kind, uint64_t n, uint32_t wa, 
         HIP_CHECK(hipStreamSynchronize(ctx->stream));
         auto run = [&]() {
             if (kind == 0) mh_gram(ctx, n, x, wa, y, wb, g, wa);
-            else mh_combine(ctx, n, x, wa, y, wb, nullptr, 0, g, wa, z, wa, nullptr);
+            else mh_combine(ctx, n, {.x = x, .wx = wa, .w = y, .ww = wb, .ct = g, .nc = wa, .out1 = z, .n1 = wa});
         };
         run();
         hipEvent_t e0, e1;
@@ -994,8 +995,10 @@ int mhl_context_dense_form(mh_context *ctx, mhl_dense_request *q) {
         double *d1 = q->in_place == 1 ? x.body() : out1.body(), *d2 = q->out2 ? out2.body() : nullptr;
         double *d_also = q->in_place == 2 ? x.body() : q->out1_also ? also.body() : nullptr;
         q->dispatched = 1;
-        mh_combine(ctx, n, xd, wx, q->w ? w.get() : nullptr, ww, q->p ? p.get() : nullptr, wp, coeff.ct, nc, d1, n1, d2, old, q->ldx, q->xmap ? xmap.get() : nullptr, q->ld1,
-                   q->omap ? omap.get() : nullptr, q->col_begin, q->col_count, d_also, q->ld1_also, q->omap_also ? omap_also.get() : nullptr);
+        // (the request's layout is the lab's own: translated field by field; an absent host array is a null pointer here as it is there)
+        mh_combine(ctx, n, {.x = xd, .wx = wx, .ldx = q->ldx, .xmap = q->xmap ? xmap.get() : nullptr, .w = q->w ? w.get() : nullptr, .ww = ww, .p = q->p ? p.get() : nullptr, .wp = wp,
+                            .ct = coeff.ct, .nc = nc, .out1 = d1, .n1 = n1, .ld1 = q->ld1, .omap = q->omap ? omap.get() : nullptr, .out2 = d2, .accumulate = old,
+                            .col_begin = q->col_begin, .col_count = q->col_count, .out1_also = d_also, .ld1_also = q->ld1_also, .omap_also = q->omap_also ? omap_also.get() : nullptr});
         HIP_CHECK(hipStreamSynchronize(ctx->stream)); // (before anything is fetched: a launch error surfaces here, with the host arrays as passed)
         out1.fetch(q->out1);
         out2.fetch(q->out2);

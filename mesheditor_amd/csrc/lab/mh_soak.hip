@@ -469,7 +469,7 @@ int mhl_soak_aggressor(mh_context *ctx, int kind, volatile int *stop, uint64_t *
                     case 6: mh_apply_q(ctx, c, d, m, c2, m, wbig); break; // (any numbers do: the reflector loads and the register file are what matter)
                     case 7: mh_small_gemm(ctx, false, false, m, m, m, 1.0, c, m, c, m, 0.0, c2, m); break;
                     case 10:
-                    case 11: mh_combine(ctx, n, x, wbig, x + wbig, wbig, x + 2 * wbig, wbig, c, wbig, y, wbig, nullptr, false, m, nullptr, wbig, nullptr, 0, 0); break;
+                    case 11: mh_combine(ctx, n, {.x = x, .wx = wbig, .ldx = m, .w = x + wbig, .ww = wbig, .p = x + 2 * wbig, .wp = wbig, .ct = c, .nc = wbig, .out1 = y, .n1 = wbig}); break;
                     case 12:
                         HIP_CHECK(hipMemcpyAsync(c2.get(), c.get(), size_t(240) * 240 * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
                         mh_sytrd_small(ctx, c2, 240, d, e, tau, 1);

@@ -49,6 +49,13 @@ struct MhError : std::runtime_error {
     } while (0)
 #define KERNEL_CHECK() HIP_CHECK(hipGetLastError())
 
+// MH_TEST holds the test and A/B hooks of a process, comma separated.  A hook is on when its name occurs in the value (a substring
+// match).  The one reader of the variable: callers keep the answer (Switches in mh_eigs.hip, function-local statics elsewhere).
+inline bool mh_test_hook(const char *name) {
+    const char *hooks = getenv("MH_TEST");
+    return hooks && strstr(hooks, name);
+}
+
 // Size-bucketed caching allocator: device buffers are recycled across solves so a steady-state solve performs no
 // hipMalloc/hipFree (which synchronise the device).  The cache of idle blocks is capped (MH_POOL_CAP_MB; default: the larger
 // of 16 GiB and an eighth of the device's memory: 36 GB here, twice the working set of a 215-pair solve of 540 k unknowns): a release that takes it over the cap frees the blocks that have been idle
@@ -167,12 +174,12 @@ struct DevicePool {
     // the hunt of DESIGN 11.1d (nothing within 64 KB of any array, in single-thread solves of 65 / 120 / 215 pairs).
     static constexpr size_t RZ = 64 << 10;
     static bool redzone() {
-        static const bool on = getenv("MH_TEST") && strstr(getenv("MH_TEST"), "redzone");
+        static const bool on = mh_test_hook("redzone");
         return on;
     }
     std::map<void *, size_t> user_bytes; // (redzone mode) user pointer -> bytes asked for
     static size_t farzone() { // (hunt aid) MH_TEST=farzone: every array sits in the middle of 2 x 32 MB of slack of its own, never checked
-        static const size_t z = getenv("MH_TEST") && strstr(getenv("MH_TEST"), "farzone") ? size_t(32) << 20 : 0;
+        static const size_t z = mh_test_hook("farzone") ? size_t(32) << 20 : 0;
         return z;
     }
     void *alloc(size_t n_user) {
@@ -390,7 +397,7 @@ template<typename T> struct DevArray {
         ptr = n ? static_cast<T *>(c->pool.alloc(n * sizeof(T))) : nullptr;
         // MH_TEST=poison (test mode): every fresh array starts as all-ones bits (NaN for floating point), so a read of
         // memory the code never wrote shows up as a wrong result instead of depending on what the pool handed back
-        static const bool poison = getenv("MH_TEST") && strstr(getenv("MH_TEST"), "poison");
+        static const bool poison = mh_test_hook("poison");
         if (poison && ptr) (void)hipMemsetAsync(ptr, 0xff, n * sizeof(T), c->stream);
     }
     void free() {
@@ -625,13 +632,31 @@ void mh_apply_patches(mh_context *ctx, const PatchSet &ps, const T *in, const T 
 // G (wa x wb, column-major, ld) = X^T Y for row-major panels (fp64 MFMA, deterministic two-stage reduction).  mh_dense.hip
 // Optional column map on Y: logical column j of Y is physical column ymap[j] of a panel of pitch ldy (0 = wb, no map).
 void mh_gram(mh_context *ctx, size_t n, const double *x, uint32_t wa, const double *y, uint32_t wb, double *g, uint32_t ld, uint32_t ldy = 0, const uint32_t *ymap = nullptr);
-// [X | W | P] * Ct -> out1 (first n1 columns), out2 (the rest); Ct row-major m x nc.  mh_dense.hip
-void mh_combine(mh_context *ctx, size_t n, const double *x, uint32_t wx, const double *w, uint32_t ww, const double *p, uint32_t wp, const double *ct, uint32_t nc,
-                double *out1, uint32_t n1, double *out2, bool accumulate = false, uint32_t ldx = 0, const uint32_t *xmap = nullptr, uint32_t ld1 = 0,
-                const uint32_t *omap = nullptr, uint32_t col_begin = 0, uint32_t col_count = 0, // optional column maps on X (read) and out1 (write), pitches
-                                                                                                // ldx / ld1; col_count > 0: only columns [col_begin, +col_count) of Ct
-                double *out1_also = nullptr, uint32_t ld1_also = 0, const uint32_t *omap_also = nullptr); // (with xmap, one launch:) out1's columns are stored a second time,
-                                                                                                         // column c to column omap_also[c] of a panel of pitch ld1_also (may be X: see k_combine)
+// [X | W | P] * Ct -> out1 (first n1 columns), out2 (the rest); Ct row-major (wx + ww + wp) x nc.  mh_dense.hip
+// The operands of one update, all n rows tall.  A default means "absent": a caller names what it uses.
+struct MhCombine {
+    const double *x = nullptr;      // first panel: wx logical columns of a panel of pitch ldx (0: wx),
+    uint32_t wx = 0, ldx = 0;
+    const uint32_t *xmap = nullptr; // logical column c at physical column xmap[c] (null: at c)
+    const double *w = nullptr;      // second panel, compact (pitch = width ww)
+    uint32_t ww = 0;
+    const double *p = nullptr;      // third panel, compact (pitch = width wp)
+    uint32_t wp = 0;
+    const double *ct = nullptr;     // the coefficients, nc columns
+    uint32_t nc = 0;
+    double *out1 = nullptr;         // takes the first n1 columns at pitch ld1 (0: n1),
+    uint32_t n1 = 0, ld1 = 0;
+    const uint32_t *omap = nullptr; // column c to physical column omap[c] (null: to c)
+    double *out2 = nullptr;         // takes the other nc - n1 columns, compact
+    bool accumulate = false;        // out += instead of out =
+    uint32_t col_begin = 0, col_count = 0; // col_count > 0: only columns [col_begin, +col_count) of Ct
+    // (with xmap, one launch:) out1's columns are stored a second time, column c to column omap_also[c] of a panel of pitch ld1_also
+    // (may be X: see k_combine)
+    double *out1_also = nullptr;
+    uint32_t ld1_also = 0;
+    const uint32_t *omap_also = nullptr;
+};
+void mh_combine(mh_context *ctx, size_t n, const MhCombine &q);
 bool mh_tridiag_lowest_wide(mh_context *ctx, const double *d, const double *e, uint32_t m, uint32_t k, double *w, double *z, uint32_t ldz, double *work, int *info2,
                             double *quality_host); // orders 257 .. 768 (mh_dense.hip)
 void mh_apply_q(mh_context *ctx, const double *a, const double *tau, uint32_t m, double *z, uint32_t ldz, uint32_t ncols); // mh_dense.hip: Z <- Q Z after mh_sytrd_small / mh_sytrd_wide (order <= 768)

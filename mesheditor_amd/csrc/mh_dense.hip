@@ -15,7 +15,7 @@
 // MH_TEST=own_gemm (A/B hook, round 5): the wide Gram blocks and basis updates of the 200-mode configuration through OUR kernels
 // (k_gram_blocked cut into 160 x 80 blocks, k_combine in 256-column chunks) instead of the vendor's dgemm -- profiles/r05_config3_gemm_ab.txt
 static bool mh_test_own_gemm() {
-    static const bool on = getenv("MH_TEST") && strstr(getenv("MH_TEST"), "own_gemm");
+    static const bool on = mh_test_hook("own_gemm");
     return on;
 }
 namespace {
@@ -535,9 +535,13 @@ const uint32_t *mh_identity_map(mh_context *ctx) {
     return ctx->iota;
 }
 
-void mh_combine(mh_context *ctx, size_t n, const double *x, uint32_t wx, const double *w, uint32_t ww, const double *p, uint32_t wp, const double *ct, uint32_t nc,
-                double *out1, uint32_t n1, double *out2, bool accumulate, uint32_t ldx, const uint32_t *xmap, uint32_t ld1, const uint32_t *omap, uint32_t col_begin,
-                uint32_t col_count, double *out1_also, uint32_t ld1_also, const uint32_t *omap_also) {
+void mh_combine(mh_context *ctx, size_t n, const MhCombine &q) {
+    const double *const x = q.x, *const w = q.w, *const p = q.p, *const ct = q.ct;
+    const uint32_t wx = q.wx, ldx = q.ldx, ww = q.ww, wp = q.wp, nc = q.nc, n1 = q.n1, ld1 = q.ld1, ld1_also = q.ld1_also;
+    const uint32_t *const xmap = q.xmap, *omap = q.omap, *const omap_also = q.omap_also;
+    double *const out1 = q.out1, *const out2 = q.out2, *const out1_also = q.out1_also;
+    const bool accumulate = q.accumulate;
+    uint32_t col_begin = q.col_begin, col_count = q.col_count;
     if (!nc) return;
     if (!col_count) { col_begin = 0; col_count = nc; }
     const bool caller_omap = omap != nullptr || out1_also != nullptr;
@@ -1414,8 +1418,8 @@ void mh_sytrd_small(mh_context *ctx, double *a, uint32_t m, double *d, double *e
     // Default since round 5: the register-resident one-CU kernel (variant 3) at every order -- 43 / 95 / 407 / 506 us at 32 / 64 / 222 / 256
     // against 94 / 172 / 741 / 890 us of the better of the other two (one workgroup with the matrix in LDS below 64, sixteen workgroups
     // with a tagged exchange per column from there: profiles/r05_sytrd_regs.txt).  MH_TEST=sytrd_multi: the round-4 choice, for A/B runs.
-    static const bool old_default = getenv("MH_TEST") && strstr(getenv("MH_TEST"), "sytrd_multi");
-    static const bool one_group = getenv("MH_TEST") && strstr(getenv("MH_TEST"), "sytrd_fused");
+    static const bool old_default = mh_test_hook("sytrd_multi");
+    static const bool one_group = mh_test_hook("sytrd_fused");
     if (variant < 0 && one_group) variant = 0;
     if (variant < 0 && !old_default) variant = 3;
     const bool multi = variant < 0 ? m >= 64 : variant == 1;

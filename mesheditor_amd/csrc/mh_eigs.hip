@@ -70,17 +70,17 @@ struct Switches {
     bool fp32_prec = !(getenv("MH_PRECOND_FP64") && atoi(getenv("MH_PRECOND_FP64")) != 0);
     int deg2 = 0, deg1 = 0, gamma = 0; // 0: the built-in cycle shape
     double cheb_ratio = 0.0, cheb_ratio1 = 0.0; // (ratio1: the P1 level's own interval, optional fifth value of MH_CYCLE)
-    bool test_sytrd_giveup = getenv("MH_TEST") && strstr(getenv("MH_TEST"), "sytrd_giveup"); // every multi-workgroup tridiagonalisation counts as timed out: the fall-backs to the one-workgroup kernel / the library's syevd run
-    bool no_tridiag_wide = getenv("MH_TEST") && strstr(getenv("MH_TEST"), "no_tridiag_wide"); // orders above 256: the fall-back of the partial-spectrum stage -- the library's divide and conquer and ormtr -- runs
-    bool test_last_resort = getenv("MH_TEST") && strstr(getenv("MH_TEST"), "last_resort"); // every solve of more than 12 288 unknowns goes straight to the last resort
-    bool test_coarse_pivot = getenv("MH_TEST") && strstr(getenv("MH_TEST"), "coarse_pivot"); // the first coarse elimination of a system reports a non-positive pivot
-    bool test_selfcheck_fail = getenv("MH_TEST") && strstr(getenv("MH_TEST"), "selfcheck_fail"); // the first solve's Rayleigh-Ritz self-check reports a failure
-    bool lmax_low = getenv("MH_TEST") && strstr(getenv("MH_TEST"), "lmax_low"); // the smoothers' spectral bounds 12 % low, below the spectrum's end (as an unconverged power iteration leaves them): the iteration stalls
-    bool potrf_chain = getenv("MH_TEST") && strstr(getenv("MH_TEST"), "potrf_chain"); // the Gram blocks' Cholesky factorisations as the chain of launches they were before round 5
-    bool no_poly_start = getenv("MH_TEST") && strstr(getenv("MH_TEST"), "no_poly_start"); // (A/B hook of round 5: the cold start block as rounds 1-4 had it)
-    bool fresh_structure = getenv("MH_TEST") && strstr(getenv("MH_TEST"), "fresh_structure"); // (A/B hook: every mh_assemble builds the mesh's structure anew -- mh_pipeline.hip reads it too -- and the start block's box comes from k_bbox, as before the structure was kept)
-    bool copy_passes = getenv("MH_TEST") && strstr(getenv("MH_TEST"), "copy_passes"); // (A/B hook: the tall copy passes that moved a panel, or computed what the next launch overwrote, run again -- the scatter after the basis update, the gather before the preconditioner, the start block's copy, image transform and full random fill, the conversion of aval -- every returned number is the same bit for bit)
-    bool smoother_stores = getenv("MH_TEST") && strstr(getenv("MH_TEST"), "smoother_stores"); // (A/B hook: the single-precision smoothers store every panel again, read or not -- r and x of a zero start, r and d' of a sequence's last step -- and the restricted residual is converted to float by a launch of its own; every returned number is the same bit for bit)
+    bool test_sytrd_giveup = mh_test_hook("sytrd_giveup"); // every multi-workgroup tridiagonalisation counts as timed out: the fall-backs to the one-workgroup kernel / the library's syevd run
+    bool no_tridiag_wide = mh_test_hook("no_tridiag_wide"); // orders above 256: the fall-back of the partial-spectrum stage -- the library's divide and conquer and ormtr -- runs
+    bool test_last_resort = mh_test_hook("last_resort"); // every solve of more than 12 288 unknowns goes straight to the last resort
+    bool test_coarse_pivot = mh_test_hook("coarse_pivot"); // the first coarse elimination of a system reports a non-positive pivot
+    bool test_selfcheck_fail = mh_test_hook("selfcheck_fail"); // the first solve's Rayleigh-Ritz self-check reports a failure
+    bool lmax_low = mh_test_hook("lmax_low"); // the smoothers' spectral bounds 12 % low, below the spectrum's end (as an unconverged power iteration leaves them): the iteration stalls
+    bool potrf_chain = mh_test_hook("potrf_chain"); // the Gram blocks' Cholesky factorisations as the chain of launches they were before round 5
+    bool no_poly_start = mh_test_hook("no_poly_start"); // (A/B hook of round 5: the cold start block as rounds 1-4 had it)
+    bool fresh_structure = mh_test_hook("fresh_structure"); // (A/B hook: every mh_assemble builds the mesh's structure anew -- mh_pipeline.hip reads it too -- and the start block's box comes from k_bbox, as before the structure was kept)
+    bool copy_passes = mh_test_hook("copy_passes"); // (A/B hook: the tall copy passes that moved a panel, or computed what the next launch overwrote, run again -- the scatter after the basis update, the gather before the preconditioner, the start block's copy, image transform and full random fill, the conversion of aval -- every returned number is the same bit for bit)
+    bool smoother_stores = mh_test_hook("smoother_stores"); // (A/B hook: the single-precision smoothers store every panel again, read or not -- r and x of a zero start, r and d' of a sequence's last step -- and the restricted residual is converted to float by a launch of its own; every returned number is the same bit for bit)
     Switches() {
         if (const char *c = getenv("MH_CYCLE")) {
             double v[5] = {0, 0, 0, 0, 0};
@@ -645,10 +645,6 @@ __global__ void k_symmetrize_lower(double *__restrict__ a, uint32_t n, uint32_t 
 unsigned grid1(size_t count) { return div_up(count, TB); }
 
 // ---- rocBLAS wrappers over row-major panels ------------------------------------------------------------------
-// G (wa x wb, column-major, ld) = Xa^T Yb for panels Xa (n x wa), Yb (n x wb): hand-written MFMA kernel (mh_dense.hip)
-void gram(mh_context *ctx, size_t n, const double *xa, uint32_t wa, const double *yb, uint32_t wb, double *g, uint32_t ld) {
-    mh_gram(ctx, n, xa, wa, yb, wb, g, ld);
-}
 // Z (n x wz) = alpha * X (n x wa) * C (wa x wz, column-major ld) + beta * Z
 void panel_mul(mh_context *ctx, size_t n, const double *x, uint32_t wa, const double *c, uint32_t ld, double *z, uint32_t wz, double alpha, double beta) {
     if (!wz) return;
@@ -664,12 +660,19 @@ void panel_trsm(mh_context *ctx, size_t n, double *wp, uint32_t w, const double 
 
 // The step's order-m products: our 32 x 32-tile MFMA kernel (mh_small_gemm: the library's 128 x 128 macro tile leaves 4 .. 36 workgroups
 // on the device at these orders); anything larger goes to the library.
-void small_dgemm(mh_context *ctx, rocblas_operation ta, rocblas_operation tb, rocblas_int M, rocblas_int N, rocblas_int K, const double *alpha, const double *a, rocblas_int lda, const double *b,
-                 rocblas_int ldb, const double *beta, double *c, rocblas_int ldc) {
-    if (M <= 1024 && N <= 1024 && K <= 4096)
-        mh_small_gemm(ctx, ta != rocblas_operation_none, tb != rocblas_operation_none, uint32_t(M), uint32_t(N), uint32_t(K), *alpha, a, uint32_t(lda), b, uint32_t(ldb), *beta, c, uint32_t(ldc));
-    else
-        ROCBLAS_CHECK(rocblas_dgemm(ctx->blas, ta, tb, M, N, K, alpha, a, lda, b, ldb, beta, c, ldc));
+void small_dgemm(mh_context *ctx, bool ta, bool tb, uint32_t M, uint32_t N, uint32_t K, double alpha, const double *a, uint32_t lda, const double *b, uint32_t ldb, double beta,
+                 double *c, uint32_t ldc) {
+    if (M <= 1024 && N <= 1024 && K <= 4096) return mh_small_gemm(ctx, ta, tb, M, N, K, alpha, a, lda, b, ldb, beta, c, ldc);
+    const auto op = [](bool t) { return t ? rocblas_operation_transpose : rocblas_operation_none; };
+    ROCBLAS_CHECK(rocblas_dgemm(ctx->blas, op(ta), op(tb), rocblas_int(M), rocblas_int(N), rocblas_int(K), &alpha, a, rocblas_int(lda), b, rocblas_int(ldb), &beta, c, rocblas_int(ldc)));
+}
+// The triangular corrections of the small matrices by a Cholesky factor's inverse (lower, column-major w x w, ld w), in place:
+// block (rows x cols at leading dimension ld) <- op(linv) block (left; w = rows) or block op(linv) (right; w = cols)
+void tri_correct(mh_context *ctx, bool left, bool transpose, uint32_t rows, uint32_t cols, const double *linv, double *block, uint32_t ld) {
+    const double one = 1;
+    const rocblas_int w = rocblas_int(left ? rows : cols);
+    ROCBLAS_CHECK(rocblas_dtrmm(ctx->blas, left ? rocblas_side_left : rocblas_side_right, rocblas_fill_lower, transpose ? rocblas_operation_transpose : rocblas_operation_none,
+                                rocblas_diagonal_non_unit, rocblas_int(rows), rocblas_int(cols), &one, linv, w, block, rocblas_int(ld), block, rocblas_int(ld)));
 }
 
 // max |gM - I| over the lower triangle, as an ordered integer so that atomicMax applies (non-negative doubles)
@@ -861,7 +864,7 @@ std::optional<int> eig_tridiag_wide(mh_context *ctx, double *gA, uint32_t m, dou
 int mh_rr_solve(mh_context *ctx, double *gA, double *gM, uint32_t m, double *evals, double *ework, DevArray<int> &info, uint32_t nwant, bool gm_is_identity,
                 std::vector<double> *host_evals) { // host_evals: receives the nwant lowest eigenvalues when the partial-spectrum path delivered them (they travel with its quality read-back: no second synchronisation for them); left empty otherwise
     // nwant: only the nwant lowest pairs are needed (the active Ritz vectors): lets the tridiagonal stage compute a partial spectrum
-    const double one = 1, zero = 0;
+    const double one = 1;
     // 1. Standard form.  The basis is built M-orthonormal (X and P by construction, W by projection + Cholesky-QR), so gM is the identity
     // up to the orthogonalisation error.  When that error is below 1e-11 the pencil is solved as a standard problem:
     // no Cholesky reduction (potrf + three trsm, ~1.2 ms of a ~4 ms solve at order 225).  Otherwise the full reduction.
@@ -895,11 +898,11 @@ int mh_rr_solve(mh_context *ctx, double *gA, double *gM, uint32_t m, double *eva
         double *e = stmp.get(), *e2 = stmp.get() + size_t(m) * m;
         k_defect_matrix<<<grid1(size_t(m) * m), TB, 0, ctx->stream>>>(gM, m, e);
         KERNEL_CHECK();
-        small_dgemm(ctx, rocblas_operation_none, rocblas_operation_none, m, m, m, &one, e, m, e, m, &zero, e2, m);
+        small_dgemm(ctx, false, false, m, m, m, 1.0, e, m, e, m, 0.0, e2, m);
         k_inverse_sqrt_series<<<grid1(size_t(m) * m), TB, 0, ctx->stream>>>(e, e2, m, sroot);
         KERNEL_CHECK();
-        small_dgemm(ctx, rocblas_operation_none, rocblas_operation_none, m, m, m, &one, sroot, m, gA, m, &zero, e, m);
-        small_dgemm(ctx, rocblas_operation_none, rocblas_operation_none, m, m, m, &one, e, m, sroot, m, &zero, gA, m);
+        small_dgemm(ctx, false, false, m, m, m, 1.0, sroot, m, gA, m, 0.0, e, m);
+        small_dgemm(ctx, false, false, m, m, m, 1.0, e, m, sroot, m, 0.0, gA, m);
         k_symmetrize_lower<<<grid1(size_t(m) * m), TB, 0, ctx->stream>>>(gA, m, m);
         KERNEL_CHECK();
         identity = true;
@@ -923,7 +926,7 @@ int mh_rr_solve(mh_context *ctx, double *gA, double *gM, uint32_t m, double *eva
     if (*hinfo != 0) return *hinfo;
     // 3. Back to the pencil's eigenvectors
     if (series) { // c = S z
-        small_dgemm(ctx, rocblas_operation_none, rocblas_operation_none, m, m, m, &one, sroot, m, gA, m, &zero, stmp, m);
+        small_dgemm(ctx, false, false, m, m, m, 1.0, sroot, m, gA, m, 0.0, stmp, m);
         HIP_CHECK(hipMemcpyAsync(gA, stmp.get(), size_t(m) * m * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
         HIP_CHECK(hipStreamSynchronize(ctx->stream)); // the workspaces go back to the pool on return
     } else if (!identity)
@@ -1491,11 +1494,9 @@ __global__ void k_cg_direction(double *__restrict__ p, const double *__restrict_
 } // namespace
 
 namespace {
-// z ~= A^-1 r for an n x w panel by `iters` steps of conjugate gradients preconditioned with the cycle, the columns independent runs in
-// lockstep (no convergence test: no read-back).  The LAST RESORT's preconditioner (eigs_impl): where the cycle alone leaves the block
-// iteration unstable -- a mesh with cells flat to 1e-9: what the cycle returns carries components along the flat cells' stiff directions
-// that the Rayleigh-Ritz step cannot digest -- a few CG steps around it hand the eigensolver (nearly) the shift-invert direction A^-1 r of
-// the reference's own method (src/audio/mesh2modes.cpp:441-512), at ten times the cost per iteration.
+// Conjugate gradients on A = K - sigma M for an n x w panel, preconditioned with the cycle, the columns independent runs in lockstep:
+// the work panels, the column dot and the three moves of the recurrence.  Two drivers: solve() below, and mh_shift_invert_panel, which
+// restarts from the true residual and reads norms back.
 struct PanelCg {
     mh_system *sys;
     mh_context *ctx;
@@ -1505,6 +1506,7 @@ struct PanelCg {
     static constexpr uint32_t rpb = 256;
     PanelCg(mh_system *s, uint32_t w) : sys(s), ctx(s->ctx), n(size_t(3) * s->n_nodes), wmax(w), rr(s->ctx, n * w), zz(s->ctx, n * w), p(s->ctx, n * w), ap(s->ctx, n * w), rz(s->ctx, w), rz_new(s->ctx, w),
                                         pap(s->ctx, w), scratch(s->ctx, size_t(div_up(n, rpb)) * w) {}
+    // out[c] = u[:, c] . v[:, c], two deterministic stages
     void dot(const double *u, const double *v, double *out, uint32_t w) {
         const uint32_t nb = uint32_t(div_up(n, rpb));
         k_coldot_partial<<<dim3(nb, div_up(w, 64)), 64, 0, ctx->stream>>>(u, v, n, w, scratch, rpb);
@@ -1512,47 +1514,92 @@ struct PanelCg {
         k_colsumsq_final<<<w, 256, 0, ctx->stream>>>(scratch, nb, w, out);
         KERNEL_CHECK();
     }
+    // The three moves of the recurrence on an iterate x and its residual r (n x w panels; r may be rr).
+    // Start from the residual: p = z = B r, rz = r . z
+    template<typename Prec> void start(Prec &prec, const double *r, uint32_t w) {
+        prec.apply(r, zz, w);
+        HIP_CHECK(hipMemcpyAsync(p.get(), zz.get(), n * w * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+        dot(r, zz, rz, w);
+    }
+    // Advance: x += alpha p, r -= alpha A p with alpha = rz / (p . A p)
+    void advance(double *x, double *r, uint32_t w) {
+        mh_spmm(ctx, sys->L2, sys->L2.aval, p, ap, nullptr, nullptr, w);
+        dot(p, ap, pap, w);
+        k_cg_advance<<<grid1(n * w), TB, 0, ctx->stream>>>(x, r, p, ap, rz, pap, n * w, w);
+        KERNEL_CHECK();
+    }
+    // New direction: z = B r, p = z + (rz_new / rz) p, rz = rz_new = r . z
+    template<typename Prec> void new_direction(Prec &prec, const double *r, uint32_t w) {
+        prec.apply(r, zz, w);
+        dot(r, zz, rz_new, w);
+        k_cg_direction<<<grid1(n * w), TB, 0, ctx->stream>>>(p, zz, rz_new, rz, n * w, w);
+        KERNEL_CHECK();
+        HIP_CHECK(hipMemcpyAsync(rz.get(), rz_new.get(), w * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+    }
+    // z ~= A^-1 r by `iters` steps (no convergence test: no read-back).  The LAST RESORT's preconditioner (eigs_impl): where the cycle
+    // alone leaves the block iteration unstable -- a mesh with cells flat to 1e-9: what the cycle returns carries components along the
+    // flat cells' stiff directions that the Rayleigh-Ritz step cannot digest -- a few CG steps around it hand the eigensolver (nearly)
+    // the shift-invert direction A^-1 r of the reference's own method (src/audio/mesh2modes.cpp:441-512), at ten times the cost per
+    // iteration.
     template<typename Prec> void solve(Prec &prec, const double *r, double *z, uint32_t w, int iters) {
-        hipStream_t st = ctx->stream;
-        HIP_CHECK(hipMemsetAsync(z, 0, n * w * sizeof(double), st));
-        HIP_CHECK(hipMemcpyAsync(rr.get(), r, n * w * sizeof(double), hipMemcpyDeviceToDevice, st));
-        prec.apply(rr, zz, w);
-        HIP_CHECK(hipMemcpyAsync(p.get(), zz.get(), n * w * sizeof(double), hipMemcpyDeviceToDevice, st));
-        dot(rr, zz, rz, w);
+        HIP_CHECK(hipMemsetAsync(z, 0, n * w * sizeof(double), ctx->stream));
+        HIP_CHECK(hipMemcpyAsync(rr.get(), r, n * w * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+        start(prec, rr, w);
         for (int k = 0; k < iters; ++k) {
-            mh_spmm(ctx, sys->L2, sys->L2.aval, p, ap, nullptr, nullptr, w);
-            dot(p, ap, pap, w);
-            k_cg_advance<<<grid1(n * w), TB, 0, st>>>(z, rr, p, ap, rz, pap, n * w, w);
-            KERNEL_CHECK();
-            if (k + 1 == iters) break;
-            prec.apply(rr, zz, w);
-            dot(rr, zz, rz_new, w);
-            k_cg_direction<<<grid1(n * w), TB, 0, st>>>(p, zz, rz_new, rz, n * w, w);
-            KERNEL_CHECK();
-            HIP_CHECK(hipMemcpyAsync(rz.get(), rz_new.get(), w * sizeof(double), hipMemcpyDeviceToDevice, st));
+            advance(z, rr, w);
+            if (k + 1 < iters) new_direction(prec, rr, w);
         }
     }
 };
 } // namespace
 
 namespace {
+// What one call of mh_eigs asks for: the entry point's arguments (include/modalhip.h says what each means), gathered at the ABI boundary.
+struct SolveRequest {
+    mh_system *sys;
+    uint32_t nev;
+    double sigma, residual_tol;
+    uint32_t max_iters;
+    const float *seed_basis;
+    uint32_t seed_rows, seed_cols;
+    const volatile unsigned char *cancel;
+    volatile float *progress;
+    double *eigenvalues;
+    mh_profile *profile;
+};
+// One solve's attempts of the block iteration (eigs_impl): the request -- a copy: its seed is cleared when a seeded basis has not
+// served -- the block width and the solve's profile, which the attempts write.
+struct Attempt : SolveRequest {
+    uint32_t b;
+    mh_profile &prof;
+    // The only place a BlockLobpcg is built (max_iters: this attempt's own limit; inner_cg: conjugate-gradient steps per search direction,
+    // 0: the cycle alone).  Returns the MhError the run ended with, nothing when it converged; any other exception propagates.
+    std::optional<MhError> run(uint32_t max_iters, int inner_cg = 0);
+    // the profile the system last stored (this solve's stiffness_nonzeros and factorize are not carried over)
+    void reset_profile() {
+        prof = sys->profile;
+        prof.dofs = uint32_t(size_t(3) * sys->n_nodes);
+    }
+    // both smoothers' spectral bounds a quarter wider, once per system
+    void widen_lmax() {
+        if (sys->lmax_widened) return;
+        sys->L1.lmax *= 1.25;
+        sys->L2.lmax *= 1.25;
+        sys->lmax_widened = true;
+    }
+};
+
 // Block LOBPCG on the pencil (A, M) = (K - sigma M, M) with hard locking: one object per solve; the
 // stages of an iteration are its member functions, in the order run() calls them.
 struct BlockLobpcg {
-    // ---- the solve
-    mh_system *sys;
-    mh_context *ctx;
-    hipStream_t st;
+    // ---- the solve: the attempt (the request's fields and the running profile are read there), and shorthands of what every stage uses
+    Attempt &at;
+    mh_system *const sys;
+    mh_context *const ctx;
+    const hipStream_t st;
     const size_t n;
-    const uint32_t nev, b, mmax;
-    const double sigma, residual_tol;
-    const uint32_t max_iters;
-    const float *seed_basis;
-    const uint32_t seed_rows, seed_cols;
-    const volatile unsigned char *cancel;
-    volatile float *progress;
-    mh_profile &prof;
-    mh_profile *profile;
+    const uint32_t b, mmax;
+    const uint32_t max_iters; // this attempt's limit (not the request's: the last resort's second try runs fewer)
     SharedPhase iterating; // released and re-taken at the top of every iteration so that a waiting factorisation gets in
     Timer t_iter;
     double precond_seconds = 0;
@@ -1574,7 +1621,7 @@ struct BlockLobpcg {
     uint32_t res_pitch = 0;
     bool res_ready = false, rw_from_rr = false;
     DevArray<int> info; // [1]: conditioning report of mh_potrf_small
-    int inner_cg = 0; // > 0: the preconditioner is that many CG steps around the (double-precision) cycle -- the last resort (eigs_impl)
+    const int inner_cg; // > 0: the preconditioner is that many CG steps around the (double-precision) cycle -- the last resort (eigs_impl)
     std::unique_ptr<Precond<float>> prec32;
     std::unique_ptr<Precond<double>> prec64;
     std::unique_ptr<PanelCg> panel_cg;
@@ -1606,13 +1653,10 @@ struct BlockLobpcg {
     // ---- this iteration
     uint32_t w = 0, wa = 0, m = 0, wp_new = 0; // active columns (= width of W), their count as the X part, order of the small problem, width of the next P
 
-    BlockLobpcg(mh_system *system, uint32_t nev_, uint32_t block, double sigma_, double residual_tol_, uint32_t max_iters_, const float *seed_basis_, uint32_t seed_rows_,
-                uint32_t seed_cols_, const volatile unsigned char *cancel_, volatile float *progress_, mh_profile &prof_, mh_profile *profile_, int inner_cg_ = 0)
-        : sys(system), ctx(system->ctx), st(system->ctx->stream), n(size_t(3) * system->n_nodes), nev(nev_), b(block), mmax(3 * block), sigma(sigma_), residual_tol(residual_tol_),
-          max_iters(max_iters_), seed_basis(seed_basis_), seed_rows(seed_rows_), seed_cols(seed_cols_), cancel(cancel_), progress(progress_), prof(prof_), profile(profile_),
-          iterating(system->ctx->device, true), t_iter(system->ctx), pproj_ok(block <= 128), scaled_norms(system->patches2.any()), theta(block), rn(block), mn(block), xn(block), norms(3 * size_t(block)),
-          theta_act(block), order(block), locked(block, 0) {
-        inner_cg = inner_cg_;
+    BlockLobpcg(Attempt &attempt, uint32_t max_iters_, int inner_cg_)
+        : at(attempt), sys(attempt.sys), ctx(sys->ctx), st(ctx->stream), n(size_t(3) * sys->n_nodes), b(attempt.b), mmax(3 * b),
+          max_iters(max_iters_), iterating(ctx->device, true), t_iter(ctx), inner_cg(inner_cg_), pproj_ok(b <= 128), scaled_norms(sys->patches2.any()), theta(b), rn(b), mn(b), xn(b),
+          norms(3 * size_t(b)), theta_act(b), order(b), locked(b, 0) {
         for (DevArray<double> *panel : {&X, &AX, &MX, &Xn, &AXn, &MXn, &W, &AW, &MW, &P, &Pn, &R, &Rw}) panel->reset(ctx, n * b);
         if (!pproj_ok) // M P is only kept for blocks wider than 128 columns (the narrower ones project against P in coefficient space)
             for (DevArray<double> *panel : {&MP, &MPn}) panel->reset(ctx, n * b);
@@ -1649,8 +1693,34 @@ struct BlockLobpcg {
         anorm = sys->L2.lmax / dmin; // lambda_max(A) <= lambda_max(D^-1 A) * max diag(A)
     }
 
-    // G = V^T M V, scaled to unit diagonal, Cholesky; V <- V L^-T (and the same for M V, A V).  False: the block is rank deficient.
+    // The Gram matrix in G (w x w, ld w) scaled to unit diagonal (D in dscale, D G D into the block Gs that follows G), Gs factored in
+    // place, the info word(s) read back.  Up to 128 columns one workgroup of ours factors, unscales and inverts in one launch (round 5;
+    // before: potrf, unscale, memset and the library's trtri or trsm -- six to twelve launches on the serial path, twice per iteration):
+    // Gs <- L = D^-1 chol(D G D), linv <- L^-1, inverse_formed.  Wider blocks, and MH_TEST=potrf_chain: the factor alone, still scaled --
+    // by mh_potrf (blocked, without rocSOLVER: its potrf is disturbed by concurrent solves), or for a caller that reads the spread
+    // (with_spread: two info words instead of one) by mh_potrf_small up to 128 columns.
+    struct ScaledCholesky {
+        int info;            // non-zero: the pivot the factorisation lost
+        int spread;          // 16 log2(max / min diagonal of the factor) where the one-workgroup kernels report it, else 1 << 20
+        bool inverse_formed; // Gs is unscaled and linv holds its inverse
+    };
+    ScaledCholesky scaled_cholesky(uint32_t w, double *linv, bool with_spread) {
+        k_scale_gram<<<grid1(size_t(w) * w), TB, 0, st>>>(G, w, w, dscale);
+        KERNEL_CHECK();
+        double *Gs = G.get() + size_t(w) * w;
+        const bool small = w <= 128, two_words = small && with_spread;
+        ScaledCholesky c{0, 1 << 20, small && !switches().potrf_chain};
+        if (c.inverse_formed) mh_potrf_small_inverse(ctx, Gs, w, info, dscale, linv);
+        else if (two_words) mh_potrf_small(ctx, Gs, w, info);
+        else mh_potrf(ctx, Gs, w, w, info);
+        int words[2] = {0, 0};
+        info.download(words, two_words ? 2 : 1);
+        c.info = words[0];
+        if (two_words) c.spread = words[1];
+        return c;
+    }
 
+    // G = V^T M V, scaled to unit diagonal, Cholesky; V <- V L^-T (and the same for M V, A V).  False: the block is rank deficient.
     bool chol_orthonormalise(double *V, double *MV, double *AV, uint32_t w, bool transform_images = true, bool allow_implicit = false,
                              const double *hp = nullptr, uint32_t hp_rows = 0) {
         // hp (hp_rows x w, = P^T M V): V is to be taken as V - P hp without forming it: G -= hp^T hp (P is M-orthonormal).  Only
@@ -1659,41 +1729,18 @@ struct BlockLobpcg {
         // with V L^-T through L^-1 on the small matrices
         // transform_images = false: M V is only read (for the Gram matrix); the caller keeps the images untransformed
         // G = V^T M V, scaled to unit diagonal, Cholesky; V <- V L^-T (and the same for MV, AV)
-        gram(ctx, n, V, w, MV, w, G, w);
-        if (hp) {
-            const double minus = -1, plus = 1;
-            small_dgemm(ctx, rocblas_operation_transpose, rocblas_operation_none, rocblas_int(w), rocblas_int(w), rocblas_int(hp_rows), &minus, hp,
-                                        rocblas_int(hp_rows), hp, rocblas_int(hp_rows), &plus, G, rocblas_int(w));
-        }
-        k_scale_gram<<<grid1(size_t(w) * w), TB, 0, st>>>(G, w, w, dscale);
-        KERNEL_CHECK();
+        mh_gram(ctx, n, V, w, MV, w, G, w);
+        if (hp) small_dgemm(ctx, true, false, w, w, hp_rows, -1.0, hp, hp_rows, hp, hp_rows, 1.0, G, w);
+        const ScaledCholesky chol = scaled_cholesky(w, Linv, true);
         double *Gs = G.get() + size_t(w) * w;
-        int hinfo = 0;
-        bool fused_inverse = false; // Gs already unscaled and Linv already formed (orders <= 128)
-        {
-            last_spread = 1 << 20;
-            if (w <= 128) {
-                // one workgroup of ours: factor, unscale and invert in one launch (round 5; before: potrf, unscale, memset and the library's
-                // trtri -- six to eight launches, ~130 us with their gaps, twice per iteration); MH_TEST=potrf_chain: the old chain
-                fused_inverse = !switches().potrf_chain;
-                if (fused_inverse) mh_potrf_small_inverse(ctx, Gs, w, info, dscale, Linv);
-                else mh_potrf_small(ctx, Gs, w, info);
-                int both[2] = {0, 0};
-                info.download(both, 2);
-                hinfo = both[0];
-                last_spread = both[1];
-            } else { // (blocked, without rocSOLVER: its potrf is disturbed by concurrent solves -- mh_potrf)
-                mh_potrf(ctx, Gs, w, w, info);
-                info.download(&hinfo, 1);
-            }
-        }
+        last_spread = chol.spread;
         p_needs_explicit = false;
-        if (hp && (hinfo != 0 || last_spread >= 16 * 8)) { // V - P hp is nearly dependent: project in the tall space instead
+        if (hp && (chol.info != 0 || last_spread >= 16 * 8)) { // V - P hp is nearly dependent: project in the tall space instead
             p_needs_explicit = true;
             return true;
         }
-        if (hinfo != 0) return false;
-        if (!fused_inverse) {
+        if (chol.info != 0) return false;
+        if (!chol.inverse_formed) {
             k_unscale_chol<<<grid1(size_t(w) * w), TB, 0, st>>>(Gs, w, w, dscale);
             KERNEL_CHECK();
         }
@@ -1704,14 +1751,15 @@ struct BlockLobpcg {
         } else {
             // V <- V L^-T through the explicit small inverse and the MFMA basis-update kernel (in place: a workgroup
             // reads its rows before it writes them): L^-1 column-major IS the k-major coefficient matrix of V L^-T
-            if (!fused_inverse) {
+            if (!chol.inverse_formed) {
                 HIP_CHECK(hipMemsetAsync(Linv, 0, size_t(w) * w * sizeof(double), st));
                 ROCBLAS_CHECK(rocblas_dtrtri(ctx->blas, rocblas_fill_lower, rocblas_diagonal_non_unit, w, Gs, w, Linv, w));
             }
             w_implicit = allow_implicit && !transform_images && last_spread < 16 * 8;
-            if (!w_implicit) mh_combine(ctx, n, V, w, nullptr, 0, nullptr, 0, Linv, w, V, w, nullptr);
-            if (MV && transform_images) mh_combine(ctx, n, MV, w, nullptr, 0, nullptr, 0, Linv, w, MV, w, nullptr);
-            if (AV && transform_images) mh_combine(ctx, n, AV, w, nullptr, 0, nullptr, 0, Linv, w, AV, w, nullptr);
+            const auto by_linv = [&](double *panel) { mh_combine(ctx, n, {.x = panel, .wx = w, .ct = Linv, .nc = w, .out1 = panel, .n1 = w}); };
+            if (!w_implicit) by_linv(V);
+            if (MV && transform_images) by_linv(MV);
+            if (AV && transform_images) by_linv(AV);
         }
         return true;
     }
@@ -1743,15 +1791,15 @@ struct BlockLobpcg {
             k_random_panel<<<grid1(n * b), TB, 0, st>>>(X, n, b, 0, 20260710ull);
             KERNEL_CHECK();
         }
-        warm = seed_basis && seed_rows == n && seed_cols >= nev;
+        warm = at.seed_basis && at.seed_rows == n && at.seed_cols >= at.nev;
         if (warm && fill_late) { // (the seed's columns and the rigid-body modes go over a full fill)
             k_random_panel<<<grid1(n * b), TB, 0, st>>>(X, n, b, 0, 20260710ull);
             KERNEL_CHECK();
         }
         if (warm) {
-            const uint32_t ncols = std::min(seed_cols, b);
+            const uint32_t ncols = std::min(at.seed_cols, b);
             DevArray<float> seed(ctx, n * ncols);
-            seed.upload(seed_basis, n * ncols);
+            seed.upload(at.seed_basis, n * ncols);
             k_load_seed<<<grid1(n * ncols), TB, 0, st>>>(seed, sys->perm, sys->n_nodes, ncols, b, X);
             KERNEL_CHECK();
             HIP_CHECK(hipStreamSynchronize(st));
@@ -1832,7 +1880,7 @@ struct BlockLobpcg {
                 Timer tp(ctx);
                 precondition(MX, Xn, b);
                 precond_seconds += tp.stop();
-                prof.op_applications += b;
+                at.prof.op_applications += b;
                 // (the smoothed block becomes X by name; MH_TEST=copy_passes: by a copy of the panel, as it was)
                 if (switches().copy_passes) HIP_CHECK(hipMemcpyAsync(X, Xn.get(), n * b * sizeof(double), hipMemcpyDeviceToDevice, st));
                 else std::swap(X, Xn);
@@ -1853,8 +1901,8 @@ struct BlockLobpcg {
         }
         mh_spmm(ctx, sys->L2, sys->L2.aval, X, AX, sys->L2.mval, MX, b);
         {
-            gram(ctx, n, X, b, AX, b, gA, b);
-            gram(ctx, n, X, b, MX, b, gM, b);
+            mh_gram(ctx, n, X, b, AX, b, gA, b);
+            mh_gram(ctx, n, X, b, MX, b, gM, b);
             // (the library's divide and conquer here: every pair of a start block's matrix, whose spectrum spans |sigma| .. ||A|| -- our partial-spectrum
             // kernels, accepted at a residual of 1e-10 ||T||, left the small pairs at 1e-8 .. 1e-7 in the step's self-check: measured in round 5)
             const int hinfo = mh_rr_solve(ctx, gA, gM, b, evals, ework, info);
@@ -1867,18 +1915,45 @@ struct BlockLobpcg {
         }
     }
 
+    // |theta| below which a pair counts as near the shift (the rigid-body pairs): the rounding-floor clause is for those alone
+    double near_limit() const { return 10.0 * std::abs(at.sigma); }
+    // The block-norms pass: R = A X - theta M X for all b columns and, in `norms` = [rn | mn | xn], the column sums of r^2, (M x)^2 and
+    // (near the shift only) x^2 -- weighted by dinv, the Jacobi scaling, when it is given (k_residual_norms).  One read-back.
+    void block_norms(const double *dinv) {
+        theta_d.upload(theta.data(), b);
+        const uint32_t rpb = 256, nblk = div_up(n, rpb);
+        if (scratch.count < size_t(nblk) * 3 * b) scratch.reset(ctx, size_t(nblk) * 3 * b);
+        k_residual_norms<<<dim3(nblk, div_up(b, 64)), 64, 0, st>>>(AX, MX, X, theta_d, near_limit(), R, n, b, rpb, scratch, dinv);
+        KERNEL_CHECK();
+        k_colsumsq_final<<<3 * b, 256, 0, st>>>(scratch, nblk, 3 * b, norms_d); // partial rows are 3b wide
+        KERNEL_CHECK();
+        norms_d.download(norms.data(), 3 * size_t(b));
+        std::copy(norms.begin(), norms.begin() + b, rn.begin());
+        std::copy(norms.begin() + b, norms.begin() + 2 * b, mn.begin());
+        std::copy(norms.begin() + 2 * b, norms.end(), xn.begin());
+    }
+    // Relative residual of column i in the norms of the latest pass: ||r|| / (|theta| ||M x||)
+    double rel_residual(uint32_t i) const { return std::sqrt(rn[i]) / (std::abs(theta[i]) * std::sqrt(mn[i])); }
+    // Its maximum over the nev wanted pairs (the nev lowest Ritz values: `order`), optionally over those not yet locked
+    double worst_wanted(bool only_unlocked = false) const {
+        double worst = 0;
+        for (uint32_t k = 0; k < at.nev; ++k)
+            if (const uint32_t i = order[k]; !(only_unlocked && locked[i])) worst = std::max(worst, rel_residual(i));
+        return worst;
+    }
+
     // Residuals and column norms of the whole block, hard locking of the converged columns, the count of converged wanted pairs;
     // true when the iteration is over (converged, nothing left to iterate on, or out of iterations).  Also the safety net
     // of the single-precision smoothers.
     bool converged_or_locked(uint32_t it) {
-        if (cancel && *cancel) mh_throw(MH_ECANCELLED, "cancelled");
+        if (at.cancel && *at.cancel) mh_throw(MH_ECANCELLED, "cancelled");
         if (g_concurrent) { // an exclusive holder synchronises the device itself: no need to drain our queue first
             iterating.release();
             iterating.acquire();
         }
         bool fused = res_ready;
         if (fused) // the rounding-floor clause needs ||x|| of the pairs near the shift: with one of them still active the separate pass runs
-            for (const uint32_t i : res_act) fused = fused && !(std::abs(theta[i]) < 10.0 * std::abs(sigma));
+            for (const uint32_t i : res_act) fused = fused && !(std::abs(theta[i]) < near_limit());
         res_ready = false;
         rw_from_rr = fused;
         if (fused) {
@@ -1888,29 +1963,16 @@ struct BlockLobpcg {
                 mn[res_act[k]] = res_norms[res_pitch + k];
             }
         } else {
-        theta_d.upload(theta.data(), b);
-        {
-            const uint32_t rpb = 256, nblk = div_up(n, rpb);
-            if (scratch.count < size_t(nblk) * 3 * b) scratch.reset(ctx, size_t(nblk) * 3 * b);
-            dim3 grid(nblk, div_up(b, 64));
-            k_residual_norms<<<grid, 64, 0, st>>>(AX, MX, X, theta_d, 10.0 * std::abs(sigma), R, n, b, rpb, scratch, scaled_norms ? sys->L2.dinv.get() : nullptr);
-            KERNEL_CHECK();
-            k_colsumsq_final<<<3 * b, 256, 0, st>>>(scratch, nblk, 3 * b, norms_d); // partial rows are 3b wide
-            KERNEL_CHECK();
-            norms_d.download(norms.data(), 3 * size_t(b));
-            std::copy(norms.begin(), norms.begin() + b, rn.begin());
-            std::copy(norms.begin() + b, norms.begin() + 2 * b, mn.begin());
-            std::copy(norms.begin() + 2 * b, norms.end(), xn.begin());
-        }
+            block_norms(scaled_norms ? sys->L2.dinv.get() : nullptr);
         }
         act.clear();
         for (uint32_t i = 0; i < b; ++i) {
             // Converged: relative residual below tol, or at the rounding floor of forming A x (which is what
             // limits the rigid-body pairs: theta = |sigma| sits 10-12 orders below ||A||).
-            const double rel = std::sqrt(rn[i]) / (std::abs(theta[i]) * std::sqrt(mn[i]));
+            const double rel = rel_residual(i);
             // The floor clause is for those pairs only (theta within 10x of |sigma|): an elastic pair of a stiff, sliver-heavy
             // mesh must not be accepted at a relative residual above the tolerance because ||A|| happens to be huge.
-            const bool near_shift = std::abs(theta[i]) < 10.0 * std::abs(sigma);
+            const bool near_shift = std::abs(theta[i]) < near_limit();
             // (Jacobi-scaled norms: the rounding floor of (A x)_i is eps lmax(D^-1 A) D_ii |x|, i.e. eps lmax ||x||_D in the D^-1 norm)
             const double floor_norm = scaled_norms ? sys->L2.lmax * std::sqrt(xn[i]) : anorm * std::sqrt(xn[i]);
             // The factor: forming (A x)_i rounds to gamma_k sum_j |a_ij| |x_j| with k the row length (~100-250 entries of a P2 row), against
@@ -1924,7 +1986,7 @@ struct BlockLobpcg {
             // cells at 3e-11, whose rows cancel entries of 1e18.  Left active they only collect noise from the search directions and the solve
             // never ends; the reference's factorisation hands the same six back at +-1e2 beside elastic values of 2e7)
             const double floor_factor = it == 0 && !warm && sys->worst_quality < kFlatShape ? 65536.0 : 256.0;
-            const bool ok = rel < residual_tol || (near_shift && std::sqrt(rn[i]) < floor_factor * 2.2e-16 * floor_norm);
+            const bool ok = rel < at.residual_tol || (near_shift && std::sqrt(rn[i]) < floor_factor * 2.2e-16 * floor_norm);
             if (ok) locked[i] = 1;
             if (!locked[i]) act.push_back(i);
         }
@@ -1932,24 +1994,22 @@ struct BlockLobpcg {
         std::iota(order.begin(), order.end(), 0u);
         std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t c) { return theta[a] < theta[c]; });
         nconv = 0;
-        for (uint32_t k = 0; k < nev; ++k) nconv += locked[order[k]];
-        if (progress) *progress = 0.3f + 0.65f * float(nconv) / float(nev);
+        for (uint32_t k = 0; k < at.nev; ++k) nconv += locked[order[k]];
+        if (at.progress) *at.progress = 0.3f + 0.65f * float(nconv) / float(at.nev);
         if (verbose) {
-            double worst = 0;
-            for (uint32_t k = 0; k < nev; ++k) { const uint32_t i = order[k]; worst = std::max(worst, std::sqrt(rn[i]) / (std::abs(theta[i]) * std::sqrt(mn[i]))); }
+            const double worst = worst_wanted();
             if (it == 0) fprintf(stderr, "[lobpcg] ||A|| <= %.3e, sliver patches %u + %u clusters (largest %u nodes; worst element shape %.2e), aggregates %u, lmax %.4f / %.4f\n", anorm, sys->patches2.n_patches, sys->patches2.n_clusters, sys->patches2.largest_cluster, double(sys->worst_quality), sys->n_agg, sys->L2.lmax, sys->L1.lmax);
-            fprintf(stderr, "[lobpcg] it %3u conv %3u/%u active %zu wp %u worst %.2e  floor-ratio[0..7]:", it, nconv, nev, act.size(), wp, worst);
+            fprintf(stderr, "[lobpcg] it %3u conv %3u/%u active %zu wp %u worst %.2e  floor-ratio[0..7]:", it, nconv, at.nev, act.size(), wp, worst);
             for (uint32_t i = 0; i < std::min(8u, b); ++i) fprintf(stderr, " %.1f", xn[i] > 0 ? std::sqrt(rn[i]) / (2.2e-16 * (scaled_norms ? sys->L2.lmax : anorm) * std::sqrt(xn[i])) : 0.0);
             fprintf(stderr, "  theta0 %.6e\n", theta[0]);
         }
         iters = it;
-        if (nconv >= nev || act.empty()) { converged = nconv >= nev; return true; }
+        if (nconv >= at.nev || act.empty()) { converged = nconv >= at.nev; return true; }
         if (it == max_iters) return true;
         // Safety net of the single-precision smoothers: no newly converged pair and no 20 % drop of the worst
         // residual over 6 iterations switches the cycle to double precision for the rest of the solve.
         {
-            double worst = 0;
-            for (uint32_t k = 0; k < nev; ++k) { const uint32_t i = order[k]; worst = std::max(worst, std::sqrt(rn[i]) / (std::abs(theta[i]) * std::sqrt(mn[i]))); }
+            const double worst = worst_wanted();
             hist_worst.push_back(worst);
             hist_nconv.push_back(nconv);
             const size_t h = hist_worst.size();
@@ -1964,11 +2024,7 @@ struct BlockLobpcg {
             // scan) leaves the last active columns at their floor; W then lies in span(X, P) to rounding, the Cholesky-QR spread grows
             // and the residuals of those columns start to GROW, doubling per iteration (tools/probe/tight_tolerance_probe.py).  Say so
             // instead of iterating into a rank failure.
-            double worst_active = 0;
-            for (uint32_t k = 0; k < nev; ++k) { // (the wanted pairs only: guard columns converge late by design)
-                const uint32_t i = order[k];
-                if (!locked[i]) worst_active = std::max(worst_active, std::sqrt(rn[i]) / (std::abs(theta[i]) * std::sqrt(mn[i])));
-            }
+            const double worst_active = worst_wanted(true); // (the wanted pairs only: guard columns converge late by design)
             best_worst_active = std::min(best_worst_active, worst_active);
             // (three iterations in a row: one step's jump is also what a guard column looks like when its Ritz value drops into the
             // wanted range late -- a missed member of a multiplet arrives with a residual of 1e-2 .. 1e-1 beside pairs just above the tolerance)
@@ -1980,17 +2036,17 @@ struct BlockLobpcg {
             hist_active.push_back(worst_active);
             if (inner_cg > 0 && it >= 40) {
                 const size_t h = hist_active.size();
-                if (h > 30 && hist_nconv[h - 31] == nconv && worst_active > 0.9 * hist_active[h - 31] && worst_active <= 10.0 * residual_tol) {
-                    pairs_at_floor = nev > nconv ? nev - nconv : 0;
-                    if (verbose) fprintf(stderr, "[lobpcg] it %3u: %u pairs have sat at a residual of %.2e (tolerance %.1e) for thirty iterations -- the rounding floor of this mesh; handed on as they are\n", it, pairs_at_floor, worst_active, residual_tol);
+                if (h > 30 && hist_nconv[h - 31] == nconv && worst_active > 0.9 * hist_active[h - 31] && worst_active <= 10.0 * at.residual_tol) {
+                    pairs_at_floor = at.nev > nconv ? at.nev - nconv : 0;
+                    if (verbose) fprintf(stderr, "[lobpcg] it %3u: %u pairs have sat at a residual of %.2e (tolerance %.1e) for thirty iterations -- the rounding floor of this mesh; handed on as they are\n", it, pairs_at_floor, worst_active, at.residual_tol);
                     converged = true;
                     return true;
                 }
             }
             floor_strikes = it >= 20 && worst_active > 1e3 * best_worst_active ? floor_strikes + 1 : 0;
             if (floor_strikes >= 3)
-                mh_throw(MH_ENOTCONVERGED, "LOBPCG: %u of %u pairs converged; the others sit at the rounding floor (residual %.1e and growing, best %.1e, tolerance %.1e)", nconv, nev,
-                         worst_active, best_worst_active, residual_tol);
+                mh_throw(MH_ENOTCONVERGED, "LOBPCG: %u of %u pairs converged; the others sit at the rounding floor (residual %.1e and growing, best %.1e, tolerance %.1e)", nconv, at.nev,
+                         worst_active, best_worst_active, at.residual_tol);
         }
         return false;
     }
@@ -2039,7 +2095,7 @@ struct BlockLobpcg {
             Timer tp(ctx);
             precondition(residuals, W, w, r_pitch, r_map);
             precond_seconds += tp.stop();
-            prof.op_applications += w;
+            at.prof.op_applications += w;
         }
         // W <- (I - X X^T M - P P^T M) W (the coefficients come from M X and M P: no M W needed yet), then A W and M W in
         // one fused product, then M-orthonormalise W carrying both images along.  Against "M W first, project W and
@@ -2050,18 +2106,18 @@ struct BlockLobpcg {
         p_implicit = false;
         if (pproj_ok && wp) {
             // project against X in the tall space, against P in coefficient space
-            gram(ctx, n, MX, b, W, w, H, b); // b x w
+            mh_gram(ctx, n, MX, b, W, w, H, b); // b x w
             mh_pack_stacked(ctx, H, b, nullptr, 0, w, -1.0, Ct);
-            mh_combine(ctx, n, X, b, nullptr, 0, nullptr, 0, Ct, w, W, w, nullptr, true);
+            mh_combine(ctx, n, {.x = X, .wx = b, .ct = Ct, .nc = w, .out1 = W, .n1 = w, .accumulate = true});
             mh_spmm(ctx, sys->L2, sys->L2.aval, W, AW, sys->L2.mval, MW, w);
-            gram(ctx, n, P, wp, MW, w, Hp, wp); // Hp = P^T M W, wp x w
+            mh_gram(ctx, n, P, wp, MW, w, Hp, wp); // Hp = P^T M W, wp x w
             lazy_images = true;
             w_implicit = false;
             ok = chol_orthonormalise(W, MW, AW, w, false, true, Hp, wp);
             if (!ok) mh_throw(MH_ENOTCONVERGED, "search directions lost rank at iteration %u", it);
             if (p_needs_explicit) { // rare: W - P Hp nearly dependent -> explicit projection, images again, ordinary Cholesky-QR
                 mh_pack_stacked(ctx, Hp, wp, nullptr, 0, w, -1.0, Ct);
-                mh_combine(ctx, n, P, wp, nullptr, 0, nullptr, 0, Ct, w, W, w, nullptr, true);
+                mh_combine(ctx, n, {.x = P, .wx = wp, .ct = Ct, .nc = w, .out1 = W, .n1 = w, .accumulate = true});
                 mh_spmm(ctx, sys->L2, sys->L2.aval, W, AW, sys->L2.mval, MW, w);
                 lazy_images = w <= 256;
                 ok = chol_orthonormalise(W, MW, AW, w, !lazy_images, lazy_images);
@@ -2070,10 +2126,10 @@ struct BlockLobpcg {
                 p_implicit = true;
             }
         } else { // no previous directions yet, or a block wider than 128 columns (M P is maintained there: update_basis)
-            gram(ctx, n, MX, b, W, w, H, b); // b x w
-            if (wp) gram(ctx, n, MP, wp, W, w, H2, wp);
+            mh_gram(ctx, n, MX, b, W, w, H, b); // b x w
+            if (wp) mh_gram(ctx, n, MP, wp, W, w, H2, wp);
             mh_pack_stacked(ctx, H, b, H2, wp, w, -1.0, Ct);
-            mh_combine(ctx, n, X, b, P, wp, nullptr, 0, Ct, w, W, w, nullptr, true);
+            mh_combine(ctx, n, {.x = X, .wx = b, .w = P, .ww = wp, .ct = Ct, .nc = w, .out1 = W, .n1 = w, .accumulate = true});
             mh_spmm(ctx, sys->L2, sys->L2.aval, W, AW, sys->L2.mval, MW, w);
             // Only W itself is multiplied by L^-T.  Its images keep their pre-orthonormalisation form (A W L^T, M W L^T): the
             // Gram blocks that involve them are corrected on the small matrices (B <- B L^-T), the recombination of M P folds
@@ -2100,32 +2156,22 @@ struct BlockLobpcg {
             KERNEL_CHECK();
             // W^T M X and P^T M W are zero by the projection that W just went through (measured 1e-14 .. 1e-12 in every run): they
             // are not formed.  W^T M W, which carries the Cholesky-QR's error, is measured unless the factor says it is tiny.
-            const double unit_one = 1;
             auto left_corrected = [&](double *block, uint32_t cols) { // block (w x cols at leading dimension m) <- L^-1 block: W was not transformed
-                if (w_implicit)
-                    ROCBLAS_CHECK(rocblas_dtrmm(ctx->blas, rocblas_side_left, rocblas_fill_lower, rocblas_operation_none, rocblas_diagonal_non_unit, rocblas_int(w),
-                                                rocblas_int(cols), &unit_one, Linv, rocblas_int(w), block, rocblas_int(m), block, rocblas_int(m)));
+                if (w_implicit) tri_correct(ctx, true, false, w, cols, Linv, block, m);
             };
             mh_gram(ctx, n, W, w, AX, wa, gA.get() + wa, m, b, idx_d);
             left_corrected(gA.get() + wa, wa);
-            const double unit = 1;
             auto untransformed = [&](double *block, uint32_t rows) { // block (rows x w at leading dimension m) <- block L^-T
-                if (lazy_images)
-                    ROCBLAS_CHECK(rocblas_dtrmm(ctx->blas, rocblas_side_right, rocblas_fill_lower, rocblas_operation_transpose, rocblas_diagonal_non_unit, rocblas_int(rows),
-                                                rocblas_int(w), &unit, Linv, rocblas_int(w), block, rocblas_int(m), block, rocblas_int(m)));
+                if (lazy_images) tri_correct(ctx, false, true, rows, w, Linv, block, m);
             };
-            gram(ctx, n, W, w, AW, w, gA.get() + size_t(wa) * m + wa, m);
+            mh_gram(ctx, n, W, w, AW, w, gA.get() + size_t(wa) * m + wa, m);
             if (p_implicit && wp) {
                 // W' = W - P Hp:  P^T A W' = Bp - App Hp,  W'^T A W' = Bw - U - U^T + Hp^T App Hp with U = Hp^T Bp  (P^T A P = App, X^T A P = 0)
-                const double plus = 1, nil = 0;
                 double *bw = gA.get() + size_t(wa) * m + wa, *bp = gA.get() + size_t(wa) * m + wa + w;
-                gram(ctx, n, P, wp, AW, w, bp, m);
-                small_dgemm(ctx, rocblas_operation_transpose, rocblas_operation_none, rocblas_int(w), rocblas_int(w), rocblas_int(wp), &plus, Hp, rocblas_int(wp), bp,
-                                            rocblas_int(m), &nil, Up, rocblas_int(w));
-                small_dgemm(ctx, rocblas_operation_none, rocblas_operation_none, rocblas_int(wp), rocblas_int(w), rocblas_int(wp), &plus, App, rocblas_int(wp), Hp,
-                                            rocblas_int(wp), &nil, T1p, rocblas_int(wp));
-                small_dgemm(ctx, rocblas_operation_transpose, rocblas_operation_none, rocblas_int(w), rocblas_int(w), rocblas_int(wp), &plus, Hp, rocblas_int(wp), T1p,
-                                            rocblas_int(wp), &nil, Vp, rocblas_int(w));
+                mh_gram(ctx, n, P, wp, AW, w, bp, m);
+                small_dgemm(ctx, true, false, w, w, wp, 1.0, Hp, wp, bp, m, 0.0, Up, w);
+                small_dgemm(ctx, false, false, wp, w, wp, 1.0, App, wp, Hp, wp, 0.0, T1p, wp);
+                small_dgemm(ctx, true, false, w, w, wp, 1.0, Hp, wp, T1p, wp, 0.0, Vp, w);
                 k_sub_block<<<grid1(size_t(wp) * w), TB, 0, st>>>(bp, m, T1p, wp, wp, w); // Bp -= App Hp
                 k_wblock_fix<<<grid1(size_t(w) * w), TB, 0, st>>>(bw, m, Up, Vp, w);
                 KERNEL_CHECK();
@@ -2140,12 +2186,12 @@ struct BlockLobpcg {
                 k_place_block<<<grid1(size_t(w) * w), TB, 0, st>>>(gM.get() + size_t(wa) * m + wa, m, nullptr, w);
                 KERNEL_CHECK();
             } else {
-                gram(ctx, n, W, w, MW, w, gM.get() + size_t(wa) * m + wa, m);
+                mh_gram(ctx, n, W, w, MW, w, gM.get() + size_t(wa) * m + wa, m);
                 untransformed(gM.get() + size_t(wa) * m + wa, w);
             }
             if (verbose) fprintf(stderr, "[lobpcg] it %3u Cholesky-QR diagonal spread 2^%.1f%s\n", it, last_spread / 16.0, w_block_trusted ? "" : " (W block measured)");
             if (wp) {
-                if (!p_implicit) gram(ctx, n, P, wp, AW, w, gA.get() + size_t(wa) * m + wa + w, m); // (already formed and corrected above otherwise)
+                if (!p_implicit) mh_gram(ctx, n, P, wp, AW, w, gA.get() + size_t(wa) * m + wa + w, m); // (already formed and corrected above otherwise)
                 untransformed(gA.get() + size_t(wa) * m + wa + w, wp);
                 {
                     // P = S_prev Cp with Cp gM-orthonormal and gM-orthogonal to the Ritz coefficients Cx, and
@@ -2176,41 +2222,30 @@ struct BlockLobpcg {
     void conjugate_directions(uint32_t it) {
         // New directions in coefficient space: the [W P] part of the active Ritz vectors, made
         // gM-orthonormal against the new X coefficients and among themselves.
-        const double one = 1, zero = 0, mone = -1;
+        const double one = 1, zero = 0;
         wp_new = w;
         k_build_cp<<<grid1(size_t(m) * w), TB, 0, st>>>(gA, nullptr, wa, m, w, m, Cp, m);
         KERNEL_CHECK();
         // (gM0 Cp is Cp itself when gM0 is the identity by construction: the two symmetric products are skipped)
         const double *mcp = gm_identity ? Cp.get() : T1.get();
         if (!gm_identity) ROCBLAS_CHECK(rocblas_dsymm(ctx->blas, rocblas_side_left, rocblas_fill_lower, m, w, &one, gM0, m, Cp, m, &zero, T1, m));
-        small_dgemm(ctx, rocblas_operation_transpose, rocblas_operation_none, wa, w, m, &one, gA, m, mcp, m, &zero, H, wa);
-        small_dgemm(ctx, rocblas_operation_none, rocblas_operation_none, m, w, wa, &mone, gA, m, H, wa, &one, Cp, m);
+        small_dgemm(ctx, true, false, wa, w, m, 1.0, gA, m, mcp, m, 0.0, H, wa);
+        small_dgemm(ctx, false, false, m, w, wa, -1.0, gA, m, H, wa, 1.0, Cp, m);
         if (!gm_identity) ROCBLAS_CHECK(rocblas_dsymm(ctx->blas, rocblas_side_left, rocblas_fill_lower, m, w, &one, gM0, m, Cp, m, &zero, T1, m));
-        small_dgemm(ctx, rocblas_operation_transpose, rocblas_operation_none, w, w, m, &one, Cp, m, mcp, m, &zero, G, w);
-        k_scale_gram<<<grid1(size_t(w) * w), TB, 0, st>>>(G, w, w, dscale);
-        KERNEL_CHECK();
-        {
+        small_dgemm(ctx, true, false, w, w, m, 1.0, Cp, m, mcp, m, 0.0, G, w);
+        // Cp <- Cp L^-T: one small product with the inverse where the factorisation formed it, else unscale and the library's trsm
+        // (a trtri and several GEMM launches of its own)
+        const ScaledCholesky chol = scaled_cholesky(w, Linv_p, false);
+        if (chol.info != 0) {
+            wp_new = 0;
+        } else if (chol.inverse_formed) {
+            mh_small_gemm(ctx, false, true, m, w, w, 1.0, Cp, m, Linv_p, w, 0.0, T1p2, m);
+            HIP_CHECK(hipMemcpyAsync(Cp, T1p2, size_t(m) * w * sizeof(double), hipMemcpyDeviceToDevice, st));
+        } else {
             double *Gs = G.get() + size_t(w) * w;
-            int hinfo = 0;
-            // Up to 128 columns: factor, unscale and invert in one launch, then Cp <- Cp L^-T as one small product (round 5; before: potrf,
-            // unscale and the library's trsm, which is a trtri and several GEMM launches of its own -- a dozen launches on the serial path of
-            // every iteration).  MH_TEST=potrf_chain: the old chain.
-            const bool fused = w <= 128 && !switches().potrf_chain;
-            {
-                if (fused) mh_potrf_small_inverse(ctx, Gs, w, info, dscale, Linv_p);
-                else mh_potrf(ctx, Gs, w, w, info); // ours at every order (one workgroup up to 128 columns, 128-column blocks above)
-                info.download(&hinfo, 1);
-            }
-            if (hinfo != 0) {
-                wp_new = 0;
-            } else if (fused) {
-                mh_small_gemm(ctx, false, true, m, w, w, 1.0, Cp, m, Linv_p, w, 0.0, T1p2, m);
-                HIP_CHECK(hipMemcpyAsync(Cp, T1p2, size_t(m) * w * sizeof(double), hipMemcpyDeviceToDevice, st));
-            } else {
-                k_unscale_chol<<<grid1(size_t(w) * w), TB, 0, st>>>(Gs, w, w, dscale);
-                KERNEL_CHECK();
-                ROCBLAS_CHECK(rocblas_dtrsm(ctx->blas, rocblas_side_right, rocblas_fill_lower, rocblas_operation_transpose, rocblas_diagonal_non_unit, m, w, &one, Gs, w, Cp, m));
-            }
+            k_unscale_chol<<<grid1(size_t(w) * w), TB, 0, st>>>(Gs, w, w, dscale);
+            KERNEL_CHECK();
+            ROCBLAS_CHECK(rocblas_dtrsm(ctx->blas, rocblas_side_right, rocblas_fill_lower, rocblas_operation_transpose, rocblas_diagonal_non_unit, m, w, &one, Gs, w, Cp, m));
         }
         // No conjugate directions in the first iterations of a cold start, while the block is far from the invariant
         // subspace: with residuals of order one the previous step carries no usable curvature information -- the iteration
@@ -2218,8 +2253,8 @@ struct BlockLobpcg {
         // (Rayleigh-Ritz of order 2w, no P Grams, narrower updates): 224 -> 213 ms per solve.
         if (!warm && it < kSkipP && !hist_worst.empty() && hist_worst.back() > 0.5) wp_new = 0;
         if (wp_new) { // App = Cp^T gA_prev Cp for the next iteration's P-P block
-            small_dgemm(ctx, rocblas_operation_none, rocblas_operation_none, m, wp_new, m, &one, gA0, m, Cp, m, &zero, T1, m);
-            small_dgemm(ctx, rocblas_operation_transpose, rocblas_operation_none, wp_new, wp_new, m, &one, Cp, m, T1, m, &zero, App, wp_new);
+            small_dgemm(ctx, false, false, m, wp_new, m, 1.0, gA0, m, Cp, m, 0.0, T1, m);
+            small_dgemm(ctx, true, false, wp_new, wp_new, m, 1.0, Cp, m, T1, m, 0.0, App, wp_new);
         }
     }
 
@@ -2237,12 +2272,8 @@ struct BlockLobpcg {
         // one product with M alone.
         {
             const uint32_t pitch = (wa + 1u) & ~1u; // 16-byte rows for the wide-load product
-            if (w_implicit) { // the basis holds W, not W L^-T: every coefficient row of the W part <- L^-T row (all columns)
-                const double unit = 1;
-                double *rows = Ct.get() + size_t(wa) * (wa + wp_new);
-                ROCBLAS_CHECK(rocblas_dtrmm(ctx->blas, rocblas_side_right, rocblas_fill_lower, rocblas_operation_none, rocblas_diagonal_non_unit, rocblas_int(wa + wp_new),
-                                            rocblas_int(w), &unit, Linv, rocblas_int(w), rows, rocblas_int(wa + wp_new), rows, rocblas_int(wa + wp_new)));
-            }
+            // the basis holds W, not W L^-T: every coefficient row of the W part <- L^-T row (all columns)
+            if (w_implicit) tri_correct(ctx, false, false, wa + wp_new, w, Linv, Ct.get() + size_t(wa) * (wa + wp_new), wa + wp_new);
             if (p_implicit && wp) { // ... and it holds W, not W - P Hp: the P rows take the difference, rows_P -= Hp rows_W (all columns)
                 const double minus = -1, plus = 1;
                 const rocblas_int pitchc = rocblas_int(wa + wp_new);
@@ -2257,8 +2288,9 @@ struct BlockLobpcg {
             // X at its own pitch, would serve only while the active columns are the leading ones: a free body's exact rigid-body
             // columns lock at the first test, so that never happens -- profiles/copy_passes_ab.txt -- and the form is not built.)
             const bool one_launch = b <= 128 && !switches().copy_passes;
-            if (one_launch) mh_combine(ctx, n, X, wa, W, w, P, wp, Ct, wa + wp_new, Xn, wa, Pn, false, b, idx_d, pitch, nullptr, 0, 0, X, b, idx_d);
-            else mh_combine(ctx, n, X, wa, W, w, P, wp, Ct, wa + wp_new, Xn, wa, Pn, false, b, idx_d, pitch);
+            MhCombine update{.x = X, .wx = wa, .ldx = b, .xmap = idx_d, .w = W, .ww = w, .p = P, .wp = wp, .ct = Ct, .nc = wa + wp_new, .out1 = Xn, .n1 = wa, .ld1 = pitch, .out2 = Pn};
+            if (one_launch) update.out1_also = X, update.ld1_also = b, update.omap_also = idx_d;
+            mh_combine(ctx, n, update);
             // M P_new (kept for blocks wider than 128 columns: the next projection needs it) from P_new itself: one pass over M.  Until
             // round 4 it was recombined from [M X, M W, M P] with the coefficients of P_new -- three tall panels read for one written:
             // 215-pair solves 1.7 ... 2.8 % slower, 129-pair solves 1 ... 1.5 % (and the image carried the recombination's rounding).
@@ -2288,63 +2320,56 @@ struct BlockLobpcg {
         wp = wp_new;
     }
 
-    void finish(double *eigenvalues) {
-        prof.restarts = iters;
-        prof.op_solve = precond_seconds;
-        if (!converged) mh_throw(MH_ENOTCONVERGED, "LOBPCG: %u of %u pairs converged in %u iterations", nconv, nev, iters);
-        for (uint32_t k = 0; k < nev; ++k) eigenvalues[k] = theta[order[k]] + sigma;
+    void finish() {
+        at.prof.restarts = iters;
+        at.prof.op_solve = precond_seconds;
+        if (!converged) mh_throw(MH_ENOTCONVERGED, "LOBPCG: %u of %u pairs converged in %u iterations", nconv, at.nev, iters);
+        for (uint32_t k = 0; k < at.nev; ++k) at.eigenvalues[k] = theta[order[k]] + at.sigma;
         sys->plain_residual = -1.0;
         if (scaled_norms) {
             // The pairs were accepted in the Jacobi-scaled norm (above): say what that means in the 2-norm relative residual
             // ||K x - lambda M x||_2 / (|lambda - sigma| ||M x||_2) the caller's tolerance is phrased in -- one pass, once per solve.
-            theta_d.upload(theta.data(), b);
-            const uint32_t rpb = 256, nblk = div_up(n, rpb);
-            if (scratch.count < size_t(nblk) * 3 * b) scratch.reset(ctx, size_t(nblk) * 3 * b);
-            k_residual_norms<<<dim3(nblk, div_up(b, 64)), 64, 0, st>>>(AX, MX, X, theta_d, 10.0 * std::abs(sigma), R, n, b, rpb, scratch, nullptr);
-            KERNEL_CHECK();
-            k_colsumsq_final<<<3 * b, 256, 0, st>>>(scratch, nblk, 3 * b, norms_d);
-            KERNEL_CHECK();
-            norms_d.download(norms.data(), 3 * size_t(b));
+            block_norms(nullptr);
             double worst = 0;
-            for (uint32_t k = 0; k < nev; ++k) {
+            for (uint32_t k = 0; k < at.nev; ++k) {
                 const uint32_t i = order[k];
-                if (std::abs(theta[i]) < 10.0 * std::abs(sigma)) continue; // (the rigid-body pairs sit at the rounding floor by construction)
-                worst = std::max(worst, std::sqrt(norms[i]) / (std::abs(theta[i]) * std::sqrt(norms[b + i])));
+                if (std::abs(theta[i]) < near_limit()) continue; // (the rigid-body pairs sit at the rounding floor by construction)
+                worst = std::max(worst, rel_residual(i));
             }
             sys->plain_residual = worst;
-            if (verbose) fprintf(stderr, "[lobpcg] accepted in the Jacobi-scaled norm at %.1e; worst elastic pair in the plain 2-norm: %.2e\n", residual_tol, worst);
+            if (verbose) fprintf(stderr, "[lobpcg] accepted in the Jacobi-scaled norm at %.1e; worst elastic pair in the plain 2-norm: %.2e\n", at.residual_tol, worst);
         }
-        sys->evecs.reset(ctx, n * nev);
-        sys->evec_cols = nev;
-        idx_d.upload(order.data(), nev);
-        k_gather_cols<<<grid1(n * nev), TB, 0, st>>>(X, idx_d, sys->evecs, n, b, nev);
+        sys->evecs.reset(ctx, n * at.nev);
+        sys->evec_cols = at.nev;
+        idx_d.upload(order.data(), at.nev);
+        k_gather_cols<<<grid1(n * at.nev), TB, 0, st>>>(X, idx_d, sys->evecs, n, b, at.nev);
         KERNEL_CHECK();
         HIP_CHECK(hipStreamSynchronize(st));
-        prof.iterate = t_iter.stop();
+        at.prof.iterate = t_iter.stop();
         read_health();
-        sys->profile = prof;
-        if (profile) *profile = prof;
-        if (switches().test_selfcheck_fail && !ctx->exchange_disabled) prof.rr_selfcheck = 1.0; // (test hook: the redo in eigs_impl)
+        sys->profile = at.prof;
+        if (at.profile) *at.profile = at.prof;
+        if (switches().test_selfcheck_fail && !ctx->exchange_disabled) at.prof.rr_selfcheck = 1.0; // (test hook: the redo in eigs_impl)
         // (1e-6, not the 1e-8 of round 5: a step whose matrix spans |sigma| .. ||A|| with an ill-conditioned block -- the first steps on two bodies joined at
         // ONE vertex, whose smoothed columns all lean on the same three hinge modes -- leaves 2e-8 honestly, and the pairs a solve returns are accepted
         // on their TRUE residuals, not on the step's; what the check is for, a wrong launch of an exchange kernel, leaves 1e-3 and more)
-        if (!(prof.rr_selfcheck < 1e-6))
-            mh_throw(MH_EHIP, "Rayleigh-Ritz self-check failed: a step's eigenpairs leave a relative residual of %.2e against the step's own matrix", prof.rr_selfcheck);
+        if (!(at.prof.rr_selfcheck < 1e-6))
+            mh_throw(MH_EHIP, "Rayleigh-Ritz self-check failed: a step's eigenpairs leave a relative residual of %.2e against the step's own matrix", at.prof.rr_selfcheck);
     }
     // the solve's health counters: redone Rayleigh-Ritz steps and the worst sampled self-check residual (k_rr_selfcheck) since start()
     void read_health() {
-        prof.sytrd_redos = ctx->sytrd_redos - redos_at_start;
-        prof.pairs_at_floor = pairs_at_floor;
-        prof.rr_selfcheck = 0.0;
+        at.prof.sytrd_redos = ctx->sytrd_redos - redos_at_start;
+        at.prof.pairs_at_floor = pairs_at_floor;
+        at.prof.rr_selfcheck = 0.0;
         if (ctx->rr_check) {
             unsigned long long bits = 0;
             HIP_CHECK(hipMemcpyAsync(&bits, ctx->rr_check, sizeof(bits), hipMemcpyDeviceToHost, st));
             HIP_CHECK(hipStreamSynchronize(st));
-            memcpy(&prof.rr_selfcheck, &bits, sizeof(double));
+            memcpy(&at.prof.rr_selfcheck, &bits, sizeof(double));
         }
     }
 
-    void run(double *eigenvalues) {
+    void run() {
         start();
         for (uint32_t it = 0; it <= max_iters; ++it) {
             if (converged_or_locked(it)) break;
@@ -2353,55 +2378,27 @@ struct BlockLobpcg {
             conjugate_directions(it);
             update_basis(it);
         }
-        finish(eigenvalues);
+        finish();
     }
 };
-// One solve's attempts of the block iteration (eigs_impl): what each hands to BlockLobpcg, the seed (cleared when a seeded basis has
-// not served) and the solve's profile, which the attempts write.
-struct Attempt {
-    mh_system *sys;
-    uint32_t nev, b;
-    double sigma, residual_tol;
-    const float *seed;
-    uint32_t srows, scols;
-    const volatile unsigned char *cancel;
-    volatile float *progress;
-    double *eigenvalues;
-    mh_profile &prof;
-    mh_profile *profile;
-    // The only place a BlockLobpcg is built (inner_cg: conjugate-gradient steps per search direction, 0: the cycle alone).  Returns the
-    // MhError the run ended with, nothing when it converged; any other exception propagates.
-    std::optional<MhError> run(uint32_t max_iters, int inner_cg = 0) {
-        try {
-            BlockLobpcg solver(sys, nev, b, sigma, residual_tol, max_iters, seed, srows, scols, cancel, progress, prof, profile, inner_cg);
-            solver.run(eigenvalues);
-            return std::nullopt;
-        } catch (const MhError &e) {
-            return e;
-        }
+std::optional<MhError> Attempt::run(uint32_t max_iters, int inner_cg) {
+    try {
+        BlockLobpcg solver(*this, max_iters, inner_cg);
+        solver.run();
+        return std::nullopt;
+    } catch (const MhError &e) {
+        return e;
     }
-    // the profile the system last stored (this solve's stiffness_nonzeros and factorize are not carried over)
-    void reset_profile() {
-        prof = sys->profile;
-        prof.dofs = uint32_t(size_t(3) * sys->n_nodes);
-    }
-    // both smoothers' spectral bounds a quarter wider, once per system
-    void widen_lmax() {
-        if (sys->lmax_widened) return;
-        sys->L1.lmax *= 1.25;
-        sys->L2.lmax *= 1.25;
-        sys->lmax_widened = true;
-    }
-};
+}
 } // namespace
 
-static void eigs_impl(mh_system *sys, uint32_t nev, double sigma, double residual_tol, uint32_t max_iters, const float *seed_basis, uint32_t seed_rows,
-                      uint32_t seed_cols, const volatile unsigned char *cancel, volatile float *progress, double *eigenvalues, mh_profile *profile) {
+static void eigs_impl(const SolveRequest &q) {
+    mh_system *const sys = q.sys;
     mh_context *ctx = sys->ctx;
     HIP_CHECK(hipSetDevice(ctx->device));
     const size_t n = size_t(3) * sys->n_nodes;
-    if (nev >= n) mh_throw(MH_EINVAL, "nev %u must be below the %zu unknowns", nev, n);
-    if (!(sigma < 0)) mh_throw(MH_EFACTOR, "shift must be negative for a positive-definite shifted operator");
+    if (q.nev >= n) mh_throw(MH_EINVAL, "nev %u must be below the %zu unknowns", q.nev, n);
+    if (!(q.sigma < 0)) mh_throw(MH_EFACTOR, "shift must be negative for a positive-definite shifted operator");
     // A mesh point that no kept tetrahedron uses has empty rows in K and M: K - sigma M is singular there and the reference's
     // Cholesky factorisation fails ("Modal shift-invert factorization failed.", CholeskyShiftInvert.cpp:44) -- so does this solve.
     if (sys->unreferenced_points) mh_throw(MH_EFACTOR, "%u mesh point(s) belong to no tetrahedron: the shifted operator is singular", sys->unreferenced_points);
@@ -2409,20 +2406,20 @@ static void eigs_impl(mh_system *sys, uint32_t nev, double sigma, double residua
     prof.dofs = uint32_t(n);
     // the reference counts the lower triangle of K (Eigen nonZeros of the lower-stored matrix, mesh2modes.cpp:615)
     prof.stiffness_nonzeros = uint32_t((sys->L2.n_blocks - sys->n_nodes) / 2 * 9 + uint64_t(6) * sys->n_nodes);
-    if (cancel && *cancel) mh_throw(MH_ECANCELLED, "cancelled");
+    if (q.cancel && *q.cancel) mh_throw(MH_ECANCELLED, "cancelled");
     // guard vectors: at least 15 (measured at S100k, nev = 65: 10 -> 23 iterations / 338 ms, 15 -> 19 / 317 ms,
     // 31 -> 15 / 338 ms), block rounded up to whole 16-column MFMA tiles
     // (every further disconnected body brings six more zero modes: the block grows by as many columns)
     // (215 pairs: 240 columns -> 23 / 24 / 21 iterations on the three 215-pair workloads, 256 columns -> 21 / 21 / 19 but +2 ... +4 % time)
-    const uint32_t guards = std::max(15u, nev * kGuardPercent / 100);
-    const uint32_t b = (nev + guards + 6u * (sys->n_components - 1u) + 15u) / 16u * 16u;
+    const uint32_t guards = std::max(15u, q.nev * kGuardPercent / 100);
+    const uint32_t b = (q.nev + guards + 6u * (sys->n_components - 1u) + 15u) / 16u * 16u;
     if (n <= 768 || n < size_t(5) * b) {
         Timer t(ctx);
-        dense_eigs(sys, nev, sigma, eigenvalues);
+        dense_eigs(sys, q.nev, q.sigma, q.eigenvalues);
         prof.iterate = t.stop();
         prof.restarts = 1;
         sys->profile = prof;
-        if (profile) *profile = prof;
+        if (q.profile) *q.profile = prof;
         return;
     }
     // Solves of any block width share the device with other contexts' work.  (Rounds 2-4 ran blocks wider than 128 columns alone, under
@@ -2431,7 +2428,7 @@ static void eigs_impl(mh_system *sys, uint32_t nev, double sigma, double residua
     // of k_sytrd_multi, whose barrier at the top of the column loop hipcc had left without its LDS wait; mh_common.h:
     // mh_lds_writes_landed, DESIGN.md section 6.  With the wait in place the lock is gone.)
     const Switches &sw = switches();
-    Attempt attempt{sys, nev, b, sigma, residual_tol, seed_basis, seed_rows, seed_cols, cancel, progress, eigenvalues, prof, profile};
+    Attempt attempt{q, b, prof};
     // The shift is negative (checked above), so K - sigma M IS positive definite and so is every Galerkin coarse operator of it in exact
     // arithmetic: a coarse elimination that meets a non-positive pivot has lost it to rounding (flat cells: entries of 1e17 cancelling).
     // That is not the caller's "factorization failed": the diagonal lift of the coarse operator goes up a thousandfold and the hierarchy
@@ -2440,24 +2437,24 @@ static void eigs_impl(mh_system *sys, uint32_t nev, double sigma, double residua
         try {
             {
                 Timer t(ctx);
-                mh_build_hierarchy(sys, sigma, true); // (the coarse elimination may still run: the first preconditioner application waits for it)
+                mh_build_hierarchy(sys, q.sigma, true); // (the coarse elimination may still run: the first preconditioner application waits for it)
                 prof.factorize = t.stop();
             }
-            if (progress) *progress = 0.3f;
+            if (q.progress) *q.progress = 0.3f;
             // The first attempt, then the rescues in order.  Each rescue runs only when the error the latest attempt left matches its guard;
             // otherwise that error passes on to the next one, and what is left after the last is thrown.
             std::optional<MhError> err;
             if (sw.test_last_resort) err = MhError(MH_ENOTCONVERGED, "MH_TEST=last_resort"); // (test hook: no first attempt and no seeded-basis retry)
-            else err = attempt.run(max_iters);
+            else err = attempt.run(q.max_iters);
             // A seeded basis that does not serve -- its columns in another order than the solve left them (the exact rigid-body vectors
             // then stand beside their seeded copies: a rank-deficient block), zeros, a NaN, one column forty-five times -- is no
             // reason to go through the rescues below with it, or to return nothing: the reference's SubspaceIterate takes what
             // it is given.  Once more from a cold start, and the rescues after that are cold as well.
-            if (err && !sw.test_last_resort && attempt.seed && err->code == MH_ENOTCONVERGED && max_iters >= 50) {
+            if (err && !sw.test_last_resort && attempt.seed_basis && err->code == MH_ENOTCONVERGED && q.max_iters >= 50) {
                 if (sw.verbose) fprintf(stderr, "[lobpcg] %s -- the seeded basis did not serve: once more from a cold start\n", err->what());
-                attempt.seed = nullptr, attempt.srows = 0, attempt.scols = 0;
+                attempt.seed_basis = nullptr, attempt.seed_rows = 0, attempt.seed_cols = 0;
                 attempt.reset_profile();
-                err = attempt.run(max_iters);
+                err = attempt.run(q.max_iters);
             }
             // A Rayleigh-Ritz step whose eigenpairs do not fit the step's own matrix (k_rr_selfcheck: sampled per step, read once at
             // the end) means a dense kernel delivered wrong numbers -- in rounds 2-4 the tagged exchange beside an LDS-bound
@@ -2467,24 +2464,24 @@ static void eigs_impl(mh_system *sys, uint32_t nev, double sigma, double residua
                 if (sw.verbose) fprintf(stderr, "[lobpcg] %s -- once more without the exchange kernels\n", err->what());
                 ctx->exchange_disabled = true;
                 attempt.reset_profile();
-                err = attempt.run(max_iters);
+                err = attempt.run(q.max_iters);
             }
             // A Chebyshev smoother whose interval ends below lmax(D^-1 A) amplifies the top of the spectrum instead of damping it -- by
             // T_deg(1 + 2 x overshoot): twelve-fold per smoothing at degree 16 for 2 %.  The bound is a power-iteration estimate times 1.1
             // (measured margin on the workloads: 6-9 %); should it fall short on some mesh, the iteration stalls or loses rank.  One retry
             // with both levels' bounds widened by a quarter (costs the smoothers a few per cent of their efficiency, nothing else).
             // (not for a mesh with flat cells: what fails there is not the bound -- the last resort below is next)
-            if (err && err->code == MH_ENOTCONVERGED && max_iters >= 50 && !sys->lmax_widened && !sw.test_last_resort && !(sys->worst_quality < kFlatShape)) {
+            if (err && err->code == MH_ENOTCONVERGED && q.max_iters >= 50 && !sys->lmax_widened && !sw.test_last_resort && !(sys->worst_quality < kFlatShape)) {
                 if (sw.verbose) fprintf(stderr, "[lobpcg] %s -- once more with the smoothers' spectral bounds widened by 25 %%\n", err->what());
                 attempt.widen_lmax();
-                err = attempt.run(max_iters);
+                err = attempt.run(q.max_iters);
             }
             // Last resort of a LARGER system (round 6): the block iteration once more with (nearly) the reference's own search directions --
             // A^-1 r by eight conjugate-gradient steps around the double-precision cycle instead of the cycle alone (PanelCg).  Ten times
             // the cost per iteration, a handful of iterations; reached only by meshes the attempts above gave up on (cells flat to
             // 1e-9 in a caller's own mesh: the front end's fills have none since round 6).  MH_ENOTCONVERGED is what is left when this
             // fails too.  MH_TEST=last_resort sends every solve here (tests).
-            if (err && err->code == MH_ENOTCONVERGED && n > kDenseLastResort && max_iters >= 50) {
+            if (err && err->code == MH_ENOTCONVERGED && n > kDenseLastResort && q.max_iters >= 50) {
                 if (sw.verbose) fprintf(stderr, "[lobpcg] %s -- last resort: conjugate-gradient search directions\n", err->what());
                 const MhError stopped = *err; // (what the caller reads first should this fail too: why the solve itself stopped)
                 attempt.reset_profile();
@@ -2494,11 +2491,11 @@ static void eigs_impl(mh_system *sys, uint32_t nev, double sigma, double residua
                 attempt.widen_lmax();
                 // (eight steps first; a mesh they do not do -- ||A|| / theta ~ 1e11: the cycle is a poor preconditioner of the flat cells' rows -- gets
                 // forty: each outer iteration is then nearly an exact inverse iteration, at fifty cycles' cost)
-                err = attempt.run(max_iters, kLastResortCg);
+                err = attempt.run(q.max_iters, kLastResortCg);
                 if (err && err->code == MH_ENOTCONVERGED) {
                     if (sw.verbose) fprintf(stderr, "[lobpcg] the last resort with %d conjugate-gradient steps: %s -- once more with %d\n", kLastResortCg, err->what(), 5 * kLastResortCg);
                     attempt.reset_profile();
-                    err = attempt.run(std::min<uint32_t>(max_iters, 120), 5 * kLastResortCg);
+                    err = attempt.run(std::min<uint32_t>(q.max_iters, 120), 5 * kLastResortCg);
                     if (err && err->code == MH_ENOTCONVERGED) mh_throw(MH_ENOTCONVERGED, "%s (the last resort too: %s)", stopped.what(), err->what());
                 }
             }
@@ -2506,15 +2503,15 @@ static void eigs_impl(mh_system *sys, uint32_t nev, double sigma, double residua
             // points -- a quarter of the tetrahedra flat to 1e-8, ||A|| / theta ~ 1e13): one dense eigensolve in the inverse
             // form.  O(n^3), seconds at the size limit: better than no modes for an editor primitive.
             // (not when the caller's own iteration limit is what stopped it: MaxRestarts exceeded stays the reference's empty result)
-            if (err && err->code == MH_ENOTCONVERGED && n <= kDenseLastResort && max_iters >= 50) {
+            if (err && err->code == MH_ENOTCONVERGED && n <= kDenseLastResort && q.max_iters >= 50) {
                 if (sw.verbose) fprintf(stderr, "[lobpcg] %s -- dense eigensolve of order %zu instead\n", err->what(), n);
                 Timer t(ctx);
-                dense_eigs(sys, nev, sigma, eigenvalues, true);
+                dense_eigs(sys, q.nev, q.sigma, q.eigenvalues, true);
                 attempt.reset_profile();
                 prof.iterate += t.stop();
-                prof.restarts = max_iters + 1;
+                prof.restarts = q.max_iters + 1;
                 sys->profile = prof;
-                if (profile) *profile = prof;
+                if (q.profile) *q.profile = prof;
                 err.reset();
             }
             if (err) throw *err;
@@ -2547,24 +2544,26 @@ uint32_t mh_shift_invert_panel(mh_system *sys, double sigma, const double *b, do
     SharedPhase solving(ctx->device);
     mh_build_hierarchy(sys, sigma); // (finished: the coarse inverse is waited for)
     Precond<double> prec(sys, w);
-    DevArray<double> r(ctx, n * w), z(ctx, n * w), p(ctx, n * w), ap(ctx, n * w), rz(ctx, w), rz_new(ctx, w), pap(ctx, w), rn(ctx, w), scratch;
-    const uint32_t rpb = 256, nb = uint32_t(div_up(n, rpb));
-    scratch.reset(ctx, size_t(nb) * w);
-    const dim3 grid(nb, div_up(w, 64));
-    auto dot = [&](const double *u, const double *v, double *out) {
-        k_coldot_partial<<<grid, 64, 0, st>>>(u, v, n, w, scratch, rpb);
-        KERNEL_CHECK();
-        k_colsumsq_final<<<w, 256, 0, st>>>(scratch, nb, w, out);
-        KERNEL_CHECK();
-    };
+    PanelCg cg(sys, w);
+    DevArray<double> rn(ctx, w);
+    double *r = cg.rr.get();
     HIP_CHECK(hipMemsetAsync(x, 0, n * w * sizeof(double), st));
     std::vector<double> bn(w), rnh(w);
-    dot(b, b, rn);
+    cg.dot(b, b, rn, w);
     rn.download(bn.data(), w);
-    auto worst_of = [&] {
+    auto worst_of = [&] { // of the squared residual norms in rn, read back
+        rn.download(rnh.data(), w);
         double worst = 0;
         for (uint32_t c = 0; c < w; ++c) worst = std::max(worst, bn[c] > 0 ? std::sqrt(rnh[c] / bn[c]) : 0.0);
         return worst;
+    };
+    auto true_residual = [&] { // r <- b - A x; the worst column's ||r|| / ||b||
+        mh_spmm(ctx, sys->L2, sys->L2.aval, x, cg.ap, nullptr, nullptr, w);
+        HIP_CHECK(hipMemcpyAsync(r, cg.ap.get(), n * w * sizeof(double), hipMemcpyDeviceToDevice, st));
+        k_axpy_panel<<<grid1(n * w), TB, 0, st>>>(r, b, n * w);
+        KERNEL_CHECK();
+        cg.dot(r, r, rn, w);
+        return worst_of();
     };
     uint32_t it = 0;
     double worst = 1.0, previous = 1e300;
@@ -2572,46 +2571,24 @@ uint32_t mh_shift_invert_panel(mh_system *sys, double sigma, const double *b, do
     // operator is nearly singular (the rigid-body components at a small |sigma|); a restart takes the drift out, and the solve ends when
     // the true residual is below the tolerance or stops improving (its floor eps ||A|| ||x|| / ||b|| -- a direct solve's residual too).
     for (int restart = 0; restart < 6 && it < max_iters; ++restart) {
-        mh_spmm(ctx, sys->L2, sys->L2.aval, x, ap, nullptr, nullptr, w);
-        HIP_CHECK(hipMemcpyAsync(r.get(), ap.get(), n * w * sizeof(double), hipMemcpyDeviceToDevice, st));
-        k_axpy_panel<<<grid1(n * w), TB, 0, st>>>(r, b, n * w); // r <- b - A x
-        KERNEL_CHECK();
-        dot(r, r, rn);
-        rn.download(rnh.data(), w);
-        worst = worst_of();
+        worst = true_residual();
         if (!(worst == worst)) mh_throw(MH_ENOTCONVERGED, "shift-invert: the conjugate gradients broke down (restart %d)", restart);
         if (worst <= rel_tol || worst > 0.5 * previous) break;
         previous = worst;
-        prec.apply(r, z, w);
-        HIP_CHECK(hipMemcpyAsync(p.get(), z.get(), n * w * sizeof(double), hipMemcpyDeviceToDevice, st));
-        dot(r, z, rz);
+        cg.start(prec, r, w);
         for (; it < max_iters;) {
-            mh_spmm(ctx, sys->L2, sys->L2.aval, p, ap, nullptr, nullptr, w);
-            dot(p, ap, pap);
-            k_cg_advance<<<grid1(n * w), TB, 0, st>>>(x, r, p, ap, rz, pap, n * w, w);
-            KERNEL_CHECK();
-            dot(r, r, rn);
-            rn.download(rnh.data(), w);
+            cg.advance(x, r, w);
+            cg.dot(r, r, rn, w);
             ++it;
             const double rec = worst_of();
             if (!(rec == rec)) mh_throw(MH_ENOTCONVERGED, "shift-invert: the conjugate gradients broke down at iteration %u", it);
             if (rec <= 0.5 * rel_tol) break;
-            prec.apply(r, z, w);
-            dot(r, z, rz_new);
-            k_cg_direction<<<grid1(n * w), TB, 0, st>>>(p, z, rz_new, rz, n * w, w);
-            KERNEL_CHECK();
-            HIP_CHECK(hipMemcpyAsync(rz.get(), rz_new.get(), w * sizeof(double), hipMemcpyDeviceToDevice, st));
+            cg.new_direction(prec, r, w);
         }
     }
     // what is reported and judged is the TRUE residual of the x that is returned, not the one a restart began with (the inner loop may
     // have ended on max_iters, or the sixth restart may just have finished)
-    mh_spmm(ctx, sys->L2, sys->L2.aval, x, ap, nullptr, nullptr, w);
-    HIP_CHECK(hipMemcpyAsync(r.get(), ap.get(), n * w * sizeof(double), hipMemcpyDeviceToDevice, st));
-    k_axpy_panel<<<grid1(n * w), TB, 0, st>>>(r, b, n * w);
-    KERNEL_CHECK();
-    dot(r, r, rn);
-    rn.download(rnh.data(), w);
-    worst = worst_of();
+    worst = true_residual();
     if (worst_rel) *worst_rel = worst;
     // accepted: the tolerance asked for, or -- where eps ||A|| ||x|| / ||b|| lies above it (a direct solve's residual too) -- 1e-8
     if (!(worst <= std::max(rel_tol, 1e-8))) mh_throw(MH_ENOTCONVERGED, "shift-invert: relative residual %.2e after %u iterations (asked %.1e)", worst, it, rel_tol);
@@ -2649,7 +2626,7 @@ extern "C" int mh_eigs(mh_system *sys, uint32_t nev, double sigma, double residu
     try {
         std::unique_lock<std::mutex> one_solve_at_a_time(g_solve_mutex, std::defer_lock);
         if (!g_concurrent) one_solve_at_a_time.lock();
-        eigs_impl(sys, nev, sigma, residual_tol, max_iters, seed_basis, seed_rows, seed_cols, cancel, progress, eigenvalues, profile);
+        eigs_impl(SolveRequest{sys, nev, sigma, residual_tol, max_iters, seed_basis, seed_rows, seed_cols, cancel, progress, eigenvalues, profile});
         HIP_CHECK(hipStreamSynchronize(sys->ctx->stream)); // nothing of this solve is in flight when the next one starts
         return MH_OK;
     } catch (const std::exception &e) {

@@ -1051,7 +1051,7 @@ uint64_t mh_structure::device_bytes() const {
 // before it was kept.  A context other than the mesh's builds a structure of its own that nobody keeps.  A failed build throws and
 // caches nothing.
 void mh_build_system(mh_context *ctx, const mh_mesh *mesh, const mh_material &mat, mh_system *sys) {
-    static const bool fresh = getenv("MH_TEST") && strstr(getenv("MH_TEST"), "fresh_structure");
+    static const bool fresh = mh_test_hook("fresh_structure");
     std::shared_ptr<const mh_structure> kept;
     if (mesh->ctx == ctx) {
         std::lock_guard<std::mutex> lock(mesh->structure_mutex);
